@@ -3,11 +3,15 @@
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, or - when no
                                                             WORLD_SIZE is set - bench.py starts the N ranks itself)
+    python bench.py ... --dump-outputs DIR                 (also writes the last timed step's results as DIR/*.npy)
+    python bench.py ... --full                             (also every other leg: see below)
 
 Metric (BASELINE.json): BA Gauss-Newton/LM iterations per second on the 200-keyframe /
 20k-landmark synthetic SE(2) graph (config 4 formulation = Map::loadLocalGraph applied to a
-whole-map window), plus ORB extract+match frames/s at 640x480 reported in the
-`orb` object of the same JSON line.
+whole-map window), timed over exactly K steps after W warm-up steps.  A plain run
+does only that.  With --full the same JSON line also carries a sustained sample of the headline
+graph (at least SE2_BENCH_MIN_TIMED_S seconds), the per-kernel pass and roofline, the batched
+local windows, ORB extract+match frames/s at 640x480 (the `orb` object) and the CPU baselines.
 
 A "step" is ONE LM outer iteration (linearise -> Schur reduction -> dense pose solve ->
 back-substitution/update -> chi^2, incl. any retry trials) of the reference's protocol
@@ -33,7 +37,8 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable)
 ITERS_PER_CALL = 10    # Config::LOCAL_ITER of the synthetic setup
-MIN_TIMED_S = float(os.environ.get("SE2_BENCH_MIN_TIMED_S", "2.0"))   # (the profiling captures of tools/capture.sh shorten it) floor of the timed region of the headline leg (long enough for a 5 s SMI sampler to see the device busy)
+MIN_TIMED_S = float(os.environ.get("SE2_BENCH_MIN_TIMED_S", "2.0"))   # (the profiling captures of tools/capture.sh shorten it) floor of the --full sustained sample of the headline graph (long enough for a 5 s SMI sampler to see the device busy)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: larger landmark arrays are written as a fixed, seeded sample of rows
 MIN_WINDOWS_S = min(0.4, MIN_TIMED_S)    # ... of every row of the window sweep (its best row is then timed again for MIN_TIMED_S)
 FP64_PEAK_TFLOPS = 78.6   # MI355X FP64 vector = matrix peak (MI355X_MICROARCH.md)
 
@@ -85,6 +90,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--kf", type=int, default=200)
     ap.add_argument("--landmarks", type=int, default=20000)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: sustained sample, per-kernel pass and roofline, BA windows, ORB and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the poses, landmarks and chi2 history of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-orb", action="store_true")
     ap.add_argument("--orb-batch", type=int, default=256)
@@ -98,7 +107,10 @@ def parse():
     ap.add_argument("--ba-windows", type=int, default=-1,
                     help="independent 50-KF local windows optimised concurrently per GPU (se2gpu_ba_optimize_batch); "
                          "-1 = sweep 1, 8, 32, 64; 0 = skip")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -248,123 +260,126 @@ def main():
         for _ in range(3 if shape else 0):
             opt.reset_estimates()
             opt.optimize(shape)
-    # The timed region is whole blocks of K steps and never shorter than MIN_TIMED_S of device work (20 steps of this
-    # graph are 4 ms).  The number of blocks comes from an untimed probe block (every rank computes the same count from
-    # the all-reduced time); should the sample still come out short, it is taken again with more blocks - the floor is
-    # enforced, not estimated.  `steps` in the JSON is what ran, `steps_requested` what was asked.
+    # The timed region is exactly K steps: `steps` in the JSON is what ran and what was asked.
     sync_all()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    trials = run_steps(args.steps)
     sync_all()
-    probe = time.perf_counter() - t0
+    dt = time.perf_counter() - t0
     if dist is not None:
-        probe = dist.allreduce_max(probe)
-    blocks = max(1, int(np.ceil(1.25 * MIN_TIMED_S / max(probe, 1e-6))))
-    while True:
-        steps = args.steps * blocks
-        sync_all()
-        t0 = time.perf_counter()
-        trials = 0
-        for _ in range(blocks):
-            trials += run_steps(args.steps)
-        sync_all()
-        dt = time.perf_counter() - t0
-        if dist is not None:
-            dt = dist.allreduce_max(dt)
-        if dt >= MIN_TIMED_S:
-            break
-        blocks *= 2
+        dt = dist.allreduce_max(dt)
+    steps = args.steps
     iters_per_s = steps / dt
     chi2_final = opt.stats["chi2_final"]
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, opt, "" if world == 1 else f".rank{rank}")
+    log(f"BA: {iters_per_s:.1f} it/s over {steps} steps")
 
-    log(f"BA: {iters_per_s:.1f} it/s over {steps} steps; per-kernel pass")
-    # ---------------- per-kernel durations with HIP events on the kernels' stream ----------------
-    # Same K steps again with an event pair around every launch (serialises the stream, so it is a
-    # separate pass and not the timed region above).
-    opt.profile(True)
-    run_steps(min(steps, 50))
-    sync_all()
-    prof = opt.profile_report()
-    opt.profile(False)
-    kern = {k: {"avg_us": 1e3 * ms / max(n, 1), "launches": n, "total_ms": ms} for k, (ms, n) in prof.items()}
-    # the dominant KERNEL: the exchange of the sharded run ("allreduce_*", timed like a launch) is reported beside it
-    only_k = {k: v for k, v in kern.items() if not k.startswith("allreduce")}
-    dom = max(only_k, key=lambda k: only_k[k]["total_ms"]) if only_k else None
-    exchange = None
-    if use_dist:
-        per_iter = lambda name: (kern[name]["total_ms"] * 1e3 / max(kern["k_chol_tiles"]["launches"], 1)
-                                 if name in kern and "k_chol_tiles" in kern else None)   # noqa: E731
-        exchange = {"what": "RCCL all-reduce (sum, f64) of the packed lower-triangular tiles of [S | b] + scalars, once per "
-                            "LM trial, on the handle's stream; per-kernel pass (event pair around every call)",
-                    "doubles_per_trial": opt.exchange_doubles(),   # of the (possibly re-ordered, padded) system this handle factorises
-                    "comm_ranks": int(nranks.value),
-                    "allreduce_system_us": kern.get("allreduce_system", {}).get("avg_us"),
-                    "allreduce_small_us": kern.get("allreduce_small", {}).get("avg_us"),
-                    "pack_unpack_us": kern.get("k_tri_pack", {}).get("avg_us"),
-                    "allreduce_us_per_iteration": (per_iter("allreduce_system") or 0.0) + (per_iter("allreduce_small") or 0.0)
-                    if "k_chol_tiles" in kern else None}
-    B_ba = g_full.algorithmic_bytes_per_iter()
-    B_ba_rank = g.algorithmic_bytes_per_iter()
+    sustained = roofline = exchange = windows_obj = orb_obj = cpu = None
+    if args.full:
+        # The same graph over whole blocks of K steps, never shorter than MIN_TIMED_S of device work (20 steps of this graph
+        # are 4 ms).  The number of blocks comes from the headline sample (every rank computes the same count from the
+        # all-reduced time); should the sample still come out short, it is taken again with more blocks - the floor is
+        # enforced, not estimated.
+        blocks = max(1, int(np.ceil(1.25 * MIN_TIMED_S / max(dt, 1e-6))))
+        while True:
+            s_steps = args.steps * blocks
+            sync_all()
+            t0 = time.perf_counter()
+            for _ in range(blocks):
+                run_steps(args.steps)
+            sync_all()
+            s_dt = time.perf_counter() - t0
+            if dist is not None:
+                s_dt = dist.allreduce_max(s_dt)
+            if s_dt >= MIN_TIMED_S:
+                break
+            blocks *= 2
+        sustained = {"iters_per_s": s_steps / s_dt, "steps": s_steps, "timed_s": s_dt, "ms_per_step": 1e3 * s_dt / s_steps}
+        log(f"BA: {s_steps / s_dt:.1f} it/s over {s_steps} steps (sustained); per-kernel pass")
+        # ---------------- per-kernel durations with HIP events on the kernels' stream ----------------
+        # Same K steps again with an event pair around every launch (serialises the stream, so it is a
+        # separate pass and not the timed region above).
+        opt.profile(True)
+        run_steps(min(s_steps, 50))
+        sync_all()
+        prof = opt.profile_report()
+        opt.profile(False)
+        kern = {k: {"avg_us": 1e3 * ms / max(n, 1), "launches": n, "total_ms": ms} for k, (ms, n) in prof.items()}
+        # the dominant KERNEL: the exchange of the sharded run ("allreduce_*", timed like a launch) is reported beside it
+        only_k = {k: v for k, v in kern.items() if not k.startswith("allreduce")}
+        dom = max(only_k, key=lambda k: only_k[k]["total_ms"]) if only_k else None
+        if use_dist:
+            per_iter = lambda name: (kern[name]["total_ms"] * 1e3 / max(kern["k_chol_tiles"]["launches"], 1)
+                                     if name in kern and "k_chol_tiles" in kern else None)   # noqa: E731
+            exchange = {"what": "RCCL all-reduce (sum, f64) of the packed lower-triangular tiles of [S | b] + scalars, once per "
+                                "LM trial, on the handle's stream; per-kernel pass (event pair around every call)",
+                        "doubles_per_trial": opt.exchange_doubles(),   # of the (possibly re-ordered, padded) system this handle factorises
+                        "comm_ranks": int(nranks.value),
+                        "allreduce_system_us": kern.get("allreduce_system", {}).get("avg_us"),
+                        "allreduce_small_us": kern.get("allreduce_small", {}).get("avg_us"),
+                        "pack_unpack_us": kern.get("k_tri_pack", {}).get("avg_us"),
+                        "allreduce_us_per_iteration": (per_iter("allreduce_system") or 0.0) + (per_iter("allreduce_small") or 0.0)
+                        if "k_chol_tiles" in kern else None}
+        B_ba = g_full.algorithmic_bytes_per_iter()
+        B_ba_rank = g.algorithmic_bytes_per_iter()
 
-    def kernel_bytes(name):
-        """Algorithmic bytes ONE launch of `name` has to move; whole-iteration figure otherwise."""
-        n3 = 3 * g.P
-        if name.startswith("k_chol"):       # dense pose solve: lower triangle of S + rhs in, x out
-            return 8 * (n3 * (n3 + 1) // 2 + n3) + 8 * n3
-        if name == "k_reduce2":             # 152 B per contributor pair + the reduced system written once
-            k = np.bincount(np.asarray(g.e_lm), minlength=g.L).astype(np.int64)
-            return int(152 * (k * (k - 1) // 2).sum() + 8 * n3 * n3)
-        if name == "k_linearize":
-            return 44 * g.E + 24 * g.L + 24 * g.P + 216 * g.E + 144 * g.L
-        if name in ("k_update", "k_finalize"):
-            return 44 * g.E + 72 * g.E + 48 * g.L + 24 * g.L
-        return B_ba_rank
-    roofline = None
-    traffic = _pmc_traffic()
-    if dom is not None:
-        avg_s = kern[dom]["avg_us"] * 1e-6
-        B_dom = kernel_bytes(dom)
-        achieved = B_dom / avg_s / 1e9
-        roofline = {
-            "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            # HBM bytes per launch of that kernel from rocprofv3 PMC passes (profiles/pmc_traffic.json, collected with
-            # tools/pmc_summarize.py on this workload; FETCH_SIZE x2 correction) - null when the file has no entry
-            "traffic": (_traffic_of(traffic, dom)[0] if world == 1 else None),
-            "traffic_commit": traffic.get("_meta", {}).get("commit"),
-            "traffic_code_sha": traffic.get(dom, {}).get("code_sha"),
-            "traffic_stale": _traffic_of(traffic, dom)[1],
-            "algorithmic_bytes_per_launch": B_dom, "avg_launch_us": kern[dom]["avg_us"],
-            "note": ("the dominant kernel is the dense pose solve: a 600-column dependency chain, bound by FP64 / LDS "
-                     "latency and inter-workgroup hand-offs, not by bandwidth (DESIGN.md 4.1, 7)"
-                     if dom.startswith("k_chol") else None),
-            "whole_step_achieved": B_ba * iters_per_s / 1e9,
-            "whole_step_frac": B_ba * iters_per_s / 1e9 / HBM_PEAK_GBS,
-            "kernels_us": {k: round(v["avg_us"], 3) for k, v in kern.items()},
-        }
-        if dom.startswith("k_chol"):
-            # what the solve IS bound by, in numbers (VERDICT r05 #8): its FP64 work against the part's FP64 rate, and the length of
-            # the dependency chain against the launch time - neither bytes nor flops limit it, the chain of pivots does
+        def kernel_bytes(name):
+            """Algorithmic bytes ONE launch of `name` has to move; whole-iteration figure otherwise."""
             n3 = 3 * g.P
-            flops = n3 ** 3 / 3.0 + 4.0 * n3 * n3          # LDL^T of the augmented system + the two triangular solves
-            roofline["fp64"] = {"flops_per_launch": flops, "achieved_tflops": flops / avg_s / 1e12, "peak_tflops": FP64_PEAK_TFLOPS,
-                                "frac": flops / avg_s / 1e12 / FP64_PEAK_TFLOPS}
-            roofline["bound_by"] = {"what": "latency: a chain of dependent pivots", "pivots": n3,
-                                    "ns_per_pivot": 1e9 * avg_s / n3}
+            if name.startswith("k_chol"):       # dense pose solve: lower triangle of S + rhs in, x out
+                return 8 * (n3 * (n3 + 1) // 2 + n3) + 8 * n3
+            if name == "k_reduce2":             # 152 B per contributor pair + the reduced system written once
+                k = np.bincount(np.asarray(g.e_lm), minlength=g.L).astype(np.int64)
+                return int(152 * (k * (k - 1) // 2).sum() + 8 * n3 * n3)
+            if name == "k_linearize":
+                return 44 * g.E + 24 * g.L + 24 * g.P + 216 * g.E + 144 * g.L
+            if name in ("k_update", "k_finalize"):
+                return 44 * g.E + 72 * g.E + 48 * g.L + 24 * g.L
+            return B_ba_rank
+        traffic = _pmc_traffic()
+        if dom is not None:
+            avg_s = kern[dom]["avg_us"] * 1e-6
+            B_dom = kernel_bytes(dom)
+            achieved = B_dom / avg_s / 1e9
+            roofline = {
+                "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                # HBM bytes per launch of that kernel from rocprofv3 PMC passes (profiles/pmc_traffic.json, collected with
+                # tools/pmc_summarize.py on this workload; FETCH_SIZE x2 correction) - null when the file has no entry
+                "traffic": (_traffic_of(traffic, dom)[0] if world == 1 else None),
+                "traffic_commit": traffic.get("_meta", {}).get("commit"),
+                "traffic_code_sha": traffic.get(dom, {}).get("code_sha"),
+                "traffic_stale": _traffic_of(traffic, dom)[1],
+                "algorithmic_bytes_per_launch": B_dom, "avg_launch_us": kern[dom]["avg_us"],
+                "note": ("the dominant kernel is the dense pose solve: a 600-column dependency chain, bound by FP64 / LDS "
+                         "latency and inter-workgroup hand-offs, not by bandwidth (DESIGN.md 4.1, 7)"
+                         if dom.startswith("k_chol") else None),
+                "whole_step_achieved": B_ba * iters_per_s / 1e9,
+                "whole_step_frac": B_ba * iters_per_s / 1e9 / HBM_PEAK_GBS,
+                "kernels_us": {k: round(v["avg_us"], 3) for k, v in kern.items()},
+            }
+            if dom.startswith("k_chol"):
+                # what the solve IS bound by, in numbers (VERDICT r05 #8): its FP64 work against the part's FP64 rate, and the length of
+                # the dependency chain against the launch time - neither bytes nor flops limit it, the chain of pivots does
+                n3 = 3 * g.P
+                flops = n3 ** 3 / 3.0 + 4.0 * n3 * n3          # LDL^T of the augmented system + the two triangular solves
+                roofline["fp64"] = {"flops_per_launch": flops, "achieved_tflops": flops / avg_s / 1e12, "peak_tflops": FP64_PEAK_TFLOPS,
+                                    "frac": flops / avg_s / 1e12 / FP64_PEAK_TFLOPS}
+                roofline["bound_by"] = {"what": "latency: a chain of dependent pivots", "pivots": n3,
+                                        "ns_per_pivot": 1e9 * avg_s / n3}
 
     # ---------------- batched local windows: the machine filled (SURVEY.md section 7 hard part 6) ----------------
-    windows_obj = None
-    if args.ba_windows != 0:
+    if args.full and args.ba_windows != 0:
         log("BA windows leg")
         try:
             windows_obj = _ba_windows(args, rank, world, sync_all, dist)
         except Exception as exc:   # never takes the headline down
             windows_obj = {"error": repr(exc)}
 
-    log("ORB leg")
     # ---------------- ORB leg (frames/s) ----------------
-    orb_obj = None
-    if not args.no_orb:
+    if args.full and not args.no_orb:
+        log("ORB leg")
         try:
             from se2lam_amd import orb_bench
             own_process = world == 1 and args.orb_inflight > 2    # the PCIe-inclusive leg with the two handles of a streaming caller
@@ -382,8 +397,7 @@ def main():
             orb_obj["cpu_baseline"] = _orb_cpu_baseline(synth, args.orb_batch)
 
     # ---------------- CPU baseline (rank 0, N=1 only): the oracle on the host cores ----------------
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("BA CPU baseline")
         cpu = _ba_cpu_baseline(g_full, args.cpu_seconds)
         log("pipeline (configs[0]) CPU baseline")
@@ -394,7 +408,7 @@ def main():
         out = {
             "metric": "BA GN-iters/s (200 KF, 20k pts)", "value": iters_per_s, "unit": "iters/s",
             "n_gpus": world, "steps": steps, "steps_requested": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / steps, "timed_s": dt,
+            "ms_per_step": 1e3 * dt / steps, "timed_s": dt, "sustained": sustained,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic",
             # the figure that CAN scale with N: every rank optimises its own independent windows, no collective (north_star:
@@ -427,6 +441,24 @@ def main():
         with _stdout_to_stderr():
             capi.lib().se2gpu_comm_destroy(comm)
         dist.close()
+
+
+def _dump_outputs(out_dir, opt, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives from its last optimize() - the pose and landmark estimates
+    (this rank's shard when N > 1) and the chi2 after every iteration - as float64 DIR/<name><suffix>.npy.  Landmarks that
+    would take the files past DUMP_MAX_BYTES are written as a fixed, seeded sample of rows, `landmarks_rows` their indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    poses, lms = opt.estimates()
+    out = {"poses": poses, "chi2_hist": np.asarray(opt.stats["chi2_hist"], np.float64)}
+    room = DUMP_MAX_BYTES - sum(a.nbytes + 4096 for a in out.values()) - 2 * 4096     # (4096: an .npy header, generously)
+    if lms.nbytes > room:
+        k = room // (lms.itemsize * lms.shape[1] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(len(lms), size=k, replace=False))
+        out["landmarks"], out["landmarks_rows"] = lms[rows], rows.astype(np.float64)
+    else:
+        out["landmarks"] = lms
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def _ba_windows(args, rank, world, sync_all, dist, P=50, L=5000, calls=6):

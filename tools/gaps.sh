@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 D=$R/gpurun_out/gaps; rm -rf $D; mkdir -p $D
-(cd /tmp && timeout 200 rocprofv3 --kernel-trace -f csv -d $D -o tr -- python $R/bench.py --steps 100 --warmup 20 --no-orb --no-cpu-baseline --ba-windows 0 > $D/stdout.log 2>&1)
+(cd /tmp && timeout 200 rocprofv3 --kernel-trace -f csv -d $D -o tr -- python $R/bench.py --full --steps 100 --warmup 20 --no-orb --no-cpu-baseline --ba-windows 0 > $D/stdout.log 2>&1)
 python - "$D" <<'PY'
 import csv, glob, sys, re, collections
 f = glob.glob(sys.argv[1] + "/*kernel_trace.csv")[0]

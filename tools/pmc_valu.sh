@@ -1,7 +1,7 @@
 #!/bin/bash
-# usage (GPU box, repo root): tools/pmc_valu.sh <tag>   -> gpurun_out/<tag>_valu.json
+# usage (GPU box, repo root): tools/pmc_valu.sh <tag>   -> $OUT/<tag>_valu.json (OUT: default out/)
 # VALUBusy (% of cycles a SIMD's VALU is busy) and LDSBankConflict (% of LDS cycles lost to bank conflicts) per kernel of
-# the bench workloads: separate rocprofv3 --pmc passes (derived metrics, never combined with the trace domains gpurun refuses)
+# the bench workloads: separate rocprofv3 --pmc passes (derived metrics, never combined with the trace domains)
 set -e
 export TMPDIR=/tmp
 # one launch per kernel and batch, as bench.py's per-kernel (profiled) pass and its algorithmic bytes per launch assume: the
@@ -9,17 +9,18 @@ export TMPDIR=/tmp
 # flight (--orb-inflight 2, the default) would stretch the kernels that overlap
 export SE2GPU_ORB_PIPELINE_MIN=1000000
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-$R/out}
 TAG=$1
 for C in VALUBusy LDSBankConflict; do
-  mkdir -p $R/gpurun_out/pmc_$C
-  (cd /tmp && timeout 300 rocprofv3 --pmc $C --kernel-trace -f csv -d $R/gpurun_out/pmc_$C -o pmc -- python $R/bench.py --steps 10 --warmup 10 --orb-batch 256 --orb-steps 2 --orb-inflight 1 --no-cpu-baseline --ba-windows 0 > $R/gpurun_out/pmc_$C/stdout.log 2>&1) || true
+  mkdir -p $OUT/pmc_$C
+  (cd /tmp && timeout 300 rocprofv3 --pmc $C --kernel-trace -f csv -d $OUT/pmc_$C -o pmc -- python $R/bench.py --full --steps 10 --warmup 10 --orb-batch 256 --orb-steps 2 --orb-inflight 1 --no-cpu-baseline --ba-windows 0 > $OUT/pmc_$C/stdout.log 2>&1) || true
 done
-python - "$R" "$TAG" <<'PY'
+python - "$OUT" "$TAG" <<'PY'
 import csv, glob, json, re, sys, collections
-R, tag = sys.argv[1], sys.argv[2]
-out = {"_meta": {"source": "rocprofv3 --pmc VALUBusy / --pmc LDSBankConflict (separate passes), bench.py --steps 10 --warmup 10 --orb-batch 256 --orb-steps 2", "unit": "percent, mean over launches"}}
+D, tag = sys.argv[1], sys.argv[2]
+out = {"_meta": {"source": "rocprofv3 --pmc VALUBusy / --pmc LDSBankConflict (separate passes), bench.py --full --steps 10 --warmup 10 --orb-batch 256 --orb-steps 2", "unit": "percent, mean over launches"}}
 for C in ("VALUBusy", "LDSBankConflict"):
-    fs = glob.glob(f"{R}/gpurun_out/pmc_{C}/*counter_collection.csv")
+    fs = glob.glob(f"{D}/pmc_{C}/*counter_collection.csv")
     if not fs:
         continue
     acc = collections.defaultdict(list)
@@ -31,9 +32,9 @@ for C in ("VALUBusy", "LDSBankConflict"):
     for k, v in acc.items():
         out.setdefault(k, {})[C] = round(sum(v) / len(v), 2)
         out[k]["launches"] = len(v)
-json.dump(out, open(f"{R}/gpurun_out/{tag}_valu.json", "w"), indent=1)
+json.dump(out, open(f"{D}/{tag}_valu.json", "w"), indent=1)
 for k in sorted(out, key=lambda k: -out[k].get("VALUBusy", 0) if k != "_meta" else 1e9):
     if k != "_meta":
         print("%-28s %s" % (k[:28], out[k]))
 PY
-rm -f $R/gpurun_out/pmc_VALUBusy/*counter_collection.csv $R/gpurun_out/pmc_LDSBankConflict/*counter_collection.csv
+rm -f $OUT/pmc_VALUBusy/*counter_collection.csv $OUT/pmc_LDSBankConflict/*counter_collection.csv

@@ -14,7 +14,7 @@ PASSES=(
 i=0
 for C in "${PASSES[@]}"; do
   D=$R/gpurun_out/pmcw_$i; mkdir -p $D
-  (cd /tmp && timeout 300 rocprofv3 --pmc $C --kernel-trace -f csv -d $D -o pmc -- python $R/bench.py --steps 10 --warmup 10 --no-orb --no-cpu-baseline --ba-windows $N > $D/stdout.log 2>&1) || echo "pass $i failed"
+  (cd /tmp && timeout 300 rocprofv3 --pmc $C --kernel-trace -f csv -d $D -o pmc -- python $R/bench.py --full --steps 10 --warmup 10 --no-orb --no-cpu-baseline --ba-windows $N > $D/stdout.log 2>&1) || echo "pass $i failed"
   i=$((i+1))
 done
 python - "$R" "$TAG" <<'PY'

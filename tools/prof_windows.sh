@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-win}; N=${2:-64}
 D=$R/gpurun_out/prof_$TAG; mkdir -p $D
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $D -o win -- python $R/bench.py --steps 20 --warmup 10 --no-orb --no-cpu-baseline --ba-windows $N > $D/stdout.log 2> $D/stderr.log)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $D -o win -- python $R/bench.py --full --steps 20 --warmup 10 --no-orb --no-cpu-baseline --ba-windows $N > $D/stdout.log 2> $D/stderr.log)
 S=$(find $D -name "*kernel_stats.csv" | head -1)
 cp $S $R/gpurun_out/${TAG}_windows_kernel_stats.csv
 python - <<PY
