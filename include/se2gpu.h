@@ -338,7 +338,10 @@ int se2gpu_ba_optimize_batch(se2gpu_ba** handles, int count, int iters, int mode
 /* Which of its three paths the calling thread's last se2gpu_ba_optimize_batch took (-1: none yet): 0 = one stream per window,
  * 1 = lock step (one launch per stage for all windows), 2 = resident (one workgroup per window for its whole optimize():
  * batches of SE2GPU_BA_RESIDENT_MIN = 96 windows or more whose windows fit a compute unit's LDS, csrc/ba_window.hip; its sums
- * are atomic, so its results equal the other paths' to rounding, not to the bit).  SE2GPU_BA_RESIDENT=0 / 1 forces the choice. */
+ * are atomic, so its results equal the other paths' to rounding, not to the bit).  SE2GPU_BA_RESIDENT=0 / 1 forces the choice.
+ * Odometry shapes: a window with a PreEdgeSE2 self loop (i, i) keeps the batch off the resident path, even when it is forced;
+ * a self loop or a pair of key frames joined by two PreEdgeSE2 (in either direction) keeps it off the lock-step path (such a
+ * window runs in synchronous mode).  Edges in any order and direction, and any number of them at one key frame, are taken. */
 int se2gpu_ba_last_batch_path(void);
 int se2gpu_ba_get_se2(se2gpu_ba* h, int id, double xyt[3]);   /* estimateVertexSE2   */
 int se2gpu_ba_get_xyz(se2gpu_ba* h, int id, double xyz[3]);   /* estimateVertexSBAXYZ */

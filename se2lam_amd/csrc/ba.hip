@@ -744,17 +744,19 @@ __global__ __launch_bounds__(kBlock) void k_reduce2(int P, int ld, int nwg_off, 
     d_reduce2(blockIdx.x, P, ld, nwg_off, lambda, root, grp, blk_a, blk_b, pair_i, pair_j, blk_odo, W, Dg, fixed, pose_ptr, pose_edges, podo_ptr, podo_item, o_i, o_j, o_meas, o_info, poses, S, bp, ctl, poses_b, epoch, pose_off, nsys);
 }
 
-// odometry pose-pose blocks: S_ij += Oij, S_ji += Oij^T.  One thread per (edge, entry).
+// odometry pose-pose blocks: S_ij += Oij, S_ji += Oij^T, at the poses' columns of the system the solver factorises (pose_off:
+// the fill-reducing order, nullptr = natural).  One thread per (edge, entry).
 __global__ void k_reduce_odo(int O, int ld, const int* __restrict__ o_i, const int* __restrict__ o_j,
-                             const double* __restrict__ Oij, double* __restrict__ S) {
+                             const double* __restrict__ Oij, double* __restrict__ S, const int* __restrict__ pose_off) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= O * 9) return;
     const int k = t / 9, r = (t % 9) / 3, c = t % 3;
     const int i = o_i[k], j = o_j[k];
     const double v = Oij[t];
     if (v == 0.0) return;
-    atomicAdd(&S[(size_t)(3 * i + r) * ld + 3 * j + c], v);
-    atomicAdd(&S[(size_t)(3 * j + c) * ld + 3 * i + r], v);
+    const int ci = pose_off ? pose_off[i] : 3 * i, cj = pose_off ? pose_off[j] : 3 * j;
+    atomicAdd(&S[(size_t)(ci + r) * ld + cj + c], v);
+    atomicAdd(&S[(size_t)(cj + c) * ld + ci + r], v);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2925,7 +2927,8 @@ struct se2gpu_ba {
     DevBuf<uint8_t> garena;        // every uploaded graph array lives in this one allocation (one H2D copy)
     DevBuf<int> plan_np, plan_base, plan_key0, plan_key1, plan_idx, plan_hist, plan_offs, plan_out, plan_tsum, plan_toff;  // device plan scratch
     DevBuf<int2> plan_st0, plan_st1;
-    bool odo_fallback = false;
+    bool odo_fallback = false;   // a self loop or a duplicate pair among the PreEdgeSE2 edges: k_odometry / k_reduce_odo
+    bool odo_self_loop = false;  // ... a self loop (i, i) among them: the resident kernel's odometry_edge<> cannot add one
     DevBuf<double> e_uv, e_info, o_meas, o_info;
     DevBuf<double> Hpl, Hpp_e, bp_e, Hll, bl, Dinv, z, Y, Dg, Hpp, bp, Oii, Ojj, Oij, obi, obj;
     DevBuf<double> red_own, xp, part, scal, diag3, Rinv;
@@ -3171,15 +3174,17 @@ __global__ void k_lower_bounds(const int* __restrict__ key, int n, int nq, int* 
     out[q] = lo;
 }
 
-// PreEdgeSE2 pose-pose blocks: at most one per (a, b) block goes through the plan (the host checked: no self loops, no
-// duplicates; otherwise the edges take the k_odometry / k_reduce_odo fallback and this kernel is not launched)
+// PreEdgeSE2 pose-pose blocks: at most one per (a, b) block goes through the plan (blk_odo), and every one is marked in the
+// block pattern the solver's order is chosen from (nz, when there is one).  With self loops or duplicates (odo_fallback) the
+// edges take the k_odometry / k_reduce_odo path instead: then blk_odo is nullptr and stays -1, and only nz is marked - the
+// fallback still adds those blocks to S, and the host plan marks them too
 __global__ void k_plan_odo(int P, int O, const int* __restrict__ o_i, const int* __restrict__ o_j, int* __restrict__ blk_odo,
                            uint8_t* __restrict__ nz) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= O) return;
     const int i = o_i[k], j = o_j[k];
     const int q = blk_index_of(P, min(i, j), max(i, j));
-    blk_odo[q] = 2 * k + (i > j ? 1 : 0);
+    if (blk_odo) blk_odo[q] = 2 * k + (i > j ? 1 : 0);
     if (nz) nz[q] = 1;
 }
 
@@ -3940,10 +3945,11 @@ int ba_upload_graph(se2gpu_ba* h) {
     }
     // PreEdgeSE2 pose-pose blocks: at most one per (a, b) block goes through the plan; self loops / duplicates fall back
     h->odo_fallback = false;
+    h->odo_self_loop = false;
     {
         std::vector<std::pair<int, int>> seen(O);
         for (int k = 0; k < O; ++k) {
-            if (o_i[k] == o_j[k]) h->odo_fallback = true;
+            if (o_i[k] == o_j[k]) h->odo_fallback = h->odo_self_loop = true;
             seen[k] = {std::min(o_i[k], o_j[k]), std::max(o_i[k], o_j[k])};
         }
         std::sort(seen.begin(), seen.end());
@@ -4204,8 +4210,9 @@ int ba_upload_graph(se2gpu_ba* h) {
                                g1, g1 + g2, g1 + g2 + g3, nzp);
         }
         hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, st, h->plan_np.p, h->plan_base.p, L);   // 20 per thread
-        if (O && !h->odo_fallback)
-            hipLaunchKernelGGL(k_plan_odo, grid1(O, 64), dim3(64), 0, st, P, O, h->o_i.p, h->o_j.p, h->blk_odo.p, nzp);
+        if (O && (!h->odo_fallback || nzp))
+            hipLaunchKernelGGL(k_plan_odo, grid1(O, 64), dim3(64), 0, st, P, O, h->o_i.p, h->o_j.p,
+                               h->odo_fallback ? nullptr : h->blk_odo.p, nzp);
         // pose -> edges CSR: edge indices stably sorted by key frame (one pass)
         if (E) SE2_CHECK(radix(h->e_kf.p, h->plan_key0.p, h->plan_idx.p, h->pose_edges.p, (size_t)E, 0, Pb));
         hipLaunchKernelGGL(k_lower_bounds, grid1((size_t)P + 1, 256), dim3(256), 0, st, h->plan_key0.p, E, P, h->pose_ptr.p);
@@ -4526,7 +4533,7 @@ int ba_reduce(se2gpu_ba* h, double lambda, int schur, bool ctl = false) {
                    h->o_meas.p, h->o_info.p, h->poses, h->fixed.p, h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p,
                    (const BaCtl*)nullptr, (const double*)nullptr);
         SE2_LAUNCH(h->prof, st, "k_reduce_odo", k_reduce_odo, grid1((size_t)h->O * 9, 256), dim3(256), 0, h->O, h->ld,
-                   h->o_i.p, h->o_j.p, h->Oij.p, S);
+                   h->o_i.p, h->o_j.p, h->Oij.p, S, (const int*)h->pose_off.p);
     }
     SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
@@ -6103,8 +6110,11 @@ int ba_resident_threads(const se2gpu_ba* h, size_t* lds) {
     }
     return 0;
 }
+// (duplicate odometry pairs are fine there - its adds are atomic and i != j; a self loop is not: odometry_edge<> would put the
+// cross terms A^T W B + B^T W A above the packed triangle's diagonal and never into the key frame's own block)
 bool ba_resident_ok(const se2gpu_ba* h) {
     return h->initialized && h->model == 0 && !h->allreduce && !h->comm && !h->host_solve && !h->prof.enabled && h->d_mail &&
+           !h->odo_self_loop &&
            h->L > 0 && h->P > 0 && (int)h->h_fixed.size() == h->P && h->Hpl.p && h->Hpl.cap * 8 >= (size_t)h->L * 16 + (size_t)h->E * 44 + 16 &&
            h->Dinv.p && h->Dinv.cap >= 6 * (size_t)h->L;
 }

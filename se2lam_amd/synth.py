@@ -694,3 +694,101 @@ def mixed_windows(count: int = 64, p_range=(30, 60), l_range=(3000, 6000), kidna
 
 # (count, seed, window) -> displacement seed whose start rejects trials (oracle trial histories e.g. [1,1,1,1,6,1,...])
 _KIDNAP_SEEDS = {(64, 4242, 5): 13, (64, 4242, 16): 4, (64, 4242, 27): 8, (64, 4242, 38): 2, (64, 4242, 49): 1, (64, 4242, 60): 3}
+
+
+# --------------------------------------------------------------------------
+# Odometry topologies beyond ba_graph's chain (k, k+1): the call surface takes PreEdgeSE2 edges between any two key frames,
+# in either direction - Map::loadLocalGraph links whichever window slots two key frames landed in, LocalMapper re-links odometry
+# across pruned key frames - and the library has separate code for each of the shapes below
+# --------------------------------------------------------------------------
+ODOMETRY_TOPOLOGIES = ("reversed", "shuffled", "long", "hub9", "hub12", "hub20", "fixed_ends", "duplicate", "self_loop",
+                       "duplicate_long")
+
+
+def with_odometry(g: "BAGraph", pairs, seed: int = 0, fixed=None) -> "BAGraph":
+    """A copy of `g` whose PreEdgeSE2 edges are the (i, j) `pairs`, in that order and orientation.  Every measurement and
+    covariance is preintegrated along the true motion from poses_true[i] to poses_true[j] with a generator of its own
+    (seed, edge), so each edge agrees with the ground truth (a self loop measures noise only).  `fixed` replaces the fixed
+    flags when given.  ba_graph's random stream is not touched: g itself and every graph it caches stay as they are."""
+    import copy
+    assert g.poses_true is not None, "the odometry is generated from the true poses"
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    assert pairs.size == 0 or (pairs.min() >= 0 and pairs.max() < g.P), "odometry edge outside the window"
+    O = pairs.shape[0]
+    o_meas, o_info = np.zeros((O, 3)), np.zeros((O, 9))
+    for k, (i, j) in enumerate(pairs):
+        m, c = _preintegrate(np.random.default_rng([seed, k]), g.poses_true[i], g.poses_true[j])
+        # PreEdgeSE2 does not wrap its angle (EdgeSE2XYZ.h:80): an edge across the +-pi seam of the headings measures the
+        # raw difference, as the poses it joins see it
+        dth = g.poses_true[j, 2] - g.poses_true[i, 2]
+        m[2] += dth - _norm_angle(dth)
+        o_meas[k] = m
+        o_info[k] = np.linalg.inv(c).reshape(-1)
+    h = copy.copy(g)
+    h.o_i, h.o_j = pairs[:, 0].astype(np.int32), pairs[:, 1].astype(np.int32)
+    h.o_meas, h.o_info = o_meas, o_info
+    if fixed is not None:
+        h.fixed = np.asarray(fixed, dtype=np.uint8).copy()
+    return h
+
+
+def covisible(g: "BAGraph") -> np.ndarray:
+    """(P, P) bool: key frames a and b observe at least one common landmark (a landmark pair makes block (a, b) of S non-zero)"""
+    M = np.zeros((g.P, g.L), dtype=np.int64)
+    M[np.asarray(g.e_kf), np.asarray(g.e_lm)] = 1
+    return (M @ M.T) > 0
+
+
+def _long_pairs(g: "BAGraph", rng, n: int):
+    """up to `n` pairs (a, b), |a - b| >= 2, of key frames that share no landmark, in mixed orientations"""
+    cov = covisible(g)
+    cand = [(a, b) for a in range(g.P) for b in range(a + 2, g.P) if not cov[a, b]]
+    if not cand:
+        raise ValueError("every two key frames of this window share a landmark: no long odometry edge possible")
+    pick = rng.choice(len(cand), size=min(n, len(cand)), replace=False)
+    return [cand[t] if s % 2 == 0 else cand[t][::-1] for s, t in enumerate(sorted(pick))]
+
+
+def odometry_topology(g: "BAGraph", kind: str, seed: int = 0) -> "BAGraph":
+    """g with the odometry of `kind` (one of ODOMETRY_TOPOLOGIES) instead of the chain (k, k+1):
+        reversed        the chain, every other edge flipped to (k+1, k)
+        shuffled        the chain in a random edge order
+        long            the chain plus 2-4 edges between key frames that share no landmark
+        hubN            the chain plus edges from the middle key frame to distinct others, N at that key frame in all (N > 8:
+                        more than k_reduce2 takes in parallel)
+        fixed_ends      the chain and an edge (P-1, 0) with key frames 0, 1, P/2, P-1 fixed: fixed-free, free-fixed, fixed-fixed
+        duplicate       the chain plus one pair again (a, a+1) and one reversed (b+1, b)
+        self_loop       the chain plus (a, a)
+        duplicate_long  duplicate plus 2-4 long edges"""
+    import zlib
+    P = g.P
+    rng = np.random.default_rng([seed, P, zlib.crc32(kind.encode())])
+    chain = [(k, k + 1) for k in range(P - 1)]
+    fixed = None
+    if kind == "reversed":
+        pairs = [(j, i) if k % 2 else (i, j) for k, (i, j) in enumerate(chain)]
+    elif kind == "shuffled":
+        pairs = [chain[t] for t in rng.permutation(len(chain))]
+    elif kind == "long":
+        pairs = chain + _long_pairs(g, rng, int(rng.integers(2, 5)))
+    elif kind.startswith("hub"):
+        n, h = int(kind[3:]), P // 2
+        others = [t for t in range(P) if abs(t - h) > 1]
+        if n - 2 > len(others):
+            raise ValueError("a hub of %d odometry edges needs more than %d key frames" % (n, P))
+        pick = sorted(rng.choice(others, size=n - 2, replace=False).tolist())
+        pairs = chain + [(h, t) if s % 2 == 0 else (t, h) for s, t in enumerate(pick)]
+    elif kind == "fixed_ends":
+        pairs = chain + [(P - 1, 0)]
+        fixed = np.zeros(P, np.uint8)
+        fixed[[0, 1, P // 2, P - 1]] = 1
+    elif kind in ("duplicate", "duplicate_long"):
+        a, b = P // 3, (2 * P) // 3
+        pairs = chain + [(a, a + 1), (b + 1, b)]
+        if kind == "duplicate_long":
+            pairs += _long_pairs(g, rng, int(rng.integers(2, 5)))
+    elif kind == "self_loop":
+        pairs = chain + [(P // 2, P // 2)]
+    else:
+        raise ValueError("unknown odometry topology %r" % kind)
+    return with_odometry(g, pairs, seed=seed, fixed=fixed)

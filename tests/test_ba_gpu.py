@@ -810,3 +810,106 @@ def test_repeated_optimize_replays_a_graph_with_identical_results(synth):
             runs.append((o.stats["trials_hist"], o.stats["chi2_hist"], o.stats["lambda_hist"]))
         assert runs[0] == runs[1] == runs[2] == runs[3]
         assert runs[4][0] == runs[0][0][:3] and runs[4][1] == runs[0][1][:3]
+
+
+# ---- odometry graphs beyond the chain (synth.odometry_topology): reversed / shuffled / long / hub / fixed-end edges go through
+# the contributor plan (k_plan_odo, d_reduce2's serial tail past 8 edges at a pose); self loops and duplicate pairs
+# (odo_fallback) through k_odometry + k_reduce_odo in synchronous mode.  P = 50 and 200 are solved in a fill-reducing order.
+def _odometry_cases():
+    from se2lam_amd import synth
+    from test_ba_oracle import odometry_cases
+    return odometry_cases(synth, ((8, 60), (21, 800), (50, 3000))) + [(200, 20000, "duplicate_long")]
+
+
+def _odo_graph(synth, P, L, kind):
+    from test_ba_oracle import assert_topology
+    g = synth.odometry_topology(synth.ba_graph(P, L), kind)
+    assert_topology(synth, g, kind)
+    return g
+
+
+@pytest.mark.parametrize("P,L,kind", _odometry_cases())
+def test_odometry_topologies_match_the_oracle(oracle, synth, P, L, kind):
+    """every odometry topology: the reduced system against the oracle, the dense solve against a host Cholesky refined in
+    extended precision (a tile the solve's pattern lost shows up here), 10 LM iterations against the oracle's g2o run"""
+    g = _odo_graph(synth, P, L, kind)
+    o = _opt(g)
+    for lam in (3.0, 40.0):
+        S, bs = o.reduced_system(lam)
+        ref = oracle.ba_reduced_system(g, lam)
+        scale = np.abs(ref["S"]).max()
+        assert np.abs(S - ref["S"]).max() <= 1e-11 * scale, (kind, lam, np.abs(S - ref["S"]).max() / scale)
+        assert np.abs(bs - ref["bs"]).max() <= 1e-11 * np.abs(ref["bs"]).max(), kind
+        c = np.linalg.cholesky(S)
+        solve = lambda r: np.linalg.solve(c.T, np.linalg.solve(c, r))
+        x_ref = solve(bs).astype(np.longdouble)
+        for _ in range(3):
+            x_ref = x_ref + solve((bs.astype(np.longdouble) - S.astype(np.longdouble) @ x_ref).astype(np.float64))
+        x, ok = o.solve(lam)
+        assert ok
+        assert np.abs(x - x_ref.astype(np.float64)).max() <= 1e-9 * np.abs(x_ref).max(), (kind, lam)
+    assert o.optimize(10) == 10
+    p_ref, l_ref, st = oracle.ba_optimize(g, 10, 0)
+    s = o.stats
+    assert s["trials_hist"] == st["trials_hist"], kind
+    assert np.allclose(s["chi2_hist"], st["chi2_hist"], rtol=REL, atol=0), kind
+    assert np.allclose(s["lambda_hist"], st["lambda_hist"], rtol=REL, atol=0), kind
+    assert s["chi2_init"] == pytest.approx(st["chi2_init"], rel=1e-12)
+    poses, _ = o.estimates()
+    _pose_update_close(poses, p_ref, g.poses)
+    f = np.asarray(g.fixed, bool)
+    assert np.array_equal(poses[f], g.poses[f])
+
+
+def test_device_plan_equals_host_plan_on_odometry_topologies(synth, monkeypatch):
+    """test_device_plan_equals_host_plan over the odometry topologies.  With self loops / duplicates the device plan must still
+    mark every odometry block in the pattern the solver's order is chosen from (the host plan does): same order, same tiles.
+    The fallback's odometry blocks are atomic adds, so those windows are compared to rounding, the others bit for bit."""
+    for P, L, kind in [c for c in _odometry_cases() if c[0] >= 21]:
+        g = _odo_graph(synth, P, L, kind)
+        fallback = kind in ("duplicate", "duplicate_long", "self_loop")
+        Sd, bd, sd, (pd_, ld_) = _run_plan(g, None, monkeypatch)
+        Sh, bh, sh, (ph, lh) = _run_plan(g, "host", monkeypatch)
+        if not fallback:
+            assert np.array_equal(Sd, Sh) and np.array_equal(bd, bh), (P, kind)
+            assert sd == sh, (P, kind)
+            assert np.array_equal(pd_, ph) and np.array_equal(ld_, lh), (P, kind)
+            continue
+        assert np.abs(Sd - Sh).max() <= 1e-13 * np.abs(Sh).max() and np.abs(bd - bh).max() <= 1e-13 * np.abs(bh).max(), (P, kind)
+        assert sd["trials_hist"] == sh["trials_hist"], (P, kind)
+        assert np.allclose(sd["chi2_hist"], sh["chi2_hist"], rtol=1e-10, atol=0), (P, kind)
+        assert np.allclose(pd_, ph, rtol=1e-9, atol=1e-9), (P, kind)
+
+
+def test_odometry_topologies_through_optimize_batch(oracle, synth):
+    """the topologies the lock-step path takes (no self loop, no duplicate) in one batch: bit-identical to one-by-one runs; then
+    a batch that also holds the fallback windows (the batch goes window by window): every window equal to its own run and to
+    the oracle"""
+    from se2lam_amd import capi
+    from se2lam_amd.optimizer import optimize_batch
+    plain = [_odo_graph(synth, P, L, k) for P, L, k in _odometry_cases()
+             if P in (21, 50) and k not in ("duplicate", "duplicate_long", "self_loop")]
+    odd = [_odo_graph(synth, P, L, k) for P, L, k in _odometry_cases() if P in (21, 50) and k in ("duplicate", "duplicate_long", "self_loop")]
+    for graphs, path in ((plain, 1), (plain[:3] + odd, 0)):
+        ref = []
+        for g in graphs:
+            o = _opt(g)
+            o.optimize(10)
+            ref.append((o.stats, o.estimates()))
+        opts = [_opt(g) for g in graphs]
+        its = optimize_batch(opts, 10)
+        assert int(capi.lib().se2gpu_ba_last_batch_path()) == path
+        for g, o, (st, (p, l)), n in zip(graphs, opts, ref, its):
+            assert n == st["iterations"]
+            pp, ll = o.estimates()
+            if path == 1:
+                assert o.stats == st, (g.P, g.O)
+                assert np.array_equal(pp, p) and np.array_equal(ll, l), (g.P, g.O)
+            else:     # (the fallback adds its odometry blocks atomically: equal to rounding)
+                assert o.stats["trials_hist"] == st["trials_hist"], (g.P, g.O)
+                assert np.allclose(o.stats["chi2_hist"], st["chi2_hist"], rtol=1e-10, atol=0), (g.P, g.O)
+                assert np.allclose(pp, p, rtol=1e-9, atol=1e-9), (g.P, g.O)
+            p_ref, _, so = oracle.ba_optimize(g, 10, 0)
+            assert o.stats["trials_hist"] == so["trials_hist"]
+            assert np.allclose(o.stats["chi2_hist"], so["chi2_hist"], rtol=REL, atol=0)
+            _pose_update_close(pp, p_ref, g.poses)

@@ -105,8 +105,10 @@ def test_lm_policy_invariants(oracle, synth):
 def test_reduced_system_properties(oracle, synth):
     """S is symmetric, fixed poses are identity rows, S(lambda) grows monotonically on the diagonal,
     and solving the reduced system equals solving the full (un-reduced) normal equations."""
-    g = synth.ba_graph(8, 60)
-    lam = 3.0
+    _reduced_system_equals_full_model(oracle, synth.ba_graph(8, 60), 3.0)
+
+
+def _reduced_system_equals_full_model(oracle, g, lam):
     r = oracle.ba_reduced_system(g, lam)
     S, bs = r["S"], r["bs"]
     assert np.allclose(S, S.T, rtol=1e-12, atol=1e-9)
@@ -114,34 +116,35 @@ def test_reduced_system_properties(oracle, synth):
         for c in range(3):
             row = S[3 * p + c]
             assert row[3 * p + c] == 1.0 and np.count_nonzero(row) == 1 and bs[3 * p + c] == 0.0
-    # full system assembled independently in numpy from oracle edge Jacobians
+    # full system assembled independently in numpy from oracle edge Jacobians: every edge's Jacobian J over the distinct
+    # vertices it touches (a vertex met twice - a self loop - gets the SUM of its two blocks), H += J^T W J, b -= J^T W e
     P, L = g.P, g.L
     N = 3 * P + 3 * L
     H = np.zeros((N, N))
     b = np.zeros(N)
+
+    def add(blocks, W, e, rho1=1.0):
+        cols = {}
+        for c0, Jb in blocks:
+            cols[c0] = cols.get(c0, 0.0) + Jb
+        idx = np.concatenate([np.arange(c0, c0 + 3) for c0 in cols])
+        J = np.concatenate([cols[c0] for c0 in cols], axis=1)
+        H[np.ix_(idx, idx)] += J.T @ (rho1 * W) @ J
+        b[idx] += -rho1 * (J.T @ W @ e)
+
     for k in range(g.E):
         kf, lm = g.e_kf[k], g.e_lm[k]
         e, Jp, Jl = oracle.ba_edge_se2xyz(g, g.poses[kf], g.lms[lm], g.e_uv[k])
         W = np.array([[g.e_info[k, 0], g.e_info[k, 1]], [g.e_info[k, 1], g.e_info[k, 2]]])
         e2 = e @ W @ e
         rho1 = 1.0 if e2 <= g.huber ** 2 else g.huber / np.sqrt(e2)
-        J = np.zeros((2, N))
-        if not g.fixed[kf]:
-            J[:, 3 * kf:3 * kf + 3] = Jp
-        J[:, 3 * P + 3 * lm:3 * P + 3 * lm + 3] = Jl
-        H += J.T @ (rho1 * W) @ J
-        b += -rho1 * (J.T @ W @ e)
+        add(([(3 * kf, Jp)] if not g.fixed[kf] else []) + [(3 * P + 3 * lm, Jl)], W, e, rho1)
     for k in range(g.O):
         i, j = g.o_i[k], g.o_j[k]
         e, Ji, Jj = oracle.ba_edge_pre_se2(g.poses[i], g.poses[j], g.o_meas[k])
-        W = g.o_info[k].reshape(3, 3)
-        J = np.zeros((3, N))
-        if not g.fixed[i]:
-            J[:, 3 * i:3 * i + 3] = Ji
-        if not g.fixed[j]:
-            J[:, 3 * j:3 * j + 3] = Jj
-        H += J.T @ W @ J
-        b += -(J.T @ W @ e)
+        blocks = ([(3 * i, Ji)] if not g.fixed[i] else []) + ([(3 * j, Jj)] if not g.fixed[j] else [])
+        if blocks:
+            add(blocks, g.o_info[k].reshape(3, 3), e)
     H += lam * np.eye(N)
     free = np.ones(N, bool)
     for p in np.nonzero(g.fixed)[0]:
@@ -150,6 +153,99 @@ def test_reduced_system_properties(oracle, synth):
     x_full[free] = np.linalg.solve(H[np.ix_(free, free)], b[free])
     x_red = np.linalg.solve(S, bs)
     assert np.allclose(x_red, x_full[:3 * P], rtol=1e-7, atol=1e-9)
+    # and the pose-pose part itself: S = Hpp - Hpl Hll^-1 Hlp of the independent model, block by block
+    Hf = H[np.ix_(free, free)]
+    nf = int(free[:3 * P].sum())
+    Sm = Hf[:nf, :nf] - Hf[:nf, nf:] @ np.linalg.solve(Hf[nf:, nf:], Hf[nf:, :nf])
+    fp = free[:3 * P]
+    assert np.abs(S[np.ix_(fp, fp)] - Sm).max() <= 1e-9 * np.abs(Sm).max()
+
+
+def odometry_cases(synth, sizes):
+    """(P, L, kind) of every odometry topology that a window of P key frames can hold (a hub of N edges needs N + 1 of them)"""
+    return [(P, L, kind) for P, L in sizes for kind in synth.ODOMETRY_TOPOLOGIES
+            if not (kind.startswith("hub") and int(kind[3:]) + 1 > P)]
+
+
+def assert_topology(synth, g, kind):
+    """the odometry of `g` has the shape synth.odometry_topology(.., kind) claims"""
+    P = g.P
+    oi, oj = np.asarray(g.o_i, np.int64), np.asarray(g.o_j, np.int64)
+    und = sorted(zip(np.minimum(oi, oj).tolist(), np.maximum(oi, oj).tolist()))
+    chain = [(k, k + 1) for k in range(P - 1)]
+    cov = synth.covisible(g)
+    far = [(i, j) for i, j in zip(oi, oj) if abs(i - j) >= 2 and not cov[i, j]]
+    dup = len(set(und)) < len(und)
+    loops = int((oi == oj).sum())
+    if kind == "reversed":
+        assert und == chain and (oi > oj).sum() == (P - 1) // 2 and (oi < oj).any()
+    elif kind == "shuffled":
+        assert und == chain and list(zip(oi.tolist(), oj.tolist())) != chain
+    elif kind in ("long", "duplicate_long"):
+        assert 2 <= len(far) <= 4, far                      # poses that share no landmark: only odometry couples them
+    if kind.startswith("hub"):
+        deg = np.bincount(np.r_[oi, oj], minlength=P)
+        h = int(deg.argmax())
+        nb = set(oj[oi == h].tolist()) | set(oi[oj == h].tolist())
+        assert deg[h] == int(kind[3:]) == len(nb) and h not in nb and (oi == h).any() and (oj == h).any()
+    if kind == "fixed_ends":
+        f = np.asarray(g.fixed, bool)
+        kinds = set(zip(f[oi].tolist(), f[oj].tolist()))
+        assert {(True, False), (False, True), (True, True), (False, False)} <= kinds and f.sum() >= 3
+    if kind in ("duplicate", "duplicate_long"):
+        pairs = list(zip(oi.tolist(), oj.tolist()))
+        assert dup and loops == 0
+        assert any(pairs.count(p) == 2 for p in pairs)                        # one pair twice, same direction
+        assert any(p[0] > p[1] and (p[1], p[0]) in pairs for p in pairs)      # and one as both (a, b) and (b, a)
+    elif kind == "self_loop":
+        k = int(np.nonzero(oi == oj)[0][0])
+        assert loops == 1 and np.abs(g.o_meas[k]).max() > 0
+    else:
+        assert not dup and loops == 0
+
+
+def test_odometry_topologies_reduce_like_the_full_model(oracle, synth):
+    """The oracle's odometry terms (ba_ref.cpp: any (i, j), a self loop included) against the independent numpy model of the
+    full normal equations, over every odometry topology the GPU tests use, at 8 and 21 key frames"""
+    for P, L, kind in odometry_cases(synth, ((8, 60), (21, 800))):
+        g = synth.odometry_topology(synth.ba_graph(P, L), kind)
+        assert_topology(synth, g, kind)
+        for lam in (0.5, 3.0):
+            _reduced_system_equals_full_model(oracle, g, lam)
+
+
+def test_odometry_topology_generator_leaves_ba_graph_alone(synth):
+    """synth.with_odometry draws from generators of its own: ba_graph's output (the benchmark's and the fixtures' windows) and the
+    cached instance are unchanged, every edge agrees with the ground truth"""
+    g = synth.ba_graph(21, 800)
+    before = (g.o_i.copy(), g.o_j.copy(), g.o_meas.copy(), g.o_info.copy(), g.fixed.copy())
+    h = synth.odometry_topology(g, "fixed_ends")
+    assert all(np.array_equal(a, b) for a, b in zip(before, (g.o_i, g.o_j, g.o_meas, g.o_info, g.fixed)))
+    assert synth.ba_graph(21, 800) is g
+    # the chain through with_odometry: same pairs as ba_graph, measurements of the same distribution (not the same draws)
+    c = synth.with_odometry(g, np.c_[g.o_i, g.o_j], seed=5)
+    assert np.array_equal(c.o_i, g.o_i) and np.array_equal(c.o_j, g.o_j)
+    assert np.abs(c.o_meas - g.o_meas).max() < 50.0 and not np.array_equal(c.o_meas, g.o_meas)
+    assert not np.array_equal(h.fixed, g.fixed)
+    # at the true poses every edge's whitened residual is small (measurement noise only)
+    from oracle import oracle
+    for k in range(h.O):
+        e, _, _ = oracle.ba_edge_pre_se2(h.poses_true[h.o_i[k]], h.poses_true[h.o_j[k]], h.o_meas[k])
+        assert e @ h.o_info[k].reshape(3, 3) @ e < 30.0, (k, h.o_i[k], h.o_j[k])
+
+
+def test_pre_edge_se2_self_loop_jacobian(oracle):
+    """e(x, x): the Jacobian of a self loop is Ji + Jj (central differences), which the reduced system must add as ONE block
+    (Ji + Jj)^T W (Ji + Jj) - for PreEdgeSE2 that is zero: the relative motion of a pose to itself does not depend on it"""
+    rng = np.random.default_rng(9)
+    for _ in range(10):
+        x = rng.normal(size=3) * [1000, 1000, 1]
+        z = rng.normal(size=3) * [50, 50, 0.05]
+        e, Ji, Jj = oracle.ba_edge_pre_se2(x, x, z)
+        Jn = _num_jac(lambda p: oracle.ba_edge_pre_se2(p, p, z)[0], x, 1e-5)
+        assert np.allclose(Ji + Jj, Jn, atol=1e-6)
+        assert np.allclose(e, -np.asarray(z), atol=1e-9)
+        assert np.abs(Ji).max() > 0.1 and np.abs(Jj).max() > 0.1    # each half alone is not zero
 
 
 def test_landmark_shards_sum_to_full_system(oracle, synth):

@@ -107,7 +107,7 @@ def test_resident_batch_equals_multi_launch_and_the_oracle(oracle, synth, reside
         assert n == st["iterations"]
         _same(o, st, est, (g.P, g.L))
     assert [r[0]["trials_hist"] for r in ref[7:]] == [c[1] for c in LM_REJECT_CASES]
-    for g, o in list(zip(graphs, opts))[:2] + list(zip(graphs, opts))[7:10]:          # the oracle itself on the small ones
+    for g, o in list(zip(graphs, opts))[:4] + list(zip(graphs, opts))[7:10]:          # the oracle itself, (50, 5000) and (30, 2000) included
         poses, lms, st = oracle.ba_optimize(g, 10, 0)
         assert o.stats["trials_hist"] == st["trials_hist"]
         assert np.allclose(o.stats["chi2_hist"][:10], st["chi2_hist"][:10], rtol=1e-7)
@@ -270,3 +270,103 @@ def test_a_window_without_room_for_the_record_copy_is_left_to_the_other_paths(sy
         _same(o, st, est, "a handle from the pool whose buffer had grown on a larger window before: room after all")
     else:
         assert o.stats == st and np.array_equal(o.estimates()[0], est[0])
+
+
+def _against_the_oracle(oracle, g, o, iters, what):
+    poses, lms, st = oracle.ba_optimize(g, iters, 0)
+    assert o.stats["trials_hist"] == st["trials_hist"], (what, o.stats["trials_hist"], st["trials_hist"])
+    assert np.allclose(o.stats["chi2_hist"][:iters], st["chi2_hist"][:iters], rtol=1e-7), what
+    assert np.allclose(o.estimates()[0], poses, rtol=1e-6, atol=1e-6), what
+
+
+def test_resident_odometry_topologies(oracle, synth, resident):
+    """odometry_edge<> (one thread per PreEdgeSE2, atomic adds into the window's LDS system) on edges that run backwards, arrive
+    in any order, join key frames that share no landmark, meet 9-20 times at one key frame, touch fixed key frames, or repeat a
+    pair in either direction: every window equal to its multi-launch run and to the oracle"""
+    from se2lam_amd import capi
+    from se2lam_amd.optimizer import optimize_batch
+    from test_ba_gpu import _odo_graph
+    cases = [(21, 800, k) for k in ("reversed", "shuffled", "long", "hub9", "hub12", "hub20", "fixed_ends", "duplicate", "duplicate_long")]
+    cases += [(50, 3000, k) for k in ("reversed", "long", "hub12", "fixed_ends")]
+    graphs = [_odo_graph(synth, *c) for c in cases]
+    ref = [_multi_launch(g, 10) for g in graphs]
+    opts = [_opt(g) for g in graphs]
+    its = optimize_batch(opts, 10)
+    assert int(capi.lib().se2gpu_ba_last_batch_path()) == 2
+    for c, g, o, (st, est), n in zip(cases, graphs, opts, ref, its):
+        assert n == st["iterations"]
+        _same(o, st, est, c)
+        _against_the_oracle(oracle, g, o, 10, c)
+
+
+def test_a_self_loop_keeps_the_batch_off_the_resident_path(oracle, synth, resident):
+    """odometry_edge<> cannot add a self loop (i, i): its cross term would land above the diagonal of the packed triangle and
+    never reach the key frame's own block.  Such a window sends the batch to the other paths, even when the resident kernel is
+    forced; every window still equals its multi-launch run and the oracle"""
+    from se2lam_amd import capi
+    from se2lam_amd.optimizer import optimize_batch
+    from test_ba_gpu import _odo_graph
+    graphs = [synth.ba_graph(8, 60), _odo_graph(synth, 21, 800, "self_loop"), _odo_graph(synth, 8, 60, "self_loop")]
+    ref = [_multi_launch(g, 10) for g in graphs]
+    opts = [_opt(g) for g in graphs]
+    optimize_batch(opts, 10)
+    assert int(capi.lib().se2gpu_ba_last_batch_path()) != 2
+    for g, o, (st, est) in zip(graphs, opts, ref):
+        _same(o, st, est, (g.P, g.O))
+        _against_the_oracle(oracle, g, o, 10, (g.P, g.O))
+
+
+def _wide_landmark(synth, k, P=70, L=1500):
+    """a window of P key frames (every fifth one fixed, so that the free ones fit a compute unit's LDS) in which one landmark
+    has exactly k observations: the observations of other landmarks by key frames it is not yet seen from are moved to it"""
+    import copy
+    g = copy.copy(synth.ba_graph(P, L))
+    e_kf, e_lm = np.asarray(g.e_kf).copy(), np.asarray(g.e_lm).copy()
+    seen = set(e_kf[e_lm == 0].tolist())
+    for b in range(1, g.L):
+        if len(seen) >= k:
+            break
+        for t in np.nonzero(e_lm == b)[0]:
+            if len(seen) < k and int(e_kf[t]) not in seen:
+                seen.add(int(e_kf[t]))
+                e_lm[t] = 0
+    assert len(seen) == k
+    keep = np.unique(e_lm)                       # landmarks that lost all their observations leave the graph
+    renum = np.full(g.L, -1, np.int64)
+    renum[keep] = np.arange(len(keep))
+    e_lm = renum[e_lm]
+    g.lms = np.asarray(g.lms)[keep].copy()
+    if g.lms_true is not None:
+        g.lms_true = np.asarray(g.lms_true)[keep].copy()
+    order = np.argsort(e_lm, kind="stable")
+    g.e_kf, g.e_lm = e_kf[order].astype(np.int32), e_lm[order].astype(np.int32)
+    g.e_uv, g.e_info = np.asarray(g.e_uv)[order].copy(), np.asarray(g.e_info)[order].copy()
+    g.fixed = np.asarray(g.fixed).copy()
+    g.fixed[::5] = 1
+    cnt = np.bincount(g.e_lm, minlength=g.L)
+    assert cnt.max() == k and int((cnt == k).sum()) == 1
+    return g
+
+
+def test_a_landmark_of_65_observations_is_refused_and_run_elsewhere(oracle, synth, resident):
+    """BaCtl::error = 2: the kernel takes landmarks of up to 64 observations.  A forced batch with a window that has one of 65:
+    that window is left untouched by the kernel and run on the multi-launch path (bit for bit its own run), the other window
+    keeps its resident result; a landmark of exactly 64 observations stays on the resident path"""
+    from se2lam_amd import capi
+    from se2lam_amd.optimizer import optimize_batch
+    small = synth.ba_graph(21, 800)
+    for k in (65, 64):
+        wide = _wide_landmark(synth, k)
+        graphs = [small, wide]
+        ref = [_multi_launch(g, 8) for g in graphs]
+        opts = [_opt(g) for g in graphs]
+        optimize_batch(opts, 8)
+        assert int(capi.lib().se2gpu_ba_last_batch_path()) == 2
+        _same(opts[0], *ref[0], ("ordinary window next to", k))
+        if k == 65:
+            st, est = ref[1]
+            assert opts[1].stats == st
+            assert np.array_equal(opts[1].estimates()[0], est[0]) and np.array_equal(opts[1].estimates()[1], est[1])
+        else:
+            _same(opts[1], *ref[1], k)
+        _against_the_oracle(oracle, wide, opts[1], 8, k)
