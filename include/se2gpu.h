@@ -331,8 +331,9 @@ int se2gpu_ba_optimize(se2gpu_ba* h, int iters, int mode, const volatile uint8_t
 /* optimize(iters) of `count` independent windows at once - one initialised handle per window, each on its own stream.
  * The Levenberg-Marquardt controller of every window runs on the device, so all windows are enqueued before the first
  * wait and the GPU works on them concurrently (a 50-KF local window occupies a few per cent of an MI355X).  This is the
- * throughput form for a mapper that keeps several local windows (or several robots' maps) in flight; results are
- * identical to calling se2gpu_ba_optimize on every handle in turn.  stats: NULL or `count` entries. */
+ * throughput form for a mapper that keeps several local windows (or several robots' maps) in flight; results are those
+ * of calling se2gpu_ba_optimize on every handle in turn - bit for bit on paths 0 and 1, equal to rounding on the resident
+ * path 2 (see se2gpu_ba_last_batch_path).  stats: NULL or `count` entries. */
 int se2gpu_ba_optimize_batch(se2gpu_ba** handles, int count, int iters, int mode, const volatile uint8_t* stop_flag,
                              se2gpu_ba_stats* stats);
 /* Which of its three paths the calling thread's last se2gpu_ba_optimize_batch took (-1: none yet): 0 = one stream per window,

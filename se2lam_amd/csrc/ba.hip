@@ -3813,7 +3813,7 @@ int ba_copy_stream(int device, hipStream_t* out) {
 int ba_allreduce(se2gpu_ba* h, double* ptr, size_t count);
 
 int ba_upload_graph(se2gpu_ba* h) {
-    static const bool trace = [] { const char* e = getenv("SE2GPU_BA_INIT_TRACE"); return e && e[0] == '1'; }();
+    static const bool trace = env_flag("SE2GPU_BA_INIT_TRACE", false);
     const auto t_begin = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (trace)
@@ -3958,8 +3958,7 @@ int ba_upload_graph(se2gpu_ba* h) {
     }
     const int nblk = P * (P + 1) / 2;
     h->nblk = nblk;
-    const char* plan_env = getenv("SE2GPU_BA_PLAN");
-    const bool device_plan = P <= 1024 && !(plan_env && std::strcmp(plan_env, "host") == 0);
+    const bool device_plan = P <= 1024 && !env_is("SE2GPU_BA_PLAN", "host");
     lap("edge check + odometry");
     HostPlan pl;
     if (!device_plan) {
@@ -4058,10 +4057,7 @@ int ba_upload_graph(se2gpu_ba* h) {
     SE2_CHECK(h->ctl.reserve(1));
     h->ld = ((n + 1 + kNB - 1) / kNB) * kNB;
     const size_t nred = (size_t)h->ld * h->ld + 4;
-    {
-        const char* env = getenv("SE2GPU_BA_HOST_SOLVE");
-        h->host_solve = env && env[0] == '1';
-    }
+    h->host_solve = env_flag("SE2GPU_BA_HOST_SOLVE", false);
     if (h->ar_buffer) {
         h->red = (double*)h->ar_buffer;
     } else {
@@ -4071,7 +4067,7 @@ int ba_upload_graph(se2gpu_ba* h) {
     if (h->host_solve) SE2_CHECK(h->h_red.reserve(nred));
     SE2_CHECK(h->Rinv.reserve(chol_work_doubles(h->ld)));
     // (the tile tasks of the solve are planned after the block pattern is known: ba_setup_solver, below)
-    static const bool nd_env = [] { const char* e = getenv("SE2GPU_BA_ND"); return !(e && e[0] == '0'); }();
+    static const bool nd_env = env_flag("SE2GPU_BA_ND", true);
     // (a sharded run can re-order too: every rank must choose the SAME order, so the ranks' block patterns - each sees its own
     // landmarks' pairs only - are merged by one small all-reduce below; a caller-owned exchange buffer keeps the natural
     // layout it was sized for)
@@ -4355,7 +4351,7 @@ int ba_upload_graph(se2gpu_ba* h) {
         SE2_HIP(hipMemsetAsync(h->chol_flags.p, 0, 2 * kSlabs * (size_t)nt2 * nbc2 * sizeof(unsigned), st));   // flags = 0 = "no epoch yet"
         SE2_CHECK(h->chol_head.reserve(1));
         SE2_HIP(hipMemsetAsync(h->chol_head.p, 0, sizeof(unsigned long long), st));
-        static const bool verify = [] { const char* e = getenv("SE2GPU_BA_CHOL_VERIFY"); return e && e[0] == '1'; }();
+        static const bool verify = env_flag("SE2GPU_BA_CHOL_VERIFY", false);
         if (verify) {
             const size_t words = kVfyChk + 2 * 2 * kSlabs * (size_t)nt2 * nbc2;
             SE2_CHECK(h->chol_vfy.reserve(words));
@@ -4363,10 +4359,8 @@ int ba_upload_graph(se2gpu_ba* h) {
         } else {
             h->chol_vfy.release();
         }
-        const char* env = getenv("SE2GPU_BA_CHOL");
-        h->chol_steps = (env && std::strcmp(env, "steps") == 0) || nt2 > 64 || h->chol_fallback;
-        const char* tr = getenv("SE2GPU_BA_CHOL_TRACE");
-        if (tr && tr[0] == '1') {
+        h->chol_steps = env_is("SE2GPU_BA_CHOL", "steps") || nt2 > 64 || h->chol_fallback;
+        if (env_flag("SE2GPU_BA_CHOL_TRACE", false)) {
             SE2_CHECK(h->chol_trace.reserve(16 * (size_t)h->chol_ntask));
             SE2_HIP(hipMemsetAsync(h->chol_trace.p, 0, 16 * (size_t)h->chol_ntask * sizeof(long long), st));
         }
@@ -4397,15 +4391,25 @@ int ba_upload_graph(se2gpu_ba* h) {
 // estimate buffer, lambda and whether it has anything to do from the block; "a"/"b" buffers are passed in fixed order)
 // and without (c = nullptr: explicit lambda, h->poses / h->lms are the estimate) for the synchronous entry points
 // (se2gpu_ba_chi2, the debug_* introspection).
-// work enqueued for this handle on a batch stream (se2gpu_ba_reset_estimates_batch) comes first
-inline int ba_join(se2gpu_ba* h) {
+// What is still pending for the handle comes before the next work on stream `st`: a batched reset on another stream
+// (join_event) and, when `st` is not the handle's own stream, the copies se2gpu_ba_reset_estimates left there (own_pending;
+// ordered through the caller's event *ev, created here on first use).  (On the handle's own stream they come first anyway:
+// own_pending then stays set until ba_run_finish.)
+int ba_join(se2gpu_ba* h, hipStream_t st, hipEvent_t* ev) {
     if (h->join_event) {
-        if (h->join_stream != h->stream) SE2_HIP(hipStreamWaitEvent(h->stream, h->join_event, 0));
+        if (h->join_stream != st) SE2_HIP(hipStreamWaitEvent(st, h->join_event, 0));
         h->join_event = nullptr;
         h->join_stream = nullptr;
     }
+    if (h->own_pending && h->stream != st) {
+        if (!*ev) SE2_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        SE2_HIP(hipEventRecord(*ev, h->stream));
+        SE2_HIP(hipStreamWaitEvent(st, *ev, 0));
+        h->own_pending = false;
+    }
     return SE2GPU_OK;
 }
+inline int ba_join(se2gpu_ba* h) { return ba_join(h, h->stream, nullptr); }
 struct ResetItem {
     double* dst_p; const double* src_p; unsigned np;
     double* dst_l; const double* src_l; unsigned nl;
@@ -4587,21 +4591,39 @@ int ba_allreduce_system(se2gpu_ba* h) {
     return SE2GPU_OK;
 }
 
-// host side of the mailbox: poll the mapped, coherent buffer until the device has written sequence number `seq`;
-// meanwhile the caller's force-stop flag is mirrored into the word the device reads
-int ba_wait_mail(se2gpu_ba* h, double seq, const volatile uint8_t* stop_flag = nullptr) {
-    volatile double* mb = h->h_mail;
+// host side of the mailbox (the mapped, coherent buffer h_mail)
+const BaCtl* ba_posted(se2gpu_ba* h) { return reinterpret_cast<const BaCtl*>(h->h_mail + 8); }
+// has word `word` reached sequence number `seq`?  A run's earlier slot (first < its number < seq) counts when it posted "done"
+bool ba_mail_at(se2gpu_ba* h, int word, double seq, double first) {
+    const double got = ((volatile double*)h->h_mail)[word];
+    if (got == seq) return true;
+    if (!(got > first && got < seq)) return false;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return ba_posted(h)->done;
+}
+// Polls until ba_mail_at(h, word, seq, first); meanwhile the caller's force-stop flag is mirrored into the word the device
+// reads, of every handle of the batch hs[0 .. count).  After `seconds` the batch's streams are synchronised (that surfaces a
+// device fault, if that is what happened) and the word is looked at once more: `what` (with `window`) is the error.
+int ba_wait_seq(se2gpu_ba* h, int word, double seq, double first, se2gpu_ba* const* hs, int count,
+                const volatile uint8_t* stop_flag, int seconds, const char* what, int window = 0) {
     const auto t0 = std::chrono::steady_clock::now();
-    long spins = 0;
-    while (mb[3] != seq) {
+    for (long spins = 0; !ba_mail_at(h, word, seq, first);) {
         __builtin_ia32_pause();
-        if (stop_flag && *stop_flag) *h->h_stop = 1;
-        if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-            SE2_HIP(hipStreamSynchronize(h->stream));  // surfaces a device fault, if that is what happened
-            SE2_REQUIRE(mb[3] == seq, SE2GPU_ERR_HIP, "the host mailbox was not written");
+        if (stop_flag && *stop_flag)
+            for (int j = 0; j < count; ++j) *hs[j]->h_stop = 1;
+        if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(seconds)) {
+            for (int j = 0; j < count; ++j) SE2_HIP(hipStreamSynchronize(hs[j]->stream));
+            SE2_REQUIRE(ba_mail_at(h, word, seq, first), SE2GPU_ERR_HIP, what, window);
+            break;
         }
     }
     std::atomic_thread_fence(std::memory_order_acquire);
+    return SE2GPU_OK;
+}
+// the result of a synchronous evaluation: sequence number `seq` in word 3, {chi2, scale, fail} in words 0..2
+int ba_wait_mail(se2gpu_ba* h, double seq) {
+    SE2_CHECK(ba_wait_seq(h, 3, seq, seq, &h, 1, nullptr, 20, "the host mailbox was not written"));
+    volatile double* mb = h->h_mail;
     h->h_scal.p[0] = mb[0]; h->h_scal.p[1] = mb[1]; h->h_scal.p[2] = mb[2];
     return SE2GPU_OK;
 }
@@ -4701,7 +4723,7 @@ int ba_solve(se2gpu_ba* h, bool ctl = false) {
         unsigned* flagR = flagA + kSlabs * (size_t)nt * nbc;
         // SE2GPU_BA_CHOL_FAULT=1 (tests): the first dataflow solve of a handle runs without its first task, so that every
         // other task times out - exercises the fallback to k_chol_step in ba_run_step
-        static const bool fault = [] { const char* e = getenv("SE2GPU_BA_CHOL_FAULT"); return e && e[0] == '1'; }();
+        static const bool fault = env_flag("SE2GPU_BA_CHOL_FAULT", false);
         const int skip = (fault && !h->chol_faulted && h->chol_ntask > 1) ? 1 : 0;
         h->chol_faulted = true;
         if (h->chol_vfy.p)
@@ -4955,7 +4977,8 @@ struct BatchPlan {
     bool verify = false;
     std::vector<hipEvent_t> events;
     ~BatchPlan() {
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (hipEvent_t e : events)
+            if (e) (void)hipEventDestroy(e);
     }
     bool matches(se2gpu_ba** h, int count, int it, int md) const {
         if ((int)hs.size() != count || it != iters || md != mode) return false;
@@ -5007,11 +5030,13 @@ struct ResetScratch {
     unsigned long deaths = 0;   // streams_destroyed() when the ring's last event was recorded
 };
 
-// a window the lock-step path can take: SE(2) model, one GPU, device controller, dataflow solve, no per-kernel profile
-bool ba_lockstep_ok(const se2gpu_ba* h) {
-    return h->initialized && h->model == 0 && !h->allreduce && !h->comm && !h->host_solve && !h->chol_steps && !h->odo_fallback &&
-           !h->prof.enabled && h->d_mail && h->L > 0;
+// a window the batched paths (lock step, resident) can take: SE(2) model, one GPU, device controller, solve on the device,
+// no per-kernel profile (se2gpu_ba_profile can switch that on after initialize: every condition here is read per call)
+bool ba_batchable(const se2gpu_ba* h) {
+    return h->initialized && h->model == 0 && !h->allreduce && !h->comm && !h->host_solve && !h->prof.enabled && h->d_mail && h->L > 0;
 }
+// ... and the lock-step path: the dataflow solve (chol_steps: also after its fallback), odometry the block plan carries
+bool ba_lockstep_ok(const se2gpu_ba* h) { return ba_batchable(h) && !h->chol_steps && !h->odo_fallback; }
 
 int ba_build_batch_plan(BatchPlan& bp, se2gpu_ba** hs, int count, int iters, int mode) {
     bp.hs.assign(hs, hs + count);
@@ -5079,11 +5104,7 @@ int ba_build_batch_plan(BatchPlan& bp, se2gpu_ba** hs, int count, int iters, int
     bp.chol.commit(bp.arena); bp.chol_v.commit(bp.arena);
     SE2_CHECK(bp.arena.dev.reserve(bp.arena.host.size()));
     SE2_HIP(hipMemcpyAsync(bp.arena.dev.p, bp.arena.host.data(), bp.arena.host.size(), hipMemcpyHostToDevice, bp.stream));
-    while ((int)bp.events.size() < count) {
-        hipEvent_t e = nullptr;
-        SE2_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        bp.events.push_back(e);
-    }
+    bp.events.resize(count);   // (created by ba_join when needed)
     return SE2GPU_OK;
 }
 
@@ -5129,7 +5150,7 @@ constexpr size_t kPoolMax = 4;
 static std::mutex g_ba_pool_mu;
 static std::vector<se2gpu_ba*> g_ba_pool;
 static bool ba_pool_enabled() {
-    static const bool on = [] { const char* e = getenv("SE2GPU_BA_POOL"); return !(e && e[0] == '0'); }();
+    static const bool on = env_flag("SE2GPU_BA_POOL", true);
     return on;
 }
 }  // namespace
@@ -5677,7 +5698,6 @@ int se2gpu_ba_reset_estimates_batch(se2gpu_ba** hs, int count) {
     Lease<ResetScratch> lease;   // (process-wide pool, never destroyed: see LeasePool)
     ResetScratch* sc = lease.obj;
     hipStream_t st = hs[0]->stream;
-    SE2_CHECK(ba_join(hs[0]));
     // the staging buffer of the previous call may still be read by its copy: the ring's event of that call says when not
     if (sc->next) {
         // (that event sits on the stream of the previous call's first window; if any handle stream has been destroyed since, it
@@ -5694,16 +5714,9 @@ int se2gpu_ba_reset_estimates_batch(se2gpu_ba** hs, int count) {
         ResetItem it{h->poses, h->poses0.p, (unsigned)((size_t)h->ps * h->P), h->lms, h->lms0.p, (unsigned)(3 * (size_t)h->L)};
         sc->host.p[i] = it;
         most = std::max(most, std::max(it.np, it.nl));
-        // a window whose own stream still has work in flight (an optimize that has not been waited for cannot happen: the
-        // optimize entry points return after the controller has posted) is ordered first
-        if (i > 0 && h->stream != st && h->own_pending) {
-            if (h->join_event) SE2_CHECK(ba_join(h));
-            hipEvent_t& e = sc->ring[sc->next++ % 64];
-            if (!e) SE2_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            SE2_HIP(hipEventRecord(e, h->stream));
-            SE2_HIP(hipStreamWaitEvent(st, e, 0));
-        }
-        h->own_pending = false;
+        // what is still enqueued for the window comes first (an optimize that has not been waited for cannot be among it:
+        // the optimize entry points return after the controller has posted)
+        SE2_CHECK(ba_join(h, st, &sc->ring[sc->next++ % 64]));
     }
     SE2_HIP(hipMemcpyAsync(sc->dev.p, sc->host.p, (size_t)count * sizeof(ResetItem), hipMemcpyHostToDevice, st));
     const unsigned gx = std::min(64u, (most + 255) / 256);
@@ -5931,25 +5944,30 @@ int se2gpu_ba_debug_solve(se2gpu_ba* h, double lambda, double* x, int* factor_ok
 namespace {
 
 bool ba_env_sync() {
-    static const bool on = [] { const char* e = getenv("SE2GPU_BA_SYNC"); return e && e[0] == '1'; }();
+    static const bool on = env_flag("SE2GPU_BA_SYNC", false);
     return on;
 }
 
-const BaCtl* ba_posted(se2gpu_ba* h) { return reinterpret_cast<const BaCtl*>(h->h_mail + 8); }
+// the start of every path's run of a handle on stream `st` (`ev`: see ba_join)
+int ba_run_prologue(se2gpu_ba* h, hipStream_t st, hipEvent_t* ev, int iters, int mode, bool sync, const volatile uint8_t* stop_flag) {
+    SE2_CHECK(ba_join(h, st, ev));
+    h->est_valid = false;
+    h->run_mode = mode;
+    h->run_iters = iters;
+    h->run_enqueued = 0;
+    h->run_sync = sync;
+    h->run_active = true;
+    *h->h_stop = (stop_flag && *stop_flag) ? 1 : 0;
+    return SE2GPU_OK;
+}
 
 int ba_run_begin(se2gpu_ba* h, int iters, int mode, const volatile uint8_t* stop_flag, int verbose) {
     SE2_REQUIRE(h && h->initialized, SE2GPU_ERR_STATE, "optimize before initialize");
     SE2_REQUIRE(mode == SE2GPU_BA_LM || mode == SE2GPU_BA_GN, SE2GPU_ERR_INVALID, "unknown mode %d", mode);
     SE2_REQUIRE(h->d_mail, SE2GPU_ERR_STATE, "SE2GPU_BA_MAILBOX=0 is no longer supported: the LM controller posts its state "
                                               "through the mapped mailbox");
-    SE2_CHECK(ba_join(h));
-    h->est_valid = false;
-    h->run_mode = mode;
-    h->run_iters = iters;
-    h->run_enqueued = 0;
-    h->run_sync = ba_env_sync() || h->prof.enabled || verbose || h->odo_fallback || h->host_solve;
-    h->run_active = true;
-    *h->h_stop = (stop_flag && *stop_flag) ? 1 : 0;
+    const bool sync = ba_env_sync() || h->prof.enabled || verbose || h->odo_fallback || h->host_solve;
+    SE2_CHECK(ba_run_prologue(h, h->stream, nullptr, iters, mode, sync, stop_flag));
     const int n0 = h->run_sync ? 1 : std::max(iters, 1);
     auto enqueue_all = [&]() -> int {
         hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(64), 0, h->stream, h->ctl.p, iters, mode);
@@ -5957,7 +5975,7 @@ int ba_run_begin(se2gpu_ba* h, int iters, int mode, const volatile uint8_t* stop
         for (int k = 0; k < n0; ++k) SE2_CHECK(ba_enqueue_trial(h, k == 0, h->run_sync ? 0 : -1, k == n0 - 1, 0.0));
         return SE2GPU_OK;
     };
-    static const bool graphs_on = [] { const char* e = getenv("SE2GPU_BA_GRAPH"); return !(e && e[0] == '0'); }();
+    static const bool graphs_on = env_flag("SE2GPU_BA_GRAPH", true);
     // (a run of zero iterations is an evaluation - se2gpu_ba_chi2 of the SE3 models: one slot, never worth a graph and never
     // allowed to push a real shape out of the cache)
     const bool graphable = graphs_on && !h->run_sync && !h->allreduce && !h->comm && iters > 0;
@@ -6005,30 +6023,10 @@ int ba_run_begin(se2gpu_ba* h, int iters, int mode, const volatile uint8_t* stop
 int ba_run_step(se2gpu_ba* h, bool wait, const volatile uint8_t* stop_flag, int verbose, int* finished) {
     *finished = 0;
     if (stop_flag && *stop_flag) *h->h_stop = 1;
-    if (!wait && ((volatile double*)h->h_mail)[kMailSeq] != h->run_seq) {
-        // an earlier slot may already have posted "done" (Terminate, stop flag): its sequence number is lower
-        const double got = ((volatile double*)h->h_mail)[kMailSeq];
-        if (!(got > h->run_seq - h->run_enqueued && got <= h->run_seq && ba_posted(h)->done)) return SE2GPU_OK;
-    } else if (wait) {
-        volatile double* mb = h->h_mail;
-        const auto t0 = std::chrono::steady_clock::now();
-        long spins = 0;
-        for (;;) {
-            const double got = mb[kMailSeq];
-            if (got == h->run_seq) break;
-            if (got > h->run_seq - h->run_enqueued && got < h->run_seq) {   // an earlier slot of this run posted: done?
-                std::atomic_thread_fence(std::memory_order_acquire);
-                if (ba_posted(h)->done) break;
-            }
-            __builtin_ia32_pause();
-            if (stop_flag && *stop_flag) *h->h_stop = 1;
-            if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30)) {
-                SE2_HIP(hipStreamSynchronize(h->stream));
-                SE2_REQUIRE(mb[kMailSeq] == h->run_seq || ba_posted(h)->done, SE2GPU_ERR_HIP, "the LM controller never reported back");
-                break;
-            }
-        }
-    }
+    // (an earlier slot may already have posted "done" - Terminate, stop flag: its sequence number is lower)
+    const double first = h->run_seq - h->run_enqueued;
+    if (wait) SE2_CHECK(ba_wait_seq(h, kMailSeq, h->run_seq, first, &h, 1, stop_flag, 30, "the LM controller never reported back"));
+    else if (!ba_mail_at(h, kMailSeq, h->run_seq, first)) return SE2GPU_OK;
     std::atomic_thread_fence(std::memory_order_acquire);
     BaCtl c;
     std::memcpy(&c, (const void*)(h->h_mail + 8), sizeof(BaCtl));
@@ -6091,6 +6089,22 @@ int ba_run_finish(se2gpu_ba* h, se2gpu_ba_stats* stats) {
     return SE2GPU_OK;
 }
 
+// The way out of a batched path (resident, lock step) once its windows' runs have begun.  A window still marked active has
+// been left by an error return: its stream - every stream these paths enqueue on is one of their windows' - is waited for
+// before the call's leased argument packs and plans can go back to their pools, and the mark is cleared.  (The normal way
+// out has finished every run: ba_run_finish cleared the marks.)
+struct BatchExit {
+    se2gpu_ba* const* hs;
+    int count;
+    ~BatchExit() {
+        for (int i = 0; i < count; ++i)
+            if (hs[i]->run_active) {
+                (void)hipStreamSynchronize(hs[i]->stream);
+                hs[i]->run_active = false;
+            }
+    }
+};
+
 // ---- optimize() of `count` windows, ONE WORKGROUP PER WINDOW (csrc/ba_window.hip): every window lives in one compute unit's
 // LDS for its whole optimize(iters) - no per-edge records, no launches per trial.  Taken for batches of SE2GPU_BA_RESIDENT_MIN
 // windows or more (default 96: below that the multi-launch paths, which spread a window over the chip, finish a batch sooner)
@@ -6100,6 +6114,7 @@ struct ResidentScratch {
     PinBuf<WindowArgs> host;
     DevBuf<WindowArgs> dev;
     DevBuf<long long> stamps;
+    std::vector<hipEvent_t> events;   // ba_join's, one per window
 };
 int ba_resident_threads(const se2gpu_ba* h, size_t* lds) {
     int nfree = 0;
@@ -6113,27 +6128,22 @@ int ba_resident_threads(const se2gpu_ba* h, size_t* lds) {
 // (duplicate odometry pairs are fine there - its adds are atomic and i != j; a self loop is not: odometry_edge<> would put the
 // cross terms A^T W B + B^T W A above the packed triangle's diagonal and never into the key frame's own block)
 bool ba_resident_ok(const se2gpu_ba* h) {
-    return h->initialized && h->model == 0 && !h->allreduce && !h->comm && !h->host_solve && !h->prof.enabled && h->d_mail &&
-           !h->odo_self_loop &&
-           h->L > 0 && h->P > 0 && (int)h->h_fixed.size() == h->P && h->Hpl.p && h->Hpl.cap * 8 >= (size_t)h->L * 16 + (size_t)h->E * 44 + 16 &&
-           h->Dinv.p && h->Dinv.cap >= 6 * (size_t)h->L;
+    return ba_batchable(h) && !h->odo_self_loop && h->P > 0 && (int)h->h_fixed.size() == h->P && h->Hpl.p &&
+           h->Hpl.cap * 8 >= (size_t)h->L * 16 + (size_t)h->E * 44 + 16 && h->Dinv.p && h->Dinv.cap >= 6 * (size_t)h->L;
 }
 int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const volatile uint8_t* stop_flag,
                          se2gpu_ba_stats* stats, int* handled) {
     *handled = 0;
     // (read per call, not once: a test - or a mapper - can switch the path between two batches)
-    const char* e_on = getenv("SE2GPU_BA_RESIDENT");
-    const char* e_min = getenv("SE2GPU_BA_RESIDENT_MIN");
-    const int env_on = e_on ? atoi(e_on) : -1, env_min = e_min ? atoi(e_min) : 96;
-    if (env_on == 0 || count < 1 || (env_on != 1 && count < env_min) || ba_env_sync() || iters < 0) return SE2GPU_OK;
-    if (mode != SE2GPU_BA_LM && mode != SE2GPU_BA_GN) return SE2GPU_OK;
+    const int env_on = env_int("SE2GPU_BA_RESIDENT", -1), env_min = env_int("SE2GPU_BA_RESIDENT_MIN", 96);
+    if (env_on == 0 || (env_on != 1 && count < env_min)) return SE2GPU_OK;
     // Windows are dealt to (at most) three launches by the widest workgroup their reduced system leaves room for in LDS (512, 256 or
     // 128 threads; a 50-key-frame window takes 512, one of 60 takes 256), each launch on the stream of its first window, the heaviest
     // windows first (workgroups start in index order: the long ones must not be the tail).
     struct Item { int i, threads; size_t lds; };
     std::vector<Item> items((size_t)count);
     for (int i = 0; i < count; ++i) {
-        if (!ba_resident_ok(hs[i]) || hs[i]->device != hs[0]->device) return SE2GPU_OK;
+        if (!ba_resident_ok(hs[i])) return SE2GPU_OK;
         size_t b = 0;
         const int t = ba_resident_threads(hs[i], &b);
         if (!t) return SE2GPU_OK;
@@ -6142,9 +6152,6 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
         if (t < 256 && env_on != 1) return SE2GPU_OK;
         items[(size_t)i] = Item{i, t, b};
     }
-    for (int i = 0; i < count; ++i)
-        for (int j = 0; j < i; ++j)
-            if (hs[i] == hs[j]) return SE2GPU_OK;
     std::stable_sort(items.begin(), items.end(), [&](const Item& a, const Item& b) {
         if (a.threads != b.threads) return a.threads > b.threads;
         return hs[a.i]->E > hs[b.i]->E;
@@ -6154,30 +6161,18 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
     ResidentScratch& rs = *lease.obj;
     SE2_CHECK(rs.host.reserve((size_t)count));
     SE2_CHECK(rs.dev.reserve((size_t)count));
-    static const bool trace = [] { const char* e = getenv("SE2GPU_BA_RESIDENT_TRACE"); return e && e[0] == '1'; }();
+    static const bool trace = env_flag("SE2GPU_BA_RESIDENT_TRACE", false);
     if (trace) SE2_CHECK(rs.stamps.reserve(16 * (size_t)count));
+    if (rs.events.size() < (size_t)count) rs.events.resize((size_t)count);
     std::vector<hipStream_t> class_streams;
     int threads = 0;
     size_t lds = 0;
+    BatchExit exit_guard{hs, count};
     for (int k = 0; k < count; ++k) {
         const int i = items[(size_t)k].i;
         se2gpu_ba* h = hs[i];
         if (k == 0 || items[(size_t)k].threads != items[(size_t)k - 1].threads) class_streams.push_back(h->stream);
-        hipStream_t st = class_streams.back();
-        h->est_valid = false;
-        h->run_mode = mode;
-        h->run_iters = iters;
-        h->run_enqueued = 1;
-        h->run_sync = false;
-        h->run_active = true;
-        *h->h_stop = (stop_flag && *stop_flag) ? 1 : 0;
-        if (h->join_event) {   // a batched reset on another stream ...
-            if (h->join_stream != st) SE2_HIP(hipStreamWaitEvent(st, h->join_event, 0));
-            h->join_event = nullptr;
-            h->join_stream = nullptr;
-        }
-        if (h->stream != st && h->own_pending) SE2_HIP(hipStreamSynchronize(h->stream));   // ... or a reset still enqueued on the window's own stream
-        h->own_pending = false;
+        SE2_CHECK(ba_run_prologue(h, class_streams.back(), &rs.events[(size_t)k], iters, mode, false, stop_flag));
         WindowArgs& a = rs.host.p[k];
         a.cam = h->cam;
         a.P = h->P; a.L = h->L; a.E = h->E; a.O = h->O; a.iters = iters; a.mode = mode;
@@ -6210,23 +6205,13 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
     for (int i = 0; i < count; ++i) {
         hs[i]->dev_seq += 1;
         hs[i]->run_seq = hs[i]->dev_seq;
+        hs[i]->run_enqueued = 1;
     }
     bool refused = false;
     for (int i = 0; i < count; ++i) {
         se2gpu_ba* h = hs[i];
-        volatile double* mb = h->h_mail;
-        const auto t0 = std::chrono::steady_clock::now();
-        long spins = 0;
-        while (mb[kMailSeq] != h->run_seq) {
-            __builtin_ia32_pause();
-            if (stop_flag && *stop_flag)
-                for (int j = 0; j < count; ++j) *hs[j]->h_stop = 1;
-            if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-                for (hipStream_t st : class_streams) SE2_HIP(hipStreamSynchronize(st));
-                SE2_REQUIRE(mb[kMailSeq] == h->run_seq, SE2GPU_ERR_HIP, "window %d of the resident batch never reported back", i);
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        SE2_CHECK(ba_wait_seq(h, kMailSeq, h->run_seq, h->run_seq, hs, count, stop_flag, 60,
+                              "window %d of the resident batch never reported back", i));
         refused |= ba_posted(h)->error == 2;
     }
     for (hipStream_t st : class_streams) SE2_HIP(hipStreamSynchronize(st));   // (the argument packs are leased: nothing of this call may be in flight when they go back)
@@ -6262,21 +6247,15 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
 int ba_optimize_lockstep(se2gpu_ba** hs, int count, int iters, int mode, const volatile uint8_t* stop_flag,
                          se2gpu_ba_stats* stats, int* handled) {
     *handled = 0;
-    static const bool on = [] { const char* e = getenv("SE2GPU_BA_LOCKSTEP"); return !(e && e[0] == '0'); }();
-    static const bool graphs_on = [] { const char* e = getenv("SE2GPU_BA_GRAPH"); return !(e && e[0] == '0'); }();
-    (void)graphs_on;
-    if (!on || count < 2 || ba_env_sync() || iters < 0) return SE2GPU_OK;
-    if (mode != SE2GPU_BA_LM && mode != SE2GPU_BA_GN) return SE2GPU_OK;
+    static const bool on = env_flag("SE2GPU_BA_LOCKSTEP", true);
+    if (!on || count < 2) return SE2GPU_OK;
     for (int i = 0; i < count; ++i)
-        if (!ba_lockstep_ok(hs[i]) || hs[i]->device != hs[0]->device) return SE2GPU_OK;
-    for (int i = 0; i < count; ++i)
-        for (int j = 0; j < i; ++j)
-            if (hs[i] == hs[j]) return SE2GPU_OK;
+        if (!ba_lockstep_ok(hs[i])) return SE2GPU_OK;
     *handled = 1;
     // Groups: the windows are dealt to a few groups, each in lock step on a stream of its own, slot by slot in turn - while
     // one group's dataflow solves wait on their chains (latency: the chip is nearly idle) the other groups' linearisation
     // and reduction (bandwidth / issue bound) run beside them.  SE2GPU_BA_BATCH_GROUPS overrides (1 = one stream).
-    static const int env_groups = [] { const char* e = getenv("SE2GPU_BA_BATCH_GROUPS"); return e ? atoi(e) : 0; }();
+    static const int env_groups = env_int("SE2GPU_BA_BATCH_GROUPS", 0);
     int G = env_groups > 0 ? env_groups : (count >= 4 ? 2 : 1);   // (two groups pay from four windows on: 4 / 8 / 12 windows +4 / +12 / +9 %)
     if (env_groups <= 0 && count >= 6) {
         // windows of different sizes: a third group.  In lock step a slot lasts as long as its group's slowest window, and
@@ -6337,29 +6316,11 @@ int ba_optimize_lockstep(se2gpu_ba** hs, int count, int iters, int mode, const v
         SE2_CHECK(acquire(ghs_all + b0, b1 - b0, &groups[g].bp, &groups[g].slot, groups));
     }
     // ---- prologue of every window (ba_run_begin) and the order behind whatever was enqueued for it before
+    BatchExit exit_guard{hs, count};
     for (Group& g : groups) {
-        hipStream_t st = g.bp->stream;
-        for (int i = 0; i < g.count; ++i) {
-            se2gpu_ba* h = g.hs[i];
-            h->est_valid = false;
-            h->run_mode = mode;
-            h->run_iters = iters;
-            h->run_enqueued = 0;
-            h->run_sync = false;
-            h->run_active = true;
-            *h->h_stop = (stop_flag && *stop_flag) ? 1 : 0;
-            if (h->join_event) {   // a batched reset on another stream ...
-                if (h->join_stream != st) SE2_HIP(hipStreamWaitEvent(st, h->join_event, 0));
-                h->join_event = nullptr;
-                h->join_stream = nullptr;
-            }
-            if (h->stream != st && h->own_pending) {   // ... or copies of se2gpu_ba_reset_estimates on the window's own stream
-                SE2_HIP(hipEventRecord(g.bp->events[i], h->stream));
-                SE2_HIP(hipStreamWaitEvent(st, g.bp->events[i], 0));
-            }
-            h->own_pending = false;
-        }
-        g.bp->ctl_init.launch(g.bp->arena, st);
+        for (int i = 0; i < g.count; ++i)
+            SE2_CHECK(ba_run_prologue(g.hs[i], g.bp->stream, &g.bp->events[i], iters, mode, false, stop_flag));
+        g.bp->ctl_init.launch(g.bp->arena, g.bp->stream);
     }
     const int n0 = std::max(iters, 1);
     for (int k = 0; k < n0; ++k)
@@ -6377,19 +6338,8 @@ int ba_optimize_lockstep(se2gpu_ba** hs, int count, int iters, int mode, const v
             int more = 0;
             for (int i = 0; i < g.count; ++i) {
                 se2gpu_ba* h = g.hs[i];
-                volatile double* mb = h->h_mail;
-                const auto t0 = std::chrono::steady_clock::now();
-                long spins = 0;
-                while (mb[kMailSeq] != h->run_seq) {
-                    __builtin_ia32_pause();
-                    if (stop_flag && *stop_flag)
-                        for (int j = 0; j < count; ++j) *hs[j]->h_stop = 1;
-                    if ((++spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30)) {
-                        SE2_HIP(hipStreamSynchronize(st));
-                        SE2_REQUIRE(mb[kMailSeq] == h->run_seq, SE2GPU_ERR_HIP, "window %d of the batch never reported back", i);
-                    }
-                }
-                std::atomic_thread_fence(std::memory_order_acquire);
+                SE2_CHECK(ba_wait_seq(h, kMailSeq, h->run_seq, h->run_seq, hs, count, stop_flag, 30,
+                                      "window %d of the batch never reported back", i));
                 BaCtl c;
                 std::memcpy(&c, (const void*)(h->h_mail + 8), sizeof(BaCtl));
                 if (c.error) {
@@ -6468,13 +6418,22 @@ int se2gpu_ba_optimize_batch(se2gpu_ba** hs, int count, int iters, int mode, con
     // A local window is a dozen launches per LM iteration; one host thread enqueues ~0.3 M launches per second, which is
     // what bounds many small windows in flight.  The windows are therefore dealt to a few enqueue threads (each window
     // stays on one thread: a handle is not thread-safe, its stream is its own).  SE2GPU_BA_BATCH_THREADS overrides.
-    {   // one workgroup per window for its whole optimize(), when the batch is large enough to fill compute units that way
+    // The batched paths take distinct windows on one device, a known mode and the asynchronous controller; each of them then
+    // asks what it needs of every window (ba_resident_ok, ba_lockstep_ok).
+    bool batched = count > 0 && iters >= 0 && (mode == SE2GPU_BA_LM || mode == SE2GPU_BA_GN) && !ba_env_sync();
+    for (int i = 0; batched && i < count; ++i) batched = hs[i]->device == hs[0]->device;
+    if (batched) {
+        std::vector<se2gpu_ba*> sorted(hs, hs + count);
+        std::sort(sorted.begin(), sorted.end());
+        batched = std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+    }
+    if (batched) {   // one workgroup per window for its whole optimize(), when the batch is large enough to fill compute units that way
         int handled = 0;
         const int rc = ba_optimize_resident(hs, count, iters, mode, stop_flag, stats, &handled);
         if (handled) t_last_batch_path = 2;
         if (handled || rc != SE2GPU_OK) return rc;
     }
-    {   // one launch per stage for all windows, when every window qualifies (model 0, one GPU, dataflow solve)
+    if (batched) {   // one launch per stage for all windows, when every window qualifies (model 0, one GPU, dataflow solve)
         int handled = 0;
         const int rc = ba_optimize_lockstep(hs, count, iters, mode, stop_flag, stats, &handled);
         if (handled) t_last_batch_path = 1;
@@ -6486,7 +6445,7 @@ int se2gpu_ba_optimize_batch(se2gpu_ba** hs, int count, int iters, int mode, con
     // event ("dependency created on uncaptured work in another stream" - found by tools/soak_fresh.sh, round 4: 91 of 130
     // per-stream batches after a batched reset).
     for (int i = 0; i < count; ++i) SE2_CHECK(ba_join(hs[i]));
-    static const int env_threads = [] { const char* e = getenv("SE2GPU_BA_BATCH_THREADS"); return e ? atoi(e) : 0; }();
+    static const int env_threads = env_int("SE2GPU_BA_BATCH_THREADS", 0);
     int nthr = env_threads > 0 ? env_threads : 8;
     nthr = std::max(1, std::min(nthr, count / 4));
     if (nthr <= 1) return ba_optimize_group(hs, count, iters, mode, stop_flag, stats);

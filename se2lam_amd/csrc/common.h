@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -19,6 +20,21 @@ bool have_device();
 int comm_allreduce(se2gpu_comm* c, void* dev_ptr, size_t count, void* hip_stream);
 int comm_rank(const se2gpu_comm* c);
 int comm_world(const se2gpu_comm* c);
+
+// The SE2GPU_* environment switches (README) are read through these; an unset variable gives `dflt`.  A flag is on for a
+// value that starts with '1', off for one that starts with '0', `dflt` for anything else; env_is compares the whole value.
+inline bool env_flag(const char* name, bool dflt) {
+    const char* e = std::getenv(name);
+    return e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : dflt;
+}
+inline int env_int(const char* name, int dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
+inline bool env_is(const char* name, const char* value) {
+    const char* e = std::getenv(name);
+    return e && std::strcmp(e, value) == 0;
+}
 
 #define SE2_HIP(expr)                                                                          \
     do {                                                                                       \

@@ -911,7 +911,7 @@ constexpr size_t kPoolMax = 4;
 static std::mutex g_mt_pool_mu;
 static std::vector<se2gpu_matcher*> g_mt_pool;
 static bool mt_pool_enabled() {
-    static const bool on = [] { const char* e = std::getenv("SE2GPU_MATCHER_POOL"); return !(e && e[0] == '0'); }();
+    static const bool on = env_flag("SE2GPU_MATCHER_POOL", true);
     return on;
 }
 }  // namespace

@@ -2188,7 +2188,7 @@ int orb_run(se2gpu_orb* h, const uint8_t* d_imgs, int pitch, int nframes, se2gpu
     // its own stream and the score and blur launches of level l start as soon as level l exists, instead of after the
     // whole pyramid - the score and blur kernels are VALU-bound and fill the gaps of the resize chain.  A single frame
     // (the tracking thread's call) keeps the short serial sequence: there the extra launches would cost more than they hide.
-    static const int pipe_min = [] { const char* e = std::getenv("SE2GPU_ORB_PIPELINE_MIN"); return e ? std::atoi(e) : 16; }();
+    static const int pipe_min = env_int("SE2GPU_ORB_PIPELINE_MIN", 16);
     const bool piped = !h->prof.enabled && nframes >= pipe_min;
     if (piped && !h->pyr_stream) {
         SE2_HIP(hipStreamCreateWithFlags(&h->pyr_stream, hipStreamNonBlocking));
@@ -2367,13 +2367,12 @@ int se2gpu_orb_create(const se2gpu_orb_params* params, se2gpu_orb** out) {
         return SE2GPU_ERR_HIP;
     }
     h->stream = h->own_stream;
-    if (const char* e = std::getenv("SE2GPU_ORB_SCORE"))
-        h->score_mode = std::strcmp(e, "dense") == 0 ? 1 : (std::strcmp(e, "sparse") == 0 ? 2 : 0);
+    h->score_mode = env_is("SE2GPU_ORB_SCORE", "dense") ? 1 : env_is("SE2GPU_ORB_SCORE", "sparse") ? 2 : 0;
     // The side stream is created here, right after the handle's own stream, and not on first use: streams land on the
     // device's few hardware queues in creation order, and a side stream that ends up on the queue of its own handle's main
     // stream (or of another handle's) overlaps nothing - measured: 154k instead of 165k frames/s with two handles in flight.
     // SE2GPU_ORB_SIDE_STREAM=0: no side stream (callers that keep three or more batches in flight, one queue per handle).
-    static const bool side_on = [] { const char* e = std::getenv("SE2GPU_ORB_SIDE_STREAM"); return !(e && e[0] == '0'); }();
+    static const bool side_on = env_flag("SE2GPU_ORB_SIDE_STREAM", true);
     if ((side_on && hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking) != hipSuccess) ||
         hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
