@@ -333,13 +333,15 @@ int se2gpu_ba_optimize(se2gpu_ba* h, int iters, int mode, const volatile uint8_t
  * wait and the GPU works on them concurrently (a 50-KF local window occupies a few per cent of an MI355X).  This is the
  * throughput form for a mapper that keeps several local windows (or several robots' maps) in flight; results are those
  * of calling se2gpu_ba_optimize on every handle in turn - bit for bit on paths 0 and 1, equal to rounding on the resident
- * path 2 (see se2gpu_ba_last_batch_path).  stats: NULL or `count` entries. */
+ * path 2 (see se2gpu_ba_last_batch_path).  A batch may mix SE(2) and SE3-expmap windows.  stats: NULL or `count` entries. */
 int se2gpu_ba_optimize_batch(se2gpu_ba** handles, int count, int iters, int mode, const volatile uint8_t* stop_flag,
                              se2gpu_ba_stats* stats);
 /* Which of its three paths the calling thread's last se2gpu_ba_optimize_batch took (-1: none yet): 0 = one stream per window,
- * 1 = lock step (one launch per stage for all windows), 2 = resident (one workgroup per window for its whole optimize():
- * batches of SE2GPU_BA_RESIDENT_MIN = 96 windows or more whose windows fit a compute unit's LDS, csrc/ba_window.hip; its sums
- * are atomic, so its results equal the other paths' to rounding, not to the bit).  SE2GPU_BA_RESIDENT=0 / 1 forces the choice.
+ * 1 = lock step (one launch per stage for all windows; SE(2) windows only), 2 = resident (one workgroup per window for its
+ * whole optimize(): batches of SE2GPU_BA_RESIDENT_MIN = 96 windows or more whose windows fit a compute unit's LDS - SE(2) windows
+ * (csrc/ba_window.hip, up to ~60 free key frames) and SE3-expmap windows (csrc/ba_window3.hip, up to 27 free key frames at 256
+ * threads, 29 at 128), in one batch if need be; pose graphs never; its sums are atomic, so its results equal the other paths' to
+ * rounding, not to the bit).  SE2GPU_BA_RESIDENT=0 / 1 forces the choice.
  * Odometry shapes: a window with a PreEdgeSE2 self loop (i, i) keeps the batch off the resident path, even when it is forced;
  * a self loop or a pair of key frames joined by two PreEdgeSE2 (in either direction) keeps it off the lock-step path (such a
  * window runs in synchronous mode).  Edges in any order and direction, and any number of them at one key frame, are taken. */

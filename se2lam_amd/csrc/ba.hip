@@ -35,6 +35,7 @@
 #include "common.h"
 #include "se3_math.h"
 #include "ba_device.h"
+#include "ba3_device.h"
 #include "ba_window.h"
 
 using namespace se2gpu;
@@ -1975,31 +1976,6 @@ __global__ void k_fill_slots(double* __restrict__ dst, const double* __restrict_
 // [3P g2o 20160424] VertexSE3Expmap, EdgeProjectXYZ2UV, EdgeSE3Expmap, SE3Quat - restated as in oracle/ba3_ref.cpp.
 // =============================================================================================
 constexpr int kGrpPerWG3 = 7;
-struct Cam3 { double f, cx, cy, huber; };
-__device__ __host__ inline int sym6(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }   // r <= c
-
-template <bool JAC>
-__device__ inline void proj3(const Cam3& cam, const double* __restrict__ T, double X0, double X1, double X2, double u, double v,
-                             double& e0, double& e1, double* Jp, double* Jl) {
-    const double x = T[0] * X0 + T[1] * X1 + T[2] * X2 + T[9];
-    const double y = T[3] * X0 + T[4] * X1 + T[5] * X2 + T[10];
-    const double z = T[6] * X0 + T[7] * X1 + T[8] * X2 + T[11];
-    const double zi = 1.0 / z;
-    e0 = u - (x * zi * cam.f + cam.cx);
-    e1 = v - (y * zi * cam.f + cam.cy);
-    if (JAC) {
-        const double f = cam.f, zi2 = zi * zi;
-        const double t02 = -x * zi * f, t12 = -y * zi * f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            Jl[c] = -zi * (f * T[c] + t02 * T[6 + c]);
-            Jl[3 + c] = -zi * (f * T[3 + c] + t12 * T[6 + c]);
-        }
-        Jp[0] = x * y * zi2 * f; Jp[1] = -(1 + (x * x * zi2)) * f; Jp[2] = y * zi * f; Jp[3] = -zi * f; Jp[4] = 0; Jp[5] = x * zi2 * f;
-        Jp[6] = (1 + y * y * zi2) * f; Jp[7] = -x * y * zi2 * f; Jp[8] = -x * zi * f; Jp[9] = 0; Jp[10] = -zi * f; Jp[11] = y * zi2 * f;
-    }
-}
-
 // Dinv-dependent part of one edge: Y = Hpl Dinv and the diagonal record
 __device__ inline void schur_edge3(const double* __restrict__ hh, const double d[6], const double* __restrict__ hp,
                                    const double* __restrict__ bpe, double z0, double z1, double z2,
@@ -5030,13 +5006,14 @@ struct ResetScratch {
     unsigned long deaths = 0;   // streams_destroyed() when the ring's last event was recorded
 };
 
-// a window the batched paths (lock step, resident) can take: SE(2) model, one GPU, device controller, solve on the device,
-// no per-kernel profile (se2gpu_ba_profile can switch that on after initialize: every condition here is read per call)
+// a window the batched paths (lock step, resident) can take: one GPU, device controller, solve on the device, no per-kernel
+// profile (se2gpu_ba_profile can switch that on after initialize: every condition here is read per call).  Which pose models a
+// path takes is its own check (ba_lockstep_ok, ba_resident_ok).
 bool ba_batchable(const se2gpu_ba* h) {
-    return h->initialized && h->model == 0 && !h->allreduce && !h->comm && !h->host_solve && !h->prof.enabled && h->d_mail && h->L > 0;
+    return h->initialized && !h->allreduce && !h->comm && !h->host_solve && !h->prof.enabled && h->d_mail && h->L > 0;
 }
-// ... and the lock-step path: the dataflow solve (chol_steps: also after its fallback), odometry the block plan carries
-bool ba_lockstep_ok(const se2gpu_ba* h) { return ba_batchable(h) && !h->chol_steps && !h->odo_fallback; }
+// ... and the lock-step path: the SE(2) model, the dataflow solve (chol_steps: also after its fallback), odometry the block plan carries
+bool ba_lockstep_ok(const se2gpu_ba* h) { return ba_batchable(h) && h->model == 0 && !h->chol_steps && !h->odo_fallback; }
 
 int ba_build_batch_plan(BatchPlan& bp, se2gpu_ba** hs, int count, int iters, int mode) {
     bp.hs.assign(hs, hs + count);
@@ -6105,31 +6082,38 @@ struct BatchExit {
     }
 };
 
-// ---- optimize() of `count` windows, ONE WORKGROUP PER WINDOW (csrc/ba_window.hip): every window lives in one compute unit's
-// LDS for its whole optimize(iters) - no per-edge records, no launches per trial.  Taken for batches of SE2GPU_BA_RESIDENT_MIN
-// windows or more (default 96: below that the multi-launch paths, which spread a window over the chip, finish a batch sooner)
-// whose windows all fit (SE(2) model, one GPU, at most ~60 free key frames, no landmark with more than 64 observations).
+// ---- optimize() of `count` windows, ONE WORKGROUP PER WINDOW (csrc/ba_window.hip: SE(2) model, csrc/ba_window3.hip: SE3-expmap
+// model): every window lives in one compute unit's LDS for its whole optimize(iters) - no per-edge records, no launches per trial.
+// Taken for batches of SE2GPU_BA_RESIDENT_MIN windows or more (default 96: below that the multi-launch paths, which spread a
+// window over the chip, finish a batch sooner) whose windows all fit (one GPU, at most ~60 free key frames of the SE(2) model or
+// ~29 of the SE3 one, no landmark with more than 64 observations).  A batch may mix the two models: one launch per (model, width).
 // SE2GPU_BA_RESIDENT=0 switches the path off, =1 takes it for any batch.  *handled = 0: the caller goes on to the other paths.
 struct ResidentScratch {
     PinBuf<WindowArgs> host;
     DevBuf<WindowArgs> dev;
+    PinBuf<Window3Args> host3;
+    DevBuf<Window3Args> dev3;
     DevBuf<long long> stamps;
     std::vector<hipEvent_t> events;   // ba_join's, one per window
 };
 int ba_resident_threads(const se2gpu_ba* h, size_t* lds) {
     int nfree = 0;
     for (int p = 0; p < h->P; ++p) nfree += h->h_fixed[p] ? 0 : 1;
-    for (int t : {512, 256, 128}) {
-        const size_t b = ba_window_lds_bytes(h->P, nfree, t);
+    for (int t : {512, 256, 128}) {   // (the SE3 kernel has no 512-thread width: ba_window3_lds_bytes says 0)
+        const size_t b = h->model == 1 ? ba_window3_lds_bytes(h->P, nfree, t) : ba_window_lds_bytes(h->P, nfree, t);
         if (b) { *lds = b; return t; }
     }
     return 0;
 }
 // (duplicate odometry pairs are fine there - its adds are atomic and i != j; a self loop is not: odometry_edge<> would put the
 // cross terms A^T W B + B^T W A above the packed triangle's diagonal and never into the key frame's own block)
+// The list of the landmarks (16 B each) and the copy of the observations (44 B each for the SE(2) model, 28 B for the SE3 one) go
+// into the multi-launch path's idle Hpl buffer (9 / 18 doubles per edge), the landmark factors into Dinv (6 per landmark).  The
+// pose graph (model 2) has no landmarks and no resident kernel.
 bool ba_resident_ok(const se2gpu_ba* h) {
-    return ba_batchable(h) && !h->odo_self_loop && h->P > 0 && (int)h->h_fixed.size() == h->P && h->Hpl.p &&
-           h->Hpl.cap * 8 >= (size_t)h->L * 16 + (size_t)h->E * 44 + 16 && h->Dinv.p && h->Dinv.cap >= 6 * (size_t)h->L;
+    const size_t rec = h->model == 1 ? 28 : 44;
+    return ba_batchable(h) && h->model <= 1 && !h->odo_self_loop && h->P > 0 && (int)h->h_fixed.size() == h->P && h->Hpl.p &&
+           h->Hpl.cap * 8 >= (size_t)h->L * 16 + (size_t)h->E * rec + 16 && h->Dinv.p && h->Dinv.cap >= 6 * (size_t)h->L;
 }
 int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const volatile uint8_t* stop_flag,
                          se2gpu_ba_stats* stats, int* handled) {
@@ -6137,10 +6121,10 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
     // (read per call, not once: a test - or a mapper - can switch the path between two batches)
     const int env_on = env_int("SE2GPU_BA_RESIDENT", -1), env_min = env_int("SE2GPU_BA_RESIDENT_MIN", 96);
     if (env_on == 0 || (env_on != 1 && count < env_min)) return SE2GPU_OK;
-    // Windows are dealt to (at most) three launches by the widest workgroup their reduced system leaves room for in LDS (512, 256 or
-    // 128 threads; a 50-key-frame window takes 512, one of 60 takes 256), each launch on the stream of its first window, the heaviest
-    // windows first (workgroups start in index order: the long ones must not be the tail).
-    struct Item { int i, threads; size_t lds; };
+    // Windows are dealt to launches by model and by the widest workgroup their reduced system leaves room for in LDS (512, 256 or
+    // 128 threads; a 50-key-frame SE(2) window takes 512, one of 60 takes 256; SE3 windows take 256 or 128), each launch on the stream
+    // of its first window, the heaviest windows first (workgroups start in index order: the long ones must not be the tail).
+    struct Item { int i, threads, model; size_t lds; };
     std::vector<Item> items((size_t)count);
     for (int i = 0; i < count; ++i) {
         if (!ba_resident_ok(hs[i])) return SE2GPU_OK;
@@ -6150,17 +6134,21 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
         // (a window that only fits the 128-thread workgroup - 61 free key frames and up - takes twice as long here as the whole
         // batch takes on the lock-step path: a batch that holds one is left to the other paths unless this one is forced)
         if (t < 256 && env_on != 1) return SE2GPU_OK;
-        items[(size_t)i] = Item{i, t, b};
+        items[(size_t)i] = Item{i, t, hs[i]->model, b};
     }
     std::stable_sort(items.begin(), items.end(), [&](const Item& a, const Item& b) {
         if (a.threads != b.threads) return a.threads > b.threads;
+        if (a.model != b.model) return a.model > b.model;
         return hs[a.i]->E > hs[b.i]->E;
     });
+    auto same_class = [&](int k0, int k1) { return items[(size_t)k0].threads == items[(size_t)k1].threads && items[(size_t)k0].model == items[(size_t)k1].model; };
     static std::mutex launch_mu;   // (hipFuncSetAttribute inside the launcher)
     Lease<ResidentScratch> lease;
     ResidentScratch& rs = *lease.obj;
     SE2_CHECK(rs.host.reserve((size_t)count));
     SE2_CHECK(rs.dev.reserve((size_t)count));
+    SE2_CHECK(rs.host3.reserve((size_t)count));
+    SE2_CHECK(rs.dev3.reserve((size_t)count));
     static const bool trace = env_flag("SE2GPU_BA_RESIDENT_TRACE", false);
     if (trace) SE2_CHECK(rs.stamps.reserve(16 * (size_t)count));
     if (rs.events.size() < (size_t)count) rs.events.resize((size_t)count);
@@ -6171,8 +6159,25 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
     for (int k = 0; k < count; ++k) {
         const int i = items[(size_t)k].i;
         se2gpu_ba* h = hs[i];
-        if (k == 0 || items[(size_t)k].threads != items[(size_t)k - 1].threads) class_streams.push_back(h->stream);
+        if (k == 0 || !same_class(k, k - 1)) class_streams.push_back(h->stream);
         SE2_CHECK(ba_run_prologue(h, class_streams.back(), &rs.events[(size_t)k], iters, mode, false, stop_flag));
+        if (h->model == 1) {
+            Window3Args& a = rs.host3.p[k];
+            a.cam = h->cam3;
+            a.P = h->P; a.L = h->L; a.E = h->E; a.O = h->O; a.iters = iters; a.mode = mode;
+            a.lm_ptr = h->lm_ptr.p; a.e_kf = h->e_kf.p; a.e_uv = h->e_uv.p; a.e_info = h->e_info.p;
+            a.poses_a = h->poses_a.p; a.poses_b = h->poses_b.p; a.lms_a = h->lms_a.p; a.lms_b = h->lms_b.p;
+            a.fixed = h->fixed.p;
+            a.prior_has = h->prior_has.p; a.prior_meas = h->prior_meas.p; a.prior_info = h->prior_info.p;
+            a.o_i = h->o_i.p; a.o_j = h->o_j.p; a.o_meas = h->o_meas.p; a.o_info = h->o_info.p;
+            a.ctl = h->ctl.p;
+            a.mail = h->d_mail;
+            a.stop = h->d_stop;
+            a.desc = reinterpret_cast<int4*>(h->Hpl.p);   // (the multi-launch path's Hpl records: 144 B per edge, idle on this path)
+            a.ainv = h->Dinv.p;
+            a.stamps = trace ? rs.stamps.p + 16 * (size_t)k : nullptr;
+            continue;
+        }
         WindowArgs& a = rs.host.p[k];
         a.cam = h->cam;
         a.P = h->P; a.L = h->L; a.E = h->E; a.O = h->O; a.iters = iters; a.mode = mode;
@@ -6194,10 +6199,15 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
         for (int k0 = 0; k0 < count;) {
             int k1 = k0;
             size_t need = 0;
-            while (k1 < count && items[(size_t)k1].threads == items[(size_t)k0].threads) { need = std::max(need, items[(size_t)k1].lds); ++k1; }
+            while (k1 < count && same_class(k1, k0)) { need = std::max(need, items[(size_t)k1].lds); ++k1; }
             hipStream_t st = class_streams[cs++];
-            SE2_HIP(hipMemcpyAsync(rs.dev.p + k0, rs.host.p + k0, (size_t)(k1 - k0) * sizeof(WindowArgs), hipMemcpyHostToDevice, st));
-            SE2_CHECK(ba_window_launch(rs.dev.p + k0, k1 - k0, items[(size_t)k0].threads, need, st));
+            if (items[(size_t)k0].model == 1) {
+                SE2_HIP(hipMemcpyAsync(rs.dev3.p + k0, rs.host3.p + k0, (size_t)(k1 - k0) * sizeof(Window3Args), hipMemcpyHostToDevice, st));
+                SE2_CHECK(ba_window3_launch(rs.dev3.p + k0, k1 - k0, items[(size_t)k0].threads, need, st));
+            } else {
+                SE2_HIP(hipMemcpyAsync(rs.dev.p + k0, rs.host.p + k0, (size_t)(k1 - k0) * sizeof(WindowArgs), hipMemcpyHostToDevice, st));
+                SE2_CHECK(ba_window_launch(rs.dev.p + k0, k1 - k0, items[(size_t)k0].threads, need, st));
+            }
             if (k0 == 0) { threads = items[0].threads; lds = need; }
             k0 = k1;
         }

@@ -1,6 +1,7 @@
-// One workgroup per local window (csrc/ba_window.hip): the argument pack of a window and the launcher.  csrc/ba.hip fills the packs
+// One workgroup per local window (csrc/ba_window.hip: SE(2), csrc/ba_window3.hip: SE3-expmap): the argument packs and the launchers.  csrc/ba.hip fills the packs
 // from its handles (se2gpu_ba_optimize_batch) - the kernel knows nothing about handles, streams or pools.
 #pragma once
+#include "ba3_device.h"
 #include "ba_device.h"
 #include "common.h"
 
@@ -32,11 +33,44 @@ struct WindowArgs {
     long long* stamps;        // debug: 16 phase time stamps (100 MHz wall clock) of the LAST trial, or NULL
 };
 
+// the SE3-expmap model's window (csrc/ba_window3.hip): poses Tcw as 12 doubles (R row-major, t), isotropic information w I per
+// projection edge, a prior per pose (EdgeSE3ExpmapPrior) and EdgeSE3Expmap odometry edges with 6 x 6 information
+struct Window3Args {
+    badev::Cam3 cam;
+    int P, L, E, O, iters, mode;
+    const int* lm_ptr;        // L + 1: the observation edges are sorted by landmark
+    const int* e_kf;          // E: pose index of an edge
+    const double* e_uv;       // E x 2
+    const double* e_info;     // E x 3 (w: the information is w I)
+    double* poses_a;          // P x 12, the two estimate buffers (BaCtl::sel says which one holds the estimate)
+    double* poses_b;
+    double* lms_a;            // L x 3
+    double* lms_b;
+    const uint8_t* fixed;     // P
+    const uint8_t* prior_has; // P: EdgeSE3ExpmapPrior of a pose (measurement P x 12, information P x 36)
+    const double* prior_meas;
+    const double* prior_info;
+    const int* o_i;           // O: EdgeSE3Expmap (i, j), measurement O x 12, information O x 36
+    const int* o_j;
+    const double* o_meas;
+    const double* o_info;
+    badev::BaCtl* ctl;        // the window's controller block (device)
+    double* mail;             // device address of the window's mapped mailbox, or NULL
+    const int* stop;          // device address of the mapped force-stop word, or NULL
+    int4* desc;               // scratch: the list of the landmarks by their observation counts (L x 16 B), then the observations
+                              // in that order (E x 28 B)
+    double* ainv;             // L x 6 of scratch: every landmark's factor A from the build pass (list order) for the update pass
+    long long* stamps;        // debug: 16 phase time stamps (100 MHz wall clock) of the LAST trial, or NULL
+};
+
 constexpr int kWindowMaxDegree = 64;     // observations of one landmark the kernel takes (a wave per landmark beyond 16)
 
 // dynamic LDS a window of P poses, nfree of them free, needs with `threads` threads per workgroup (0: does not fit 160 KiB)
 size_t ba_window_lds_bytes(int P, int nfree, int threads);
 // count workgroups of `threads` (128, 256 or 512) threads, one per pack; asynchronous on st
 int ba_window_launch(const WindowArgs* d_args, int count, int threads, size_t lds_bytes, hipStream_t st);
+// the same for SE3-expmap windows (csrc/ba_window3.hip)
+size_t ba_window3_lds_bytes(int P, int nfree, int threads);
+int ba_window3_launch(const Window3Args* d_args, int count, int threads, size_t lds_bytes, hipStream_t st);
 
 }  // namespace se2gpu

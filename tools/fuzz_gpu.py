@@ -242,10 +242,15 @@ while time.time() < t_end:
         if not ok:
             fail("bow")
         continue
-    if kind == 11:   # a batch of random windows through the one-workgroup-per-window kernel (csrc/ba_window.hip), each against the oracle
+    if kind == 11:   # a batch of random windows through the one-workgroup-per-window kernels (csrc/ba_window.hip, ba_window3.hip)
+        # SE(2) windows against the oracle; SE3-expmap windows (drawn half the time, up to 28 key frames) against the multi-launch path
         nb = int(rng.integers(1, 7))
         gs, its = [], int(rng.integers(1, 11))
         for _ in range(nb):
+            if rng.random() < 0.5:
+                P = int(rng.integers(3, 29)); nref = int(rng.integers(0, min(4, P - 2) + 1))
+                gs.append(synth.ba3_graph(P, int(rng.integers(2 * P, 30 * P)), nref, seed=int(rng.integers(1, 10**6))))
+                continue
             P = int(rng.integers(2, 61))
             L = int(rng.integers(max(8, P), 30 * P))
             g = synth.ba_graph(P, L, obs_per_lm=float(rng.uniform(2.5, 12.0)), seed=int(rng.integers(1, 10**6)))
@@ -253,18 +258,35 @@ while time.time() < t_end:
                 k = int(rng.integers(1, P))
                 g.poses[k, :2] += rng.normal(0, 400, 2)
             gs.append(g)
-        os.environ["SE2GPU_BA_RESIDENT"] = "1"
-        opts = []
-        for g in gs:
+        def opt_of(g):
             o = SlamOptimizer()
-            o.load(g)
+            if isinstance(g, synth.BA3Graph):
+                op.load_se3_graph(o, g)
+            else:
+                o.load(g)
             o.initializeOptimization(0)
-            opts.append(o)
+            return o
+        os.environ["SE2GPU_BA_RESIDENT"] = "1"
+        opts = [opt_of(g) for g in gs]
         op.optimize_batch(opts, its)
         os.environ.pop("SE2GPU_BA_RESIDENT")
         from se2lam_amd import capi as _capi
         path = int(_capi.lib().se2gpu_ba_last_batch_path())
         for g, o in zip(gs, opts):
+            if isinstance(g, synth.BA3Graph):
+                os.environ["SE2GPU_BA_RESIDENT"] = "0"
+                m = opt_of(g)
+                m.optimize(its)
+                os.environ.pop("SE2GPU_BA_RESIDENT")
+                st, n = m.stats, m.stats["iterations"]
+                ok = o.stats["iterations"] == n and o.stats["trials_hist"][:n] == st["trials_hist"][:n] and \
+                    np.allclose(o.stats["chi2_hist"][:n], st["chi2_hist"][:n], rtol=1e-9) and \
+                    np.allclose(o.estimates()[0], m.estimates()[0], rtol=1e-9, atol=1e-9)
+                print(f"baw3 path {path} P {g.P} L {g.L} E {g.E} iters {its}: trials {o.stats['trials_hist'][:n]} {'ok' if ok else 'MISMATCH'}")
+                if not ok or path != 2:
+                    print(o.stats["chi2_hist"][:n], st["chi2_hist"][:n], st["trials_hist"][:n])
+                    sys.exit(1)
+                continue
             ref = oracle.ba_optimize(g, its)[2]
             n = ref["iterations"]
             got, want = np.array(o.stats["chi2_hist"][:o.stats["iterations"]]), np.array(ref["chi2_hist"][:n])
