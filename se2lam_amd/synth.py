@@ -467,7 +467,7 @@ def plane_motion_prior_np(Tcw, Rbc=RBC, tbc=TBC, xrot=PLANEMOTION_XROT_INFO, yro
 class BA3Graph:
     """poses (P,4,4) Tcw, fixed (P,), lms (L,3), e_kf/e_lm (E,), e_uv (E,2), e_w (E,) = invSigma2,
     has_prior (P,), prior_meas (P,4,4), prior_info (P,6,6), o_i/o_j (O,) (vertex 0 / 1 of EdgeSE3Expmap), o_meas (O,4,4),
-    o_info (O,6,6)."""
+    o_info (O,6,6).  poses_true (P,4,4): the Tcw the measurements were generated from (odometry_topology3 draws other edges from them)."""
     poses: np.ndarray
     fixed: np.ndarray
     lms: np.ndarray
@@ -486,6 +486,7 @@ class BA3Graph:
     cx: float = CX
     cy: float = CY
     huber: float = TH_HUBER
+    poses_true: np.ndarray = None
     P = property(lambda self: int(self.poses.shape[0]))
     L = property(lambda self: int(self.lms.shape[0]))
     E = property(lambda self: int(self.e_kf.shape[0]))
@@ -528,7 +529,7 @@ def ba3_graph(P: int = 50, L: int = 5000, n_ref: int = 0, seed: int = BA_SEED) -
         assert np.linalg.eigvalsh(o_info[k]).min() > 0
     return BA3Graph(poses=poses, fixed=fixed, lms=g.lms.copy(), e_kf=g.e_kf, e_lm=g.e_lm, e_uv=g.e_uv, e_w=e_w,
                     has_prior=has_prior, prior_meas=np.stack([m for m, _ in pm]), prior_info=np.stack([i for _, i in pm]),
-                    o_i=o_i, o_j=o_j, o_meas=o_meas, o_info=o_info)
+                    o_i=o_i, o_j=o_j, o_meas=o_meas, o_info=o_info, poses_true=true)
 
 
 # --------------------------------------------------------------------------
@@ -739,14 +740,38 @@ def covisible(g: "BAGraph") -> np.ndarray:
     return (M @ M.T) > 0
 
 
-def _long_pairs(g: "BAGraph", rng, n: int):
-    """up to `n` pairs (a, b), |a - b| >= 2, of key frames that share no landmark, in mixed orientations"""
+def _long_pairs(g: "BAGraph", rng, n: int, among: int = None):
+    """up to `n` pairs (a, b), |a - b| >= 2, of key frames (the first `among` of them, default all) that share no landmark, in
+    mixed orientations"""
     cov = covisible(g)
-    cand = [(a, b) for a in range(g.P) for b in range(a + 2, g.P) if not cov[a, b]]
+    P = g.P if among is None else among
+    cand = [(a, b) for a in range(P) for b in range(a + 2, P) if not cov[a, b]]
     if not cand:
         raise ValueError("every two key frames of this window share a landmark: no long odometry edge possible")
     pick = rng.choice(len(cand), size=min(n, len(cand)), replace=False)
     return [cand[t] if s % 2 == 0 else cand[t][::-1] for s, t in enumerate(sorted(pick))]
+
+
+def _chain_variant(g, kind: str, rng, n: int):
+    """the pair lists both pose models use, over the first `n` key frames of g: (pairs, key frames to fix or None) for reversed /
+    shuffled / long / hubN / fixed_ends, None for any other kind"""
+    chain = [(k, k + 1) for k in range(n - 1)]
+    if kind == "reversed":
+        return [(j, i) if k % 2 else (i, j) for k, (i, j) in enumerate(chain)], None
+    if kind == "shuffled":
+        return [chain[t] for t in rng.permutation(len(chain))], None
+    if kind == "long":
+        return chain + _long_pairs(g, rng, int(rng.integers(2, 5)), n), None
+    if kind.startswith("hub"):
+        m, h = int(kind[3:]), n // 2
+        others = [t for t in range(n) if abs(t - h) > 1]
+        if m - 2 > len(others):
+            raise ValueError("a hub of %d odometry edges needs more than %d key frames" % (m, n))
+        pick = sorted(rng.choice(others, size=m - 2, replace=False).tolist())
+        return chain + [(h, t) if s % 2 == 0 else (t, h) for s, t in enumerate(pick)], None
+    if kind == "fixed_ends":
+        return chain + [(n - 1, 0)], [0, 1, n // 2, n - 1]
+    return None
 
 
 def odometry_topology(g: "BAGraph", kind: str, seed: int = 0) -> "BAGraph":
@@ -765,23 +790,12 @@ def odometry_topology(g: "BAGraph", kind: str, seed: int = 0) -> "BAGraph":
     rng = np.random.default_rng([seed, P, zlib.crc32(kind.encode())])
     chain = [(k, k + 1) for k in range(P - 1)]
     fixed = None
-    if kind == "reversed":
-        pairs = [(j, i) if k % 2 else (i, j) for k, (i, j) in enumerate(chain)]
-    elif kind == "shuffled":
-        pairs = [chain[t] for t in rng.permutation(len(chain))]
-    elif kind == "long":
-        pairs = chain + _long_pairs(g, rng, int(rng.integers(2, 5)))
-    elif kind.startswith("hub"):
-        n, h = int(kind[3:]), P // 2
-        others = [t for t in range(P) if abs(t - h) > 1]
-        if n - 2 > len(others):
-            raise ValueError("a hub of %d odometry edges needs more than %d key frames" % (n, P))
-        pick = sorted(rng.choice(others, size=n - 2, replace=False).tolist())
-        pairs = chain + [(h, t) if s % 2 == 0 else (t, h) for s, t in enumerate(pick)]
-    elif kind == "fixed_ends":
-        pairs = chain + [(P - 1, 0)]
-        fixed = np.zeros(P, np.uint8)
-        fixed[[0, 1, P // 2, P - 1]] = 1
+    shared = _chain_variant(g, kind, rng, P)
+    if shared is not None:
+        pairs, fix = shared
+        if fix is not None:
+            fixed = np.zeros(P, np.uint8)
+            fixed[fix] = 1
     elif kind in ("duplicate", "duplicate_long"):
         a, b = P // 3, (2 * P) // 3
         pairs = chain + [(a, a + 1), (b + 1, b)]
@@ -792,3 +806,97 @@ def odometry_topology(g: "BAGraph", kind: str, seed: int = 0) -> "BAGraph":
     else:
         raise ValueError("unknown odometry topology %r" % kind)
     return with_odometry(g, pairs, seed=seed, fixed=fixed)
+
+
+# --------------------------------------------------------------------------
+# The same for the SE3-expmap window (pose model 1): EdgeSE3Expmap between any two key frames in either direction, priors on some
+# key frames only.  Duplicate pairs and self loops are refused by se2gpu_ba_add_edge_se3 for this model: they are not kinds.
+# --------------------------------------------------------------------------
+ODOMETRY_TOPOLOGIES3 = ("reversed", "shuffled", "long", "hub9", "hub20", "dense", "fixed_ends", "to_reference", "none",
+                        "sparse_priors")
+DENSE_TERMS = 264    # P + O of a `dense` window: more than the 256 threads of the resident SE3 kernel's wider workgroup
+
+
+def n_local(g: "BA3Graph") -> int:
+    """the local key frames of a BA3Graph come first; the reference key frames (fixed, without a prior) are the rest"""
+    ref = (np.asarray(g.fixed) != 0) & (np.asarray(g.has_prior) == 0)
+    n = g.P
+    while n > 0 and ref[n - 1]:
+        n -= 1
+    return n
+
+
+def with_odometry3(g: "BA3Graph", pairs, seed: int = 0, fixed=None, has_prior=None) -> "BA3Graph":
+    """A copy of `g` whose EdgeSE3Expmap edges are the (i, j) `pairs`, in that order and orientation, each drawn with ba3_graph's
+    formulas - noise on true_j true_i^-1, a positive definite 6x6 information - from a generator of its own (seed, edge).  `fixed`
+    and `has_prior` replace those flags when given.  ba3_graph's random stream is not touched: g and the cached graphs stay as
+    they are."""
+    import copy
+    assert g.poses_true is not None, "the odometry is generated from the true poses"
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    assert pairs.size == 0 or (pairs.min() >= 0 and pairs.max() < g.P), "odometry edge outside the window"
+    O = pairs.shape[0]
+    o_meas, o_info = np.zeros((O, 4, 4)), np.zeros((O, 6, 6))
+    for k, (i, j) in enumerate(pairs):
+        rng = np.random.default_rng([seed, k])
+        noise = se3_exp_np(rng.normal(0, 1.0, 6) * np.array([1e-3, 1e-3, 2e-3, 2.0, 2.0, 2.0]))
+        o_meas[k] = noise @ g.poses_true[j] @ np.linalg.inv(g.poses_true[i])
+        A = np.diag([5e5, 5e5, 2e5, 0.2, 0.2, 0.2]) + 0.05 * np.diag([700, 700, 450, 0.45, 0.45, 0.45]) @ rng.normal(0, 1, (6, 6))
+        o_info[k] = 0.5 * (A + A.T) + np.diag([1e4, 1e4, 1e4, 0.02, 0.02, 0.02])
+        assert np.linalg.eigvalsh(o_info[k]).min() > 0
+    h = copy.copy(g)
+    h.o_i, h.o_j = pairs[:, 0].astype(np.int32), pairs[:, 1].astype(np.int32)
+    h.o_meas, h.o_info = o_meas, o_info
+    if fixed is not None:
+        h.fixed = np.asarray(fixed, dtype=np.uint8).copy()
+    if has_prior is not None:
+        h.has_prior = np.asarray(has_prior, dtype=np.uint8).copy()
+    return h
+
+
+def odometry_topology3(g: "BA3Graph", kind: str, seed: int = 0) -> "BA3Graph":
+    """g with the odometry (and priors) of `kind`, one of ODOMETRY_TOPOLOGIES3, instead of the chain over the local key frames with
+    a prior on each.  Pairs join local key frames unless the kind says otherwise:
+        reversed, shuffled, long, hubN, fixed_ends    as odometry_topology (fixed_ends keeps the priors of the key frames it fixes)
+        dense           the chain plus random local-local and local-reference pairs in both orientations until P + O = DENSE_TERMS
+                        (ValueError when the window has fewer distinct pairs than that)
+        to_reference    the chain plus up to 4 edges between a local and a reference key frame, in both orientations (n_ref > 0)
+        none            no odometry edge at all
+        sparse_priors   the chain; every third free key frame loses its prior, the fixed ones keep theirs"""
+    import zlib
+    P, nL = g.P, n_local(g)
+    rng = np.random.default_rng([seed, P, zlib.crc32(kind.encode()), 3])
+    chain = [(k, k + 1) for k in range(nL - 1)]
+    fixed = has_prior = None
+    if kind == "fixed_ends" and nL < 5:
+        raise ValueError("fixed_ends fixes 4 of the %d local key frames: none would be left free" % nL)
+    shared = _chain_variant(g, kind, rng, nL)
+    if shared is not None:
+        pairs, fix = shared
+        if fix is not None:
+            fixed = np.asarray(g.fixed).copy()
+            fixed[:nL] = 0
+            fixed[fix] = 1
+    elif kind == "dense":
+        cand = [(a, b) for a in range(nL) for b in range(a + 2, P)]            # (a, a + 1), a + 1 < nL, is the chain's
+        cand += [(nL - 1, nL)] if nL < P else []
+        need = DENSE_TERMS - P - len(chain)
+        if need > len(cand):
+            raise ValueError("%d key frames (%d local) have no %d distinct pairs" % (P, nL, DENSE_TERMS - P))
+        pick = sorted(rng.choice(len(cand), size=max(need, 0), replace=False).tolist())
+        pairs = chain + [cand[t] if s % 2 == 0 else cand[t][::-1] for s, t in enumerate(pick)]
+    elif kind == "to_reference":
+        if nL == P:
+            raise ValueError("to_reference needs reference key frames")
+        cand = [(a, b) for a in range(nL) for b in range(nL, P)]
+        pick = sorted(rng.choice(len(cand), size=min(4, len(cand)), replace=False).tolist())
+        pairs = chain + [cand[t] if s % 2 == 0 else cand[t][::-1] for s, t in enumerate(pick)]
+    elif kind == "none":
+        pairs = []
+    elif kind == "sparse_priors":
+        pairs = chain
+        has_prior = np.asarray(g.has_prior).copy()
+        has_prior[np.nonzero(np.asarray(g.fixed) == 0)[0][2::3]] = 0
+    else:
+        raise ValueError("unknown SE3 odometry topology %r" % kind)
+    return with_odometry3(g, pairs, seed=seed, fixed=fixed, has_prior=has_prior)

@@ -127,8 +127,9 @@ class BA3ProblemNumpy:
     """The SE3-expmap local BA cost (Map.cpp:414-566) from the definitions, with numpy / scipy.spatial only:
     sum_e rho_huber(w_e |uv - pi(T X)|^2) + sum_a |log(M_a T_a^-1)|^2_Omega_a + sum_o |log(T_j^-1 C T_i)|^2_Omega_o."""
 
-    def __init__(self, g):
+    def __init__(self, g, log=None):
         self.g = g
+        self.log = synth.se3_log_np if log is None else log      # the exact logarithm, or g2o's (se3_log_g2o below)
 
     def cost(self, poses, lms):
         g = self.g
@@ -142,9 +143,72 @@ class BA3ProblemNumpy:
         chi = np.where(s <= d2, s, 2 * np.sqrt(s) * g.huber - d2).sum()
         for a in range(g.P):
             if g.has_prior[a]:
-                e = synth.se3_log_np(g.prior_meas[a] @ np.linalg.inv(T[a]))
+                e = self.log(g.prior_meas[a] @ np.linalg.inv(T[a]))
                 chi += e @ g.prior_info[a] @ e
         for k in range(g.O):
-            e = synth.se3_log_np(np.linalg.inv(T[g.o_j[k]]) @ g.o_meas[k] @ T[g.o_i[k]])
+            e = self.log(np.linalg.inv(T[g.o_j[k]]) @ g.o_meas[k] @ T[g.o_i[k]])
             chi += e @ g.o_info[k] @ e
         return float(chi)
+
+
+def se3_log_g2o(T):
+    """SE3Quat::log as g2o defines it, (omega, upsilon): with d = (tr R - 1) / 2 and (R - R')^v the vector of the antisymmetric
+    part, omega = (R - R')^v / 2 and V^-1 = I - Omega / 2 + Omega^2 / 12 when d > 0.99999 (below 4.5 mrad: first order), else
+    omega = theta / (2 sqrt(1 - d^2)) (R - R')^v and V^-1 = I - Omega / 2 + (1 - theta / (2 tan(theta / 2))) / theta^2 Omega^2"""
+    R, t = T[:3, :3], T[:3, 3]
+    d = 0.5 * (np.trace(R) - 1)
+    dR = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    if d > 0.99999:
+        w, c = 0.5 * dR, 1.0 / 12.0
+    else:
+        th = np.arccos(d)
+        w, c = th / (2 * np.sqrt(1 - d * d)) * dR, (1 - th / (2 * np.tan(th / 2))) / th ** 2
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0.0]])
+    return np.concatenate([w, (np.eye(3) - 0.5 * K + c * K @ K) @ t])
+
+
+def ba3_full_normal_equations(g, lam, log=se3_log_g2o):
+    """The full (6P + 3L) Levenberg-Marquardt normal equations H dx = b of a synth.BA3Graph at its own estimate, from the definitions
+    of the three edge types (g2o's types_six_dof_expmap and the reference's EdgeSE3ExpmapPrior), every vertex updated as
+    exp(d) * T with d = (omega, upsilon) or X + d:
+      EdgeProjectXYZ2UV   e = uv - pi(T X), p = T X: de/dX = -dpi/dp R, de/dd = -dpi/dp [-[p]x  I]; information w I, Huber weight
+                          rho' = 1 if w |e|^2 <= delta^2 else delta / sqrt(w |e|^2), on these edges only
+      EdgeSE3ExpmapPrior  e = log(M T^-1), J = -I (the reference's linearizeOplus; its adjoint forms are commented out there)
+      EdgeSE3Expmap       e = log(T_j^-1 C T_i), J_i = adj(T_j^-1 C), J_j = -adj(T_i^-1 C^-1)
+    H = sum J' rho' W J + lam I, b = -sum J' rho' W e.  Fixed poses keep their rows here: the caller deletes them.
+    -> (H, b), unknowns ordered poses then landmarks."""
+    P, L = g.P, g.L
+    N = 6 * P + 3 * L
+    H, b = np.zeros((N, N)), np.zeros(N)
+
+    def add(cols, Js, W, e):
+        idx = np.concatenate(cols)
+        J = np.concatenate(Js, axis=1)
+        H[np.ix_(idx, idx)] += J.T @ W @ J
+        b[idx] -= J.T @ W @ e
+
+    T = np.asarray(g.poses)
+    for k in range(g.E):
+        a, l = int(g.e_kf[k]), int(g.e_lm[k])
+        R = T[a][:3, :3]
+        p = R @ g.lms[l] + T[a][:3, 3]
+        x, y, z = p
+        e = g.e_uv[k] - np.array([g.fx * x / z + g.cx, g.fx * y / z + g.cy])
+        dpi = g.fx / z * np.array([[1, 0, -x / z], [0, 1, -y / z]])
+        px = np.array([[0, -z, y], [z, 0, -x], [-y, x, 0.0]])
+        s = g.e_w[k] * (e @ e)
+        rho1 = 1.0 if s <= g.huber ** 2 else g.huber / np.sqrt(s)
+        add([np.arange(6 * a, 6 * a + 6), np.arange(6 * P + 3 * l, 6 * P + 3 * l + 3)],
+            [-dpi @ np.concatenate([-px, np.eye(3)], axis=1), -dpi @ R], rho1 * g.e_w[k] * np.eye(2), e)
+    for a in range(P):
+        if g.has_prior[a]:
+            add([np.arange(6 * a, 6 * a + 6)], [-np.eye(6)], g.prior_info[a], log(g.prior_meas[a] @ np.linalg.inv(T[a])))
+    for k in range(g.O):
+        i, j = int(g.o_i[k]), int(g.o_j[k])
+        C = g.o_meas[k]
+        e = log(np.linalg.inv(T[j]) @ C @ T[i])
+        Ji = synth.se3_adj_np(np.linalg.inv(T[j]) @ C)
+        Jj = -synth.se3_adj_np(np.linalg.inv(T[i]) @ np.linalg.inv(C))
+        add([np.arange(6 * i, 6 * i + 6), np.arange(6 * j, 6 * j + 6)], [Ji, Jj], g.o_info[k], e)
+    H += lam * np.eye(N)
+    return H, b

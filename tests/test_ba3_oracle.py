@@ -4,7 +4,8 @@ exp(update) * estimate, the full (un-reduced) normal equations, and the structur
 import numpy as np
 import pytest
 
-from independent import BA3ProblemNumpy
+from se2lam_amd import synth as _synth            # (the parametrisations below; tests take the `synth` fixture)
+from independent import BA3ProblemNumpy, ba3_full_normal_equations, se3_log_g2o
 
 
 @pytest.mark.parametrize("P,L,n_ref", [(8, 60, 0), (21, 800, 0), (21, 800, 4)])
@@ -83,3 +84,250 @@ def test_remove_outlier_chi2_rule(oracle, synth):
     bad = ec > 25
     assert 0 < bad.sum() < 0.06 * g.E
     assert np.median(ec[~bad]) < 3.0
+
+
+# ---- SE3 windows beyond ba3_graph's chain (synth.odometry_topology3) ---------------------------------------------------------
+def odometry_cases3(synth, sizes, kinds=None):
+    """(P, L, n_ref, kind) of every SE3 odometry topology a window of that size can hold: a hub of N edges needs N + 1 local key
+    frames, to_reference needs reference key frames, dense needs DENSE_TERMS - P distinct pairs"""
+    out = []
+    for P, L, n_ref in sizes:
+        nL = P - n_ref
+        for kind in (synth.ODOMETRY_TOPOLOGIES3 if kinds is None else kinds):
+            if kind.startswith("hub") and int(kind[3:]) + 1 > nL:
+                continue
+            if kind == "to_reference" and n_ref == 0:
+                continue
+            if kind == "dense" and synth.DENSE_TERMS - P - (nL - 1) > nL * (nL - 1) // 2 - (nL - 1) + nL * n_ref:
+                continue
+            out.append((P, L, n_ref, kind))
+    return out
+
+
+def assert_topology3(synth, g, kind, base):
+    """the odometry and the priors of `g` have the shape synth.odometry_topology3(base, kind) claims"""
+    P, nL = g.P, synth.n_local(base)
+    oi, oj = np.asarray(g.o_i, np.int64), np.asarray(g.o_j, np.int64)
+    und = sorted(zip(np.minimum(oi, oj).tolist(), np.maximum(oi, oj).tolist()))
+    chain = [(k, k + 1) for k in range(nL - 1)]
+    assert len(set(und)) == len(und) and not (oi == oj).any()          # the SE3 call surface refuses duplicates and self loops
+    assert g.o_meas.shape == (g.O, 4, 4) and g.o_info.shape == (g.O, 6, 6)
+    if kind != "none":
+        assert set(chain) <= set(und)
+        assert np.linalg.eigvalsh(g.o_info).min() > 0
+    if kind not in ("dense", "to_reference"):
+        assert g.O == 0 or max(oi.max(), oj.max()) < nL                # pairs among the local key frames
+    f = np.asarray(g.fixed, bool)
+    if kind != "fixed_ends":
+        assert np.array_equal(g.fixed, base.fixed)
+    if kind != "sparse_priors":
+        assert np.array_equal(g.has_prior, base.has_prior)
+    cov = synth.covisible(g)
+    if kind == "reversed":
+        assert und == chain and (oi > oj).sum() == (nL - 1) // 2 and (oi < oj).any()
+    elif kind == "shuffled":
+        assert und == chain and list(zip(oi.tolist(), oj.tolist())) != chain
+    elif kind == "long":
+        far = [(i, j) for i, j in zip(oi, oj) if abs(i - j) >= 2]
+        assert 2 <= len(far) <= 4 and not any(cov[i, j] for i, j in far)     # only the odometry edge couples these key frames
+        assert any(i < j for i, j in far) and any(i > j for i, j in far)
+    elif kind.startswith("hub"):
+        deg = np.bincount(np.r_[oi, oj], minlength=P)
+        h = int(deg.argmax())
+        assert h == nL // 2 and deg[h] == int(kind[3:]) and (oi == h).sum() >= 2 and (oj == h).sum() >= 2
+    elif kind == "dense":
+        assert P + g.O == synth.DENSE_TERMS > 256
+        assert (oi > oj).sum() > 20 and (oi < oj).sum() > 20
+        assert (np.maximum(oi, oj) >= nL).any() == (nL < P) and np.minimum(oi, oj).max() < nL     # never reference to reference
+    elif kind == "fixed_ends":
+        kinds = set(zip(f[oi].tolist(), f[oj].tolist()))
+        assert {(True, False), (False, True), (True, True), (False, False)} <= kinds
+        assert f[[0, 1, nL // 2, nL - 1]].all() and f[:nL].sum() == 4 and np.array_equal(f[nL:], np.asarray(base.fixed, bool)[nL:])
+        assert g.has_prior[[1, nL // 2, nL - 1]].all()                 # priors on fixed poses other than pose 0
+    elif kind == "to_reference":
+        ref = [(i, j) for i, j in zip(oi, oj) if max(i, j) >= nL]
+        assert 2 <= len(ref) <= 4 and all(min(i, j) < nL for i, j in ref)
+        assert any(i < j for i, j in ref) and any(i > j for i, j in ref)
+    elif kind == "none":
+        assert g.O == 0
+    elif kind == "sparse_priors":
+        assert und == chain
+        free = ~f
+        lost = free & (np.asarray(g.has_prior) == 0)
+        assert lost.sum() == len(np.nonzero(free)[0][2::3]) > 0 and (free & (np.asarray(g.has_prior) == 1)).any()
+        assert np.array_equal(np.asarray(g.has_prior)[f], np.asarray(base.has_prior)[f])
+
+
+def odo_graph3(synth, P, L, n_ref, kind):
+    base = synth.ba3_graph(P, L, n_ref)
+    if kind == "chain":
+        return base
+    g = synth.odometry_topology3(base, kind)
+    assert_topology3(synth, g, kind, base)
+    return g
+
+
+def _refined_solve(A, b):
+    """A x = b by LU with three rounds of refinement on an extended-precision residual: what is left between two such solutions is
+    the difference of the two systems, not the rounding of either solve"""
+    from scipy.linalg import lu_factor, lu_solve
+    lu = lu_factor(A)
+    x = lu_solve(lu, b).astype(np.longdouble)
+    Al, bl = A.astype(np.longdouble), b.astype(np.longdouble)
+    for _ in range(3):
+        x = x + lu_solve(lu, (bl - Al @ x).astype(np.float64))
+    return x.astype(np.float64)
+
+
+def _reduced_system_equals_full_model3(oracle, g, lam):
+    """oracle.ba3_reduced_system against the Schur complement of independent.ba3_full_normal_equations (fixed rows and columns
+    deleted).  The numpy model restates the small-angle branch of SE3Quat::log (independent.se3_log_g2o) rather than taking the
+    exact logarithm, so b and the solution are held to the same 1e-9 as S and no theta^2 / 6 term enters.
+    Largest differences seen (x86-64 CPU, every case of test_odometry_topologies3_reduce_like_the_full_model):
+    S 7.3e-14 of max|S|, b 4.7e-14 of max|b|, solution 4.7e-12 of max|x| (both solves refined, _refined_solve).  -> the model's (S, b) over the free poses"""
+    S, bs = oracle.ba3_reduced_system(g, lam)
+    P, L = g.P, g.L
+    assert np.abs(S - S.T).max() <= 1e-12 * np.abs(S).max()
+    fp = np.repeat(np.asarray(g.fixed) == 0, 6)
+    assert np.array_equal(S[~fp][:, ~fp], np.eye((~fp).sum())) and not S[~fp][:, fp].any() and not S[fp][:, ~fp].any()
+    assert not bs[~fp].any()
+    H, b = ba3_full_normal_equations(g, lam)
+    free = np.r_[fp, np.ones(3 * L, bool)]
+    Hf, bf = H[np.ix_(free, free)], b[free]
+    nf = int(fp.sum())
+    Hll_inv_Hlp = np.linalg.solve(Hf[nf:, nf:], np.c_[Hf[nf:, :nf], bf[nf:]])
+    Sm = Hf[:nf, :nf] - Hf[:nf, nf:] @ Hll_inv_Hlp[:, :nf]
+    bm = bf[:nf] - Hf[:nf, nf:] @ Hll_inv_Hlp[:, nf]
+    dS = np.abs(S[np.ix_(fp, fp)] - Sm).max() / np.abs(Sm).max()
+    db = np.abs(bs[fp] - bm).max() / np.abs(bm).max()
+    x_full = _refined_solve(Hf, bf)[:nf]                      # the pose part of the full step, not through the Schur complement
+    x_red = _refined_solve(S, bs)
+    dx = np.abs(x_red[fp] - x_full).max() / np.abs(x_full).max()
+    print("full model: P %d O %d lam %g  dS %.2e  db %.2e  dx %.2e" % (P, g.O, lam, dS, db, dx))
+    assert dS <= 1e-9 and db <= 1e-9 and dx <= 1e-9, (dS, db, dx)
+    assert not x_red[~fp].any()
+    return Sm, bm, fp
+
+
+FULL_MODEL_SIZES = ((8, 60, 0), (21, 800, 0), (21, 800, 4), (30, 600, 0))     # (30, 600): the smallest window `dense` fits
+
+
+@pytest.mark.parametrize("P,L,n_ref,kind", [(8, 60, 0, "chain"), (21, 800, 4, "chain")]
+                         + [c for c in odometry_cases3(_synth, FULL_MODEL_SIZES)
+                            if c[0] != 30 or c[3] == "dense"])
+def test_odometry_topologies3_reduce_like_the_full_model(oracle, synth, P, L, n_ref, kind):
+    """The oracle's reduced system (ba3_ref.cpp) against an independent assembly of the full normal equations, on the chain and
+    on every topology the GPU tests use.  A transposed cross block of a reversed edge, a dropped odometry-only block, a prior or
+    an odometry term on the wrong side of a fixed pose: all show here with no GPU involved."""
+    g = odo_graph3(synth, P, L, n_ref, kind)
+    for lam in (0.0, 2.5):
+        Sm, bm, fp = _reduced_system_equals_full_model3(oracle, g, lam)
+    S, _ = oracle.ba3_reduced_system(g, 0.0)
+    # blocks that only an odometry edge fills (the key frames share no landmark) are there, each held to its own size - a dropped
+    # or transposed block cannot hide behind the bound on the whole matrix
+    cov = synth.covisible(g)
+    slot = np.cumsum(np.asarray(g.fixed) == 0) - 1
+    lonely = [(int(i), int(j)) for i, j in zip(g.o_i, g.o_j) if not cov[i, j] and not g.fixed[i] and not g.fixed[j]]
+    if kind in ("long", "dense"):
+        assert len(lonely) >= 1
+    for i, j in lonely:
+        B = S[6 * i:6 * i + 6, 6 * j:6 * j + 6]
+        Bm = Sm[6 * slot[i]:6 * slot[i] + 6, 6 * slot[j]:6 * slot[j] + 6]
+        assert np.abs(B).max() > 0 and np.abs(B - Bm).max() <= 1e-9 * np.abs(Bm).max(), (i, j)
+        assert np.abs(B - B.T).max() > 1e-3 * np.abs(B).max()          # (not symmetric: its transpose is a different matrix)
+        assert np.array_equal(S[6 * j:6 * j + 6, 6 * i:6 * i + 6], B.T)
+
+
+def test_flipped_odometry_edge_jacobians_against_numeric_derivatives(oracle, synth):
+    """test_edge_jacobians_against_numeric_derivatives on an edge stored as (k + 1, k): vertex 0 is the LATER key frame, the
+    measurement is inverted to match (true_k true_{k+1}^-1), and at zero error J_i, J_j are the central differences through
+    exp(update) * estimate"""
+    g = synth.odometry_topology3(synth.ba3_graph(8, 60), "reversed")
+    k = int(np.nonzero(g.o_i > g.o_j)[0][0])
+    i, j = int(g.o_i[k]), int(g.o_j[k])
+    assert i == j + 1
+    # the stored measurement takes vertex 0 to vertex 1 (noise only at the true poses): C = T_j T_i^-1, not its inverse
+    e_true = synth.se3_log_np(np.linalg.inv(g.poses_true[j]) @ g.o_meas[k] @ g.poses_true[i])
+    assert np.abs(e_true[:3]).max() < 0.02 and np.abs(e_true[3:]).max() < 20.0
+    Ti, Tj = g.poses[i], g.poses[j]
+    Cm = Tj @ np.linalg.inv(Ti)
+    e, Ji, Jj = oracle.ba3_odo_edge(Ti, Tj, Cm)
+    assert np.abs(e).max() < 1e-9
+    h = 1e-6
+    for c in range(6):
+        d = np.zeros(6); d[c] = h
+        ei = (oracle.ba3_odo_edge(synth.se3_exp_np(d) @ Ti, Tj, Cm)[0] - oracle.ba3_odo_edge(synth.se3_exp_np(-d) @ Ti, Tj, Cm)[0]) / (2 * h)
+        ej = (oracle.ba3_odo_edge(Ti, synth.se3_exp_np(d) @ Tj, Cm)[0] - oracle.ba3_odo_edge(Ti, synth.se3_exp_np(-d) @ Tj, Cm)[0]) / (2 * h)
+        assert np.allclose(Ji[:, c], ei, atol=1e-5 * max(1.0, np.abs(ei).max()))
+        assert np.allclose(Jj[:, c], ej, atol=1e-5 * max(1.0, np.abs(ej).max()))
+    e, Ji, Jj = oracle.ba3_odo_edge(Ti, Tj, g.o_meas[k])
+    assert np.allclose(Ji, synth.se3_adj_np(np.linalg.inv(Tj) @ g.o_meas[k]), rtol=1e-9, atol=1e-9)
+    assert np.allclose(Jj, -synth.se3_adj_np(np.linalg.inv(Ti) @ np.linalg.inv(g.o_meas[k])), rtol=1e-9, atol=1e-9)
+
+
+@pytest.mark.parametrize("P,L,n_ref,kind", odometry_cases3(_synth,
+                                                          ((8, 60, 0), (21, 800, 0), (21, 800, 4))))
+def test_cost_equals_the_numpy_model_on_odometry_topologies(oracle, synth, P, L, n_ref, kind):
+    """test_cost_equals_the_numpy_model's cost checks on the other odometry and prior layouts (BA3ProblemNumpy takes any o_i, o_j)"""
+    g = odo_graph3(synth, P, L, n_ref, kind)
+    # with the exact logarithm the two costs differ by up to theta^2 / 3 <= 6.8e-6 of the prior and odometry terms (the file's 1e-7
+    # of the whole cost is what the chain gives, and a window without odometry misses it: 1.6e-7).  Here the model restates
+    # g2o's first-order branch instead (independent.se3_log_g2o), so only rounding is left: 1e-11 covers sums of ~1e4 terms in
+    # doubles; the largest difference seen on an x86-64 CPU is 9.1e-15
+    m = BA3ProblemNumpy(g, log=se3_log_g2o)
+    c0, ec = oracle.ba3_chi2(g)
+    c_np = m.cost(g.poses, g.lms)
+    print("cost %s %s: oracle / numpy - 1 = %.2e" % ((P, L, n_ref), kind, c0 / c_np - 1))
+    assert c0 == pytest.approx(c_np, rel=1e-11)
+    assert np.allclose(ec, m.edge_chi2, rtol=1e-10)
+    p, l, ec2, st = oracle.ba3_optimize(g, 10)
+    assert st["chi2_final"] == pytest.approx(m.cost(p, l), rel=1e-11)
+    assert np.allclose(ec2, m.edge_chi2, rtol=1e-8)
+    assert st["chi2_final"] < st["chi2_init"]
+    for a in np.nonzero(g.fixed)[0]:
+        assert np.array_equal(p[a], g.poses[a])
+
+
+BA3_GRAPH_SHA256 = {   # of ba3_graph's arrays before odometry_topology3 existed (_digest3 below)
+    (8, 60, 0): "c29a9169fe88d7fa0bd2e0b9668e11aa84062a19e0ed4ae8b1c29f476bdae891",
+    (21, 800, 4): "bf6df5696de741849b042a7f2b6fc69b2da1f432bc23f30826b3c03056c8aa4b",
+    (50, 5000, 10): "904a358ef7887e1ed2319bc2cdc45509407430b61d289647cb75febf87e63338",
+}
+
+
+def _digest3(g):
+    import hashlib
+    h = hashlib.sha256()
+    for f in ("poses", "fixed", "lms", "e_kf", "e_lm", "e_uv", "e_w", "has_prior", "prior_meas", "prior_info", "o_i", "o_j", "o_meas",
+              "o_info"):
+        a = np.ascontiguousarray(getattr(g, f))
+        h.update(f.encode()); h.update(str(a.dtype).encode()); h.update(str(a.shape).encode()); h.update(a.tobytes())
+    h.update(repr((g.fx, g.cx, g.cy, g.huber)).encode())
+    return h.hexdigest()
+
+
+def test_odometry_topology3_generator_leaves_ba3_graph_alone(synth):
+    """ba3_graph's output (the fixtures' and the fuzzers' windows) is what it was before the generator of other layouts was added,
+    to the bit, also after that generator ran on the cached instance; every generated edge agrees with the ground truth"""
+    for key, want in BA3_GRAPH_SHA256.items():
+        g = synth.ba3_graph(*key)
+        assert _digest3(g) == want, key
+        kinds = [c[3] for c in odometry_cases3(synth, (key,))]
+        made = [synth.odometry_topology3(g, kind) for kind in kinds]
+        assert _digest3(g) == want and synth.ba3_graph(*key) is g, key
+        for kind, h in zip(kinds, made):
+            assert_topology3(synth, h, kind, g)
+            assert h.poses is g.poses and h.lms is g.lms and h.e_uv is g.e_uv
+            for k in range(0, h.O, max(1, h.O // 40)):
+                # C = noise true_j true_i^-1: what is left of C true_i true_j^-1 is the noise, six terms of known deviation
+                e = synth.se3_log_np(h.o_meas[k] @ h.poses_true[h.o_i[k]] @ np.linalg.inv(h.poses_true[h.o_j[k]]))
+                assert np.abs(e / np.array([1e-3, 1e-3, 2e-3, 2.0, 2.0, 2.0])).max() < 6.0, (key, kind, k)
+    # the chain through with_odometry3: ba3_graph's pairs, measurements of the same distribution (not the same draws)
+    g = synth.ba3_graph(21, 800, 4)
+    c = synth.with_odometry3(g, np.c_[g.o_i, g.o_j], seed=5)
+    assert np.array_equal(c.o_i, g.o_i) and np.array_equal(c.o_j, g.o_j) and not np.array_equal(c.o_meas, g.o_meas)
+    assert np.abs(c.o_meas - g.o_meas)[:, :3, 3].max() < 30.0 and np.abs(c.o_meas - g.o_meas)[:, :3, :3].max() < 0.02
+    with pytest.raises(ValueError):
+        synth.odometry_topology3(synth.ba3_graph(21, 800, 0), "dense")       # 210 pairs: fewer than DENSE_TERMS - 21
+    with pytest.raises(ValueError):
+        synth.odometry_topology3(synth.ba3_graph(21, 800, 0), "to_reference")

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from se2lam_amd import synth as _synth            # (for a parametrisation; tests take the `synth` fixture)
 from test_ba_gpu import _opt
 
 pytestmark = pytest.mark.gpu
@@ -295,3 +296,130 @@ def test_se3_default_threshold(synth):
         assert _last_path() == 2
         for o in large[::8]:
             _same(o, ref, "96 windows", g)
+
+
+# ---- SE3 windows beyond ba3_graph's chain (synth.odometry_topology3) on the resident kernel: odometry_term's two tri() arms
+# (edges stored as (i > j)), blocks only an odometry edge fills, pose_terms' stride once P + O exceeds the workgroup (`dense`),
+# fixed ends and reference key frames, no odometry at all, free key frames without a prior
+RESIDENT_SIZES3 = ((8, 60, 0), (21, 800, 0), (21, 800, 4))                  # at most 27 free key frames: the 256-thread width
+KIDNAP_REVERSED_LONG = (21, 800, 0, 3000.0, 0.8, 2, 8)   # the oracle (picked with it, once): trials [1, 1, 1, 5, 1, 3, 1, 4, 1, 1],
+                                                         # the closest gain ratio 7.8e-3 from zero
+
+
+def _kidnapped_reversed_long(synth):
+    """a kidnapped start under the `reversed` chain plus the `long` kind's extra edges: rejected trials re-evaluate edges stored as
+    (i > j) and edges between key frames without a common landmark"""
+    k = _kidnapped3(synth, *KIDNAP_REVERSED_LONG)
+    rv, lg = synth.odometry_topology3(k, "reversed"), synth.odometry_topology3(k, "long")
+    extra = list(zip(lg.o_i[rv.O:].tolist(), lg.o_j[rv.O:].tolist()))
+    cov = synth.covisible(k)
+    assert len(extra) >= 2 and not any(cov[i, j] for i, j in extra) and any(i > j for i, j in extra)
+    g = synth.with_odometry3(k, list(zip(rv.o_i.tolist(), rv.o_j.tolist())) + extra)
+    assert (g.o_i > g.o_j).sum() >= 10
+    return g
+
+
+def _resident_cases3(synth, kind):
+    """the windows of `kind` that fit the resident kernel: RESIDENT_SIZES3, and 20 local + 50 reference key frames for to_reference
+    and dense"""
+    from test_ba3_oracle import odo_graph3, odometry_cases3
+    cases = odometry_cases3(synth, RESIDENT_SIZES3, (kind,)) + odometry_cases3(synth, ((70, 1500, 50),), (kind,) if kind in ("to_reference", "dense") else ())
+    assert cases, kind                                                       # every kind fits somewhere
+    return [(c, odo_graph3(synth, *c)) for c in cases]
+
+
+@pytest.mark.parametrize("kind", _synth.ODOMETRY_TOPOLOGIES3 + ("kidnapped",))
+def test_forced_se3_odometry_topologies_equal_multi_launch_and_the_oracle(oracle, synth, kind):
+    """one forced batch per layout (every size of it that fits, and for "kidnapped" a start that rejects trials under reversed and
+    long edges): test_forced_se3_batch_equals_multi_launch_and_the_oracle's checks"""
+    from se2lam_amd.optimizer import optimize_batch
+    if kind == "kidnapped":
+        cases = [("kidnapped, reversed + long", _kidnapped_reversed_long(synth))]
+    else:
+        cases = _resident_cases3(synth, kind)
+    graphs = [g for _, g in cases]
+    if kind == "dense":
+        assert all(g.P + g.O > 256 and int((np.asarray(g.fixed) == 0).sum()) <= 27 for g in graphs)   # pose_terms strides at 256 threads
+    ref = [_multi_launch(g, 10) for g in graphs]
+    if kind == "kidnapped":
+        assert max(ref[0][0]["trials_hist"]) > 1, ref[0][0]["trials_hist"]                    # the kidnapped start rejects trials
+    opts = [_opt3(g) for g in graphs]
+    with _resident("1"):
+        its = optimize_batch(opts, 10)
+    assert _last_path() == 2
+    for (c, g), o, r, n in zip(cases, opts, ref, its):
+        assert n == r[0]["iterations"], c
+        _same(o, r, c, g)
+        p_ref, l_ref, ec_ref, st = oracle.ba3_optimize(g, 10)
+        assert o.stats["trials_hist"] == st["trials_hist"], c
+        assert np.allclose(o.stats["chi2_hist"][:10], st["chi2_hist"][:10], rtol=1e-7), c
+
+
+def _lds3_bytes(P, nfree, threads):
+    """ba_window3_lds_bytes (csrc/ba_window3.hip) restated by reading it, not from a run: dynamic LDS = the column list (P ints), two
+    sets of poses (12 doubles each per key frame of the window, fixed ones included), x and 1 / diag (6 nfree each), the staging
+    strip (19 doubles per thread) and the packed triangle of S with b_s and a zero block row ((n + 6)(n + 7) / 2), n = 6 nfree;
+    static LDS = BaCtl (1392 bytes) + the histogram, wave totals and lists (232 ints) + 45 doubles + 128; 160 KiB in all, n <= 192.
+    -> bytes, 0 when the window does not fit"""
+    if threads not in (256, 128):
+        return 0
+    n = 6 * nfree
+    doubles = (P + 1) // 2 + 24 * P + 2 * n + threads * 19 + (n + 6) * (n + 7) // 2
+    fixed = 1392 + (64 + 2 + 18 * 8 + 18 + 4) * 4 + (24 + 21) * 8 + 128
+    return 0 if n > 192 or doubles * 8 + fixed > 160 * 1024 else doubles * 8
+
+
+def _lds3_threads(g):
+    nfree = int((np.asarray(g.fixed) == 0).sum())
+    return next((t for t in (256, 128) if _lds3_bytes(g.P, nfree, t)), 0)
+
+
+def _limit_windows(synth):
+    """windows of 27, 28, 29 and 30 free key frames with 2 reference key frames each (P = 29 .. 32).  By _lds3_bytes at these P: 27
+    free take the 256-thread workgroup, 28 and 29 only the 128-thread one, 30 none - the limits the kernel's commit states.  (They
+    move with P: 24 doubles per key frame of the window.  27 free fit 256 threads up to P = 30, 29 free fit 128 up to P = 43.)
+    Each in another layout; `dense` strides pose_terms at 128 threads too."""
+    out = []
+    for nfree, kind, threads in ((27, "reversed", 256), (28, "dense", 128), (29, "long", 128), (30, "hub9", 0)):
+        g = synth.odometry_topology3(synth.ba3_graph(nfree + 2, 600, 2), kind)
+        assert int((np.asarray(g.fixed) == 0).sum()) == nfree and g.P == nfree + 2
+        assert _lds3_threads(g) == threads, (nfree, g.P, _lds3_threads(g))                  # up front: the intended side of each limit
+        out.append(g)
+    assert out[1].P + out[1].O > 256
+    return out
+
+
+def test_se3_lds_limits(synth):
+    """on either side of the two LDS limits of k_window_lm3: forced, 27 / 28 / 29 free key frames run resident (one launch of 256
+    threads, one of 128) and equal the multi-launch run; with a 30-free window the batch stays off the resident path, bit-identical
+    to one-by-one runs; unforced, one 28-free window keeps a batch of 96 off it (the t < 256 rule)"""
+    from se2lam_amd.optimizer import optimize_batch
+    w27, w28, w29, w30 = _limit_windows(synth)
+    ref = [_multi_launch(g, 8) for g in (w27, w28, w29, w30)]
+    opts = [_opt3(g) for g in (w27, w28, w29)]
+    with _resident("1"):
+        optimize_batch(opts, 8)
+    assert _last_path() == 2
+    for g, o, r in zip((w27, w28, w29), opts, ref):
+        _same(o, r, ("free", g.P - 2), g)
+    opts = [_opt3(g) for g in (w27, w30)]
+    with _resident("1"):
+        optimize_batch(opts, 8)
+    assert _last_path() != 2
+    for o, (st, est, _) in zip(opts, (ref[0], ref[3])):
+        assert o.stats == st and np.array_equal(o.estimates()[0], est[0]) and np.array_equal(o.estimates()[1], est[1])
+    small = synth.odometry_topology3(synth.ba3_graph(8, 60, 0), "reversed")
+    rs = _multi_launch(small, 8)
+    with _resident(None):
+        opts = [_opt3(small) for _ in range(95)] + [_opt3(w28)]
+        optimize_batch(opts, 8)
+        assert _last_path() != 2
+        for o in opts[:3]:
+            assert o.stats == rs[0] and np.array_equal(o.estimates()[0], rs[1][0])
+        assert opts[-1].stats == ref[1][0] and np.array_equal(opts[-1].estimates()[0], ref[1][1][0])
+        del opts
+        opts = [_opt3(small) for _ in range(95)] + [_opt3(w27)]               # (with a 27-free window instead the batch goes resident)
+        optimize_batch(opts, 8)
+        assert _last_path() == 2
+        _same(opts[-1], ref[0], "27 free among 96", w27)
+        _same(opts[0], rs, "8 key frames among 96", small)

@@ -2,7 +2,8 @@
 """Randomised parity sweep on the GPU (not part of the test suite: it runs for as long as it is given).
    python tools/fuzz_gpu.py [seconds] [seed] [kinds, comma separated]
 ORB: random image sizes / feature counts / level counts / score types, single frames and batches against the oracle.
-BA : random SE(2) windows (sizes, fixed patterns, kidnapped starts) - LM histories against the oracle.
+BA : random SE(2) windows (sizes, fixed patterns, kidnapped starts) - LM histories against the oracle; SE3-expmap windows under a
+     random odometry / prior layout (synth.odometry_topology3), alone and in resident batches.
 Prints one line per case and exits non-zero at the first mismatch."""
 import os
 import sys
@@ -34,6 +35,17 @@ def feats(t):
     if t not in feat_cache:
         feat_cache[t] = oracle.orb_extract(synth.frame(t))
     return feat_cache[t]
+
+
+def ba3_layout(g):
+    """g under a random odometry / prior layout (synth.odometry_topology3), or as it is when the window cannot hold the one drawn"""
+    kind = str(rng.choice(("chain",) + synth.ODOMETRY_TOPOLOGIES3))
+    if kind == "chain":
+        return g, kind
+    try:
+        return synth.odometry_topology3(g, kind, seed=int(rng.integers(1, 10**6))), kind
+    except ValueError:
+        return g, "chain"
 
 
 def fail(msg):
@@ -82,14 +94,14 @@ while time.time() < t_end:
         continue
     if kind == 4:   # marginalising SE3-expmap window
         P = int(rng.integers(3, 40)); L = int(rng.integers(2 * P, 30 * P)); nref = int(rng.integers(0, min(4, P - 2) + 1))
-        g = synth.ba3_graph(P, L, nref, seed=int(rng.integers(1, 10**6)))
+        g, layout = ba3_layout(synth.ba3_graph(P, L, nref, seed=int(rng.integers(1, 10**6))))
         o = op.SlamOptimizer(); op.load_se3_graph(o, g); o.initializeOptimization(0)
         iters = int(rng.integers(1, 11))
         o.optimize(iters)
         st = oracle.ba3_optimize(g, iters)[3]
         s_ = o.stats
         ok = s_["trials_hist"] == st["trials_hist"] and np.allclose(s_["chi2_hist"], st["chi2_hist"], rtol=1e-5, atol=0)
-        print(f"ba3  P {P} L {L} ref {nref} E {g.E} iters {iters}: trials {s_['trials_hist']} {'ok' if ok else ''}")
+        print(f"ba3  P {P} L {L} ref {nref} E {g.E} O {g.O} {layout} iters {iters}: trials {s_['trials_hist']} {'ok' if ok else ''}")
         if not ok:
             fail("ba3")
         continue
@@ -249,7 +261,7 @@ while time.time() < t_end:
         for _ in range(nb):
             if rng.random() < 0.5:
                 P = int(rng.integers(3, 29)); nref = int(rng.integers(0, min(4, P - 2) + 1))
-                gs.append(synth.ba3_graph(P, int(rng.integers(2 * P, 30 * P)), nref, seed=int(rng.integers(1, 10**6))))
+                gs.append(ba3_layout(synth.ba3_graph(P, int(rng.integers(2 * P, 30 * P)), nref, seed=int(rng.integers(1, 10**6))))[0])
                 continue
             P = int(rng.integers(2, 61))
             L = int(rng.integers(max(8, P), 30 * P))
