@@ -362,6 +362,12 @@ int se2gpu_ba_debug_solve(se2gpu_ba* h, double lambda, double* x, int* factor_ok
  * dependency timed out earlier in the handle's life (reported once on stderr), 3 = host solve (SE2GPU_BA_HOST_SOLVE=1).
  * Tests use it to make sure that results were not produced by the fallback. */
 int se2gpu_ba_debug_solver_path(const se2gpu_ba* h);
+/* The speculating trial slot of the single-window SE(2) run (k_update<true> also linearises the trial state; SE2GPU_BA_SPECULATE=0
+ * switches it off), for the handle's last optimize(): *runs = trial slots whose stand-alone linearisation did its work (the
+ * first trial, every retry, every accept whose new damping was not lambda / 3), *skips = slots where it returned at once because
+ * the slot before had already written the records; runs + skips = trials.  *twin_bytes = size of the handle's second record set
+ * (0 until a run of the handle has speculated).  Any of the three pointers may be NULL. */
+int se2gpu_ba_debug_linearize_counts(const se2gpu_ba* h, int* runs, int* skips, long long* twin_bytes);
 /* Test introspection: idle sets in the library's two process-wide lease pools - {plan caches of the lock-step batch driver,
  * staging buffers of se2gpu_ba_reset_estimates_batch}.  A set is leased per call and returned, whichever thread calls. */
 int se2gpu_ba_debug_pool_sizes(int out2[2]);

@@ -150,6 +150,7 @@ SYMBOLS = {
     "se2gpu_ba_debug_reduced_system": (_I, [_VP, _D, _PD, _PD]),
     "se2gpu_ba_debug_solve": (_I, [_VP, _D, _PD, C.POINTER(C.c_int)]),
     "se2gpu_ba_debug_solver_path": (_I, [_VP]),
+    "se2gpu_ba_debug_linearize_counts": (_I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "se2gpu_ba_debug_chol_verify": (_I, [_VP, _VP, _VP, _I]),
     "se2gpu_ba_debug_pool_sizes": (_I, [_VP]),
     "se2gpu_ba_debug_solve_plan": (_I, [_I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _I]),

@@ -37,6 +37,10 @@ struct BaCtl {
     int mode, error, pad;
     double chi2_hist[64], lambda_hist[64];
     int trials_hist[64];
+    // speculative linearisation (k_update<true>, csrc/ba.hip): which of the two record sets the consumers of this slot read,
+    // whether it already holds the records of the current estimate at the current lambda (k_linearize then returns at once),
+    // and how many stand-alone linearisations of this run did their work / returned at the flag
+    int rec_sel, rec_valid, lin_runs, lin_skips;
     // survive k_ctl_init (and, like sel, say something about the handle rather than about one run):
     double seq;       // trial slots finished so far; posted next to the block (mail[kMailSeq]) - the host mirrors the count
     unsigned epoch;   // dense solves so far = the value the tile flags of k_chol_tiles are compared with
@@ -212,6 +216,26 @@ __device__ inline void lm_advance(BaCtl* c, const double* sc, bool stopped) {
     if (c->mode == SE2GPU_BA_LM && (qmax == 10 || rho == 0)) { c->terminated = 1; c->done = 1; }
     if (stopped) { c->stopped = 1; c->done = 1; }
     if (c->it >= c->iters) c->done = 1;
+}
+
+// The damping k_update<true> assumes for the trial after the one it evaluates: lm_advance's accept branch with
+// alpha = 1 - (2 rho - 1)^3 <= 1/3, i.e. every gain ratio rho >= 0.937 (the same expression, so a hit is a bitwise hit);
+// Gauss-Newton never changes it.
+__host__ __device__ inline double lm_lambda_spec(double lambda, int mode) {
+    if (mode == SE2GPU_BA_GN) return lambda;
+    lambda *= 1. / 3.;
+    return lambda;
+}
+
+// After lm_advance, by the same thread: account for this slot's stand-alone linearisation (it returned at the flag or did its
+// work) and say whether the records k_update<true> has just written are the next slot's: the trial was accepted (sel moved on from
+// sel0) and the new damping is the one they were whitened with.  Then the record sets change roles.
+__device__ inline void lm_records_advance(BaCtl* c, bool speculated, int sel0, double lambda_spec) {
+    if (c->rec_valid) c->lin_skips += 1;
+    else c->lin_runs += 1;
+    const bool hit = speculated && c->sel != sel0 && c->lambda == lambda_spec;
+    c->rec_valid = hit ? 1 : 0;
+    if (hit) c->rec_sel ^= 1;
 }
 
 }  // namespace badev

@@ -127,6 +127,13 @@ class SlamOptimizer:
         """se2gpu_ba_debug_solver_path: 0 dataflow, 1 column launches (configured), 2 column launches (fallback), 3 host"""
         return int(capi.lib().se2gpu_ba_debug_solver_path(self._h))
 
+    def linearize_counts(self):
+        """se2gpu_ba_debug_linearize_counts of the last optimize(): (stand-alone linearisations that did their work, those that
+        returned because the slot before had speculated right, bytes of the handle's second record set)"""
+        runs, skips, twin = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        capi.check(capi.lib().se2gpu_ba_debug_linearize_counts(self._h, C.byref(runs), C.byref(skips), C.byref(twin)))
+        return int(runs.value), int(skips.value), int(twin.value)
+
     def activeRobustChi2(self) -> float:
         v = capi.lib().se2gpu_ba_chi2(self._h)
         if v < 0:
