@@ -693,11 +693,17 @@ extern "C" {
 
 // mask[i] (n entries) for the n correspondences m1[i] <-> m2[i] (x, y interleaved); returns the number of inliers,
 // 0 with an all-zero mask when findFundamentalMat leaves the mask empty or finds no model
-int match_ref_fundamental_mask(const float* m1, const float* m2, int n, uint8_t* mask) {
+// info4 (nullable) = {inliers, winning sample, winning model of that sample, iterations the loop ran} - the four numbers of
+// se2gpu_track_last_ransac; {0 or 7, -1, -1, 0} where no sample is drawn (n <= 7)
+int match_ref_fundamental_mask_info(const float* m1, const float* m2, int n, uint8_t* mask, int* info4) {
+    int none[4];
+    int* info = info4 ? info4 : none;
+    info[0] = 0; info[1] = info[2] = -1; info[3] = 0;
     for (int i = 0; i < n; ++i) mask[i] = 0;
     if (n < 7) return 0;
     if (n == 7) {
         for (int i = 0; i < n; ++i) mask[i] = 1;
+        info[0] = n;
         return n;
     }
     CvRng rng((uint64_t)-1);
@@ -720,10 +726,12 @@ int match_ref_fundamental_mask(const float* m1, const float* m2, int n, uint8_t*
                 if (good > std::max(maxGood, 6)) {
                     std::memcpy(mask, cur.data(), n);
                     maxGood = good;
+                    info[1] = iter; info[2] = k;
                     niters = fm_update_num_iters(0.99, (double)(n - good) / n, 7, niters);
                 }
             }
         }
+        info[0] = maxGood; info[3] = niters;
         return maxGood;
     }
     // LMedS
@@ -744,10 +752,12 @@ int match_ref_fundamental_mask(const float* m1, const float* m2, int n, uint8_t*
             const double median = n % 2 != 0 ? (double)hi : (double)((lo + hi) * 0.5);
             if (median < minMedian) {
                 minMedian = median;
+                info[1] = iter; info[2] = k;
                 std::memcpy(best, F + 9 * k, sizeof(best));
             }
         }
     }
+    info[3] = niters;
     if (!(minMedian < 1.7976931348623157e308)) return 0;
     double sigma = 2.5 * 1.4826 * (1 + 5. / (n - 7)) * std::sqrt(minMedian);
     sigma = std::fmax(sigma, 0.001);
@@ -757,7 +767,12 @@ int match_ref_fundamental_mask(const float* m1, const float* m2, int n, uint8_t*
         mask[i] = fm_error(best, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1]) <= t;
         good += mask[i];
     }
+    info[0] = good;
     return good;
+}
+
+int match_ref_fundamental_mask(const float* m1, const float* m2, int n, uint8_t* mask) {
+    return match_ref_fundamental_mask_info(m1, m2, n, mask, nullptr);
 }
 
 // Track::removeOutliers (src/Track.cpp:308-344): matches[i] = -1 for the outliers; fewer than 10 inliers => every

@@ -519,6 +519,21 @@ def fundamental_mask(pt1, pt2):
     return mask[:n], int(ni)
 
 
+def fundamental_mask_info(pt1, pt2):
+    """fundamental_mask plus the four numbers of se2gpu_track_last_ransac
+    -> (mask (n,) u8, dict(inliers, sample, model, iterations))"""
+    p1 = np.ascontiguousarray(pt1, np.float32).reshape(-1, 2)
+    p2 = np.ascontiguousarray(pt2, np.float32).reshape(-1, 2)
+    n = len(p1)
+    mask = np.zeros(max(n, 1), np.uint8)
+    info = np.zeros(4, np.int32)
+    f = lib().match_ref_fundamental_mask_info
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    f(p1.ctypes.data, p2.ctypes.data, n, mask.ctypes.data, info.ctypes.data)
+    return mask[:n], dict(inliers=int(info[0]), sample=int(info[1]), model=int(info[2]), iterations=int(info[3]))
+
+
 def remove_outliers(kps1, kps2, matches):
     """Track::removeOutliers -> (matches with the outliers set to -1, n_inliers)"""
     k1 = np.ascontiguousarray(kps1); k2 = np.ascontiguousarray(kps2)

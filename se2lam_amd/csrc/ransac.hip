@@ -21,7 +21,11 @@
 // members of the pencil do not depend on it.  cv::solveCubic's acos / cos / cubeRoot are replaced by Newton iterations
 // made of + - * / sqrt, with the same branches and root order, so that the result does not depend on a math library;
 // the CPU test restatement runs the identical operation sequence and the masks agree bit for bit.  Compiled with
-// -ffp-contract=off.  Agreement with OpenCV itself is unpinned (not installed here).
+// -ffp-contract=off.  Beyond the restatement (tests/test_track_independent.py): the winning (sample, model) that
+// se2gpu_track_last_ransac reports is matched to numpy's 7-point roots (SVD null space, np.roots) within 1e-6, its FP64
+// inlier set equals the mask outside the float band of the error (at most 1 % of the points inside), and the first-maximum
+// rule, the stop rule's iteration count and the LMedS first-minimum rule are replayed in FP64.  Agreement with OpenCV
+// itself is unpinned (not installed here).
 #include "track_ws.h"
 
 #include <algorithm>

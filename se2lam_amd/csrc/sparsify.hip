@@ -191,23 +191,25 @@ __device__ void clamp_spectrum6(double* I) {
         for (int c = r + 1; c < 6; ++c) { const double m = 0.5 * (I[6 * r + c] + I[6 * c + r]); I[6 * r + c] = I[6 * c + r] = m; }
 }
 
-// mp_ptr: points of pair p = [mp_ptr[p], mp_ptr[p+1]); mm_ptr: measurements of point j = [mm_ptr[j], mm_ptr[j+1]) in the
-// order they were given; m_kf in {0, 1}; scratch: 288 doubles per POINT (its key-frame blocks and its Schur term), so that
-// the sums can be taken in exactly the reference's order whatever lane computed a point.
+// mp_ptr: points of pair p = [mp_ptr[p], mp_ptr[p+1]); mm_ptr: measurements of point j = [mm_ptr[j], mm_ptr[j+1]) (grouped by
+// point on the host); m_kf in {0, 1}; ord: the grouped slots of pair p's measurements, [ord_ptr[p], ord_ptr[p+1]), in the order
+// the caller gave them.  Scratch: 36 doubles per MEASUREMENT (its 6x6 key-frame block of J' W J) and 144 per POINT (its Schur
+// term), so that the sums can be taken in exactly the reference's order whatever lane computed a point.
 __global__ __launch_bounds__(64) void k_sparsify(int npairs, const double* __restrict__ kf12, const int* __restrict__ mp_ptr,
                                                  const double* __restrict__ mp_xyz, const int* __restrict__ mm_ptr,
                                                  const int* __restrict__ m_kf, const double* __restrict__ m_info,
-                                                 double* __restrict__ scratch, double* __restrict__ z_out,
-                                                 double* __restrict__ info_out) {
+                                                 const int* __restrict__ ord_ptr, const int* __restrict__ ord,
+                                                 double* __restrict__ kf_blk, double* __restrict__ schur,
+                                                 double* __restrict__ z_out, double* __restrict__ info_out) {
     const int p = blockIdx.x;
     if (p >= npairs) return;
     const int lane = threadIdx.x;
     const Q3 KF0 = from_pose12(kf12 + 24 * (size_t)p), KF1 = from_pose12(kf12 + 24 * (size_t)p + 12);
     __shared__ double h11s[144];
     for (int j = mp_ptr[p] + lane; j < mp_ptr[p + 1]; j += 64) {
-        // this point's part of H11 (12 x 12): [0,144) its J' W J key-frame blocks, [144,288) its Schur term
-        double* acc = scratch + (size_t)j * 288;
-        for (int i = 0; i < 288; ++i) acc[i] = 0.0;
+        // this point's Schur term of H11 (12 x 12); the key-frame blocks of J' W J go to their measurement's slot
+        double* acc = schur + (size_t)j * 144;
+        for (int i = 0; i < 144; ++i) acc[i] = 0.0;
         double Hmm[9], Hkm[36];
         for (int i = 0; i < 9; ++i) Hmm[i] = 0.0;
         for (int i = 0; i < 36; ++i) Hkm[i] = 0.0;
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(64) void k_sparsify(int npairs, const double* __res
             for (int a = 0; a < 9; ++a)
                 for (int b = 0; b < 9; ++b) {
                     const double v = J[a] * WJ[b] + J[9 + a] * WJ[9 + b] + J[18 + a] * WJ[18 + b];
-                    if (a < 6 && b < 6) acc[12 * (6 * k + a) + 6 * k + b] += v;
+                    if (a < 6 && b < 6) kf_blk[36 * (size_t)i + 6 * a + b] = v;
                     else if (a >= 6 && b >= 6) Hmm[3 * (a - 6) + (b - 6)] += v;
                     else if (a < 6) Hkm[3 * (6 * k + a) + (b - 6)] += v;
                 }
@@ -236,19 +238,28 @@ __global__ __launch_bounds__(64) void k_sparsify(int npairs, const double* __res
             for (int c = 0; c < 3; ++c) BD[3 * r + c] = Hkm[3 * r] * Hmm[c] + Hkm[3 * r + 1] * Hmm[3 + c] + Hkm[3 * r + 2] * Hmm[6 + c];
         for (int r = 0; r < 12; ++r)
             for (int c = 0; c < 12; ++c)
-                acc[144 + 12 * r + c] += BD[3 * r] * Hkm[3 * c] + BD[3 * r + 1] * Hkm[3 * c + 1] + BD[3 * r + 2] * Hkm[3 * c + 2];
+                acc[12 * r + c] += BD[3 * r] * Hkm[3 * c] + BD[3 * r + 1] * Hkm[3 * c + 1] + BD[3 * r + 2] * Hkm[3 * c + 2];
     }
     __threadfence_block();
     __syncthreads();
-    // Order of the sums: the reference (and the oracle) add the key-frame blocks measurement by measurement (= point by
-    // point: the measurements are grouped by point), then the regulariser, then subtract the Schur terms point by point.
-    // H11 is kept regular only by that 1e-6 I, so the order is part of the result (a pre-summed H11 moved the clamped
-    // spectrum by up to 100 % at 220 points): every entry is summed by one lane over the points in exactly that order.
+    // Order of the sums: the reference (and the oracle) add the key-frame blocks measurement by measurement IN THE ORDER THE
+    // MEASUREMENTS WERE GIVEN (sparsifier.cpp:134-161), then the regulariser, then subtract the Schur terms point by point
+    // (H12 * T).  H11 is kept regular only by that 1e-6 I, so the order is part of the result (a pre-summed H11, or the blocks
+    // added point by point for a caller that listed them otherwise, moved the clamped spectrum by up to 100 % at 220 points):
+    // every entry is summed by one lane in exactly that order.  An entry of key frame k's diagonal block takes the
+    // measurements of key frame k; the off-diagonal blocks receive Schur terms only.
     for (int i = lane; i < 144; i += 64) {
+        const int r = i / 12, c = i % 12, k = r / 6;
         double hsum = 0.0;
-        for (int j = mp_ptr[p]; j < mp_ptr[p + 1]; ++j) hsum += scratch[(size_t)j * 288 + i];
+        if (c / 6 == k) {
+            const int e = 6 * (r - 6 * k) + (c - 6 * k);
+            for (int q = ord_ptr[p]; q < ord_ptr[p + 1]; ++q) {
+                const int t = ord[q];
+                if (m_kf[t] == k) hsum += kf_blk[36 * (size_t)t + e];
+            }
+        }
         if (i % 13 == 0) hsum += 1e-6;
-        for (int j = mp_ptr[p]; j < mp_ptr[p + 1]; ++j) hsum -= scratch[(size_t)j * 288 + 144 + i];
+        for (int j = mp_ptr[p]; j < mp_ptr[p + 1]; ++j) hsum -= schur[(size_t)j * 144 + i];
         h11s[i] = hsum;
     }
     __syncthreads();
@@ -310,7 +321,7 @@ int se2gpu_sparsify_se3xyz(int npairs, const double* kf12, const int32_t* mp_ptr
                 "sparsify: NULL array");
     // measurements grouped by point (stable): a point's list in the order its measurements were given; measurements of a
     // key frame other than 0 / 1 are dropped (sparsifier.cpp:117-119)
-    std::vector<int> mm_ptr((size_t)NP + 1, 0), kf_s, src;
+    std::vector<int> mm_ptr((size_t)NP + 1, 0), kf_s, src, ord, ord_ptr((size_t)npairs + 1, 0);
     for (int p = 0; p < npairs; ++p) {
         const int n = mp_ptr[p + 1] - mp_ptr[p];
         for (int i = m_ptr[p]; i < m_ptr[p + 1]; ++i) {
@@ -322,20 +333,24 @@ int se2gpu_sparsify_se3xyz(int npairs, const double* kf12, const int32_t* mp_ptr
     for (int j = 0; j < NP; ++j) mm_ptr[j + 1] += mm_ptr[j];
     kf_s.resize(mm_ptr[NP]);
     src.resize(mm_ptr[NP]);
+    ord.reserve(src.size());   // ord: per pair, the grouped slot of every kept measurement in the order it was given
     {
         std::vector<int> fill(mm_ptr.begin(), mm_ptr.end() - 1);
-        for (int p = 0; p < npairs; ++p)
+        for (int p = 0; p < npairs; ++p) {
             for (int i = m_ptr[p]; i < m_ptr[p + 1]; ++i) {
                 if (m_kf[i] != 0 && m_kf[i] != 1) continue;
                 const int t = fill[(size_t)mp_ptr[p] + m_mp[i]]++;
                 kf_s[t] = m_kf[i];
                 src[t] = i;
+                ord.push_back(t);
             }
+            ord_ptr[(size_t)p + 1] = (int)ord.size();
+        }
     }
     std::vector<double> info_s(9 * (size_t)src.size());
     for (size_t t = 0; t < src.size(); ++t) std::memcpy(&info_s[9 * t], m_info + 9 * (size_t)src[t], 72);
-    DevBuf<double> d_kf, d_mp, d_info, d_scratch, d_z, d_out;
-    DevBuf<int> d_mpp, d_mmp, d_mkf;
+    DevBuf<double> d_kf, d_mp, d_info, d_blk, d_schur, d_z, d_out;
+    DevBuf<int> d_mpp, d_mmp, d_mkf, d_ordp, d_ord;
     hipStream_t st = nullptr;
     SE2_CHECK(d_kf.upload(kf12, 24 * (size_t)npairs, st));
     SE2_CHECK(d_mpp.upload(mp_ptr, (size_t)npairs + 1, st));
@@ -347,11 +362,15 @@ int se2gpu_sparsify_se3xyz(int npairs, const double* kf12, const int32_t* mp_ptr
     if (!kf_s.empty()) SE2_HIP(hipMemcpyAsync(d_mkf.p, kf_s.data(), kf_s.size() * 4, hipMemcpyHostToDevice, st));
     SE2_CHECK(d_info.reserve(std::max<size_t>(info_s.size(), 1)));
     if (!info_s.empty()) SE2_HIP(hipMemcpyAsync(d_info.p, info_s.data(), info_s.size() * 8, hipMemcpyHostToDevice, st));
-    SE2_CHECK(d_scratch.reserve((size_t)std::max(NP, 1) * 288));
+    SE2_CHECK(d_ordp.upload(ord_ptr.data(), ord_ptr.size(), st));
+    SE2_CHECK(d_ord.reserve(std::max<size_t>(ord.size(), 1)));
+    if (!ord.empty()) SE2_HIP(hipMemcpyAsync(d_ord.p, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, st));
+    SE2_CHECK(d_blk.reserve(std::max<size_t>(ord.size(), 1) * 36));
+    SE2_CHECK(d_schur.reserve((size_t)std::max(NP, 1) * 144));
     SE2_CHECK(d_z.reserve(12 * (size_t)npairs));
     SE2_CHECK(d_out.reserve(36 * (size_t)npairs));
     hipLaunchKernelGGL(k_sparsify, dim3(npairs), dim3(64), 0, st, npairs, d_kf.p, d_mpp.p, d_mp.p, d_mmp.p, d_mkf.p, d_info.p,
-                       d_scratch.p, d_z.p, d_out.p);
+                       d_ordp.p, d_ord.p, d_blk.p, d_schur.p, d_z.p, d_out.p);
     SE2_HIP(hipGetLastError());
     SE2_HIP(hipMemcpyAsync(z_out12, d_z.p, 12 * (size_t)npairs * 8, hipMemcpyDeviceToHost, st));
     SE2_HIP(hipMemcpyAsync(info_out36, d_out.p, 36 * (size_t)npairs * 8, hipMemcpyDeviceToHost, st));

@@ -5,8 +5,11 @@
 //   cvu::checkParallax /root/reference/src/cvutil.cpp:95-101
 // One thread per feature of the reference key frame.  cv::SVD::compute is OpenCV's one-sided Jacobi (Hestenes) in FP32;
 // the same algorithm runs here in FP64 on the FP32 system matrix, the point is rounded to FP32 at the end.  The CPU test
-// restatement executes the identical operation sequence, so the two agree bit for bit; agreement with OpenCV's own
-// float iteration is unpinned (OpenCV is not installed), expected ~1e-5 relative.
+// restatement executes the identical operation sequence, so the two agree bit for bit.  Beyond the restatement
+// (tests/test_track_independent.py): positions against LAPACK's SVD of the same float32 systems to 3 * 2^-24 per coordinate
+// plus 8 * 2^-52 * s1 / (s3 - s4) of singular-vector sensitivity; gates, flags and both counters recomputed from those FP64
+// positions, with at most 1 % of a scene's matches inside the tolerance of a threshold.  Agreement with OpenCV's own float
+// iteration is unpinned (OpenCV is not installed), expected ~1e-5 relative.
 // Compiled with -ffp-contract=off like the matchers.
 #include "track_ws.h"
 

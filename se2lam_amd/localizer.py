@@ -59,10 +59,14 @@ class Localizer:
         a, m = _pose12(Tcw), _pose12(prior_meas)
         pi = np.ascontiguousarray(prior_info, np.float64).reshape(-1)
         out = np.zeros(12)
-        st = capi.BaStats()
+        # the statistics struct inside a larger buffer: the bytes behind it must come back untouched
+        buf = (C.c_uint8 * (C.sizeof(capi.BaStats) + 64))()
+        C.memset(C.byref(buf, C.sizeof(capi.BaStats)), 0xA5, 64)
+        st = capi.BaStats.from_buffer(buf)
         capi.check(capi.lib().se2gpu_track_pose_ba(self._h, a.ctypes.data, m.ctypes.data, pi.ctypes.data, len(xyz),
                                                    xyz.ctypes.data, uv.ctypes.data, w.ctypes.data, float(f), float(cx),
                                                    float(cy), float(delta), int(iterations), out.ctypes.data, C.byref(st)))
+        self.stats_tail_intact = all(b == 0xA5 for b in buf[C.sizeof(capi.BaStats):])
         n = min(st.iterations, 64)
         self.stats = dict(iterations=st.iterations, trials=st.trials, terminated=bool(st.terminated),
                           chi2_init=st.chi2_init, chi2_final=st.chi2_final, lambda_final=st.lambda_final,

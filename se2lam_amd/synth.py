@@ -900,3 +900,133 @@ def odometry_topology3(g: "BA3Graph", kind: str, seed: int = 0) -> "BA3Graph":
     else:
         raise ValueError("unknown SE3 odometry topology %r" % kind)
     return with_odometry3(g, pairs, seed=seed, fixed=fixed, has_prior=has_prior)
+
+
+# --------------------------------------------------------------------------
+# Tracking / mapping thread inputs (Track::doTriangulate, Track::removeOutliers, Localizer::DoLocalBA,
+# Sparsifier::DoMarginalizeSE3XYZ): scene families for tests/test_track_independent.py and tools/fuzz_gpu.py
+# --------------------------------------------------------------------------
+KEYPOINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                     ("class_id", "<i4")])
+
+# name -> (baseline mm, turn rad, depth range mm, pixel noise, current camera == reference camera)
+TRIANGULATION_SCENES = {
+    "benign": (150.0, 0.03, (300.0, 12000.0), 0.0, False),
+    "low_parallax": (2.0, 0.0005, (300.0, 12000.0), 0.0, False),
+    "far": (150.0, 0.03, (20000.0, 200000.0), 0.0, False),
+    "behind": (150.0, 0.03, (-3000.0, 600.0), 0.0, False),
+    "zero_baseline": (0.0, 0.0, (300.0, 12000.0), 0.0, True),
+    "noisy": (150.0, 0.03, (300.0, 12000.0), 0.3, False),
+}
+
+
+def triangulation_scene(kind: str = "benign", n: int = 600, seed: int = 7):
+    """Two views of n points for Track::doTriangulate: the reference camera at the origin (Config::PrjMtrxEye), the current one
+    `baseline` mm to the side and turned about y.  Every reference feature is matched (a permutation) except each 17th.
+    -> (kps_ref, kps_cur, match_idx, has_obs, P_ref, P_cur, Ocam, X)"""
+    base, th, (zlo, zhi), noise, same = TRIANGULATION_SCENES[kind]
+    rng = np.random.default_rng(seed)
+    K = np.array([[FX, 0, CX], [0, FX, CY], [0, 0, 1]], np.float32)
+    R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]], np.float32)
+    t = np.array([-base, base / 30.0, base / 7.5], np.float32)
+    Tcr = np.eye(4, dtype=np.float32)
+    if not same:
+        Tcr[:3, :3] = R
+        Tcr[:3, 3] = t
+    P1 = (K @ np.eye(3, 4, dtype=np.float32)).astype(np.float32)
+    P2 = (K @ Tcr[:3]).astype(np.float32)
+    z = rng.uniform(zlo, zhi, n)
+    z = np.where(np.abs(z) < 50.0, 50.0, z)                     # nothing in the camera's own plane (u = x / 0)
+    X = np.stack([rng.uniform(-0.125, 0.125, n) * np.abs(z) * 4, rng.uniform(-0.1, 0.1, n) * np.abs(z) * 4, z], 1).astype(np.float32)
+    Xh = np.concatenate([X, np.ones((n, 1), np.float32)], 1)
+    u1 = (P1 @ Xh.T).T; u1 = u1[:, :2] / u1[:, 2:]
+    u2 = (P2 @ Xh.T).T; u2 = u2[:, :2] / u2[:, 2:]
+    if noise:
+        u2 = u2 + rng.normal(0, noise, (n, 2))
+    k1 = np.zeros(n, KEYPOINT); k2 = np.zeros(n, KEYPOINT)
+    k1["x"], k1["y"] = u1[:, 0], u1[:, 1]
+    perm = rng.permutation(n)
+    k2["x"][perm], k2["y"][perm] = u2[:, 0], u2[:, 1]
+    match = perm.astype(np.int32)
+    match[::17] = -1
+    has_obs = np.zeros(n, np.uint8); has_obs[5::23] = 1
+    Ocam = np.linalg.inv(Tcr)[:3, 3].astype(np.float32)
+    return k1, k2, match, has_obs, P1, P2, Ocam, X
+
+
+def two_view_matches(seed: int, n: int, outlier_frac: float = 0.3, noise: float = 0.5):
+    """n correspondences between two views for cv::findFundamentalMat: a turn about y of up to 0.08 rad and up to 300 mm of
+    translation, `noise` px on both sides, a share `outlier_frac` of the second view moved by up to 80 px.
+    -> (pt1 (n,2) f32, pt2 (n,2) f32, outlier flags)"""
+    rng = np.random.default_rng(seed)
+    X = np.stack([rng.uniform(-3000, 3000, n), rng.uniform(-2000, 2000, n), rng.uniform(3000, 9000, n)], 1)
+    K = np.array([[400, 0, 320], [0, 400, 240], [0, 0, 1.0]])
+    th = rng.uniform(-0.08, 0.08)
+    R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]])
+    t = rng.uniform(-300, 300, 3)
+
+    def proj(R, t):
+        uv = (X @ R.T + t) @ K.T
+        return uv[:, :2] / uv[:, 2:]
+
+    p1 = proj(np.eye(3), np.zeros(3)) + rng.normal(0, noise, (n, 2))
+    p2 = proj(R, t) + rng.normal(0, noise, (n, 2))
+    out = rng.random(n) < outlier_frac
+    p2[out] += rng.uniform(-80, 80, (int(out.sum()), 2))
+    return p1.astype(np.float32), p2.astype(np.float32), out
+
+
+def body_pose(x, y, th):
+    c, s = np.cos(th), np.sin(th)
+    return np.array([[c, -s, 0, x], [s, c, 0, y], [0, 0, 1, 0], [0, 0, 0, 1.0]])
+
+
+def pose_ba_case(seed: int, n: int = 400, outliers: float = 0.1, noise: float = 0.7, yaw=None, weights: str = "levels",
+                 behind: int = 0, start=(40.0, 0.03)):
+    """One Localizer::DoLocalBA problem: n map points in front of a camera on the plane, observed with `noise` px and a share
+    of gross outliers, and a start pose start[0] mm / start[1] rad (standard deviations) away.
+    yaw: the body's heading (default: uniform in +-3); weights "levels" = 1.2^-2l for l < 8, "wide" = 1.2^-l for l <= 14 with a
+    few exact zeros; behind: that many points moved to negative camera depth.
+    -> (Tcw_true, Tcw0, Xw (n,3), uv (n,2), w (n,), pose (x, y, yaw))"""
+    rng = np.random.default_rng(seed)
+    pose = (rng.uniform(-2000, 2000), rng.uniform(-2000, 2000), rng.uniform(-3, 3))
+    if yaw is not None:
+        pose = (pose[0], pose[1], float(yaw))
+    Tbc = np.eye(4); Tbc[:3, :3] = RBC; Tbc[:3, 3] = TBC
+    Tcw_true = np.linalg.inv(body_pose(*pose) @ Tbc)
+    Xc = np.stack([rng.uniform(-2000, 2000, n), rng.uniform(-1500, 1500, n), rng.uniform(1500, 8000, n)], 1)
+    uv = FX * Xc[:, :2] / Xc[:, 2:] + [CX, CY] + rng.normal(0, noise, (n, 2))
+    if behind:
+        Xc[rng.choice(n, min(behind, n), replace=False), 2] *= -1.0
+    Xw = (np.linalg.inv(Tcw_true) @ np.c_[Xc, np.ones(n)].T).T[:, :3]
+    out = rng.random(n) < outliers
+    uv[out] += rng.uniform(-50, 50, (int(out.sum()), 2))
+    if weights == "levels":
+        w = 1.0 / 1.2 ** (2 * rng.integers(0, 8, n))
+    else:
+        w = 1.0 / 1.2 ** rng.integers(0, 15, n).astype(np.float64)
+        w[rng.random(n) < 0.03] = 0.0
+    Tcw0 = np.linalg.inv(body_pose(pose[0] + rng.normal(0, start[0]), pose[1] + rng.normal(0, start[0]),
+                                   pose[2] + rng.normal(0, start[1])) @ Tbc)
+    return Tcw_true, Tcw0, Xw, uv, w, pose
+
+
+KF_PAIR_ORDERS = ("grouped", "kf_major", "reversed", "permuted")
+
+
+def kf_pair_reorder(pair, order: str, seed: int = 0):
+    """The measurements of a kf_pair in another order: "grouped" (point, key frame 0, key frame 1 - as generated), "kf_major"
+    (all of key frame 0, then all of key frame 1: GlobalMapper::CreateVecMeasSE3XYZ), "reversed", "permuted"."""
+    kf, mp, m_kf, m_mp, m_info = pair
+    M = len(m_kf)
+    if order == "grouped":
+        idx = np.arange(M)
+    elif order == "kf_major":
+        idx = np.argsort(m_kf, kind="stable")
+    elif order == "reversed":
+        idx = np.arange(M)[::-1]
+    elif order == "permuted":
+        idx = np.random.default_rng(seed).permutation(M)
+    else:
+        raise ValueError(order)
+    return kf, mp, m_kf[idx].copy(), m_mp[idx].copy(), m_info[idx].copy()

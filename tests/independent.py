@@ -212,3 +212,469 @@ def ba3_full_normal_equations(g, lam, log=se3_log_g2o):
         add([np.arange(6 * i, 6 * i + 6), np.arange(6 * j, 6 * j + 6)], [Ji, Jj], g.o_info[k], e)
     H += lam * np.eye(N)
     return H, b
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Tracking / mapping thread kernels (csrc/triangulate.hip, ransac.hip, pose_ba.hip, sparsify.hip): references written from
+# the definitions with numpy / scipy only.  Each check_* function takes the inputs and ONE implementation's outputs (the CPU
+# restatement's or the HIP path's - the same checker serves both) and raises AssertionError; it returns the measured figures.
+# ------------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24          # unit round-off of float
+U64 = 2.0 ** -53
+MIN_COS = (0.9998, 0.9994, 0.9986, 0.9976)   # cvu::checkParallax, minDegree 1..4 (as floats in the kernel)
+
+# Constant of the singular-vector term of the triangulation tolerance, see triangulation_reference.  LAPACK's dgesdd and a
+# one-sided Jacobi SVD are both backward stable: each returns the exact singular vectors of A + E with |E| <= p(4) * 2^-52 * s1
+# for a modest polynomial p of the dimension.  The two vectors then differ by at most (|E_lapack| + |E_jacobi|) / gap.  C = 8
+# allows p(4) = 4 (the dimension) on each side; it was fixed from this argument before any HIP output was looked at, and the
+# restatement needs less than 1 % of it on every scene of the suite (profiles/track_independent.md).
+TRI_C = 8.0
+
+
+def triangulation_reference(kps_ref, kps_cur, match_idx, P_ref, P_cur):
+    """cvu::triangulate (cvutil.cpp:46-59) from its definition: the 4x4 system built in float exactly as the cv::Mat
+    arithmetic does (those float rows ARE the input), widened, numpy's (LAPACK's) SVD, the last right singular vector
+    dehomogenised in FP64.  -> X (n,3) f64 (NaN rows where unmatched), tol (n,3) absolute per coordinate, sv (n,4).
+    Tolerance, derived: the implementation rounds v0..v3 to float and divides in float - three roundings per coordinate,
+    3 * 2^-24 relative to the coordinate; and its unit singular vector may differ from LAPACK's by eta = TRI_C * 2^-52 *
+    s1 / (s3 - s4) (perturbation of a simple singular vector, gap to the nearest other singular value), which moves
+    X_c = v_c / v_3 by at most eta * (1 + |X_c|) / |v_3| = eta * (1 + |X_c|) * |(X, 1)|."""
+    n = len(kps_ref)
+    m = np.asarray(match_idx)
+    sel = np.flatnonzero(m >= 0)
+    X = np.full((n, 3), np.nan); tol = np.full((n, 3), np.nan); sv = np.full((n, 4), np.nan)
+    if sel.size == 0:
+        return X, tol, sv
+    P1 = np.asarray(P_ref, np.float32).reshape(3, 4); P2 = np.asarray(P_cur, np.float32).reshape(3, 4)
+    x1 = kps_ref["x"][sel].astype(np.float32)[:, None]; y1 = kps_ref["y"][sel].astype(np.float32)[:, None]
+    x2 = kps_cur["x"][m[sel]].astype(np.float32)[:, None]; y2 = kps_cur["y"][m[sel]].astype(np.float32)[:, None]
+    A = np.stack([x1 * P1[2] - P1[0], y1 * P1[2] - P1[1], x2 * P2[2] - P2[0], y2 * P2[2] - P2[1]], 1)
+    assert A.dtype == np.float32
+    _, s, Vt = np.linalg.svd(A.astype(np.float64))
+    v = Vt[:, 3, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Xs = v[:, :3] / v[:, 3:]
+        eta = TRI_C * 2.0 ** -52 * s[:, 0] / (s[:, 2] - s[:, 3])
+        t = 3 * U32 * np.abs(Xs) + eta[:, None] * (1 + np.abs(Xs)) * np.sqrt(1 + (Xs * Xs).sum(1))[:, None]
+    X[sel], tol[sel], sv[sel] = Xs, t, s
+    return X, tol, sv
+
+
+def check_triangulation(inputs, outputs, degenerate=False):
+    """inputs = (kps_ref, kps_cur, match_idx, has_obs, P_ref, P_cur, Ocam, lower, upper, min_degree); outputs = (pos, good,
+    match_out, n_good, n_tracked_old) of Track::doTriangulate.  Positions against triangulation_reference within its tolerance;
+    the depth gate, the match_idx update, the parallax flag and both counters recomputed from the FP64 positions.  A point
+    whose FP64 depth (parallax cosine) lies within the tolerance of a threshold may fall either way; at most 1 % of the matched
+    points of a scene may be such points.  degenerate: the null space is not a line (P_cur == P_ref) - only "finite or dropped,
+    never a NaN kept" is asserted.  -> dict(worst share of the tolerance used, borderline share)"""
+    kps_ref, kps_cur, match_idx, has_obs, P_ref, P_cur, Ocam, lower, upper, min_degree = inputs
+    pos, good, m_out, n_good, n_old = outputs
+    n = len(kps_ref)
+    m_in = np.asarray(match_idx, np.int32)
+    pos = np.asarray(pos); good = np.asarray(good).astype(bool); m_out = np.asarray(m_out)
+    assert pos.shape == (n, 3) and good.shape == (n,) and m_out.shape == (n,) and pos.dtype == np.float32
+    obs = np.zeros(n, bool) if has_obs is None else np.asarray(has_obs).astype(bool)
+    matched = m_in >= 0
+    todo = matched & ~obs
+    # the counters come from device atomics: they must equal what the arrays say, always
+    assert n_good == int(good.sum()), (n_good, int(good.sum()))
+    assert n_old == int((matched & obs).sum()), (n_old, int((matched & obs).sum()))
+    # features that are not triangulated: untouched
+    assert np.array_equal(m_out[~todo], m_in[~todo]) and not pos[~todo].any() and not good[~todo].any()
+    kept = todo & (m_out >= 0)
+    assert np.array_equal(m_out[kept], m_in[kept]) and (m_out[todo & ~kept] == -1).all()
+    assert not pos[todo & ~kept].any() and not good[todo & ~kept].any()
+    assert np.isfinite(pos).all()                                   # never a NaN kept, whatever the geometry
+    assert (pos[kept, 2] >= np.float32(lower)).all() and (pos[kept, 2] <= np.float32(upper)).all()
+    if degenerate or not todo.any():
+        return dict(used=0.0, borderline=0.0)
+    X, tol, _ = triangulation_reference(kps_ref, kps_cur, m_in, P_ref, P_cur)
+    assert np.isfinite(X[todo]).all() and np.isfinite(tol[todo]).all()
+    Z, tz = X[:, 2], tol[:, 2]
+    lo, hi = float(np.float32(lower)), float(np.float32(upper))
+    near_gate = todo & ((np.abs(Z - lo) <= tz) | (np.abs(Z - hi) <= tz))
+    inside = (Z >= lo) & (Z <= hi)
+    clear = todo & ~near_gate
+    assert np.array_equal(kept[clear], inside[clear]), "depth gate differs from the FP64 depth outside the tolerance"
+    used = np.abs(pos[kept].astype(np.float64) - X[kept]) / tol[kept]
+    worst = float(used.max()) if used.size else 0.0
+    assert worst <= 1.0, "position off by %.3g of the derived tolerance" % worst
+    # cvu::checkParallax(o1 = 0, o2 = Ocam, pt3): cos = |p . (p - O)| / (|p| |p - O|) < minCos (a float constant).  Tolerance of
+    # the cosine: d cos <= d angle <= |dp| / |p| + |dp| / |p - O| from the position tolerance, plus the float evaluation: one
+    # rounding in each p - O, one per product, two sums, |dot| <= |p||q| and cos ~ 1: 4 * 2^-24 / cos; one for p - O inside the
+    # norms; one for the final cast: 6 * 2^-24, taken as 8.
+    O = np.asarray(Ocam, np.float32).astype(np.float64)
+    q = X - O
+    npn, nq = np.linalg.norm(X, axis=1), np.linalg.norm(q, axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cosp = np.abs((X * q).sum(1)) / (npn * nq)
+        tcos = 8 * U32 + np.linalg.norm(tol, axis=1) * (1 / npn + 1 / nq)
+    mc = float(np.float32(MIN_COS[min_degree - 1]))
+    near_cos = kept & (np.abs(cosp - mc) <= tcos)
+    sure = kept & ~near_cos & ~near_gate
+    assert np.array_equal(good[sure], cosp[sure] < mc), "parallax flag differs from the FP64 cosine outside the tolerance"
+    share = float((near_gate | near_cos).sum()) / float(matched.sum())
+    assert share <= 0.01, "%.2f %% of the matched points lie within the tolerance of a threshold" % (100 * share)
+    return dict(used=worst, borderline=share)
+
+
+# ---------------------------------------------------------------------------------------------------------- sparsifier
+def _min_of(T):
+    from scipy.spatial.transform import Rotation
+    q = Rotation.from_matrix(T[:3, :3]).as_quat()
+    if q[3] < 0:
+        q = -q
+    return np.r_[T[:3, 3], q[:3]]
+
+
+def _from_min(v):
+    from scipy.spatial.transform import Rotation
+    w2 = 1 - v[3:] @ v[3:]
+    T = np.eye(4)
+    T[:3, :3] = Rotation.from_quat([v[3], v[4], v[5], np.sqrt(max(w2, 0.0))]).as_matrix()
+    T[:3, 3] = v[:3]
+    return T
+
+
+def sparsify_numpy_model(kf, mp, m_kf, m_mp, m_info):
+    """Sparsifier::DoMarginalizeSE3XYZ from its definition: central-difference Jacobians of the minimal parametrisation with
+    scipy's quaternions, dense Schur complement, numpy's inverse and eigh -> (z, information, marginal Hessian)"""
+    N = len(mp)
+    H = np.zeros((12 + 3 * N, 12 + 3 * N))
+    h = 1e-6
+    for k, m, W in zip(m_kf, m_mp, m_info):
+        if k not in (0, 1):
+            continue                                   # sparsifier.cpp:117-119
+        v = _min_of(kf[k])
+        f = lambda vv, pp: (np.linalg.inv(_from_min(vv)) @ np.r_[pp, 1.0])[:3]
+        J = np.zeros((3, 9))
+        for i in range(6):
+            d = np.zeros(6); d[i] = h
+            J[:, i] = (f(v + d, mp[m]) - f(v - d, mp[m])) / (2 * h)
+        for i in range(3):
+            d = np.zeros(3); d[i] = h
+            J[:, 6 + i] = (f(v, mp[m] + d) - f(v, mp[m] - d)) / (2 * h)
+        idx = np.r_[6 * k + np.arange(6), 12 + 3 * m + np.arange(3)]
+        H[np.ix_(idx, idx)] += J.T @ W @ J
+    H[:12, :12] += 1e-6 * np.eye(12)
+    seen = np.flatnonzero(np.abs(H[12:, 12:]).reshape(N, 3, -1).sum((1, 2)) > 0) if N else np.zeros(0, int)
+    pts = (12 + 3 * seen[:, None] + np.arange(3)).reshape(-1)      # points without a measurement drop out
+    Hm = H[:12, :12] - (H[:12, pts] @ np.linalg.solve(H[np.ix_(pts, pts)], H[pts, :12]) if pts.size else 0.0)
+    z = lambda a, b: _min_of(np.linalg.inv(_from_min(a)) @ _from_min(b))
+    v1, v2 = _min_of(kf[0]), _min_of(kf[1])
+    J = np.zeros((6, 12))
+    for i in range(6):
+        d = np.zeros(6); d[i] = h
+        J[:, i] = (z(v1 + d, v2) - z(v1 - d, v2)) / (2 * h)
+        J[:, 6 + i] = (z(v1, v2 + d) - z(v1, v2 - d)) / (2 * h)
+    I = np.linalg.inv(J @ np.linalg.inv(Hm) @ J.T)
+    I = 0.5 * (I + I.T)
+    lam, U = np.linalg.eigh(I)
+    lam = np.where(lam < 0, 1e-6, np.clip(lam, 1e-6, 1e4))
+    return np.linalg.inv(kf[0]) @ kf[1], (U * lam) @ U.T, Hm
+
+
+def check_sparsify(pair, z, info, model=None, spectrum=True):
+    """One implementation's (z, information) of a key-frame pair against the numpy model: z = KF0^-1 KF1 to 1e-9, exact
+    symmetry, the spectrum inside the clamp [1e-6, 1e4]; and with spectrum=True (pairs with enough points for the model to be
+    well determined) the rotation eigenvalues at the 1e4 clamp and the translation ones within a factor 2 of the model's.
+    (The step from the marginal Hessian to the information is ill-conditioned by construction - six gauge freedoms held by
+    a 1e-6 regulariser - so forward against central differences move the small eigenvalues by tens of per cent.)"""
+    kf = pair[0]
+    z = np.asarray(z); info = np.asarray(info)
+    assert np.isfinite(z).all() and np.isfinite(info).all()
+    assert np.allclose(z, np.linalg.inv(kf[0]) @ kf[1], rtol=0, atol=1e-9)
+    assert np.abs(info - info.T).max() == 0
+    lam = np.linalg.eigvalsh(info)
+    # (eigvalsh and the implementation's own V diag(lam) V' are each exact for a matrix 2^-52 |info| p(6) away, so an eigenvalue
+    # sitting AT the 1e-6 floor of a matrix of norm 1e4 is only known to 64 * 2^-52 * 1e4 = 1.4e-10 absolute)
+    assert lam.min() >= 1e-6 * (1 - 1e-9) - 64 * 2.0 ** -52 * lam.max() and lam.max() <= 1e4 * (1 + 1e-9)
+    if not spectrum:
+        return
+    zn, infon, _ = sparsify_numpy_model(*pair) if model is None else model
+    assert np.allclose(z, zn, rtol=0, atol=1e-9)
+    ln = np.sort(np.linalg.eigvalsh(infon))
+    lo = np.sort(lam)
+    assert np.allclose(lo[3:], 1e4, rtol=1e-6) and np.allclose(ln[3:], 1e4, rtol=1e-6)
+    assert np.all(lo[1:3] > 0.5 * ln[1:3]) and np.all(lo[1:3] < 2.0 * ln[1:3]) and 1e-6 <= lo[0] < lo[1]
+
+
+def check_sparsify_equals(z, info, z_ref, info_ref):
+    """an implementation's output against the restatement's FOR THE SAME MEASUREMENT ORDER: the suite's tolerances"""
+    assert np.allclose(z, z_ref, atol=1e-12)
+    assert np.abs(info - info_ref).max() <= 1e-5 * np.abs(info_ref).max(), np.abs(info - info_ref).max() / np.abs(info_ref).max()
+
+
+# ------------------------------------------------------------------------------------------------------- pose-only BA
+def _hat(w):
+    return np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def se3_log_scipy(T):
+    """log of a rigid transform in g2o's order (rotation vector, then V^-1 t), the rotation vector from scipy"""
+    from scipy.spatial.transform import Rotation
+    w = Rotation.from_matrix(T[:3, :3]).as_rotvec()
+    th = np.linalg.norm(w)
+    K = _hat(w)
+    Vi = np.eye(3) - 0.5 * K + ((1 / 12.0) if th < 1e-6 else (1 - th / (2 * np.tan(th / 2))) / th ** 2) * K @ K
+    return np.concatenate([w, Vi @ T[:3, 3]])
+
+
+def se3_exp_scipy(d):
+    from scipy.spatial.transform import Rotation
+    w, v = np.asarray(d[:3], float), np.asarray(d[3:], float)
+    th = np.linalg.norm(w)
+    K = _hat(w)
+    if th < 1e-6:
+        V = np.eye(3) + 0.5 * K + K @ K / 6.0
+    else:
+        V = np.eye(3) + (1 - np.cos(th)) / th ** 2 * K + (th - np.sin(th)) / th ** 3 * K @ K
+    T = np.eye(4)
+    T[:3, :3] = Rotation.from_rotvec(w).as_matrix()
+    T[:3, 3] = V @ v
+    return T
+
+
+class PoseBANumpy:
+    """Localizer::DoLocalBA's cost from the definitions of its two edge types:
+       sum_i huber(w_i |uv_i - project(T X_i)|^2) + e' Omega e,  e = log(meas T^-1) in (rotation, translation) order,
+    huber(s) = s if s <= delta^2 else 2 delta sqrt(s) - delta^2 (g2o's RobustKernelHuber on the edge's chi2; none on the prior)."""
+
+    def __init__(self, meas, info, X, uv, w, f, cx, cy, delta):
+        self.meas = np.asarray(meas, float); self.info = np.asarray(info, float).reshape(6, 6)
+        self.X = np.asarray(X, float).reshape(-1, 3); self.uv = np.asarray(uv, float).reshape(-1, 2)
+        self.w = np.asarray(w, float).reshape(-1)
+        self.f, self.cx, self.cy, self.delta = float(f), float(cx), float(cy), float(delta)
+        lam, U = np.linalg.eigh(0.5 * (self.info + self.info.T))
+        self.S = np.sqrt(np.clip(lam, 0, None))[:, None] * U.T     # Omega = S' S up to round-off: for the residual vector only
+
+    def _parts(self, T):
+        p = self.X @ T[:3, :3].T + T[:3, 3]
+        r = self.uv - np.stack([self.f * p[:, 0] / p[:, 2] + self.cx, self.f * p[:, 1] / p[:, 2] + self.cy], 1)
+        return r, se3_log_scipy(self.meas @ np.linalg.inv(T))
+
+    def cost(self, T):
+        r, e = self._parts(np.asarray(T, float))
+        s = self.w * (r * r).sum(1)
+        d2 = self.delta ** 2
+        return float(np.where(s <= d2, s, 2 * self.delta * np.sqrt(s) - d2).sum() + e @ self.info @ e)
+
+    def residuals(self, T):
+        """vector whose squared norm is cost(T)"""
+        r, e = self._parts(T)
+        s = self.w * (r * r).sum(1)
+        d2 = self.delta ** 2
+        rho = np.where(s <= d2, s, 2 * self.delta * np.sqrt(np.maximum(s, 1e-300)) - d2)
+        k = np.sqrt(self.w * rho / np.maximum(s, 1e-300))
+        return np.concatenate([(r * k[:, None]).reshape(-1), self.S @ e])
+
+    def minimise(self, T0):
+        """scipy's trust-region least squares over d, T = exp(d) T0 -> (T, cost(T))"""
+        from scipy.optimize import least_squares
+        T0 = np.asarray(T0, float)
+        sol = least_squares(lambda d: self.residuals(se3_exp_scipy(d) @ T0), np.zeros(6), jac="3-point", method="trf",
+                            x_scale=np.array([1e-3] * 3 + [1.0] * 3), ftol=1e-15, xtol=1e-15, gtol=1e-13, max_nfev=400)
+        T = se3_exp_scipy(sol.x) @ T0
+        return T, self.cost(T)
+
+
+def check_pose_ba(problem, Tcw0, T_out, stats, tol_final, margin):
+    """problem: PoseBANumpy; T_out, stats: one implementation's result.  chi2_init / chi2_final equal the independent cost at
+    the input / returned pose (1e-12 / tol_final relative); scipy started from the returned pose lowers the cost by at most
+    `margin` (relative), and started from the input pose does not end lower than the result by more than `margin`.
+    -> dict of the measured figures (relative)."""
+    c0, c1 = problem.cost(Tcw0), problem.cost(T_out)
+    assert np.isfinite(np.asarray(T_out)).all()
+    d_init = abs(stats["chi2_init"] - c0) / c0
+    d_final = abs(stats["chi2_final"] - c1) / c1
+    assert d_init <= 1e-12, ("chi2_init", stats["chi2_init"], c0, d_init)
+    assert d_final <= tol_final, ("chi2_final", stats["chi2_final"], c1, d_final)
+    _, ca = problem.minimise(T_out)
+    _, cb = problem.minimise(Tcw0)
+    short_a, short_b = (c1 - ca) / c1, (c1 - cb) / c1
+    assert short_a <= margin, ("scipy improves on the returned pose", c1, ca, short_a)
+    assert short_b <= margin, ("scipy from the input pose ends lower", c1, cb, short_b)
+    return dict(d_init=d_init, d_final=d_final, shortfall=max(short_a, short_b, 0.0))
+
+
+def plane_motion_prior_numpy(Tcw, Tbc, xrot=1e6, yrot=1e6, zinfo=1.0):
+    """addPlaneMotionSE3Expmap (optimizer.cpp:236-314) from its definition.  Measurement: the body pose T_bw = T_bc T_cw with
+    height, roll and pitch removed (yaw = z component of the rotation vector... of the body rotation, translation (x, y, 0)),
+    back in the camera frame.  Information: adj(T_bc)' diag(xrot, yrot, 1e-4, 1e-4, 1e-4, zinfo) adj(T_bc), the SE(3) adjoint in
+    (rotation, translation) order: adj(T) = [[R, 0], [[t]x R, R]]; the upper triangle copied down (:296-298)."""
+    from scipy.spatial.transform import Rotation
+    Tcw = np.asarray(Tcw, float); Tbc = np.asarray(Tbc, float)
+    Tbw = Tbc @ Tcw
+    yaw = Rotation.from_matrix(Tbw[:3, :3]).as_rotvec()[2]
+    M = np.eye(4)
+    M[:3, :3] = Rotation.from_rotvec([0, 0, yaw]).as_matrix()
+    M[:3, 3] = [Tbw[0, 3], Tbw[1, 3], 0.0]
+    R, t = Tbc[:3, :3], Tbc[:3, 3]
+    A = np.zeros((6, 6))
+    A[:3, :3] = R; A[3:, 3:] = R; A[3:, :3] = _hat(t) @ R
+    info = A.T @ np.diag([xrot, yrot, 1e-4, 1e-4, 1e-4, zinfo]) @ A
+    iu = np.triu_indices(6, 1)
+    info[(iu[1], iu[0])] = info[iu]
+    return np.linalg.inv(Tbc) @ M, info
+
+
+# ------------------------------------------------------------------------------------------ fundamental-matrix RANSAC
+def ransac_update_num_iters(p, ep, model_points, max_iters):
+    """cv::RANSACUpdateNumIters (ptsetreg.cpp) written out: log(1 - p) / log(1 - (1 - ep)^model_points), rounded to nearest,
+    never above max_iters; 0 when every point is an inlier"""
+    p = min(max(p, 0.0), 1.0); ep = min(max(ep, 0.0), 1.0)
+    num = max(1.0 - p, 2.2250738585072014e-308)
+    denom = 1.0 - (1.0 - ep) ** model_points
+    if denom < 2.2250738585072014e-308:
+        return 0
+    num, denom = np.log(num), np.log(denom)
+    if denom >= 0 or -num >= max_iters * (-denom):
+        return max_iters
+    return int(np.rint(num / denom))
+
+
+def seven_point_numpy(x1, x2):
+    """OpenCV's documented 7-point method on seven correspondences (7,2) f64: null space of the 7x9 system by numpy's SVD, the
+    cubic det(l F1 + (1 - l) F2) by interpolation at four l and np.roots, the real roots, each F scaled to F[2,2] = 1
+    -> list of 3x3"""
+    A = np.stack([x2[:, 0] * x1[:, 0], x2[:, 0] * x1[:, 1], x2[:, 0], x2[:, 1] * x1[:, 0], x2[:, 1] * x1[:, 1], x2[:, 1],
+                  x1[:, 0], x1[:, 1], np.ones(7)], 1)
+    if not np.isfinite(A).all():
+        return []
+    Vt = np.linalg.svd(A)[2]
+    F1, F2 = Vt[7].reshape(3, 3), Vt[8].reshape(3, 3)
+    ls = np.array([0.0, 1.0, -1.0, 2.0])
+    dets = np.array([np.linalg.det(l * F1 + (1 - l) * F2) for l in ls])
+    coef = np.linalg.solve(np.vander(ls, 4), dets)
+    if not np.isfinite(coef).all() or not np.any(coef[:3]):
+        return []
+    out = []
+    for r in np.roots(coef):
+        if r.imag != 0:
+            continue
+        Fm = r.real * F1 + (1 - r.real) * F2
+        if abs(Fm[2, 2]) > 2.220446049250313e-16:
+            Fm = Fm / Fm[2, 2]
+        out.append(Fm)
+    return out
+
+
+def epipolar_errors(F, p1, p2):
+    """FMEstimatorCallback::computeError from its definition, FP64: err_i = max(d1^2 / (b0^2 + b1^2), d2^2 / (a0^2 + a1^2)) with
+    a = F x1, b = F' x2, d2 = x2 . a, d1 = x1 . b; and per point a forward bound `dev` of what evaluating the same expression in
+    float32 can move it by: a sum of k terms evaluated in float is off by at most (k + 1) u32 sum |terms| (products rounded,
+    then added left to right), so  |dd| <= 8 u S_d  (nine products of three factors),  |da| <= 4 u S_a;  then
+    d^2 / (a0^2 + a1^2) moves by at most  (2 |dd| |d| + err * 2 (|a0| da0 + |a1| da1)) / (a0^2 + a1^2) + 8 u err.
+    F: (m,3,3); p1, p2: (n,2) -> err (m,n), dev (m,n)"""
+    F = np.asarray(F, float).reshape(-1, 3, 3)
+    x1 = np.c_[np.asarray(p1, float), np.ones(len(p1))]; x2 = np.c_[np.asarray(p2, float), np.ones(len(p2))]
+    aF = np.abs(F)
+    a = np.einsum("mij,nj->mni", F, x1); Sa = np.einsum("mij,nj->mni", aF, np.abs(x1))
+    b = np.einsum("mji,nj->mni", F, x2); Sb = np.einsum("mji,nj->mni", aF, np.abs(x2))
+    d2 = (a * x2).sum(2); Sd2 = (Sa * np.abs(x2)).sum(2)
+    d1 = (b * x1).sum(2); Sd1 = (Sb * np.abs(x1)).sum(2)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        na = a[..., 0] ** 2 + a[..., 1] ** 2; nb = b[..., 0] ** 2 + b[..., 1] ** 2
+        e2 = d2 * d2 / na; e1 = d1 * d1 / nb
+        v2 = (16 * U32 * Sd2 * np.abs(d2) + e2 * 8 * U32 * (np.abs(a[..., 0]) * Sa[..., 0] + np.abs(a[..., 1]) * Sa[..., 1])) / na + 8 * U32 * e2
+        v1 = (16 * U32 * Sd1 * np.abs(d1) + e1 * 8 * U32 * (np.abs(b[..., 0]) * Sb[..., 0] + np.abs(b[..., 1]) * Sb[..., 1])) / nb + 8 * U32 * e1
+    return np.maximum(e1, e2), np.maximum(v1, v2)
+
+
+def fm_all_models(p1, p2, subsets):
+    """the numpy 7-point models of every sample -> (F (M,3,3), sample index (M,)) in (sample, root) order"""
+    x1 = np.asarray(p1, float); x2 = np.asarray(p2, float)
+    Fs, its = [], []
+    for it, idx in enumerate(subsets):
+        for Fm in seven_point_numpy(x1[idx], x2[idx]):
+            Fs.append(Fm); its.append(it)
+    return np.array(Fs).reshape(-1, 3, 3), np.array(its, int)
+
+
+def _match_model(Fs, F_impl):
+    """index of the numpy model closest to the implementation's matrix, and the relative distance"""
+    d = np.array([np.abs(Fm - F_impl).max() / np.abs(F_impl).max() for Fm in Fs])
+    return int(np.argmin(d)), float(d.min())
+
+
+def check_fundamental_mask(p1, p2, subsets, mask, n_inliers, info, F_winner):
+    """findFundamentalMat's RANSAC mask (n >= 15) against an independent FP64 replay.  subsets: the samples the RNG draws (data);
+    mask, n_inliers, info = {sample, model, iterations, inliers}: one implementation's answer; F_winner: the 7-point matrix
+    that implementation computes for (sample, model), used only to find the same model among numpy's roots.
+    -> dict(band share, matrix distance)"""
+    p1 = np.asarray(p1, np.float32); p2 = np.asarray(p2, np.float32)
+    n = len(p1)
+    mask = np.asarray(mask).astype(bool)
+    assert n >= 15 and mask.shape == (n,) and n_inliers == int(mask.sum()) == info["inliers"]
+    s_w, R = info["sample"], info["iterations"]
+    assert 0 <= s_w < len(subsets) and 0 <= R <= 1000
+    Fs, its = fm_all_models(p1, p2, subsets)
+    mine = np.flatnonzero(its == s_w)
+    assert mine.size, "numpy finds no model for the reported sample"
+    assert 0 <= info["model"] < 3
+    k, dist = _match_model(Fs[mine], F_winner)
+    assert dist <= 1e-6, "the winning matrix is %.2g (relative) away from every numpy root of that sample" % dist
+    w = int(mine[k])
+    lo = np.zeros(len(Fs), int); hi = np.zeros(len(Fs), int)
+    for c in range(0, len(Fs), 256):
+        err, dev = epipolar_errors(Fs[c:c + 256], p1, p2)
+        lo[c:c + 256] = (err + dev < 9.0).sum(1)
+        hi[c:c + 256] = (err - dev <= 9.0).sum(1)
+        if c <= w < c + 256:
+            e_w, d_w = err[w - c], dev[w - c]
+    inside, outside = e_w + d_w < 9.0, e_w - d_w > 9.0
+    band = ~(inside | outside)
+    share = float(band.sum()) / n
+    assert share <= 0.01, "%d of %d points within the float band of the threshold" % (band.sum(), n)
+    assert mask[inside].all() and not mask[outside].any(), "mask differs from the FP64 inlier set outside the band"
+    assert lo[w] <= n_inliers <= hi[w] and n_inliers > 6
+    # RANSACPointSetRegistrator::run keeps the FIRST model that reaches the maximum
+    order = np.arange(len(Fs))
+    early = order < w
+    assert not (lo[early] >= hi[w]).any(), "an earlier model has at least as many inliers"
+    late = (order > w) & (its < R)
+    assert not (lo[late] > hi[w]).any(), "a later model inside the loop has more inliers"
+    # the loop bound only falls, and a model with g inliers implies a bound of at most f(g): the winner must lie inside
+    # every bound the earlier models imply, and the final count is f(inliers of the winner)
+    f = lambda g: ransac_update_num_iters(0.99, (n - g) / n, 7, 1000)
+    for m in np.flatnonzero(early & (lo > 6)):
+        assert s_w < f(int(lo[m])), "the loop had ended before the reported sample"
+    assert f(int(hi[w])) <= R <= f(int(lo[w])), (f(int(hi[w])), R, f(int(lo[w])))
+    return dict(band=share, dist=dist)
+
+
+def check_lmeds_mask(p1, p2, subsets, mask, n_inliers, info, F_winner):
+    """the LMedS branch (8 <= n <= 14): the winner's FP64 median is the first strict minimum over (sample, model) up to the band,
+    the mask follows from sigma = 2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median)"""
+    p1 = np.asarray(p1, np.float32); p2 = np.asarray(p2, np.float32)
+    n = len(p1)
+    mask = np.asarray(mask).astype(bool)
+    assert 8 <= n <= 14 and n_inliers == int(mask.sum()) == info["inliers"]
+    assert info["iterations"] == len(subsets) == max(ransac_update_num_iters(0.99, 0.45, 7, 1000), 3)
+    Fs, its = fm_all_models(p1, p2, subsets)
+    mine = np.flatnonzero(its == info["sample"])
+    assert mine.size
+    k, dist = _match_model(Fs[mine], F_winner)
+    assert dist <= 1e-6, dist
+    w = int(mine[k])
+    err, dev = epipolar_errors(Fs, p1, p2)
+    srt = np.argsort(err, axis=1)
+    rows = np.arange(len(Fs))
+    pick = lambda a, j: a[rows, srt[:, j]]
+    if n % 2:
+        med, mdev = pick(err, n // 2), pick(dev, n // 2)
+    else:
+        med = 0.5 * (pick(err, n // 2 - 1) + pick(err, n // 2))
+        mdev = 0.5 * (pick(dev, n // 2 - 1) + pick(dev, n // 2)) + 2 * U32 * med
+    ok = np.isfinite(med)
+    other = ok & (rows != w)
+    assert not (med[other] + mdev[other] < med[w] - mdev[w]).any(), "another model has a smaller median"
+    early = other & (rows < w)
+    assert not (med[early] + mdev[early] <= med[w] - mdev[w]).any()
+    c = (2.5 * 1.4826 * (1 + 5.0 / (n - 7))) ** 2
+    thr, tdev = max(c * med[w], 1e-6), c * mdev[w] + 4 * U32 * c * med[w]
+    inside, outside = err[w] + dev[w] < thr - tdev, err[w] - dev[w] > thr + tdev
+    band = ~(inside | outside)
+    assert band.sum() <= 0.01 * n, "%d of %d points within the float band of the threshold" % (band.sum(), n)
+    assert mask[inside].all() and not mask[outside].any()
+    return dict(band=float(band.sum()) / n, dist=dist)

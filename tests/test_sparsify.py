@@ -3,54 +3,9 @@ against an independent numpy model (central-difference Jacobians of the same min
 quaternions, dense Schur complement, numpy's inverse and eigh), and the batched HIP kernel against the oracle."""
 import numpy as np
 import pytest
-from scipy.spatial.transform import Rotation
 
 
-def _min_of(T):
-    q = Rotation.from_matrix(T[:3, :3]).as_quat()
-    if q[3] < 0:
-        q = -q
-    return np.r_[T[:3, 3], q[:3]]
-
-
-def _from_min(v):
-    w2 = 1 - v[3:] @ v[3:]
-    T = np.eye(4)
-    T[:3, :3] = Rotation.from_quat([v[3], v[4], v[5], np.sqrt(max(w2, 0.0))]).as_matrix()
-    T[:3, 3] = v[:3]
-    return T
-
-
-def _numpy_model(kf, mp, m_kf, m_mp, m_info):
-    N = len(mp)
-    H = np.zeros((12 + 3 * N, 12 + 3 * N))
-    h = 1e-6
-    for k, m, W in zip(m_kf, m_mp, m_info):
-        v = _min_of(kf[k])
-        f = lambda vv, pp: (np.linalg.inv(_from_min(vv)) @ np.r_[pp, 1.0])[:3]
-        J = np.zeros((3, 9))
-        for i in range(6):
-            d = np.zeros(6); d[i] = h
-            J[:, i] = (f(v + d, mp[m]) - f(v - d, mp[m])) / (2 * h)
-        for i in range(3):
-            d = np.zeros(3); d[i] = h
-            J[:, 6 + i] = (f(v, mp[m] + d) - f(v, mp[m] - d)) / (2 * h)
-        idx = np.r_[6 * k + np.arange(6), 12 + 3 * m + np.arange(3)]
-        H[np.ix_(idx, idx)] += J.T @ W @ J
-    H[:12, :12] += 1e-6 * np.eye(12)
-    Hm = H[:12, :12] - H[:12, 12:] @ np.linalg.solve(H[12:, 12:], H[12:, :12])
-    z = lambda a, b: _min_of(np.linalg.inv(_from_min(a)) @ _from_min(b))
-    v1, v2 = _min_of(kf[0]), _min_of(kf[1])
-    J = np.zeros((6, 12))
-    for i in range(6):
-        d = np.zeros(6); d[i] = h
-        J[:, i] = (z(v1 + d, v2) - z(v1 - d, v2)) / (2 * h)
-        J[:, 6 + i] = (z(v1, v2 + d) - z(v1, v2 - d)) / (2 * h)
-    I = np.linalg.inv(J @ np.linalg.inv(Hm) @ J.T)
-    I = 0.5 * (I + I.T)
-    lam, U = np.linalg.eigh(I)
-    lam = np.where(lam < 0, 1e-6, np.clip(lam, 1e-6, 1e4))
-    return np.linalg.inv(kf[0]) @ kf[1], (U * lam) @ U.T, Hm
+from independent import sparsify_numpy_model as _numpy_model
 
 
 @pytest.mark.parametrize("N,seed", [(12, 0), (80, 1), (200, 2)])

@@ -74,21 +74,15 @@ while time.time() < t_end:
             fail("match")
         continue
     if kind == 3:   # findFundamentalMat masks
-        n = int(rng.choice([0, 5, 7, 8, 12, 15, 16, 40, 300, 1000]))
-        X = np.stack([rng.uniform(-3000, 3000, n), rng.uniform(-2000, 2000, n), rng.uniform(3000, 9000, n)], 1)
-        K = np.array([[400, 0, 320], [0, 400, 240], [0, 0, 1.0]])
-        th = rng.uniform(-0.08, 0.08)
-        R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]])
-        tt = rng.uniform(-300, 300, 3)
-        uv1 = X @ K.T; uv2 = (X @ R.T + tt) @ K.T
-        p1 = (uv1[:, :2] / uv1[:, 2:] + rng.normal(0, 0.5, (n, 2))).astype(np.float32) if n else np.zeros((0, 2), np.float32)
-        p2 = (uv2[:, :2] / uv2[:, 2:] + rng.normal(0, 0.5, (n, 2))).astype(np.float32) if n else np.zeros((0, 2), np.float32)
-        out = rng.random(n) < rng.uniform(0, 0.7)
-        p2[out] += rng.uniform(-80, 80, (int(out.sum()), 2)).astype(np.float32)
+        n = int(rng.choice([0, 5, 7, 8, 12, 14, 15, 16, 40, 300, 1000, 3001]))
+        # synth.two_view_matches: the generator of tests/test_ransac.py / test_track_independent.py, with pure-inlier and
+        # noise-free draws (the loop stops after a handful of samples) and up to 70 % outliers (it runs all 1000)
+        frac = float(rng.choice([0.0, rng.uniform(0, 0.7), 0.7]))
+        p1, p2, _ = synth.two_view_matches(int(rng.integers(0, 10**6)), n, frac, float(rng.choice([0.0, 0.5])))
         mask, ni = track.findFundamentalMat(p1, p2)
-        mask_ref, ni_ref = oracle.fundamental_mask(p1, p2)
-        ok = ni == ni_ref and np.array_equal(mask, mask_ref)
-        print(f"ransac n {n}: {ni} inliers {'ok' if ok else ''}")
+        mask_ref, info_ref = oracle.fundamental_mask_info(p1, p2)
+        ok = ni == info_ref["inliers"] and np.array_equal(mask, mask_ref) and (n < 8 or track.last_ransac() == info_ref)
+        print(f"ransac n {n} outliers {frac:.2f}: {ni} inliers {'ok' if ok else ''}")
         if not ok:
             fail("ransac")
         continue
@@ -144,39 +138,24 @@ while time.time() < t_end:
             fail("proj")
         continue
     if kind == 7:   # doTriangulate
-        n = int(rng.choice([0, 1, 30, 600, 1000]))
-        K = np.array([[400.0, 0, 320.0], [0, 400.0, 240.0], [0, 0, 1]], np.float32)
-        th = float(rng.uniform(-0.05, 0.05))
-        R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]], np.float32)
-        tt = np.array([rng.uniform(-300, -50), rng.uniform(-20, 20), rng.uniform(-50, 50)], np.float32)
-        Tcr = np.eye(4, dtype=np.float32); Tcr[:3, :3] = R; Tcr[:3, 3] = tt
-        P1 = (K @ np.eye(3, 4, dtype=np.float32)).astype(np.float32); P2 = (K @ Tcr[:3]).astype(np.float32)
-        X = np.stack([rng.uniform(-1500, 1500, n), rng.uniform(-800, 800, n), rng.uniform(200, 14000, n)], 1).astype(np.float32)
-        Xh = np.concatenate([X, np.ones((n, 1), np.float32)], 1)
-        u1 = (P1 @ Xh.T).T; u2 = (P2 @ Xh.T).T
-        KPd = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
-        k1 = np.zeros(n, KPd); k2 = np.zeros(n, KPd)
-        if n:
-            k1["x"], k1["y"] = (u1[:, 0] / u1[:, 2]), (u1[:, 1] / u1[:, 2])
-            perm = rng.permutation(n)
-            k2["x"][perm], k2["y"][perm] = (u2[:, 0] / u2[:, 2]) + rng.normal(0, 0.3, n), (u2[:, 1] / u2[:, 2]) + rng.normal(0, 0.3, n)
-            match = perm.astype(np.int32); match[rng.random(n) < 0.1] = -1
-        else:
-            match = np.zeros(0, np.int32)
-        has_obs = (rng.random(n) < 0.15).astype(np.uint8)
-        Ocam = np.linalg.inv(Tcr)[:3, 3].astype(np.float32)
+        n = int(rng.choice([0, 1, 30, 127, 128, 129, 600, 1000, 20000]))
+        scene = str(rng.choice(list(synth.TRIANGULATION_SCENES)))      # benign, low parallax, far, behind the camera, zero baseline, noisy
+        k1, k2, match, has_obs, P1, P2, Ocam, _ = synth.triangulation_scene(scene, n, int(rng.integers(0, 10**6)))
+        match[rng.random(n) < 0.1] = -1
+        has_obs = [(rng.random(n) < 0.15).astype(np.uint8), np.ones(n, np.uint8), np.zeros(n, np.uint8), None][int(rng.integers(0, 4))]
         mind = int(rng.integers(1, 5))
         ref = oracle.triangulate(k1, k2, match, has_obs, P1, P2, Ocam, 500.0, 8000.0, mind)
         got = track.doTriangulate(k1, k2, match, has_obs, P1, P2, Ocam, 500.0, 8000.0, mind)
         ok = np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and got[3:] == ref[3:]
-        print(f"tri  n {n} minDegree {mind}: {got[3]} good {'ok' if ok else ''}")
+        print(f"tri  {scene} n {n} minDegree {mind}: {got[3]} good {'ok' if ok else ''}")
         if not ok:
             fail("tri")
         continue
     if kind == 8:   # Sparsifier::DoMarginalizeSE3XYZ, a batch of key-frame pairs
         from se2lam_amd.sparsifier import DoMarginalizeSE3XYZ_batch
-        spec = [(int(rng.integers(8, 250)), int(rng.integers(0, 10**6)), float(rng.uniform(80, 900))) for _ in range(int(rng.integers(1, 9)))]
-        pairs = [synth.kf_pair(*sp) for sp in spec]
+        spec = [(int(rng.integers(1, 250)), int(rng.integers(0, 10**6)), float(rng.uniform(80, 900))) for _ in range(int(rng.integers(1, 9)))]
+        # each pair with its measurements in one of synth.KF_PAIR_ORDERS: the answer depends on the order (H11 is summed in it)
+        pairs = [synth.kf_pair_reorder(synth.kf_pair(*sp), str(rng.choice(synth.KF_PAIR_ORDERS)), int(rng.integers(0, 10**6))) for sp in spec]
         got = DoMarginalizeSE3XYZ_batch(pairs)
         ok = True
         for sp, (kf, mp, m_kf, m_mp, m_info), (z, info) in zip(spec, pairs, got):
@@ -193,23 +172,12 @@ while time.time() < t_end:
         continue
     if kind == 9:   # Localizer::DoLocalBA (pose-only BA with the plane-motion prior)
         from se2lam_amd.localizer import Localizer
-        RBC = np.array([[0, 0, 1], [-1, 0, 0], [0, -1, 0.0]])
-        TBC = np.eye(4); TBC[:3, :3] = RBC; TBC[:3, 3] = [100.0, 0.0, 300.0]
-
-        def Twb(x, y, th):
-            T = np.eye(4); c_, s_ = np.cos(th), np.sin(th)
-            T[:3, :3] = [[c_, -s_, 0], [s_, c_, 0], [0, 0, 1.0]]; T[:3, 3] = [x, y, 0]
-            return T
-        n = int(rng.choice([0, 3, 6, 40, 400, 1500]))
-        pose = (rng.uniform(-2000, 2000), rng.uniform(-2000, 2000), rng.uniform(-3, 3))
-        Tcw_true = np.linalg.inv(Twb(*pose) @ TBC)
-        Xc = np.stack([rng.uniform(-2000, 2000, n), rng.uniform(-1500, 1500, n), rng.uniform(1500, 8000, n)], 1)
-        Xw = (np.linalg.inv(Tcw_true) @ np.c_[Xc, np.ones(n)].T).T[:, :3]
-        uv = 400.0 * Xc[:, :2] / Xc[:, 2:] + [320.0, 240.0] + rng.normal(0, 0.7, (n, 2))
-        out = rng.random(n) < rng.uniform(0, 0.3)
-        uv[out] += rng.uniform(-50, 50, (int(out.sum()), 2))
-        w = 1.0 / 1.2 ** (2 * rng.integers(0, 8, n))
-        Tcw0 = np.linalg.inv(Twb(pose[0] + rng.normal(0, 40), pose[1] + rng.normal(0, 40), pose[2] + rng.normal(0, 0.03)) @ TBC)
+        TBC = np.eye(4); TBC[:3, :3] = synth.RBC; TBC[:3, 3] = synth.TBC
+        n = int(rng.choice([0, 1, 3, 6, 40, 63, 64, 65, 255, 256, 257, 400, 1023, 1500]))
+        # synth.pose_ba_case: headings next to +-pi, weights over 1 .. 1.2^-14 with exact zeros, a few points behind the camera
+        kw = dict(outliers=float(rng.uniform(0, 0.3)), yaw=[None, np.pi - 5e-4, -np.pi + 5e-4][int(rng.integers(0, 3))],
+                  weights=str(rng.choice(["levels", "wide"])), behind=int(rng.choice([0, 0, 3])))
+        _, Tcw0, Xw, uv, w, pose = synth.pose_ba_case(int(rng.integers(0, 10**6)), n, **kw)
         delta = float(np.sqrt(5.991))
         loc = Localizer()
         T = loc.DoLocalBA(Tcw0, TBC, Xw, uv, w, 400.0, 320.0, 240.0, delta, 30)
