@@ -496,6 +496,83 @@ int se2gpu_ba_set_comm(se2gpu_ba* h, se2gpu_comm* c);
 int se2gpu_ba_shard_landmarks(int L, int E, const int32_t* e_kf, const int32_t* e_lm, int world, int32_t* owner);
 
 /* ------------------------------------------------------------------------------------------
+ * DBoW2 vocabulary  -  se2lam::ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) on the device
+ *   transform(features, bow, fv, levelsup)   Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1150-1216, 1241-1280
+ *                                            (KeyFrame::ComputeBoW, src/KeyFrame.cpp:244-254; Localizer.cpp:195-205, 323-335)
+ *   score(v1, v2)                            Thirdparty/DBoW2/DBoW2/ScoringObject.cpp
+ *   the candidate loop of DetectLoopClose    src/GlobalMapper.cpp:201-254, src/Localizer.cpp:337-391
+ * Every output equals the host mirror include/se2lam_amd/ORBVocabulary.h bit for bit: word ids, node ids, feature indices,
+ * BowVector values and scores (all floating-point sums are added in ascending word id, as the mirror adds them).
+ * Scoring / weighting constants are DBoW2's: scoring 0 L1_NORM, 1 L2_NORM, 2 CHI_SQUARE, 3 KL, 4 BHATTACHARYYA,
+ * 5 DOT_PRODUCT; weighting 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY.
+ * ------------------------------------------------------------------------------------------ */
+/* The tree on the device.  Immutable after creation: any number of contexts, data bases and threads may share one, as the
+ * reference shares one ORBVocabulary between GlobalMapper and Localizer.  It must outlive everything created from it. */
+typedef struct se2gpu_voc se2gpu_voc;
+/* The records of the binary vocabulary file: `nodes` nodes including the root, which is node 0 (its entries are ignored);
+ * parent[nodes], desc[nodes * 32], weight[nodes] (rounded to float, which is what the file stores), leaf[nodes].  Children
+ * keep the order of their ids.  Refuses (SE2GPU_ERR_INVALID) exactly what ORBVocabulary::loadFromBinaryFile refuses - the
+ * check is the same code (include/se2lam_amd/VocabularyTree.h): a header out of range, a parent that does not precede its
+ * child, a childless node that is not a leaf. */
+int se2gpu_voc_create(int k, int L, int scoring, int weighting, int nodes, const int32_t* parent, const uint8_t* desc,
+                      const double* weight, const uint8_t* leaf, se2gpu_voc** out);
+/* the file TemplatedVocabulary::saveToBinaryFile writes; a missing or truncated file is refused as well */
+int se2gpu_voc_load(const char* path, se2gpu_voc** out);
+void se2gpu_voc_destroy(se2gpu_voc* v);
+int se2gpu_voc_words(const se2gpu_voc* v);      /* size(); the accessors return SE2GPU_ERR_INVALID for a NULL handle */
+int se2gpu_voc_nodes(const se2gpu_voc* v);      /* including the root */
+int se2gpu_voc_k(const se2gpu_voc* v);
+int se2gpu_voc_L(const se2gpu_voc* v);
+int se2gpu_voc_scoring(const se2gpu_voc* v);
+int se2gpu_voc_weighting(const se2gpu_voc* v);
+
+/* A per-thread context: its stream and scratch for batches of up to max_batch frames of up to max_features (<= 4096)
+ * features.  Not thread-safe; several contexts may share one vocabulary. */
+typedef struct se2gpu_bow se2gpu_bow;
+int se2gpu_bow_create(const se2gpu_voc* voc, int max_features, int max_batch, se2gpu_bow** out);
+void se2gpu_bow_destroy(se2gpu_bow* h);
+int se2gpu_bow_set_stream(se2gpu_bow* h, void* hip_stream);  /* NULL -> the context's own stream */
+int se2gpu_bow_sync(se2gpu_bow* h);
+void* se2gpu_bow_stream(se2gpu_bow* h);
+/* transform(.., levelsup) of nframes frames whose descriptors lie where se2gpu_orb_extract_batch_device wrote them
+ * (d_desc: nframes * cap * 32 bytes, 16-byte aligned; d_counts: nframes ints, clamped to 0..cap).  Outputs of frame f, all
+ * device memory: the BowVector d_bow_word (u32) / d_bow_value (f64) from f * cap, ascending word id, d_bow_n[f] words; the
+ * FeatureVector as the CSR se2gpu_search_by_bow takes - d_fv_nodes from f * cap (ascending node ids of the file), d_fv_ptr
+ * from f * (cap + 1), d_fv_idx from f * cap (ascending within a node), d_fv_nn[f] nodes.  A feature on a word of weight 0
+ * is in neither vector; the node of a feature is its ancestor at level L - levelsup (the root when that is not positive,
+ * the leaf when the leaf lies above that level); an empty frame gives empty vectors.  Asynchronous on the context's stream. */
+int se2gpu_bow_transform_batch_device(se2gpu_bow* h, const uint8_t* d_desc, const int32_t* d_counts, int cap, int nframes,
+                                      int levelsup, uint32_t* d_bow_word, double* d_bow_value, int32_t* d_bow_n,
+                                      int32_t* d_fv_nodes, int32_t* d_fv_ptr, int32_t* d_fv_idx, int32_t* d_fv_nn);
+/* the same for one frame with host buffers (n descriptors; bow_*, fv_nodes, fv_idx: n entries, fv_ptr: n + 1); synchronous */
+int se2gpu_bow_transform(se2gpu_bow* h, const uint8_t* desc, int n, int levelsup, uint32_t* bow_word, double* bow_value,
+                         int* nb, int32_t* fv_nodes, int32_t* fv_ptr, int32_t* fv_idx, int* nn);
+
+/* The key frames' BowVectors, resident on the device, in insertion order.  One thread at a time; KL scoring is refused at
+ * create (SE2GPU_ERR_INVALID): it needs the host's log() bit for bit and nothing in se2lam uses it. */
+typedef struct se2gpu_bowdb se2gpu_bowdb;
+int se2gpu_bowdb_create(const se2gpu_voc* voc, se2gpu_bowdb** out);
+void se2gpu_bowdb_destroy(se2gpu_bowdb* db);
+/* host buffers: n ascending word ids and their values, as transform() leaves them; synchronous */
+int se2gpu_bowdb_add(se2gpu_bowdb* db, int kf_id, const uint32_t* word, const double* value, int n);
+/* a frame's slice of se2gpu_bow_transform_batch_device's output where it lies: d_word / d_value point at the slice (cap
+ * entries), d_n at its d_bow_n entry.  Asynchronous on the context's stream, after the transform that writes the slice. */
+int se2gpu_bowdb_add_device(se2gpu_bowdb* db, se2gpu_bow* ctx, int kf_id, const uint32_t* d_word, const double* d_value,
+                            const int32_t* d_n, int cap);
+/* Map::pruneRedundantKF deletes key frames: drops the first entry with that id; the later entries move up one place */
+int se2gpu_bowdb_remove(se2gpu_bowdb* db, int kf_id);
+int se2gpu_bowdb_size(const se2gpu_bowdb* db);
+/* scores_out[i] (host, size() doubles, may be NULL) = score(query, entry i) for every entry, and the candidate
+ * DetectLoopClose would keep: entries with abs(kf_id - cur_kf_id) < min_kfid_offset are skipped, the best starts at 0 and
+ * an entry replaces it when its score is strictly greater - so *best_entry is the first entry at the maximal score, or -1
+ * (with *best_kf_id = -1, *best_score = 0) when no score is above 0.  The comparison with the minimal accepted score stays
+ * with the caller.  The query (n ascending words, n <= the context's max_features) is read from host memory, or from
+ * device memory when query_on_device != 0.  Synchronous. */
+int se2gpu_bowdb_query(se2gpu_bowdb* db, se2gpu_bow* ctx, const uint32_t* word, const double* value, int n,
+                       int query_on_device, int cur_kf_id, int min_kfid_offset, double* scores_out, int* best_entry,
+                       int* best_kf_id, double* best_score);
+
+/* ------------------------------------------------------------------------------------------
  * Timing helpers for bench.py: HIP events on the stream the kernels are launched on.
  * ------------------------------------------------------------------------------------------ */
 typedef struct se2gpu_timer se2gpu_timer;

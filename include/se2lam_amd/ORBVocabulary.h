@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ORBmatcher.h"   // FeatureVectorView
+#include "VocabularyTree.h"
 
 namespace se2lam_amd {
 
@@ -76,51 +77,15 @@ public:
     ScoringType getScoringType() const { return m_scoring; }
     unsigned nodes() const { return (unsigned)m_parent.size(); }   // incl. the root (node 0)
 
-    // header: nb_nodes (= nodes incl. root), size_node (41), k, L, scoring, weighting; then per node 1 .. nb_nodes-1:
-    // parent (int32), descriptor (32 bytes), weight (float), is_leaf (1 byte)
+    // the file format and every check on it live in VocabularyTree.h, which the device vocabulary (se2gpu_voc_load) shares
     bool loadFromBinaryFile(const std::string& filename) {
         clear();
-        std::FILE* f = std::fopen(filename.c_str(), "rb");
-        if (!f) return false;
-        uint32_t nb_nodes = 0, size_node = 0;
-        int32_t k = 0, L = 0, scoring = 0, weighting = 0;
-        bool ok = std::fread(&nb_nodes, 4, 1, f) == 1 && std::fread(&size_node, 4, 1, f) == 1 && std::fread(&k, 4, 1, f) == 1 &&
-                  std::fread(&L, 4, 1, f) == 1 && std::fread(&scoring, 4, 1, f) == 1 && std::fread(&weighting, 4, 1, f) == 1;
-        ok = ok && size_node == 4 + kDescBytes + 4 + 1 && nb_nodes >= 1 && k >= 1 && L >= 0 && scoring >= 0 && scoring <= 5 &&
-             weighting >= 0 && weighting <= 3;
-        if (!ok) { std::fclose(f); return false; }
-        std::vector<uint8_t> rec((size_t)size_node * (nb_nodes - 1));
-        const size_t got = rec.empty() ? 0 : std::fread(rec.data(), size_node, nb_nodes - 1, f);
-        std::fclose(f);
-        if (got != nb_nodes - 1) return false;
-        m_k = k; m_L = L;
-        m_scoring = (ScoringType)scoring; m_weighting = (WeightingType)weighting;
-        const uint32_t N = nb_nodes;
-        m_parent.assign(N, 0); m_weight.assign(N, 0.0); m_word.assign(N, -1); m_leaf.assign(N, 0);
-        m_desc.assign((size_t)N * kDescBytes, 0);
-        std::vector<int32_t> count(N + 1, 0);
-        for (uint32_t id = 1; id < N; ++id) {
-            const uint8_t* r = rec.data() + (size_t)(id - 1) * size_node;
-            int32_t parent; float w;
-            std::memcpy(&parent, r, 4);
-            std::memcpy(&w, r + 4 + kDescBytes, 4);
-            if (parent < 0 || (uint32_t)parent >= id) { clear(); return false; }   // a parent precedes its children in the file
-            m_parent[id] = parent;
-            std::memcpy(&m_desc[(size_t)id * kDescBytes], r + 4, kDescBytes);
-            m_weight[id] = (WordValue)w;
-            m_leaf[id] = r[4 + kDescBytes + 4] ? 1 : 0;
-            if (m_leaf[id]) { m_word[id] = (int32_t)m_words.size(); m_words.push_back(id); }
-            ++count[parent + 1];
-        }
-        // children in file order (CSR)
-        m_child_ptr.assign(N + 1, 0);
-        for (uint32_t i = 0; i < N; ++i) m_child_ptr[i + 1] = m_child_ptr[i] + count[i + 1];
-        m_child.assign(m_child_ptr[N], 0);
-        std::vector<int32_t> fill(m_child_ptr.begin(), m_child_ptr.end() - 1);
-        for (uint32_t id = 1; id < N; ++id) m_child[fill[m_parent[id]]++] = (int32_t)id;
-        // a node without children must be a leaf, or a feature that reaches it could not go on
-        for (uint32_t id = 0; id < N; ++id)
-            if (m_child_ptr[id + 1] == m_child_ptr[id] && !(id > 0 && m_leaf[id]) && N > 1) { clear(); return false; }
+        VocabularyTree t;
+        if (!t.loadFromBinaryFile(filename)) return false;
+        m_k = t.k; m_L = t.L;
+        m_scoring = (ScoringType)t.scoring; m_weighting = (WeightingType)t.weighting;
+        m_parent.swap(t.parent); m_child_ptr.swap(t.child_ptr); m_child.swap(t.child); m_word.swap(t.word);
+        m_desc.swap(t.desc); m_leaf.swap(t.leaf); m_weight.swap(t.weight); m_words.swap(t.words);
         return true;
     }
 

@@ -29,6 +29,7 @@ PER_FILE = {
     "match.hip": ["-ffp-contract=off"],
     "triangulate.hip": ["-ffp-contract=off"],
     "ransac.hip": ["-ffp-contract=off"],
+    "bow.hip": ["-ffp-contract=off"],        # BowVector values and scores equal the host vocabulary's to the bit
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
 }
 
@@ -55,7 +56,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
-    headers.append(os.path.abspath(__file__))
+    sub = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTree.h")   # the one adapter header a translation unit (bow.hip) includes
+    headers += [sub, os.path.abspath(__file__)]
     objs = []
     for src in sources():
         obj = os.path.join(OBJDIR, src[:-4] + ".o")

@@ -182,6 +182,30 @@ SYMBOLS = {
     "se2gpu_ba_edge_information": (_I, [_I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _F, _F, _F, _VP]),
     "se2gpu_ba_profile": (_I, [_VP, _I]),
     "se2gpu_ba_profile_get": (_I, [_VP, _I, C.POINTER(C.c_char_p), _PD, C.POINTER(C.c_int64)]),
+    # DBoW2 vocabulary
+    "se2gpu_voc_create": (_I, [_I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),
+    "se2gpu_voc_load": (_I, [C.c_char_p, C.POINTER(_VP)]),
+    "se2gpu_voc_destroy": (None, [_VP]),
+    "se2gpu_voc_words": (_I, [_VP]),
+    "se2gpu_voc_nodes": (_I, [_VP]),
+    "se2gpu_voc_k": (_I, [_VP]),
+    "se2gpu_voc_L": (_I, [_VP]),
+    "se2gpu_voc_scoring": (_I, [_VP]),
+    "se2gpu_voc_weighting": (_I, [_VP]),
+    "se2gpu_bow_create": (_I, [_VP, _I, _I, C.POINTER(_VP)]),
+    "se2gpu_bow_destroy": (None, [_VP]),
+    "se2gpu_bow_set_stream": (_I, [_VP, _VP]),
+    "se2gpu_bow_sync": (_I, [_VP]),
+    "se2gpu_bow_stream": (_VP, [_VP]),
+    "se2gpu_bow_transform_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "se2gpu_bow_transform": (_I, [_VP, _VP, _I, _I, _VP, _VP, C.POINTER(_I), _VP, _VP, _VP, C.POINTER(_I)]),
+    "se2gpu_bowdb_create": (_I, [_VP, C.POINTER(_VP)]),
+    "se2gpu_bowdb_destroy": (None, [_VP]),
+    "se2gpu_bowdb_add": (_I, [_VP, _I, _VP, _VP, _I]),
+    "se2gpu_bowdb_add_device": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I]),
+    "se2gpu_bowdb_remove": (_I, [_VP, _I]),
+    "se2gpu_bowdb_size": (_I, [_VP]),
+    "se2gpu_bowdb_query": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, C.POINTER(_I), C.POINTER(_I), _PD]),
     # timers / memory
     "se2gpu_timer_create": (_I, [C.POINTER(_VP)]),
     "se2gpu_timer_destroy": (None, [_VP]),
