@@ -91,6 +91,27 @@ int se2gpu_orb_debug_score(se2gpu_orb* h, int frame, int level, uint8_t* out, si
  * them.  force_global != 0 runs the in-place global-memory path that cells beyond the LDS capacity take. */
 int se2gpu_orb_debug_nth_element(uint64_t* entries, int n, int nth, int force_global);
 
+/* Camera model of the first step of Frame::Frame (the reference's src/Frame.cpp:19-25): cv::undistort(im, img, Kcam, Dcam)
+ * in front of the extractor.  d holds OpenCV's order k1, k2, p1, p2 [, k3 [, k4, k5, k6]]; nd is 4, 5 or 8 (the thin-prism
+ * and tilt models, 12 / 14 coefficients, are refused), entries from nd on are ignored.  The arithmetic is OpenCV 3.2's,
+ * restated in DESIGN.md ("Camera undistortion"). */
+typedef struct se2gpu_camera {
+    float fx, fy, cx, cy;
+    float d[8];
+    int32_t nd;
+} se2gpu_camera;
+
+/* The fixed-point maps cv::undistort builds for a rows x cols image (initUndistortRectifyMap, CV_16SC2 + CV_16UC1, in stripes):
+ * map_xy = rows * cols * 2 int16 (source column, source row), map_frac = rows * cols uint16 ((fy5 << 5) | fx5).  Host code, no device. */
+int se2gpu_undistort_map(const se2gpu_camera* cam, int rows, int cols, int16_t* map_xy, uint16_t* map_frac);
+/* cv::undistortPoints(src, dst, K, D, Mat(), K) for n points (x, y floats; xy_out may be xy_in).  Host code, no device. */
+int se2gpu_undistort_points(const se2gpu_camera* cam, const float* xy_in, int n, float* xy_out);
+/* A handle with a camera treats the images of se2gpu_orb_extract / se2gpu_orb_extract_batch_device as RAW camera images:
+ * a remap kernel (INTER_LINEAR, BORDER_CONSTANT 0) undistorts them on the device in front of the pyramid, and level 0 of
+ * se2gpu_orb_debug_level is the undistorted image.  The maps of an image size are built at the first extract of that size
+ * and kept.  NULL takes the camera away again (the default: images are used as they come).  Waits for the handle's work. */
+int se2gpu_orb_set_camera(se2gpu_orb* h, const se2gpu_camera* cam);
+
 /* ------------------------------------------------------------------------------------------
  * ORB matcher  -  replaces se2lam::ORBmatcher
  *   DescriptorDistance   /root/reference/src/ORBmatcher.cpp:110-126
@@ -118,6 +139,9 @@ int se2gpu_matcher_spill_calls(const se2gpu_matcher* h, long long* calls);
 typedef struct se2gpu_frame_bounds {
     float min_x, min_y, max_x, max_y;
 } se2gpu_frame_bounds;
+/* Frame::computeBoundUn (Frame.cpp:183-200): the image rectangle when d[0] == 0 (the reference's rule, whatever the other
+ * coefficients are), else the bounds of its four undistorted corners.  Host code, no device. */
+int se2gpu_frame_bounds_un(const se2gpu_camera* cam, int rows, int cols, se2gpu_frame_bounds* out);
 
 /* MatchByWindow(frame1, frame2, vbPrevMatched, winSize, vnMatches12, levelOffset, minLevel, maxLevel)
  * with ORBmatcher(nnratio, checkOri=true).  Host buffers.  prev_xy (n1 x 2 floats) is updated in place

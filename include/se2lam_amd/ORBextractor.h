@@ -61,6 +61,18 @@ public:
     }
 #endif
 
+    // Not in the reference's class: Frame::Frame runs cv::undistort(im, img, Config::Kcam, Config::Dcam) before it calls the
+    // extractor (Frame.cpp:22-25).  An extractor that carries the camera takes `im` itself and undistorts it on the device.
+    // K: 3x3 CV_32F; D: 4, 5 or 8 CV_32F coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]]), any shape.  clearCamera() undoes it.
+    void setCamera(const MatF& K, const MatF& D) {
+        const se2gpu_camera c = toCamera(K, D);
+        check(se2gpu_orb_set_camera(h_, &c), "ORBextractor::setCamera");
+    }
+    void clearCamera() { check(se2gpu_orb_set_camera(h_, nullptr), "ORBextractor::clearCamera"); }
+#ifdef SE2LAM_AMD_HAVE_OPENCV
+    void setCamera(const cv::Mat& K, const cv::Mat& D) { setCamera(toMatF(K), toMatF(D)); }
+#endif
+
     int GetLevels() { return se2gpu_orb_levels(h_); }
     float GetScaleFactor() { return se2gpu_orb_scale_factor(h_); }
 

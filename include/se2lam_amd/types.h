@@ -127,6 +127,19 @@ inline void check(int rc, const char* what) {
     if (rc != SE2GPU_OK) throw std::runtime_error(std::string(what) + ": " + se2gpu_last_error());
 }
 
+// Config::Kcam (3x3 CV_32F) and Config::Dcam (4, 5 or 8 CV_32F coefficients, a row or a column) as the C ABI's camera
+inline se2gpu_camera toCamera(const MatF& K, const MatF& D) {
+    if (K.rows != 3 || K.cols != 3) throw std::invalid_argument("toCamera: K must be 3x3");
+    const size_t nd = D.v.size();
+    if ((D.rows != 1 && D.cols != 1) || (nd != 4 && nd != 5 && nd != 8))
+        throw std::invalid_argument("toCamera: D must hold 4, 5 or 8 coefficients in one row or column");
+    se2gpu_camera c{};
+    c.fx = K.at<float>(0, 0); c.fy = K.at<float>(1, 1); c.cx = K.at<float>(0, 2); c.cy = K.at<float>(1, 2);
+    for (size_t i = 0; i < nd; ++i) c.d[i] = D.v[i];
+    c.nd = (int32_t)nd;
+    return c;
+}
+
 }  // namespace se2lam_amd
 
 #include "conversions.h"

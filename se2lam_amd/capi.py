@@ -44,6 +44,21 @@ class FrameBounds(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float)]
 
 
+class Camera(C.Structure):
+    """se2gpu_camera: fx, fy, cx, cy, d[8] (OpenCV order k1 k2 p1 p2 [k3 [k4 k5 k6]]), nd in {4, 5, 8}"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("d", C.c_float * 8),
+                ("nd", C.c_int32)]
+
+    @classmethod
+    def from_KD(cls, K, D):
+        K = np.asarray(K, np.float32).reshape(3, 3)
+        D = np.asarray(D, np.float32).ravel()
+        c = cls(K[0, 0], K[1, 1], K[0, 2], K[1, 2], (C.c_float * 8)(), len(D))
+        for i, v in enumerate(D[:8]):
+            c.d[i] = v
+        return c
+
+
 class LocalGraph(C.Structure):
     _fields_ = [("n_local_kf", C.c_int32), ("n_ref_kf", C.c_int32), ("n_mp", C.c_int32), ("n_obs", C.c_int32),
                 ("kf_id", C.c_void_p), ("kf_Twb", C.c_void_p), ("kf_Rcw", C.c_void_p),
@@ -91,6 +106,10 @@ SYMBOLS = {
     "se2gpu_orb_debug_score": (_I, [_VP, _I, _I, _VP, _SZ, C.POINTER(_I), C.POINTER(_I)]),
     "se2gpu_orb_debug_nth_element": (_I, [_VP, _I, _I, _I]),
     "se2gpu_orb_stream": (_VP, [_VP]),
+    "se2gpu_undistort_map": (_I, [C.POINTER(Camera), _I, _I, _VP, _VP]),
+    "se2gpu_undistort_points": (_I, [C.POINTER(Camera), _VP, _I, _VP]),
+    "se2gpu_frame_bounds_un": (_I, [C.POINTER(Camera), _I, _I, C.POINTER(FrameBounds)]),
+    "se2gpu_orb_set_camera": (_I, [_VP, C.POINTER(Camera)]),
     "se2gpu_orb_score_kernel": (_I, [_VP, _VP]),
     "se2gpu_orb_profile": (_I, [_VP, _I]),
     "se2gpu_orb_profile_get": (_I, [_VP, _I, C.POINTER(C.c_char_p), _PD, C.POINTER(C.c_int64)]),

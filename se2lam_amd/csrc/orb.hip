@@ -33,6 +33,8 @@
 #include <cmath>
 
 #include <cstdlib>
+#include <map>
+#include <utility>
 
 #include "common.h"
 
@@ -163,6 +165,49 @@ __global__ __launch_bounds__(256) void k_level0(Geom g, const uint8_t* __restric
     *reinterpret_cast<uint4*>(pyr + off) = v;
     // the blurred pyramid keeps the un-blurred frame (see k_blur): frame rows, the left chunk, the chunks from the right edge on
     if (!interior || Y < kEdge || Y >= H + kEdge) *reinterpret_cast<uint4*>(blur + off) = v;
+}
+
+// Camera undistortion in front of level 0 (only on a handle that carries a camera): cv::remap(INTER_LINEAR, BORDER_CONSTANT 0)
+// over the fixed-point maps of cv::undistort.  One thread = 4 adjacent output bytes, one 32-bit store; its map entries are one
+// 128-bit load ({sx | sy << 16} as int16 pairs, OpenCV's CV_16SC2 bytes) and one 64-bit load ((ay << 5) | ax per pixel) from
+// rows padded to `upitch` pixels (a multiple of 4, as are the rows of `out`), shared by every frame of the batch - frame =
+// blockIdx.x keeps the workgroups that read the same map lines next to each other in launch order.  Per pixel and source
+// row the taps (sx, sx + 1) are one 16-bit gather at a column clamped into [0, W - 2] and a row clamped into [0, H - 1]: every
+// address lies inside the image, and what the clamp moved is a neighbour outside the image = 0.  The weights 32 a b of 5-bit
+// bilinear interpolation sum to 32768 exactly (OpenCV's table correction never fires): (32 S + 16384) >> 15 = (S + 512) >> 10.
+__device__ __forceinline__ uint2 undistort_taps(const uint8_t* __restrict__ src, int W, int H, int sy, int sx, int xc) {
+    const int yc = min(max(sy, 0), H - 1);
+    const uint32_t v = *reinterpret_cast<const uint16_t*>(src + (size_t)yc * W + xc);    // (unaligned) u16: columns xc, xc + 1
+    const uint32_t b0 = v & 0xffu, b1 = v >> 8;
+    const int d = sx - xc;                                 // 0 inside; -1: sx = -1; 1: sx = W - 1; anything else: both taps outside
+    const bool row = yc == sy;
+    return make_uint2(row ? (d == 0 ? b0 : (d == 1 ? b1 : 0u)) : 0u, row ? (d == 0 ? b1 : (d == -1 ? b0 : 0u)) : 0u);
+}
+
+__global__ __launch_bounds__(256) void k_undistort(Geom g, const uint8_t* __restrict__ imgs, const uint32_t* __restrict__ map_xy,
+                                                    const uint16_t* __restrict__ map_frac, int upitch, uint8_t* __restrict__ out) {
+    SE2_FRAME_GRID(f, bx);
+    const int W = g.cols, H = g.rows, ng = upitch / 4;
+    const int item = bx * 256 + threadIdx.x;
+    if (item >= ng * H) return;
+    const int y = item / ng, x0 = (item - y * ng) * 4;
+    const size_t m = (size_t)y * upitch + x0;
+    const uint4 xy4 = *reinterpret_cast<const uint4*>(map_xy + m);
+    const uint2 fr2 = *reinterpret_cast<const uint2*>(map_frac + m);
+    const uint32_t xy[4] = {xy4.x, xy4.y, xy4.z, xy4.w};
+    const uint32_t fr[4] = {fr2.x & 0xffffu, fr2.x >> 16, fr2.y & 0xffffu, fr2.y >> 16};
+    const uint8_t* src = imgs + (size_t)f * W * H;
+    uint32_t res = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int sx = (int)(short)(xy[q] & 0xffffu), sy = (int)xy[q] >> 16;
+        const uint32_t ax = fr[q] & 31u, ay = (fr[q] >> 5) & 31u;
+        const int xc = min(max(sx, 0), W - 2);
+        const uint2 t0 = undistort_taps(src, W, H, sy, sx, xc), t1 = undistort_taps(src, W, H, sy + 1, sx, xc);
+        const uint32_t S = (32u - ay) * ((32u - ax) * t0.x + ax * t0.y) + ay * ((32u - ax) * t1.x + ax * t1.y);
+        res |= ((S + 512u) >> 10) << (8 * q);
+    }
+    *reinterpret_cast<uint32_t*>(out + ((size_t)f * H + y) * upitch + x0) = res;
 }
 
 // level l >= 1: cv::resize(level l-1, INTER_LINEAR) + reflect-101 border, 4 output bytes per thread.
@@ -1937,6 +1982,19 @@ struct se2gpu_orb {
     DevBuf<int> fs_count;
     PinBuf<int> h_fs_count;
     hipEvent_t ev_fs = nullptr;
+    // Camera (se2gpu_orb_set_camera): without one nothing below is allocated or launched.  The maps of cv::undistort for an
+    // image size are built on the host at the first extract of that size and kept per size; k_undistort writes the
+    // undistorted frames of a batch into `undist` (rows of cam_pitch(cols) bytes) and k_level0 reads them from there.
+    // `cam_maps` keeps one pair of maps (6 B per pixel) for every distinct size extracted under the current camera, without
+    // a bound: a handle sees a handful of sizes.  Setting another camera, or none, drops them all; none also frees `undist`.
+    bool has_cam = false;
+    se2gpu_camera cam{};
+    struct CamMaps {
+        DevBuf<uint32_t> xy;
+        DevBuf<uint16_t> frac;
+    };
+    std::map<std::pair<int, int>, CamMaps> cam_maps;
+    DevBuf<uint8_t> undist;
     ~se2gpu_orb() {
         if (own_stream) (void)hipStreamDestroy(own_stream);
         if (side_stream) (void)hipStreamDestroy(side_stream);
@@ -2173,6 +2231,118 @@ int orb_configure(se2gpu_orb* h, int rows, int cols) {
     return SE2GPU_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// camera: cv::undistort's maps, cv::undistortPoints, Frame::computeBoundUn (host code, OpenCV 3.2's arithmetic as DESIGN.md
+// restates it; every operation in double on the float members widened to double, no contraction in this translation unit)
+// ---------------------------------------------------------------------------------------------
+struct CamD {
+    double fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6;
+};
+
+int cam_check(const se2gpu_camera* c, const char* what) {
+    SE2_REQUIRE(c, SE2GPU_ERR_INVALID, "%s: camera is NULL", what);
+    SE2_REQUIRE(c->nd == 4 || c->nd == 5 || c->nd == 8, SE2GPU_ERR_INVALID,
+                "%s: %d distortion coefficients (4, 5 or 8: k1 k2 p1 p2 [k3 [k4 k5 k6]])", what, c->nd);
+    SE2_REQUIRE(c->fx != 0.f && c->fy != 0.f && std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) &&
+                    std::isfinite(c->cy), SE2GPU_ERR_INVALID, "%s: focal lengths must be finite and non-zero", what);
+    for (int i = 0; i < c->nd; ++i)
+        SE2_REQUIRE(std::isfinite(c->d[i]), SE2GPU_ERR_INVALID, "%s: distortion coefficient %d is not finite", what, i);
+    return SE2GPU_OK;
+}
+
+CamD cam_widen(const se2gpu_camera& c) {
+    double d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < c.nd; ++i) d[i] = (double)c.d[i];
+    return CamD{(double)c.fx, (double)c.fy, (double)c.cx, (double)c.cy, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]};
+}
+
+// round-half-even (the current rounding mode) into int32, as cvRound(double) does
+inline int cam_round(double v) { return (int)(long long)std::llrint(v); }
+
+// cv::undistort: initUndistortRectifyMap (R = I, newK = K, CV_16SC2) for stripes of min(max(1, 4096 / cols), rows) rows, each with
+// the principal point shifted by the stripe's first row; the column terms are ACCUMULATED along a row, as OpenCV does
+void cam_build_maps(const se2gpu_camera& cam, int rows, int cols, int16_t* map_xy, uint16_t* map_frac) {
+    const CamD c = cam_widen(cam);
+    const int stripe0 = std::min(std::max(1, 4096 / std::max(cols, 1)), rows);
+    for (int y0 = 0; y0 < rows; y0 += stripe0) {
+        const int n = std::min(stripe0, rows - y0);
+        const double a00 = c.fx, a01 = 0, a02 = c.cx, a10 = 0, a11 = c.fy, a12 = c.cy - (double)y0, a20 = 0, a21 = 0, a22 = 1;
+        // cv::invert, 3x3 closed form
+        const double det = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
+        const double d = 1. / det;
+        const double ir[9] = {(a11 * a22 - a12 * a21) * d, (a02 * a21 - a01 * a22) * d, (a01 * a12 - a02 * a11) * d,
+                              (a12 * a20 - a10 * a22) * d, (a00 * a22 - a02 * a20) * d, (a02 * a10 - a00 * a12) * d,
+                              (a10 * a21 - a11 * a20) * d, (a01 * a20 - a00 * a21) * d, (a00 * a11 - a01 * a10) * d};
+        for (int i = 0; i < n; ++i) {
+            int16_t* m1 = map_xy + (size_t)(y0 + i) * cols * 2;
+            uint16_t* m2 = map_frac + (size_t)(y0 + i) * cols;
+            double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+            for (int j = 0; j < cols; ++j, _x += ir[0], _y += ir[3], _w += ir[6]) {
+                const double w = 1. / _w, x = _x * w, y = _y * w;
+                const double x2 = x * x, y2 = y * y;
+                const double r2 = x2 + y2, _2xy = 2 * x * y;
+                const double kr = (1 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2) / (1 + ((c.k6 * r2 + c.k5) * r2 + c.k4) * r2);
+                const double u = c.fx * (x * kr + c.p1 * _2xy + c.p2 * (r2 + 2 * x2)) + c.cx;
+                const double v = c.fy * (y * kr + c.p1 * (r2 + 2 * y2) + c.p2 * _2xy) + c.cy;   // the camera's cy, not the stripe's
+                const int iu = cam_round(u * 32), iv = cam_round(v * 32);
+                m1[2 * j] = (int16_t)(iu >> 5);        // plain narrowing, as OpenCV's (short) casts
+                m1[2 * j + 1] = (int16_t)(iv >> 5);
+                m2[j] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+            }
+        }
+    }
+}
+
+// cv::undistortPoints(src, dst, K, D, Mat(), K): five fixed-point iterations, then the projection by K written out as the
+// 3x3 product it is (R = I, P = K)
+void cam_undistort_point(const CamD& c, float u, float v, float* out) {
+    const double ifx = 1. / c.fx, ify = 1. / c.fy;
+    double x = ((double)u - c.cx) * ifx, y = ((double)v - c.cy) * ify;
+    const double x0 = x, y0 = y;
+    for (int it = 0; it < 5; ++it) {
+        const double r2 = x * x + y * y;
+        const double icdist = (1 + ((c.k6 * r2 + c.k5) * r2 + c.k4) * r2) / (1 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2);
+        const double dX = 2 * c.p1 * x * y + c.p2 * (r2 + 2 * x * x);
+        const double dY = c.p1 * (r2 + 2 * y * y) + 2 * c.p2 * x * y;
+        x = (x0 - dX) * icdist;
+        y = (y0 - dY) * icdist;
+    }
+    const double xx = c.fx * x + 0. * y + c.cx, yy = 0. * x + c.fy * y + c.cy, ww = 1. / (0. * x + 0. * y + 1.);
+    out[0] = (float)(xx * ww);
+    out[1] = (float)(yy * ww);
+}
+
+// rows of the device maps and of the undistorted frames: whole groups of 4 pixels
+inline int cam_pitch(int cols) { return (cols + 3) & ~3; }
+
+// the handle's maps for the configured image size, built at the first extract of that size
+int cam_maps_for(se2gpu_orb* h, const se2gpu_orb::CamMaps** out) {
+    const int rows = h->g.rows, cols = h->g.cols, up = cam_pitch(cols);
+    se2gpu_orb::CamMaps& m = h->cam_maps[std::make_pair(rows, cols)];
+    if (!m.xy.p) {
+        std::vector<int16_t> xy((size_t)rows * cols * 2);
+        std::vector<uint16_t> fr((size_t)rows * cols);
+        cam_build_maps(h->cam, rows, cols, xy.data(), fr.data());
+        // device layout: OpenCV's bytes, rows padded to `up` pixels with entries that read pixel (0, 0)
+        std::vector<uint32_t> dxy((size_t)rows * up, 0u);
+        std::vector<uint16_t> dfr((size_t)rows * up, 0);
+        for (int r = 0; r < rows; ++r) {
+            std::memcpy(&dxy[(size_t)r * up], &xy[(size_t)r * cols * 2], (size_t)cols * 4);
+            std::memcpy(&dfr[(size_t)r * up], &fr[(size_t)r * cols], (size_t)cols * 2);
+        }
+        SE2_CHECK(m.frac.upload(dfr, h->stream));
+        const int rc = m.xy.upload(dxy, h->stream);      // (xy.p marks the pair as complete: last)
+        const hipError_t e = hipStreamSynchronize(h->stream);   // the host vectors leave scope
+        if (rc != SE2GPU_OK || e != hipSuccess) {
+            h->cam_maps.erase(std::make_pair(rows, cols));
+            if (rc != SE2GPU_OK) return rc;
+            SE2_HIP(e);
+        }
+    }
+    *out = &m;
+    return SE2GPU_OK;
+}
+
 // the device pipeline for `nframes` frames already in d_imgs (pitch = cols)
 int orb_run(se2gpu_orb* h, const uint8_t* d_imgs, int pitch, int nframes, se2gpu_keypoint* d_kps, uint8_t* d_desc,
             int32_t* d_counts, int cap) {
@@ -2184,6 +2354,13 @@ int orb_run(se2gpu_orb* h, const uint8_t* d_imgs, int pitch, int nframes, se2gpu
     SE2_CHECK(h->kp_list.reserve((size_t)h->max_batch * cap));
     SE2_CHECK(h->angles.reserve((size_t)h->max_batch * cap));
     SE2_CHECK(h->angle_cs.reserve((size_t)h->max_batch * cap));
+    // camera: the maps of this size and the buffer of undistorted frames, before anything is forked (the first extract of a
+    // size builds and uploads the maps and waits for the upload)
+    const se2gpu_orb::CamMaps* cm = nullptr;
+    if (h->has_cam) {
+        SE2_CHECK(cam_maps_for(h, &cm));
+        SE2_CHECK(h->undist.reserve((size_t)h->max_batch * g.rows * cam_pitch(g.cols)));
+    }
     // Batches are pipelined by level: the pyramid chain (k_level0, k_resize x 7: latency-bound, half the VALU idle) runs on
     // its own stream and the score and blur launches of level l start as soon as level l exists, instead of after the
     // whole pyramid - the score and blur kernels are VALU-bound and fill the gaps of the resize chain.  A single frame
@@ -2250,6 +2427,13 @@ int orb_run(se2gpu_orb* h, const uint8_t* d_imgs, int pitch, int nframes, se2gpu
     const int lgroup = std::min(L, 3);   // levels >= lgroup are scored / blurred by one launch each, after the last resize
     for (int l = 0; l < L; ++l) {
         if (l == 0) {
+            if (h->has_cam) {   // raw camera images: cv::undistort in front of the pyramid, level 0 reads its output
+                const int up = cam_pitch(g.cols);
+                SE2_LAUNCH(h->prof, sp, "k_undistort", k_undistort, dim3(F8, ((up / 4) * g.rows + 255) / 256), dim3(256), 0, g, d_imgs,
+                           cm->xy.p, cm->frac.p, up, h->undist.p);
+                d_imgs = h->undist.p;
+                pitch = up;
+            }
             dim3 grid(F8, ((g.stride[0] / 16) * (g.h[0] + 2 * kEdge) + 255) / 256);
             SE2_LAUNCH(h->prof, sp, "k_level0", k_level0, grid, dim3(256), 0, g, d_imgs, pitch, h->pyr.p, h->blur.p);
         } else {
@@ -2430,6 +2614,54 @@ void* se2gpu_orb_stream(se2gpu_orb* h) { return h ? (void*)h->stream : nullptr; 
 int se2gpu_orb_set_stream(se2gpu_orb* h, void* s) {
     SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "orb handle is NULL");
     h->stream = s ? (hipStream_t)s : h->own_stream;
+    return SE2GPU_OK;
+}
+
+int se2gpu_undistort_map(const se2gpu_camera* cam, int rows, int cols, int16_t* map_xy, uint16_t* map_frac) {
+    SE2_CHECK(cam_check(cam, "undistort_map"));
+    SE2_REQUIRE(map_xy && map_frac, SE2GPU_ERR_INVALID, "undistort_map: NULL output");
+    SE2_REQUIRE(rows > 0 && cols > 0, SE2GPU_ERR_INVALID, "undistort_map: image %dx%d", rows, cols);
+    cam_build_maps(*cam, rows, cols, map_xy, map_frac);
+    return SE2GPU_OK;
+}
+
+int se2gpu_undistort_points(const se2gpu_camera* cam, const float* xy_in, int n, float* xy_out) {
+    SE2_CHECK(cam_check(cam, "undistort_points"));
+    SE2_REQUIRE(n >= 0 && (n == 0 || (xy_in && xy_out)), SE2GPU_ERR_INVALID, "undistort_points: NULL argument");
+    const CamD c = cam_widen(*cam);
+    for (int i = 0; i < n; ++i) cam_undistort_point(c, xy_in[2 * i], xy_in[2 * i + 1], xy_out + 2 * i);
+    return SE2GPU_OK;
+}
+
+int se2gpu_frame_bounds_un(const se2gpu_camera* cam, int rows, int cols, se2gpu_frame_bounds* out) {
+    SE2_CHECK(cam_check(cam, "frame_bounds_un"));
+    SE2_REQUIRE(out, SE2GPU_ERR_INVALID, "frame_bounds_un: NULL output");
+    SE2_REQUIRE(rows > 0 && cols > 0, SE2GPU_ERR_INVALID, "frame_bounds_un: image %dx%d", rows, cols);
+    const float x = (float)cols, y = (float)rows;
+    if (cam->d[0] == 0.f) {   // Frame.cpp:186: decided by k1 alone
+        *out = se2gpu_frame_bounds{0.f, 0.f, x, y};
+        return SE2GPU_OK;
+    }
+    const CamD c = cam_widen(*cam);
+    const float in[4][2] = {{0.f, 0.f}, {x, 0.f}, {0.f, y}, {x, y}};
+    float p[4][2];
+    for (int i = 0; i < 4; ++i) cam_undistort_point(c, in[i][0], in[i][1], p[i]);
+    *out = se2gpu_frame_bounds{std::min(p[0][0], p[2][0]), std::min(p[0][1], p[1][1]), std::max(p[1][0], p[3][0]),
+                               std::max(p[2][1], p[3][1])};
+    return SE2GPU_OK;
+}
+
+int se2gpu_orb_set_camera(se2gpu_orb* h, const se2gpu_camera* cam) {
+    SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "orb handle is NULL");
+    if (cam) SE2_CHECK(cam_check(cam, "orb_set_camera"));
+    // nothing in flight may still read the maps that go away here
+    SE2_HIP(hipStreamSynchronize(h->stream));
+    if (h->side_stream) SE2_HIP(hipStreamSynchronize(h->side_stream));
+    if (h->pyr_stream) SE2_HIP(hipStreamSynchronize(h->pyr_stream));
+    h->cam_maps.clear();
+    if (!cam) h->undist.release();
+    h->has_cam = cam != nullptr;
+    if (cam) h->cam = *cam;
     return SE2GPU_OK;
 }
 

@@ -17,6 +17,35 @@ HARRIS_SCORE, FAST_SCORE = 0, 1
 KP_DTYPE = capi.KP_DTYPE
 
 
+def undistort_map(K, D, rows, cols):
+    """-> (map_xy (rows, cols, 2) int16, map_frac (rows, cols) uint16): the fixed-point maps of cv::undistort (host code)"""
+    cam = capi.Camera.from_KD(K, D)
+    rows, cols = int(rows), int(cols)
+    if rows <= 0 or cols <= 0:
+        raise ValueError(f"undistort_map: image {rows}x{cols}")
+    xy = np.zeros((rows, cols, 2), np.int16)
+    frac = np.zeros((rows, cols), np.uint16)
+    capi.check(capi.lib().se2gpu_undistort_map(C.byref(cam), rows, cols, xy.ctypes.data, frac.ctypes.data))
+    return xy, frac
+
+
+def undistort_points(K, D, pts):
+    """cv::undistortPoints(pts, out, K, D, Mat(), K): (n, 2) float32 pixel coordinates -> (n, 2) float32 (host code)"""
+    cam = capi.Camera.from_KD(K, D)
+    pts = np.ascontiguousarray(np.asarray(pts, np.float32).reshape(-1, 2))
+    out = np.zeros_like(pts)
+    capi.check(capi.lib().se2gpu_undistort_points(C.byref(cam), pts.ctypes.data, len(pts), out.ctypes.data))
+    return out
+
+
+def frame_bounds_un(K, D, rows, cols):
+    """Frame::computeBoundUn -> capi.FrameBounds (what the matcher's MatchByWindow / MatchByProjection take; host code)"""
+    cam = capi.Camera.from_KD(K, D)
+    b = capi.FrameBounds()
+    capi.check(capi.lib().se2gpu_frame_bounds_un(C.byref(cam), rows, cols, C.byref(b)))
+    return b
+
+
 class ORBextractor:
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, scoreType=FAST_SCORE, fastTh=20,
                  max_rows=480, max_cols=640, max_batch=1):
@@ -31,6 +60,14 @@ class ORBextractor:
 
     def GetScaleFactor(self) -> float:
         return float(capi.lib().se2gpu_orb_scale_factor(self._h))
+
+    def set_camera(self, K, D=None):
+        """set_camera(K, D): the extractor takes RAW camera images from now on and undistorts them on the device first, as
+        Frame::Frame does with cv::undistort(im, img, Kcam, Dcam) (Frame.cpp:22).  set_camera(None): no camera (the default)."""
+        if K is None:
+            capi.check(capi.lib().se2gpu_orb_set_camera(self._h, None))
+        else:
+            capi.check(capi.lib().se2gpu_orb_set_camera(self._h, C.byref(capi.Camera.from_KD(K, D))))
 
     def __call__(self, image, mask=None, cap=None):
         """-> (keypoints (n,) structured cv::KeyPoint array, descriptors (n,32) uint8)"""
