@@ -6342,6 +6342,21 @@ bool ba_resident_ok(const se2gpu_ba* h) {
     return ba_batchable(h) && h->model <= 1 && !h->odo_self_loop && h->P > 0 && (int)h->h_fixed.size() == h->P && h->Hpl.p &&
            h->Hpl.cap * 8 >= (size_t)h->L * 16 + (size_t)h->E * rec + 16 && h->Dinv.p && h->Dinv.cap >= 6 * (size_t)h->L;
 }
+// what the packs of both models hold.  The list and the records go into the multi-launch path's Hpl records (72 / 144 B per edge), the
+// landmark factors into its A_l (6 L + 1 doubles): both idle on this path
+void ba_fill_window(WindowArgsBase& a, const se2gpu_ba* h, int iters, int mode, long long* stamps) {
+    a.P = h->P; a.L = h->L; a.E = h->E; a.O = h->O; a.iters = iters; a.mode = mode;
+    a.lm_ptr = h->lm_ptr.p; a.e_kf = h->e_kf.p; a.e_uv = h->e_uv.p; a.e_info = h->e_info.p;
+    a.poses_a = h->poses_a.p; a.poses_b = h->poses_b.p; a.lms_a = h->lms_a.p; a.lms_b = h->lms_b.p;
+    a.fixed = h->fixed.p;
+    a.o_i = h->o_i.p; a.o_j = h->o_j.p; a.o_meas = h->o_meas.p; a.o_info = h->o_info.p;
+    a.ctl = h->ctl.p;
+    a.mail = h->d_mail;
+    a.stop = h->d_stop;
+    a.desc = reinterpret_cast<int4*>(h->Hpl.p);
+    a.ainv = h->Dinv.p;
+    a.stamps = stamps;
+}
 int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const volatile uint8_t* stop_flag,
                          se2gpu_ba_stats* stats, int* handled) {
     *handled = 0;
@@ -6388,37 +6403,17 @@ int ba_optimize_resident(se2gpu_ba** hs, int count, int iters, int mode, const v
         se2gpu_ba* h = hs[i];
         if (k == 0 || !same_class(k, k - 1)) class_streams.push_back(h->stream);
         SE2_CHECK(ba_run_prologue(h, class_streams.back(), &rs.events[(size_t)k], iters, mode, false, stop_flag));
+        long long* stamps = trace ? rs.stamps.p + 16 * (size_t)k : nullptr;
         if (h->model == 1) {
             Window3Args& a = rs.host3.p[k];
+            ba_fill_window(a, h, iters, mode, stamps);
             a.cam = h->cam3;
-            a.P = h->P; a.L = h->L; a.E = h->E; a.O = h->O; a.iters = iters; a.mode = mode;
-            a.lm_ptr = h->lm_ptr.p; a.e_kf = h->e_kf.p; a.e_uv = h->e_uv.p; a.e_info = h->e_info.p;
-            a.poses_a = h->poses_a.p; a.poses_b = h->poses_b.p; a.lms_a = h->lms_a.p; a.lms_b = h->lms_b.p;
-            a.fixed = h->fixed.p;
             a.prior_has = h->prior_has.p; a.prior_meas = h->prior_meas.p; a.prior_info = h->prior_info.p;
-            a.o_i = h->o_i.p; a.o_j = h->o_j.p; a.o_meas = h->o_meas.p; a.o_info = h->o_info.p;
-            a.ctl = h->ctl.p;
-            a.mail = h->d_mail;
-            a.stop = h->d_stop;
-            a.desc = reinterpret_cast<int4*>(h->Hpl.p);   // (the multi-launch path's Hpl records: 144 B per edge, idle on this path)
-            a.ainv = h->Dinv.p;
-            a.stamps = trace ? rs.stamps.p + 16 * (size_t)k : nullptr;
-            continue;
+        } else {
+            WindowArgs& a = rs.host.p[k];
+            ba_fill_window(a, h, iters, mode, stamps);
+            a.cam = h->cam;
         }
-        WindowArgs& a = rs.host.p[k];
-        a.cam = h->cam;
-        a.P = h->P; a.L = h->L; a.E = h->E; a.O = h->O; a.iters = iters; a.mode = mode;
-        a.lm_ptr = h->lm_ptr.p; a.e_kf = h->e_kf.p; a.e_uv = h->e_uv.p; a.e_info = h->e_info.p;
-        a.poses_a = h->poses_a.p; a.poses_b = h->poses_b.p; a.lms_a = h->lms_a.p; a.lms_b = h->lms_b.p;
-        a.fixed = h->fixed.p;
-        a.o_i = h->o_i.p; a.o_j = h->o_j.p; a.o_meas = h->o_meas.p; a.o_info = h->o_info.p;
-        a.ctl = h->ctl.p;
-        a.mail = h->d_mail;
-        a.stop = h->d_stop;
-        a.desc = reinterpret_cast<int4*>(h->Hpl.p);   // (the multi-launch path's W records: 72 B per edge, idle on this path; the list + the records by class)
-        a.ainv = h->Dinv.p;   // (the multi-launch path's A_l: 6 L + 1 doubles, idle on this path)
-        a.debug = 0;
-        a.stamps = trace ? rs.stamps.p + 16 * (size_t)k : nullptr;
     }
     {
         std::lock_guard<std::mutex> lk(launch_mu);

@@ -1,5 +1,5 @@
 // Device-side pieces of the SE3-expmap bundle adjustment that more than one translation unit needs (csrc/ba.hip: the multi-launch
-// k3_* kernels; csrc/ba_window3.hip: the one-workgroup-per-window solver): the camera of EdgeProjectXYZ2UV and its residual with
+// k3_* kernels; csrc/ba_window3.hip: the SE3 model of the one-workgroup-per-window solver, csrc/ba_window_skeleton.h): the camera of EdgeProjectXYZ2UV and its residual with
 // the 2x6 pose / 2x3 landmark Jacobians.  [3P g2o 20160424] EdgeProjectXYZ2UV::computeError / linearizeOplus, restated as in
 // oracle/ba3_ref.cpp.
 #pragma once

@@ -1,5 +1,6 @@
 // Device-side pieces of the SE(2)-XYZ bundle adjustment that more than one translation unit needs (csrc/ba.hip: the
-// multi-launch solver; csrc/ba_window.hip: the one-workgroup-per-window solver): the controller block of the device-side
+// multi-launch solver; csrc/ba_window_skeleton.h with its models csrc/ba_window.hip and csrc/ba_window3.hip: the
+// one-workgroup-per-window solver): the controller block of the device-side
 // Levenberg-Marquardt policy, the edge arithmetic of /root/reference/src/EdgeSE2XYZ.cpp:61-106 and
 // include/se2lam/EdgeSE2XYZ.h:62-102, the 3 x 3 landmark factor.  Everything is inline / internal.
 #pragma once

@@ -1,4 +1,4 @@
-// Helpers of the one-workgroup-per-window solvers (csrc/ba_window.hip: SE(2)-XYZ, csrc/ba_window3.hip: SE3-expmap): cross-lane
+// Helpers of the one-workgroup-per-window solver (csrc/ba_window_skeleton.h; its models csrc/ba_window.hip: SE(2)-XYZ, csrc/ba_window3.hip: SE3-expmap): cross-lane
 // sums by DPP, the packed lower triangle, LDS atomics, the fast reciprocal (square root), the 3x3 landmark factor, the Huber
 // weight, workgroup reductions.  Everything is force-inlined and internal to the translation unit that includes it.
 #pragma once

@@ -356,7 +356,7 @@ def test_forced_se3_odometry_topologies_equal_multi_launch_and_the_oracle(oracle
 
 
 def _lds3_bytes(P, nfree, threads):
-    """ba_window3_lds_bytes (csrc/ba_window3.hip) restated by reading it, not from a run: dynamic LDS = the column list (P ints), two
+    """ba_window3_lds_bytes (csrc/ba_window3.hip: window_lds_bytes of csrc/ba_window_skeleton.h with the SE3 model's constants) restated by reading it, not from a run: dynamic LDS = the column list (P ints), two
     sets of poses (12 doubles each per key frame of the window, fixed ones included), x and 1 / diag (6 nfree each), the staging
     strip (19 doubles per thread) and the packed triangle of S with b_s and a zero block row ((n + 6)(n + 7) / 2), n = 6 nfree;
     static LDS = BaCtl (1392 bytes) + the histogram, wave totals and lists (232 ints) + 45 doubles + 128; 160 KiB in all, n <= 192.
