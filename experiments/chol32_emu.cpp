@@ -84,7 +84,7 @@ int main(int argc, char** argv) {
         unsigned long long sw = 0;
         static unsigned long long head = 0;   // the launch's task counter (round 6): a workgroup's task is the number it draws, not its block index
         auto task = [&]() {
-            d_chol_tiles<false>(blockIdx.x, S.A.data(), PUB.data(), YU, S.ld, S.n, S.nbc, S.plan.tasks.data(), S.plan.deps.data(), nullptr, flagA.data(), flagR.data(),
+            d_chol_tiles<false>(blockIdx.x, S.A.data(), PUB.data(), YU, S.ld, S.n, S.nbc, S.plan.tasks.data(), S.plan.deps.data(), S.plan.neager.data(), nullptr, flagA.data(), flagR.data(),
                                 &epoch, &fail, nullptr, nullptr, x.data(), nullptr, &head, ntask);
             WAIT_VM();      // (the end of a wave completes what it has in flight)
         };

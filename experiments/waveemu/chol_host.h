@@ -9,7 +9,27 @@
 struct Plan {
     std::vector<int4> tasks;
     std::vector<int> deps;
+    std::vector<int> neager;   // per task: the entries at the end of its list that it polls in earnest (plan_neager)
 };
+
+// What solve_plan_build records beside the lists, derived from the lists themselves (a plan read from a file carries none): the
+// depth of a block column is one more than the largest depth in its diagonal task's list, and a tile task polls the trailing
+// entries of the largest depth in earnest.  x tasks: the last entry.  Any value is VALID for the kernel - it only chooses the
+// length of a sleep.
+inline void plan_neager(Plan& p, int nbc) {
+    std::vector<int> depth(nbc, 1);
+    for (const int4& t : p.tasks)
+        if ((t.x >> 16) == 0 && (t.x & 0xffff) == t.y)
+            for (int q = t.z; q < t.w; ++q) depth[t.y] = std::max(depth[t.y], depth[p.deps[q] & 0x7fff] + 1);
+    p.neager.clear();
+    for (const int4& t : p.tasks) {
+        int ne = 0;
+        if ((t.x >> 16) == 2) ne = 1;
+        else
+            for (int q = t.w - 1; q >= t.z && depth[p.deps[q] & 0x7fff] == depth[t.y] - 1; --q) ++ne;
+        p.neager.push_back(ne);
+    }
+}
 
 // The plan over a tile pattern.  P[i][j] (i >= j; i < nt tile rows, j < nbc block columns): tile (i, j) of the lower triangle is
 // non-zero; the tile row of the rhs row is non-zero everywhere.  Symbolic fill on tiles, then the tasks by block column -
@@ -40,18 +60,20 @@ inline Plan plan_from_pattern(std::vector<std::vector<char>> P, int nt, int nbc,
     for (int j = 0; j < nbc; ++j) {
         for (int m = 0; m < j; ++m)
             if (P[j][m]) depth[j] = std::max(depth[j], depth[m] + 1);
+        std::vector<int> cols;                    // the columns of the list in the order they are published: by depth, ties by index
+        for (int m = 0; m < j; ++m)
+            if (P[j][m]) cols.push_back(m);
+        std::stable_sort(cols.begin(), cols.end(), [&](int a, int b) { return depth[a] < depth[b]; });
         for (int i = j; i < nt; ++i) {            // the diagonal task, then the L tiles of the column
             if (i > j && !P[i][j]) continue;
             std::vector<int> d;
-            for (int m = 0; m < j; ++m)
-                if (P[j][m]) d.push_back(m | (i != j && P[i][m] ? 1 << 15 : 0));      // (the diagonal task's T is the identity: no T products)
+            for (int m : cols) d.push_back(m | (i != j && P[i][m] ? 1 << 15 : 0));      // (the diagonal task's T is the identity: no T products)
             add(0, i, j, d);
         }
         for (int r = 0; r < j; ++r) {
             if (!R[r][j]) continue;
             std::vector<int> d;
-            for (int m = 0; m < j; ++m)
-                if (P[j][m]) d.push_back(m | (m >= r && R[r][m] ? 1 << 15 : 0));
+            for (int m : cols) d.push_back(m | (m >= r && R[r][m] ? 1 << 15 : 0));
             add(1, r, j, d);
         }
     }
@@ -62,6 +84,7 @@ inline Plan plan_from_pattern(std::vector<std::vector<char>> P, int nt, int nbc,
         add(2, r, 0, d);
     }
     *chain_len = *std::max_element(depth.begin(), depth.end());
+    plan_neager(p, nbc);
     return p;
 }
 
@@ -123,6 +146,7 @@ inline bool chol_system_from_file(int NB, const char* path, CholSystem& S) {
     ok = ok && std::fread(S.A.data(), 8, S.A.size(), f) == S.A.size();
     std::fclose(f);
     for (int c = 0; ok && c < S.n; ++c) S.b[c] = S.A[(size_t)S.n * S.ld + c];
+    if (ok) plan_neager(S.plan, S.nbc);
     return ok;
 }
 // |A x - b|_inf / |b|_inf

@@ -408,6 +408,13 @@ int se2gpu_ba_debug_solve_plan(int P, int D, const uint8_t* pattern, int allow_n
 /* the same with the tile size of the dense solve as an argument (32 or 64) */
 int se2gpu_ba_debug_solve_plan_tile(int P, int D, const uint8_t* pattern, int allow_nd, int tile, int* nsys, int* nbc, int* depth, int* ntask,
                                     int* ndep, int32_t* pose_off, int32_t* tasks4, int task_cap, int32_t* deps, int dep_cap);
+/* A tile task's list is in the order in which its block columns are published (by depth on the dependency chain, ties by
+ * index), and the task polls the last `neager` entries - the columns of the largest depth - in earnest: one int per task of
+ * the plan above, in task order (1 for the x tasks, 0 for a task with an empty list). */
+int se2gpu_ba_debug_solve_plan_neager(int P, int D, const uint8_t* pattern, int allow_nd, int tile, int32_t* neager, int cap);
+/* ... and of the plan an initialised handle runs, read back from the device: *nsys = order of the (padded) system,
+ * *permuted = 1 when the fill-reducing order was taken, *ntask = tasks; neager (cap >= *ntask ints) may be NULL. */
+int se2gpu_ba_debug_plan_neager(se2gpu_ba* h, int* nsys, int* permuted, int* ntask, int32_t* neager, int cap);
 
 /* Track::doTriangulate (/root/reference/src/Track.cpp:378-419) for every match of a frame pair in one device pass -
  * SURVEY section 8(f).3.  Per feature i of the reference key frame with match_idx[i] >= 0 and no map point yet:

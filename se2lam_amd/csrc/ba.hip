@@ -1172,6 +1172,7 @@ template <bool VERIFY>
 __device__ __forceinline__ void d_chol_tiles(const unsigned bx_dispatch, const double* __restrict__ A, double* __restrict__ PUB,
                                                      double* __restrict__ YU, int ld, int n,
                                                      int nbc, const int4* __restrict__ tasks, const int* __restrict__ deps,
+                                                     const int* __restrict__ neager,
                                                      const int* __restrict__ col_src,
                                                      unsigned* __restrict__ flagA, unsigned* __restrict__ flagR,
                                                      const unsigned* __restrict__ epoch_ptr, double* __restrict__ fail,
@@ -1223,6 +1224,7 @@ __device__ __forceinline__ void d_chol_tiles(const unsigned bx_dispatch, const d
     long long* stamp = dbg ? dbg + (size_t)bx * 16 : nullptr;  // SE2GPU_BA_CHOL_TRACE=1: 100 MHz stamps
     if (stamp && tid == 0) stamp[0] = wall_clock64();
     const int4 tk = tasks[bx];   // {tile row | kind << 16, block column, first, one past the last entry of its dependency list}
+    const int ne = neager[bx];   // how many entries at the end of the list belong to the columns published last (solve_plan_build)
     if (tid < tk.w - tk.z && tid < 64) deps_s[tid] = deps[tk.z + tid];
     __syncthreads();
     if ((tk.x >> 16) == 2) {
@@ -1288,7 +1290,8 @@ __device__ __forceinline__ void d_chol_tiles(const unsigned bx_dispatch, const d
         D0[v] = A[(size_t)(kNB * j + orow + 4 * v) * ld + kNB * j + ocol];
         if (!isR && !isDiag) T0[v] = A[(size_t)(kNB * i + orow + 4 * v) * ld + kNB * j + ocol];
     }
-    // the block columns m < j with a non-zero L(j, m), ascending (all of them for a dense system); bit 15 of an entry: the
+    // the block columns m < j with a non-zero L(j, m), in the order they are published (by depth on the dependency chain,
+    // solve_plan_build; ascending for a dense system, where it is all of them); bit 15 of an entry: the
     // task's own tile row has a non-zero tile in that column too (L(i, m) / R(r, m)), otherwise only D is updated
     // A tile travels in the four 8-column slabs its producer's waves finish in (wave w eliminates columns 8 w .. 8 w + 7 and
     // publishes them with a flag of their own while the later waves still work).  Wave w of this task fetches slab w of
@@ -1308,7 +1311,7 @@ __device__ __forceinline__ void d_chol_tiles(const unsigned bx_dispatch, const d
             if (tid == 0) fail[0] = 1e6;
             return;
         }
-        const bool lazy = dq + 1 < tk.w;       // not the block column this task's elimination waits for
+        const bool lazy = dq < tk.w - ne;      // not one of the block columns this task's elimination waits for (the deepest ones)
         const unsigned* f0 = flagA + ((size_t)j * nbc + m) * kSlabs + wv;
         const unsigned* f1 = hasT ? (isR ? flagR : flagA) + ((size_t)i * nbc + m) * kSlabs + wv : f0;
         const int need = dq - tk.z + 1;
@@ -1565,13 +1568,14 @@ template <bool VERIFY>
 __global__ __launch_bounds__(256) void k_chol_tiles(const double* __restrict__ A, double* __restrict__ PUB,
                                                      double* __restrict__ YU, int ld, int n,
                                                      int nbc, const int4* __restrict__ tasks, const int* __restrict__ deps,
+                                                     const int* __restrict__ neager,
                                                      const int* __restrict__ col_src,
                                                      unsigned* __restrict__ flagA, unsigned* __restrict__ flagR,
                                                      const unsigned* __restrict__ epoch_ptr, double* __restrict__ fail,
                                                      long long* __restrict__ dbg, const BaCtl* __restrict__ ctl,
                                                      double* __restrict__ xout, unsigned long long* __restrict__ vfy,
                                                      unsigned long long* __restrict__ head, int ntask) {
-    d_chol_tiles<VERIFY>(blockIdx.x, A, PUB, YU, ld, n, nbc, tasks, deps, col_src, flagA, flagR, epoch_ptr, fail, dbg, ctl, xout, vfy, head, ntask);
+    d_chol_tiles<VERIFY>(blockIdx.x, A, PUB, YU, ld, n, nbc, tasks, deps, neager, col_src, flagA, flagR, epoch_ptr, fail, dbg, ctl, xout, vfy, head, ntask);
 }
 
 // x = R y  (R = L^-T upper triangular, y = augmented row n of A).  One wave per row.
@@ -3087,13 +3091,14 @@ struct se2gpu_ba {
     DevBuf<double> red_packed;    // sharded runs: the lower-triangular tiles of [S; b^T], what the all-reduce ships
     DevBuf<int4> chol_tasks;      // k_chol_tiles: {tile row | kind << 16, block column, dependency list [first, last)}, by column
     DevBuf<int> chol_deps;        // the dependency lists: block column | (own tile row non-zero there) << 15
+    DevBuf<int> chol_neager;      // per task: trailing list entries polled in earnest (solve_plan_build)
     DevBuf<int> pose_off;         // fill-reducing order of the pose solve: first system column of pose p (nullptr = 3 p)
     DevBuf<int> col_src;          // system column -> 3 * pose + component, -1 = padding (nullptr = identity)
     std::vector<int> h_pose_off;  // host copy (debug_reduced_system gathers S back into pose order)
     DevBuf<uint8_t> plan_nz;      // per block of the upper triangle: structurally non-zero (k_plan_odo, k_plan_pairs2)
     DevBuf<double> plan_nzd;      // the same as doubles: what a sharded run's all-reduce can merge
     PinBuf<uint8_t> h_plan_nz;
-    DevBuf<uint8_t> solver_arena; // chol_tasks | chol_deps | pose_off | col_src
+    DevBuf<uint8_t> solver_arena; // chol_tasks | chol_deps | chol_neager | pose_off | col_src
     int nsys = 0;                 // order of the (padded) system the solver factorises; D * P in natural order
     int solve_depth = 0;          // block columns on the longest dependency chain of the plan (debug)
     DevBuf<unsigned> chol_flags;  // [2][nt][nbc][kSlabs] epochs
@@ -3753,6 +3758,7 @@ struct SolvePlan {
     std::vector<int> pose_off, col_src;
     std::vector<int4> tasks;
     std::vector<int> deps;
+    std::vector<int> neager;   // per task: the trailing entries of its list that are polled in earnest (tile tasks: those of the deepest column)
 };
 
 // parts: the poses of every partition in order; pad: partitions (and therefore the rhs row) start on tile boundaries;
@@ -3826,37 +3832,48 @@ void solve_plan_build(int P, int D, const uint8_t* pat, const std::vector<std::v
     }
     sp.tasks.clear();
     sp.deps.clear();
+    sp.neager.clear();
     sp.ntile = 0;
-    std::vector<int> depth(nbc, 0);
+    std::vector<int> depth(nbc, 0), cols;
     sp.depth = 0;
     for (int j = 0; j < nbc; ++j) {
-        int dj = 0;
+        // A task takes the entries of its list strictly one after the other, so the list is written in the order in which the
+        // columns are PUBLISHED - by depth, ties by index - not by index: where two chains of equal length meet (the last columns
+        // of the two arcs in front of the first separator column) everything but the chains' last columns is multiplied while
+        // those are still being eliminated, and the `neager` entries at the end - the columns of the largest depth - are the
+        // ones the task polls in earnest.  In the natural order depth = index + 1: the lists are the ascending ones, neager = 1.
+        cols.clear();
         for (int m = 0; m < j; ++m)
-            if (L(j, m)) dj = std::max(dj, depth[m]);
+            if (L(j, m)) cols.push_back(m);
+        std::stable_sort(cols.begin(), cols.end(), [&](int a, int b) { return depth[a] < depth[b]; });
+        const int dj = cols.empty() ? 0 : depth[cols.back()];
+        int ne = 0;
+        for (int m : cols) ne += depth[m] == dj ? 1 : 0;
         depth[j] = dj + 1;
         sp.depth = std::max(sp.depth, depth[j]);
         for (int i = j; i < nt; ++i) {
             if (!L(i, j)) continue;
             const int first = (int)sp.deps.size();
-            for (int m = 0; m < j; ++m)
-                if (L(j, m)) sp.deps.push_back(m | ((i != j && L(i, m)) ? 0x8000 : 0));
+            for (int m : cols) sp.deps.push_back(m | ((i != j && L(i, m)) ? 0x8000 : 0));
             sp.tasks.push_back(make_int4(i, j, first, (int)sp.deps.size()));
+            sp.neager.push_back(ne);
             ++sp.ntile;
         }
         for (int r = 0; r < j; ++r) {
             if (!R(r, j)) continue;
             const int first = (int)sp.deps.size();
-            for (int m = 0; m < j; ++m)
-                if (L(j, m)) sp.deps.push_back(m | ((m >= r && R(r, m)) ? 0x8000 : 0));
+            for (int m : cols) sp.deps.push_back(m | ((m >= r && R(r, m)) ? 0x8000 : 0));
             sp.tasks.push_back(make_int4(r | (1 << 16), j, first, (int)sp.deps.size()));
+            sp.neager.push_back(ne);
             ++sp.ntile;
         }
     }
-    for (int r = 0; r < nbc; ++r) {   // x = R y, one task per tile row
+    for (int r = 0; r < nbc; ++r) {   // x = R y, one task per tile row: ascending block columns, the last one waited for in earnest
         const int first = (int)sp.deps.size();
         for (int j = r; j < nbc; ++j)
             if (R(r, j)) sp.deps.push_back(j);
         sp.tasks.push_back(make_int4(r | (2 << 16), 0, first, (int)sp.deps.size()));
+        sp.neager.push_back(1);
     }
 }
 
@@ -4459,27 +4476,30 @@ int ba_upload_graph(se2gpu_ba* h) {
         h->nsys = sp.nsys;
         h->solve_depth = sp.depth;
         h->chol_ntask = (int)sp.tasks.size();
-        {   // tasks | dependency lists | pose_off | col_src: one copy, through a pinned buffer of their own
+        {   // tasks | dependency lists | neager | pose_off | col_src: one copy, through a pinned buffer of their own
             auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
             const size_t b0 = up(sp.tasks.size() * sizeof(int4)), b1 = up(std::max<size_t>(sp.deps.size(), 1) * 4);
+            const size_t bn = up(sp.neager.size() * 4);
             const size_t b2 = sp.permuted ? up(sp.pose_off.size() * 4) : 0, b3 = sp.permuted ? up(sp.col_src.size() * 4) : 0;
             // (at least 1 MB each: the lists of the next window differ in length, and growing a pinned or a device buffer
             // costs more than a whole initialize - seen as +0.25 ms on the first window after se2gpu_ba_reserve)
-            SE2_CHECK(h->h_stage_solver.reserve(std::max<size_t>(b0 + b1 + b2 + b3, (size_t)1 << 20)));
-            SE2_CHECK(h->solver_arena.reserve(std::max<size_t>(b0 + b1 + b2 + b3, (size_t)1 << 20)));
+            SE2_CHECK(h->h_stage_solver.reserve(std::max<size_t>(b0 + b1 + bn + b2 + b3, (size_t)1 << 20)));
+            SE2_CHECK(h->solver_arena.reserve(std::max<size_t>(b0 + b1 + bn + b2 + b3, (size_t)1 << 20)));
             uint8_t* hp = h->h_stage_solver.p;
             std::memcpy(hp, sp.tasks.data(), sp.tasks.size() * sizeof(int4));
             std::memcpy(hp + b0, sp.deps.data(), sp.deps.size() * 4);
+            std::memcpy(hp + b0 + b1, sp.neager.data(), sp.neager.size() * 4);
             if (sp.permuted) {
-                std::memcpy(hp + b0 + b1, sp.pose_off.data(), sp.pose_off.size() * 4);
-                std::memcpy(hp + b0 + b1 + b2, sp.col_src.data(), sp.col_src.size() * 4);
+                std::memcpy(hp + b0 + b1 + bn, sp.pose_off.data(), sp.pose_off.size() * 4);
+                std::memcpy(hp + b0 + b1 + bn + b2, sp.col_src.data(), sp.col_src.size() * 4);
             }
-            SE2_HIP(hipMemcpyAsync(h->solver_arena.p, hp, b0 + b1 + b2 + b3, hipMemcpyHostToDevice, st));
+            SE2_HIP(hipMemcpyAsync(h->solver_arena.p, hp, b0 + b1 + bn + b2 + b3, hipMemcpyHostToDevice, st));
             h->chol_tasks.alias(reinterpret_cast<int4*>(h->solver_arena.p));
             h->chol_deps.alias(reinterpret_cast<int*>(h->solver_arena.p + b0));
+            h->chol_neager.alias(reinterpret_cast<int*>(h->solver_arena.p + b0 + b1));
             if (sp.permuted) {
-                h->pose_off.alias(reinterpret_cast<int*>(h->solver_arena.p + b0 + b1));
-                h->col_src.alias(reinterpret_cast<int*>(h->solver_arena.p + b0 + b1 + b2));
+                h->pose_off.alias(reinterpret_cast<int*>(h->solver_arena.p + b0 + b1 + bn));
+                h->col_src.alias(reinterpret_cast<int*>(h->solver_arena.p + b0 + b1 + bn + b2));
             }
         }
         if (sp.permuted) {
@@ -4903,11 +4923,11 @@ int ba_solve(se2gpu_ba* h, bool ctl = false) {
         h->chol_faulted = true;
         if (h->chol_vfy.p)
             SE2_LAUNCH(h->prof, st, "k_chol_tiles", k_chol_tiles<true>, dim3(h->chol_ntask - skip), dim3(256), 0, A, Rm, YU, ld, n, nbc,
-                       h->chol_tasks.p + skip, (const int*)h->chol_deps.p, (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
+                       h->chol_tasks.p + skip, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p + skip, (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
                        fail, h->chol_trace.p, c, h->xp.p, h->chol_vfy.p, head, h->chol_ntask - skip);
         else
             SE2_LAUNCH(h->prof, st, "k_chol_tiles", k_chol_tiles<false>, dim3(h->chol_ntask - skip), dim3(256), 0, A, Rm, YU, ld, n, nbc,
-                       h->chol_tasks.p + skip, (const int*)h->chol_deps.p, (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
+                       h->chol_tasks.p + skip, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p + skip, (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
                        fail, h->chol_trace.p, c, h->xp.p, (unsigned long long*)nullptr, head, h->chol_ntask - skip);
     }
     SE2_HIP(hipGetLastError());
@@ -5274,11 +5294,11 @@ int ba_build_batch_plan(BatchPlan& bp, se2gpu_ba** hs, int count, int iters, int
             double* fail = h->red + (size_t)ld * ld + 2;
             bp.verify = hs[0]->chol_vfy.p != nullptr;
             if (bp.verify)
-                bp.chol_v.add(h->chol_ntask, (const double*)h->red, Rm, YU, ld, n, nbc, h->chol_tasks.p, (const int*)h->chol_deps.p,
+                bp.chol_v.add(h->chol_ntask, (const double*)h->red, Rm, YU, ld, n, nbc, h->chol_tasks.p, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p,
                               (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
                               fail, h->chol_trace.p, (const BaCtl*)h->ctl.p, h->xp.p, h->chol_vfy.p, h->chol_head.p, h->chol_ntask);
             else
-                bp.chol.add(h->chol_ntask, (const double*)h->red, Rm, YU, ld, n, nbc, h->chol_tasks.p, (const int*)h->chol_deps.p,
+                bp.chol.add(h->chol_ntask, (const double*)h->red, Rm, YU, ld, n, nbc, h->chol_tasks.p, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p,
                             (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
                             fail, h->chol_trace.p, (const BaCtl*)h->ctl.p, h->xp.p, (unsigned long long*)nullptr, h->chol_head.p, h->chol_ntask);
         }
@@ -6057,6 +6077,29 @@ int se2gpu_ba_debug_solve_plan(int P, int D, const uint8_t* pattern, int allow_n
     return SE2GPU_OK;
 }
 
+// neager of every task of that plan (same arguments as se2gpu_ba_debug_solve_plan_tile, same task order)
+int se2gpu_ba_debug_solve_plan_neager(int P, int D, const uint8_t* pattern, int allow_nd, int tile, int32_t* neager, int cap) {
+    SE2_REQUIRE(P > 0 && (D == 3 || D == 6) && (tile == 32 || tile == 64) && neager, SE2GPU_ERR_INVALID, "debug_solve_plan_neager: bad argument");
+    SolvePlan sp;
+    solve_plan_choose(P, D, pattern, allow_nd != 0, sp, false, tile);
+    SE2_REQUIRE(cap >= (int)sp.neager.size(), SE2GPU_ERR_CAPACITY, "debug_solve_plan_neager: %zu tasks", sp.neager.size());
+    std::memcpy(neager, sp.neager.data(), sp.neager.size() * 4);
+    return SE2GPU_OK;
+}
+
+// ... and of the plan an initialised handle runs, read back from the device: *permuted = the fill-reducing order was taken
+int se2gpu_ba_debug_plan_neager(se2gpu_ba* h, int* nsys, int* permuted, int* ntask, int32_t* neager, int cap) {
+    SE2_REQUIRE(h && h->initialized && nsys && permuted && ntask, SE2GPU_ERR_STATE, "debug_plan_neager before initialize");
+    SE2_CHECK(ba_join(h));
+    SE2_HIP(hipStreamSynchronize(h->stream));
+    *nsys = h->nsys; *permuted = h->col_src.p ? 1 : 0; *ntask = h->chol_ntask;
+    if (neager) {
+        SE2_REQUIRE(cap >= h->chol_ntask && h->chol_neager.p, SE2GPU_ERR_CAPACITY, "debug_plan_neager: %d tasks", h->chol_ntask);
+        SE2_HIP(hipMemcpy(neager, h->chol_neager.p, (size_t)h->chol_ntask * 4, hipMemcpyDeviceToHost));
+    }
+    return SE2GPU_OK;
+}
+
 // SE2GPU_BA_CHOL_VERIFY=1: {mismatches, half-slabs checked} and up to `cap` records of 8 words (see d_chol_tiles); returns
 // SE2GPU_ERR_STATE when the handle does not run in verify mode
 int se2gpu_ba_debug_chol_verify(se2gpu_ba* h, unsigned long long* counts2, unsigned long long* records, int cap) {
@@ -6128,6 +6171,15 @@ int se2gpu_ba_debug_solve(se2gpu_ba* h, double lambda, double* x, int* factor_ok
             for (int q = 0; q < 6; ++q) std::fprintf(stderr, " %lld", tr[16 * (size_t)t + q] ? tr[16 * (size_t)t + q] - t0 : -1);
             std::fprintf(stderr, " %lld %lld", tr[16 * (size_t)t + 6], tr[16 * (size_t)t + 7] ? tr[16 * (size_t)t + 7] - t0 : -1);
             for (int q = 8; q < 16; ++q) std::fprintf(stderr, " %lld", tr[16 * (size_t)t + q] ? tr[16 * (size_t)t + q] - t0 : -1);
+            std::fprintf(stderr, "\n");
+        }
+        // the entries every tile task polls in earnest (the end of its list): any of them may be the one it waited for
+        std::vector<int> ne(h->chol_ntask);
+        SE2_HIP(hipMemcpy(ne.data(), h->chol_neager.p, ne.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int t = 0; t < h->chol_ntask; ++t) {
+            if ((tk[t].x >> 16) == 2 || ne[t] < 2) continue;
+            std::fprintf(stderr, "choleager %d", t);
+            for (int q = tk[t].w - ne[t]; q < tk[t].w; ++q) std::fprintf(stderr, " %d", dp[q]);
             std::fprintf(stderr, "\n");
         }
     }

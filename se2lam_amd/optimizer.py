@@ -123,6 +123,14 @@ class SlamOptimizer:
         capi.check(capi.lib().se2gpu_ba_debug_chol_verify(self._h, counts.ctypes.data, rec.ctypes.data, 64))
         return int(counts[0]), int(counts[1]), rec[:min(int(counts[0]), 64)]
 
+    def plan_neager(self):
+        """se2gpu_ba_debug_plan_neager: (order of the system the dense solve factorises, fill-reducing order taken, neager per task)"""
+        nsys, perm, ntask = C.c_int(0), C.c_int(0), C.c_int(0)
+        capi.check(capi.lib().se2gpu_ba_debug_plan_neager(self._h, C.byref(nsys), C.byref(perm), C.byref(ntask), None, 0))
+        ne = np.zeros(max(ntask.value, 1), np.int32)
+        capi.check(capi.lib().se2gpu_ba_debug_plan_neager(self._h, C.byref(nsys), C.byref(perm), C.byref(ntask), ne.ctypes.data, len(ne)))
+        return int(nsys.value), bool(perm.value), ne[:ntask.value]
+
     def solver_path(self) -> int:
         """se2gpu_ba_debug_solver_path: 0 dataflow, 1 column launches (configured), 2 column launches (fallback), 3 host"""
         return int(capi.lib().se2gpu_ba_debug_solver_path(self._h))

@@ -1,32 +1,42 @@
 """Critical path of k_chol_tiles from a trace written by `SE2GPU_BA_CHOL_TRACE=1 python tools/chol_trace.py 200 2> trace.txt`:
     python tools/chol_trace_summary.py trace.txt
-Walks back from the tile task that publishes last through the producer of its last dependency that published later (the
-tasks' dependency lists are in ascending block-column order, so the last entry is the one the elimination waits for)."""
+Walks back from the tile task that publishes last through the producer that published last among the entries it polls in
+earnest: the end of its dependency list, which is in depth order - one entry on a plain chain, the last columns of both arcs at
+the junction in front of the first separator column (`choleager` lines; a trace without them has one such entry per task)."""
 import sys
 
-rows = [l.split() for l in open(sys.argv[1]) if l.startswith("choltrace")]
+lines = [l.split() for l in open(sys.argv[1])]
+rows = [l for l in lines if l and l[0] == "choltrace"]
+eager = {int(l[1]): list(map(int, l[2:])) for l in lines if l and l[0] == "choleager"}   # (the same for every solve of the trace)
 n = len(rows) // 3          # tools/chol_trace.py solves three times; the last solve is analysed
 T = {}
 for r in rows[-n:]:
     t, i, kind, j, dep = map(int, r[1:6])
-    T[(i, kind, j)] = (dep, list(map(int, r[6:])))
+    T[(i, kind, j)] = (dep, list(map(int, r[6:])), eager.get(t, [dep]))
 tiles = {k: v for k, v in T.items() if k[1] != 2}
 print("tile tasks %d, x tasks %d, last tile published at %.1f us, last x task started at %.1f us" % (
     len(tiles), len(T) - len(tiles), max(v[1][5] for v in tiles.values()) / 100, max(v[1][0] for k, v in T.items() if k[1] == 2) / 100))
 k = max(tiles, key=lambda k: tiles[k][1][5])
 path = []
 while True:
-    dep, st = tiles[k]
-    path.append((k, dep, st))
-    if dep < 0: break
-    m, hasT = dep & 0x7fff, dep >> 15
+    dep, st, last = tiles[k]
+    if dep < 0:
+        path.append((k, dep, st))
+        break
     i, kind, j = k
-    cands = [(j, 0, m)]
-    if hasT: cands.append((i, kind, m))
-    cands = [c if c in tiles else (c[0], 1, c[2]) for c in cands]   # the diagonal task publishes R(m, m)
-    cands = [c for c in cands if c in tiles]
-    if not cands: break
-    k = max(cands, key=lambda c: tiles[c][1][5])
+    cands = []
+    for e in last:
+        m, hasT = e & 0x7fff, e >> 15
+        cs = [(j, 0, m)]
+        if hasT: cs.append((i, kind, m))
+        cs = [c if c in tiles else (c[0], 1, c[2]) for c in cs]   # the diagonal task publishes R(m, m)
+        cands += [(c, e) for c in cs if c in tiles]
+    if not cands:
+        path.append((k, dep, st))
+        break
+    nxt, dep = max(cands, key=lambda c: tiles[c[0]][1][5])
+    path.append((k, dep, st))
+    k = nxt
 path.reverse()
 prev = None
 tot = dict(flag=0, loads=0, mfma=0, staging=0, elim=0, publish=0)
