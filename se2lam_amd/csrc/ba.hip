@@ -31,7 +31,6 @@
 #include <limits>
 #include <mutex>
 #include <thread>
-#include <tuple>
 #include <memory>
 #include <unordered_map>
 
@@ -308,60 +307,62 @@ __device__ __forceinline__ void lin_landmark(int l, int sub, int beg, int end, i
     wave_copy_out(W + (size_t)E0 * 9, stage, ne * 9);
 }
 
+// The arguments of k_linearize (lin_args).  With `ctl` (device-side LM) poses / lms are the "a" buffers, poses_b / lms_b the
+// "b" buffers and `alt` the twin of the records W .. Dg; the controller says which of each the pass takes, and lambda.
+struct LinArgs {
+    CamDev cam;
+    int L;
+    const int *lm_ptr, *e_kf;
+    const double *e_uv, *e_info, *poses;
+    const uint8_t* fixed;
+    const double* lms;
+    double *W, *Hpp_e, *bp_e, *Hll, *bl;
+    double lambda;
+    double *Ainv, *zeta, *Dg;
+    const BaCtl* ctl;
+    const double *poses_b, *lms_b;
+    RecSet alt;
+};
 template <bool FUSED>
-__device__ __forceinline__ void d_linearize(const unsigned bx, CamDev cam, int L, const int* __restrict__ lm_ptr,
-                                                       const int* __restrict__ e_kf, const double* __restrict__ e_uv,
-                                                       const double* __restrict__ e_info,
-                                                       const double* __restrict__ poses,
-                                                       const uint8_t* __restrict__ fixed,
-                                                       const double* __restrict__ lms, double* W,
-                                                       double* Hpp_e, double* bp_e,
-                                                       double* __restrict__ Hll, double* __restrict__ bl, double lambda,
-                                                       double* __restrict__ Ainv, double* __restrict__ zeta,
-                                                       double* __restrict__ Dg,
-                                                       const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                       const double* __restrict__ lms_b, RecSet alt) {
-    if (ctl) {   // device-side LM: nothing to do after the run has ended, or when the k_update<true> of the slot before has
-                 // already written these very records (rec_valid); a retry runs like any other trial (the estimate did not
-                 // move, only lambda did)
-        if (ctl->done | ctl->rec_valid) return;
-        if (ctl->sel) { poses = poses_b; lms = lms_b; }
-        if (ctl->rec_sel) { W = alt.W; Dg = alt.Dg; Hll = alt.Hll; bl = alt.bl; Ainv = alt.Ainv; zeta = alt.zeta; }
-        lambda = ctl->lambda;
+__device__ __forceinline__ void d_linearize(const unsigned bx, const LinArgs& a) {
+    const double *poses = a.poses, *lms = a.lms;
+    RecSet rec{a.W, a.Dg, a.Hll, a.bl, a.Ainv, a.zeta};
+    double lambda = a.lambda;
+    // (FUSED, the only form that uses lambda: opaque to the compiler, which otherwise merges this load and the one of ctl->lambda
+    // below into ONE load of a chosen address - the struct's lambda then lives in scratch memory.  A scalar register: the value
+    // is uniform over the wave, as a kernel argument and as k_batched's copy of the window's entry)
+    if constexpr (FUSED) asm volatile("" : "+s"(lambda));
+    if (a.ctl) {   // device-side LM: nothing to do after the run has ended, or when the k_update<true> of the slot before has
+                   // already written these very records (rec_valid); a retry runs like any other trial (the estimate did not
+                   // move, only lambda did)
+        if (a.ctl->done | a.ctl->rec_valid) return;
+        if (a.ctl->sel) { poses = a.poses_b; lms = a.lms_b; }
+        if (a.ctl->rec_sel) rec = a.alt;
+        lambda = a.ctl->lambda;
     }
     const int gid = bx * kBlock + threadIdx.x;
     const int l = gid / kGroup, sub = gid % kGroup;
     double hll[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
     __shared__ double keep[(kBlock / 64) * kWaveLds];   // lin_park, lin_landmark
     int beg = 0, end = 0;
-    if (l < L) {
+    if (l < a.L) {
         const double lx = lms[3 * l], ly = lms[3 * l + 1], lz = lms[3 * l + 2];
-        beg = lm_ptr[l];
-        end = lm_ptr[l + 1];
+        beg = a.lm_ptr[l];
+        end = a.lm_ptr[l + 1];
         for (int e = beg + sub; e < end; e += kGroup) {
-            const int kf = e_kf[e];
+            const int kf = a.e_kf[e];
             double hpl[9], hpp[6], bpe[3], r0;
-            lin_edge(cam, poses[3 * kf], poses[3 * kf + 1], poses[3 * kf + 2], lx, ly, lz, e_uv[2 * e], e_uv[2 * e + 1],
-                     e_info[3 * e], e_info[3 * e + 1], e_info[3 * e + 2], !fixed[kf], hll, b, hpl, hpp, bpe, r0);
-            lin_park<FUSED>(e == beg + sub, e, hpl, hpp, bpe, keep, W, Hpp_e, bp_e);
+            lin_edge(a.cam, poses[3 * kf], poses[3 * kf + 1], poses[3 * kf + 2], lx, ly, lz, a.e_uv[2 * e], a.e_uv[2 * e + 1],
+                     a.e_info[3 * e], a.e_info[3 * e + 1], a.e_info[3 * e + 2], !a.fixed[kf], hll, b, hpl, hpp, bpe, r0);
+            lin_park<FUSED>(e == beg + sub, e, hpl, hpp, bpe, keep, rec.W, a.Hpp_e, a.bp_e);
         }
     }
-    lin_landmark<FUSED>(l, sub, beg, end, L, hll, b, lambda, keep, W, Hpp_e, bp_e, Hll, bl, Ainv, zeta, Dg);
+    lin_landmark<FUSED>(l, sub, beg, end, a.L, hll, b, lambda, keep, rec.W, a.Hpp_e, a.bp_e, rec.Hll, rec.bl, rec.Ainv, rec.zeta,
+                        rec.Dg);
 }
 template <bool FUSED>
-__global__ __launch_bounds__(kBlock) void k_linearize(CamDev cam, int L, const int* __restrict__ lm_ptr,
-                                                       const int* __restrict__ e_kf, const double* __restrict__ e_uv,
-                                                       const double* __restrict__ e_info,
-                                                       const double* __restrict__ poses,
-                                                       const uint8_t* __restrict__ fixed,
-                                                       const double* __restrict__ lms, double* W,
-                                                       double* Hpp_e, double* bp_e,
-                                                       double* __restrict__ Hll, double* __restrict__ bl, double lambda,
-                                                       double* __restrict__ Ainv, double* __restrict__ zeta,
-                                                       double* __restrict__ Dg,
-                                                       const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                       const double* __restrict__ lms_b, RecSet alt) {
-    d_linearize<FUSED>(blockIdx.x, cam, L, lm_ptr, e_kf, e_uv, e_info, poses, fixed, lms, W, Hpp_e, bp_e, Hll, bl, lambda, Ainv, zeta, Dg, ctl, poses_b, lms_b, alt);
+__global__ __launch_bounds__(kBlock) void k_linearize(LinArgs a) {
+    d_linearize<FUSED>(blockIdx.x, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -369,19 +370,24 @@ __global__ __launch_bounds__(kBlock) void k_linearize(CamDev cam, int L, const i
 // row-major) and gradients obi, obj.  Fixed vertices get zero blocks (constructQuadraticForm skips them).
 // ---------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void d_odometry(const unsigned bx, int O, const int* __restrict__ o_i, const int* __restrict__ o_j,
-                           const double* __restrict__ o_meas, const double* __restrict__ o_info,
-                           const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                           double* __restrict__ Oii, double* __restrict__ Ojj, double* __restrict__ Oij,
-                           double* __restrict__ obi, double* __restrict__ obj, const BaCtl* __restrict__ ctl,
-                           const double* __restrict__ poses_b) {
-    if (ctl && ctl->sel) poses = poses_b;   // (poses = the "a" buffer then: the controller says which holds the estimate)
+struct OdoArgs {
+    int O;
+    const int *o_i, *o_j;
+    const double *o_meas, *o_info, *poses;
+    const uint8_t* fixed;
+    double *Oii, *Ojj, *Oij, *obi, *obj;
+    const BaCtl* ctl;
+    const double* poses_b;
+};
+__device__ __forceinline__ void d_odometry(const unsigned bx, const OdoArgs& a) {
+    const double* poses = a.poses;
+    if (a.ctl && a.ctl->sel) poses = a.poses_b;   // (poses = the "a" buffer then: the controller says which holds the estimate)
     const int k = bx * blockDim.x + threadIdx.x;
-    if (k >= O) return;
-    const int i = o_i[k], j = o_j[k];
+    if (k >= a.O) return;
+    const int i = a.o_i[k], j = a.o_j[k];
     double e[3], A[9], B[9];
-    pre_se2(poses + 3 * i, poses + 3 * j, o_meas + 3 * k, e, A, B);
-    const double* W = o_info + 9 * k;
+    pre_se2(poses + 3 * i, poses + 3 * j, a.o_meas + 3 * k, e, A, B);
+    const double* W = a.o_info + 9 * k;
     double omr[3], WA[9], WB[9];
     for (int r = 0; r < 3; ++r) {
         omr[r] = -(W[r * 3] * e[0] + W[r * 3 + 1] * e[1] + W[r * 3 + 2] * e[2]);
@@ -390,27 +396,22 @@ __device__ __forceinline__ void d_odometry(const unsigned bx, int O, const int* 
             WB[r * 3 + c] = W[r * 3] * B[c] + W[r * 3 + 1] * B[3 + c] + W[r * 3 + 2] * B[6 + c];
         }
     }
-    const bool fi = !fixed[i], fj = !fixed[j];
+    const bool fi = !a.fixed[i], fj = !a.fixed[j];
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c) {
             const double aa = A[r] * WA[c] + A[3 + r] * WA[3 + c] + A[6 + r] * WA[6 + c];
             const double ab = A[r] * WB[c] + A[3 + r] * WB[3 + c] + A[6 + r] * WB[6 + c];
             const double bb = B[r] * WB[c] + B[3 + r] * WB[3 + c] + B[6 + r] * WB[6 + c];
-            Oii[k * 9 + r * 3 + c] = fi ? aa : 0.0;
-            Ojj[k * 9 + r * 3 + c] = fj ? bb : 0.0;
-            Oij[k * 9 + r * 3 + c] = (fi && fj) ? ab : 0.0;
+            a.Oii[k * 9 + r * 3 + c] = fi ? aa : 0.0;
+            a.Ojj[k * 9 + r * 3 + c] = fj ? bb : 0.0;
+            a.Oij[k * 9 + r * 3 + c] = (fi && fj) ? ab : 0.0;
         }
-        obi[k * 3 + r] = fi ? A[r] * omr[0] + A[3 + r] * omr[1] + A[6 + r] * omr[2] : 0.0;
-        obj[k * 3 + r] = fj ? B[r] * omr[0] + B[3 + r] * omr[1] + B[6 + r] * omr[2] : 0.0;
+        a.obi[k * 3 + r] = fi ? A[r] * omr[0] + A[3 + r] * omr[1] + A[6 + r] * omr[2] : 0.0;
+        a.obj[k * 3 + r] = fj ? B[r] * omr[0] + B[3 + r] * omr[1] + B[6 + r] * omr[2] : 0.0;
     }
 }
-__global__ void k_odometry(int O, const int* __restrict__ o_i, const int* __restrict__ o_j,
-                           const double* __restrict__ o_meas, const double* __restrict__ o_info,
-                           const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                           double* __restrict__ Oii, double* __restrict__ Ojj, double* __restrict__ Oij,
-                           double* __restrict__ obi, double* __restrict__ obj, const BaCtl* __restrict__ ctl,
-                           const double* __restrict__ poses_b) {
-    d_odometry(blockIdx.x, O, o_i, o_j, o_meas, o_info, poses, fixed, Oii, Ojj, Oij, obi, obj, ctl, poses_b);
+__global__ void k_odometry(OdoArgs a) {
+    d_odometry(blockIdx.x, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -456,24 +457,20 @@ __device__ __forceinline__ double d_pose_reduce_max(const unsigned bx, int P, co
     }
     return 0.0;
 }
-__device__ __forceinline__ void d_pose_reduce(const unsigned bx, int P, const int* __restrict__ pose_ptr,
-                                              const int* __restrict__ pose_edges, const double* __restrict__ Hpp_e,
-                                              const double* __restrict__ bp_e, const int* __restrict__ podo_ptr,
-                                              const int* __restrict__ podo_item, const double* __restrict__ Oii,
-                                              const double* __restrict__ Ojj, const double* __restrict__ obi,
-                                              const double* __restrict__ obj, double* __restrict__ Hpp, double* __restrict__ bp) {
-    (void)d_pose_reduce_max(bx, P, pose_ptr, pose_edges, Hpp_e, bp_e, podo_ptr, podo_item, Oii, Ojj, obi, obj, Hpp, bp);
+struct PoseReduceArgs {
+    int P;
+    const int *pose_ptr, *pose_edges;
+    const double *Hpp_e, *bp_e;
+    const int *podo_ptr, *podo_item;
+    const double *Oii, *Ojj, *obi, *obj;
+    double *Hpp, *bp;
+};
+__device__ __forceinline__ void d_pose_reduce(const unsigned bx, const PoseReduceArgs& a) {
+    (void)d_pose_reduce_max(bx, a.P, a.pose_ptr, a.pose_edges, a.Hpp_e, a.bp_e, a.podo_ptr, a.podo_item, a.Oii, a.Ojj, a.obi, a.obj,
+                            a.Hpp, a.bp);
 }
-__global__ __launch_bounds__(kBlock) void k_pose_reduce(int P, const int* __restrict__ pose_ptr,
-                                                         const int* __restrict__ pose_edges,
-                                                         const double* __restrict__ Hpp_e,
-                                                         const double* __restrict__ bp_e,
-                                                         const int* __restrict__ podo_ptr,
-                                                         const int* __restrict__ podo_item,
-                                                         const double* __restrict__ Oii, const double* __restrict__ Ojj,
-                                                         const double* __restrict__ obi, const double* __restrict__ obj,
-                                                         double* __restrict__ Hpp, double* __restrict__ bp) {
-    d_pose_reduce(blockIdx.x, P, pose_ptr, pose_edges, Hpp_e, bp_e, podo_ptr, podo_item, Oii, Ojj, obi, obj, Hpp, bp);
+__global__ __launch_bounds__(kBlock) void k_pose_reduce(PoseReduceArgs a) {
+    d_pose_reduce(blockIdx.x, a);
 }
 
 // k_pose_reduce and k_maxdiag in one launch (single GPU, first trial of an optimize()): the pose blocks by the first
@@ -533,42 +530,48 @@ __global__ __launch_bounds__(kBlock) void k_lambda0(int P, const int* __restrict
 // max |diag H| over the landmark blocks and the free poses' blocks (computeLambdaInit).  The pose diagonals come either as
 // `dpp` values per pose (Hpp_diag3) or, with stride9 set, straight from the 3 x 3 row-major blocks of k_pose_reduce; with
 // `ctl` the kernel also sets lambda_0 = 1e-5 * max itself (single GPU: no k_extract_diag / k_set_lambda launches).
-__device__ __forceinline__ void d_maxdiag(const unsigned bx, int L, const double* __restrict__ Hll, int P, const double* __restrict__ Hpp_diag3,
-                          const uint8_t* __restrict__ fixed, double* __restrict__ out, int dpp, int stride9,
-                          BaCtl* __restrict__ ctl) {
+struct MaxdiagArgs {
+    int L;
+    const double* Hll;
+    int P;
+    const double* Hpp_diag3;
+    const uint8_t* fixed;
+    double* out;
+    int dpp, stride9;
+    BaCtl* ctl;
+};
+__device__ __forceinline__ void d_maxdiag(const unsigned bx, const MaxdiagArgs& a) {
     __shared__ double sm[16];
     double m = 0;
-    for (int i0 = threadIdx.x; i0 < L; i0 += 4 * blockDim.x) {   // four landmarks' diagonals in flight per thread
+    for (int i0 = threadIdx.x; i0 < a.L; i0 += 4 * blockDim.x) {   // four landmarks' diagonals in flight per thread
         double v[4][3];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const size_t i = (size_t)min(i0 + u * (int)blockDim.x, L - 1);
-            v[u][0] = Hll[i * 6 + 0]; v[u][1] = Hll[i * 6 + 3]; v[u][2] = Hll[i * 6 + 5];
+            const size_t i = (size_t)min(i0 + u * (int)blockDim.x, a.L - 1);
+            v[u][0] = a.Hll[i * 6 + 0]; v[u][1] = a.Hll[i * 6 + 3]; v[u][2] = a.Hll[i * 6 + 5];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) m = fmax(m, fmax(fabs(v[u][0]), fmax(fabs(v[u][1]), fabs(v[u][2]))));
     }
-    for (int i = threadIdx.x; i < P; i += blockDim.x)
-        if (!fixed[i])
-            for (int r = 0; r < dpp; ++r)
-                m = fmax(m, fabs(stride9 ? Hpp_diag3[(size_t)i * 9 + r * 4] : Hpp_diag3[(size_t)i * dpp + r]));
+    for (int i = threadIdx.x; i < a.P; i += blockDim.x)
+        if (!a.fixed[i])
+            for (int r = 0; r < a.dpp; ++r)
+                m = fmax(m, fabs(a.stride9 ? a.Hpp_diag3[(size_t)i * 9 + r * 4] : a.Hpp_diag3[(size_t)i * a.dpp + r]));
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) m = fmax(m, __shfl_xor(m, s));
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmax(m, sm[w]);
-        out[0] = m;
-        if (ctl) {
-            ctl->lambda = 1e-5 * m;
-            ctl->ni = 2;
+        a.out[0] = m;
+        if (a.ctl) {
+            a.ctl->lambda = 1e-5 * m;
+            a.ctl->ni = 2;
         }
     }
 }
-__global__ void k_maxdiag(int L, const double* __restrict__ Hll, int P, const double* __restrict__ Hpp_diag3,
-                          const uint8_t* __restrict__ fixed, double* __restrict__ out, int dpp, int stride9,
-                          BaCtl* __restrict__ ctl) {
-    d_maxdiag(blockIdx.x, L, Hll, P, Hpp_diag3, fixed, out, dpp, stride9, ctl);
+__global__ void k_maxdiag(MaxdiagArgs a) {
+    d_maxdiag(blockIdx.x, a);
 }
 
 __global__ void k_extract_diag(int P, const double* __restrict__ Hpp, double* __restrict__ d3) {
@@ -616,39 +619,45 @@ constexpr int kChunk = 16;      // contributor pairs per group (d_reduce2 keeps 
 // entry of a 3x3 block) accumulating one chunk of <= kChunk contributor pairs of ONE reduced-system block; blocks
 // with several chunks are packed into the same workgroup and combined in LDS in chunk order (deterministic).
 // grp = {block index or -1, first pair, last pair, (first group of the block in this WG) | (number of groups << 8)}
-__device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int nwg_off, double lambda, int root,
-                                                     const int4* __restrict__ grp, const int* __restrict__ blk_a,
-                                                     const int* __restrict__ blk_b, const int* __restrict__ pair_i,
-                                                     const int* __restrict__ pair_j, const int* __restrict__ blk_odo,
-                                                     const double* __restrict__ W,
-                                                     const double* __restrict__ Dg,
-                                                     const uint8_t* __restrict__ fixed, const int* __restrict__ pose_ptr,
-                                                     const int* __restrict__ pose_edges, const int* __restrict__ podo_ptr,
-                                                     const int* __restrict__ podo_item, const int* __restrict__ o_i,
-                                                     const int* __restrict__ o_j, const double* __restrict__ o_meas,
-                                                     const double* __restrict__ o_info, const double* __restrict__ poses,
-                                                     double* __restrict__ S, double* __restrict__ bp,
-                                                     const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                     unsigned* __restrict__ epoch, const int* __restrict__ pose_off, int nsys,
-                                                     const double* __restrict__ W_alt, const double* __restrict__ Dg_alt) {
-    if (ctl && ctl->rec_sel) { W = W_alt; Dg = Dg_alt; }   // the record set of this slot (RecSet)
+struct Reduce2Args {
+    int P, ld, nwg_off;
+    double lambda;
+    int root;
+    const int4* grp;
+    const int *blk_a, *blk_b, *pair_i, *pair_j, *blk_odo;
+    const double *W, *Dg;
+    const uint8_t* fixed;
+    const int *pose_ptr, *pose_edges, *podo_ptr, *podo_item, *o_i, *o_j;
+    const double *o_meas, *o_info, *poses;
+    double *S, *bp;
+    const BaCtl* ctl;
+    const double* poses_b;
+    unsigned* epoch;
+    const int* pose_off;
+    int nsys;
+    const double *W_alt, *Dg_alt;
+};
+__device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& ra) {
+    const double *W = ra.W, *Dg = ra.Dg, *poses = ra.poses;
+    if (ra.ctl && ra.ctl->rec_sel) { W = ra.W_alt; Dg = ra.Dg_alt; }   // the record set of this slot (RecSet)
+    double lambda = ra.lambda;
     // pose p's three unknowns live in the columns pose_off[p] .. + 2 of the system (the solver's fill-reducing order, with
     // identity padding between its partitions: solve_plan_build); nullptr = natural order, 3 p
-    const int n = pose_off ? nsys : 3 * P;
+    const int n = ra.pose_off ? ra.nsys : 3 * ra.P;
     __shared__ double part[kGrpPerWG][9];
     __shared__ double dpart[kBlock / 64][12];
     // grid = [P + 1 diagonal workgroups | off-diagonal workgroups, rounded up to a multiple of the 8 XCDs].  The diagonal
     // ones have the longest dependent chain (edge list -> edge rows -> landmark z, then the PreEdgeSE2 terms) and must
     // not queue behind the others for a CU slot, so they come FIRST.
-    const int ndiag = (P + 1 + 7) & ~7;
+    const int ndiag = (ra.P + 1 + 7) & ~7;
     if ((int)bx >= ndiag) {
         const int bid = (int)bx - ndiag;
-        const int nwg_pad = (nwg_off + 7) & ~7;
+        const int nwg_pad = (ra.nwg_off + 7) & ~7;
         // XCD-aware order: workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  The plan is ordered
         // by pose block row, so XCD x takes the x-th CONTIGUOUS eighth of it: the W rows of its pose range are
         // fetched into one L2 instead of all eight (measured: 178 MB of HBM traffic per launch for 51 MB of operands).
         const int wg = (bid & 7) * (nwg_pad >> 3) + (bid >> 3);
-        if (wg >= nwg_off) return;
+        if (wg >= ra.nwg_off) return;
         // 7 groups of 9 lanes per wave (lane 63 idles), 4 waves: the 9 lanes of a group share their loads through
         // ds_bpermute, so a group must not straddle two waves
         const int lane = threadIdx.x & 63, gw = lane / 9, en = lane - 9 * gw;
@@ -659,10 +668,10 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
         // as its address is known: the group descriptor beside the controller block, the block descriptor and the indices of
         // ALL pairs of the chunk beside each other, the fixed flags and columns beside the edge blocks.
         int4 d = make_int4(-1, 0, 0, 0);
-        if (g < kGrpPerWG) d = grp[(size_t)wg * kGrpPerWG + g];
-        if (ctl) {
-            if (ctl->done) return;
-            if (ctl->sel) poses = poses_b;
+        if (g < kGrpPerWG) d = ra.grp[(size_t)wg * kGrpPerWG + g];
+        if (ra.ctl) {
+            if (ra.ctl->done) return;
+            if (ra.ctl->sel) poses = ra.poses_b;
         }
         const int r = en / 3, c = en - 3 * r;
         double acc0 = 0, acc1 = 0;
@@ -675,13 +684,13 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
             const int gb = 9 * gw, t8 = min(en, 7);
             int q0 = min(d.y + t8, d.z - 1), q1 = min(d.y + 8 + t8, d.z - 1);
             int my_i0 = 0, my_j0 = 0, my_i1 = 0, my_j1 = 0;
-            if (d.z > d.y) { my_i0 = pair_i[q0]; my_j0 = pair_j[q0]; my_i1 = pair_i[q1]; my_j1 = pair_j[q1]; }
-            a = blk_a[d.x];
-            b = blk_b[d.x];
-            od = blk_odo[d.x];
-            free_ab = !fixed[a] && !fixed[b];      // (a block may have no pairs at all - an odometry edge only)
-            ca = pose_off ? pose_off[a] : 3 * a;
-            cb = pose_off ? pose_off[b] : 3 * b;
+            if (d.z > d.y) { my_i0 = ra.pair_i[q0]; my_j0 = ra.pair_j[q0]; my_i1 = ra.pair_i[q1]; my_j1 = ra.pair_j[q1]; }
+            a = ra.blk_a[d.x];
+            b = ra.blk_b[d.x];
+            od = ra.blk_odo[d.x];
+            free_ab = !ra.fixed[a] && !ra.fixed[b];      // (a block may have no pairs at all - an odometry edge only)
+            ca = ra.pose_off ? ra.pose_off[a] : 3 * a;
+            cb = ra.pose_off ? ra.pose_off[b] : 3 * b;
             // The group loads every word ONCE (counters: 21 L1 accesses per load instruction with one row per lane): lane t
             // the t-th word of both 72-byte blocks of every pair (16 load instructions per round of 8 pairs instead of 48),
             // and the row of W_i / row of W_j an entry needs comes from the neighbours' registers (ds_bpermute).
@@ -690,7 +699,7 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
                 const bool second = ((q - d.y) & 8) != 0;
                 if (!second && q != d.y) {   // a long chunk: the indices of its next sixteen pairs
                     q0 = min(q + t8, d.z - 1); q1 = min(q + 8 + t8, d.z - 1);
-                    my_i0 = pair_i[q0]; my_j0 = pair_j[q0]; my_i1 = pair_i[q1]; my_j1 = pair_j[q1];
+                    my_i0 = ra.pair_i[q0]; my_j0 = ra.pair_j[q0]; my_i1 = ra.pair_i[q1]; my_j1 = ra.pair_j[q1];
                 }
                 const int my_i = second ? my_i1 : my_i0, my_j = second ? my_j1 : my_j0;
                 double wi[8], wj[8];
@@ -727,7 +736,7 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
                 out = -tot;
                 if (od >= 0) {  // PreEdgeSE2 between a and b: A^T W B (transposed when the edge runs b -> a)
                     double e[3], A[9], B[9], WA[9], WB[9], omr[3];
-                    odo_terms(poses, fixed, o_i, o_j, o_meas, o_info, od >> 1, e, A, B, WA, WB, omr);
+                    odo_terms(poses, ra.fixed, ra.o_i, ra.o_j, ra.o_meas, ra.o_info, od >> 1, e, A, B, WA, WB, omr);
                     // (no dynamic index into the private arrays: that would put them - and a scratch segment - into memory)
                     const int rr = (od & 1) ? c : r, cc = (od & 1) ? r : c;
                     const double a0 = rr == 0 ? A[0] : (rr == 1 ? A[1] : A[2]), a1 = rr == 0 ? A[3] : (rr == 1 ? A[4] : A[5]),
@@ -737,38 +746,38 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
                     out += a0 * b0 + a1 * b1 + a2 * b2;
                 }
             }
-            S[(size_t)(ca + r) * ld + cb + c] = out;
-            S[(size_t)(cb + c) * ld + ca + r] = out;
+            ra.S[(size_t)(ca + r) * ra.ld + cb + c] = out;
+            ra.S[(size_t)(cb + c) * ra.ld + ca + r] = out;
         }
         return;
     }
-    if (ctl) {
-        if (ctl->done) return;
-        if (ctl->sel) poses = poses_b;
-        lambda = ctl->lambda;
+    if (ra.ctl) {
+        if (ra.ctl->done) return;
+        if (ra.ctl->sel) poses = ra.poses_b;
+        lambda = ra.ctl->lambda;
     }
     // ---- diagonal part: one workgroup per pose (+ one that clears the padding)
     const int p = (int)bx;
-    if (p > P) return;
+    if (p > ra.P) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double* __restrict__ bs = S + (size_t)n * ld;
-    if (p == P) {
-        for (size_t t = (size_t)n * ld + n + threadIdx.x; t < (size_t)ld * ld; t += kBlock) S[t] = 0.0;
+    double* __restrict__ bs = ra.S + (size_t)n * ra.ld;
+    if (p == ra.P) {
+        for (size_t t = (size_t)n * ra.ld + n + threadIdx.x; t < (size_t)ra.ld * ra.ld; t += kBlock) ra.S[t] = 0.0;
         if (threadIdx.x == 0) {
-            S[(size_t)ld * ld + 2] = 0.0;  // factorisation flag of the solve that follows
-            *epoch += 1u;                   // ... and its epoch (the tile flags of k_chol_tiles are compared with it)
+            ra.S[(size_t)ra.ld * ra.ld + 2] = 0.0;  // factorisation flag of the solve that follows
+            *ra.epoch += 1u;                   // ... and its epoch (the tile flags of k_chol_tiles are compared with it)
         }
         return;
     }
     double acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // S diag (6 sym), bp (3), g (3)
-    const bool fa = fixed[p];
+    const bool fa = ra.fixed[p];
     __shared__ double odoc[8][12];  // PreEdgeSE2 contributions of this pose, one lane each (sin/cos: kept off thread 0)
-    const int no = fa ? 0 : podo_ptr[p + 1] - podo_ptr[p];
+    const int no = fa ? 0 : ra.podo_ptr[p + 1] - ra.podo_ptr[p];
     if ((int)threadIdx.x >= kBlock - 8 && (int)threadIdx.x - (kBlock - 8) < min(no, 8)) {
-        const int t = podo_ptr[p] + (int)threadIdx.x - (kBlock - 8);
-        const int k = podo_item[t] >> 1, isj = podo_item[t] & 1;
+        const int t = ra.podo_ptr[p] + (int)threadIdx.x - (kBlock - 8);
+        const int k = ra.podo_item[t] >> 1, isj = ra.podo_item[t] & 1;
         double e[3], A[9], B[9], WA[9], WB[9], omr[3];
-        odo_terms(poses, fixed, o_i, o_j, o_meas, o_info, k, e, A, B, WA, WB, omr);
+        odo_terms(poses, ra.fixed, ra.o_i, ra.o_j, ra.o_meas, ra.o_info, k, e, A, B, WA, WB, omr);
         double J[9], WJ[9];   // (element-wise selects: a pointer to one of two private arrays would put both into scratch memory)
 #pragma unroll
         for (int t9 = 0; t9 < 9; ++t9) { J[t9] = isj ? B[t9] : A[t9]; WJ[t9] = isj ? WB[t9] : WA[t9]; }
@@ -783,7 +792,7 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
     if (!fa) {
         // gather of the per-edge diagonal records (write_diag_record): edge list -> one 96-byte record per edge; the
         // indices of up to four edges per thread are fetched first, then all the records
-        const int e0 = pose_ptr[p], ne = pose_ptr[p + 1] - e0;
+        const int e0 = ra.pose_ptr[p], ne = ra.pose_ptr[p + 1] - e0;
         for (int base = 0; base < ne; base += 4 * kBlock) {
             int ee[4];
             double wgt[4];
@@ -791,7 +800,7 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
             for (int u = 0; u < 4; ++u) {
                 const int t = base + u * kBlock + (int)threadIdx.x;
                 wgt[u] = t < ne ? 1.0 : 0.0;
-                ee[u] = pose_edges[e0 + min(t, ne - 1)];
+                ee[u] = ra.pose_edges[e0 + min(t, ne - 1)];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -820,10 +829,10 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
         const int src = i < 9 ? sym[i] : i - 3;  // H entry, or bp component (slots 6..8)
         double v = dpart[0][src] + dpart[1][src] + dpart[2][src] + dpart[3][src];
         for (int t = 0; t < min(no, 8); ++t) v += odoc[t][i];
-        for (int t = podo_ptr[p] + 8; t < podo_ptr[p] + no; ++t) {  // more than 8 PreEdgeSE2 at one pose: serial tail
-            const int k = podo_item[t] >> 1, isj = podo_item[t] & 1;
+        for (int t = ra.podo_ptr[p] + 8; t < ra.podo_ptr[p] + no; ++t) {  // more than 8 PreEdgeSE2 at one pose: serial tail
+            const int k = ra.podo_item[t] >> 1, isj = ra.podo_item[t] & 1;
             double e[3], A[9], B[9], WA[9], WB[9], omr[3];
-            odo_terms(poses, fixed, o_i, o_j, o_meas, o_info, k, e, A, B, WA, WB, omr);
+            odo_terms(poses, ra.fixed, ra.o_i, ra.o_j, ra.o_meas, ra.o_info, k, e, A, B, WA, WB, omr);
             // (selects, no pointers or dynamic indices into the private arrays: they would live in scratch memory, and the
             // kernel would need a scratch segment for a tail that practically never runs)
             const int r = i < 9 ? i / 3 : i - 9, c = i < 9 ? i - 3 * (i / 3) : 0;
@@ -840,34 +849,20 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, int P, int ld, int 
         if (i < 9) {
             const int r = i / 3, c = i - 3 * r;
             double out;
-            if (fa) out = (r == c && root) ? 1.0 : 0.0;
-            else out = v + ((r == c && root) ? lambda : 0.0);
-            const int cp = pose_off ? pose_off[p] : 3 * p;
-            S[(size_t)(cp + r) * ld + cp + c] = out;
+            if (fa) out = (r == c && ra.root) ? 1.0 : 0.0;
+            else out = v + ((r == c && ra.root) ? lambda : 0.0);
+            const int cp = ra.pose_off ? ra.pose_off[p] : 3 * p;
+            ra.S[(size_t)(cp + r) * ra.ld + cp + c] = out;
         } else {
             const int r = i - 9;
             const double gz = dpart[0][9 + r] + dpart[1][9 + r] + dpart[2][9 + r] + dpart[3][9 + r];
-            bs[(pose_off ? pose_off[p] : 3 * p) + r] = fa ? 0.0 : v - gz;
-            bp[(size_t)p * 3 + r] = fa ? 0.0 : v;
+            bs[(ra.pose_off ? ra.pose_off[p] : 3 * p) + r] = fa ? 0.0 : v - gz;
+            ra.bp[(size_t)p * 3 + r] = fa ? 0.0 : v;
         }
     }
 }
-__global__ __launch_bounds__(kBlock) void k_reduce2(int P, int ld, int nwg_off, double lambda, int root,
-                                                     const int4* __restrict__ grp, const int* __restrict__ blk_a,
-                                                     const int* __restrict__ blk_b, const int* __restrict__ pair_i,
-                                                     const int* __restrict__ pair_j, const int* __restrict__ blk_odo,
-                                                     const double* __restrict__ W,
-                                                     const double* __restrict__ Dg,
-                                                     const uint8_t* __restrict__ fixed, const int* __restrict__ pose_ptr,
-                                                     const int* __restrict__ pose_edges, const int* __restrict__ podo_ptr,
-                                                     const int* __restrict__ podo_item, const int* __restrict__ o_i,
-                                                     const int* __restrict__ o_j, const double* __restrict__ o_meas,
-                                                     const double* __restrict__ o_info, const double* __restrict__ poses,
-                                                     double* __restrict__ S, double* __restrict__ bp,
-                                                     const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                     unsigned* __restrict__ epoch, const int* __restrict__ pose_off, int nsys,
-                                                     const double* __restrict__ W_alt, const double* __restrict__ Dg_alt) {
-    d_reduce2(blockIdx.x, P, ld, nwg_off, lambda, root, grp, blk_a, blk_b, pair_i, pair_j, blk_odo, W, Dg, fixed, pose_ptr, pose_edges, podo_ptr, podo_item, o_i, o_j, o_meas, o_info, poses, S, bp, ctl, poses_b, epoch, pose_off, nsys, W_alt, Dg_alt);
+__global__ __launch_bounds__(kBlock) void k_reduce2(Reduce2Args a) {
+    d_reduce2(blockIdx.x, a);
 }
 
 // odometry pose-pose blocks: S_ij += Oij, S_ji += Oij^T, at the poses' columns of the system the solver factorises (pose_off:
@@ -906,6 +901,26 @@ inline size_t chol_work_doubles(int ld) {
     const size_t nt = (size_t)ld / kNB;
     return std::max((size_t)ld * ld, 2 * nt * nt * kSlabs * kSlabDoubles + (size_t)ld);
 }   // k_chol_tiles: a tile is handed on in the four 8-column slabs its waves eliminate
+
+// The arguments of k_chol_tiles (chol_args).  d_chol_tiles itself keeps its positional list: the wave emulator
+// (experiments/chol32_emu.cpp) compiles its lines and calls that form.
+struct CholArgs {
+    const double* A;
+    double *PUB, *YU;
+    int ld, n, nbc;
+    const int4* tasks;
+    const int *deps, *neager, *col_src;
+    unsigned *flagA, *flagR;
+    const unsigned* epoch_ptr;
+    double* fail;
+    long long* dbg;
+    const BaCtl* ctl;
+    double* xout;
+    unsigned long long *vfy, *head;
+    int ntask;
+};
+template <bool VERIFY>
+__device__ __forceinline__ void d_chol_tiles(const unsigned bx, const CholArgs& a);   // (behind k_chol_tiles)
 
 __device__ inline double bcast_lane(double v, int lane) {  // lane must be a compile-time / wave-uniform constant
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
@@ -1565,17 +1580,13 @@ __device__ __forceinline__ void d_chol_tiles(const unsigned bx_dispatch, const d
     if (stamp && tid == 192) stamp[5] = wall_clock64();
 }
 template <bool VERIFY>
-__global__ __launch_bounds__(256) void k_chol_tiles(const double* __restrict__ A, double* __restrict__ PUB,
-                                                     double* __restrict__ YU, int ld, int n,
-                                                     int nbc, const int4* __restrict__ tasks, const int* __restrict__ deps,
-                                                     const int* __restrict__ neager,
-                                                     const int* __restrict__ col_src,
-                                                     unsigned* __restrict__ flagA, unsigned* __restrict__ flagR,
-                                                     const unsigned* __restrict__ epoch_ptr, double* __restrict__ fail,
-                                                     long long* __restrict__ dbg, const BaCtl* __restrict__ ctl,
-                                                     double* __restrict__ xout, unsigned long long* __restrict__ vfy,
-                                                     unsigned long long* __restrict__ head, int ntask) {
-    d_chol_tiles<VERIFY>(blockIdx.x, A, PUB, YU, ld, n, nbc, tasks, deps, neager, col_src, flagA, flagR, epoch_ptr, fail, dbg, ctl, xout, vfy, head, ntask);
+__global__ __launch_bounds__(256) void k_chol_tiles(CholArgs a) {
+    d_chol_tiles<VERIFY>(blockIdx.x, a);
+}
+template <bool VERIFY>
+__device__ __forceinline__ void d_chol_tiles(const unsigned bx, const CholArgs& a) {
+    d_chol_tiles<VERIFY>(bx, a.A, a.PUB, a.YU, a.ld, a.n, a.nbc, a.tasks, a.deps, a.neager, a.col_src, a.flagA, a.flagR, a.epoch_ptr, a.fail,
+                         a.dbg, a.ctl, a.xout, a.vfy, a.head, a.ntask);
 }
 
 // x = R y  (R = L^-T upper triangular, y = augmented row n of A).  One wave per row.
@@ -1635,22 +1646,28 @@ struct SpecArgs {
 // robust chi^2 of the landmark's edges at the trial state, and the landmark part of computeScale().
 // With xp == nullptr it evaluates chi^2 at the current state (x = 0).  Per-block partials -> part[2*blockIdx].
 // ---------------------------------------------------------------------------------------------
+struct UpdArgs {
+    CamDev cam;
+    int L;
+    double lambda;
+    const int *lm_ptr, *e_kf;
+    const double *e_uv, *e_info, *poses;
+    const uint8_t* fixed;
+    const double *lms, *xp, *zeta, *W, *bl;
+    double *lms_trial, *part;
+    const BaCtl* ctl;
+    const double* poses_b;
+    FinArgs fin;
+    const double* Ainv;
+    SpecArgs sp;
+};
 template <bool LIN>
-__device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, double lambda, const int* __restrict__ lm_ptr,
-                                                    const int* __restrict__ e_kf, const double* __restrict__ e_uv,
-                                                    const double* __restrict__ e_info,
-                                                    const double* __restrict__ poses,
-                                                    const uint8_t* __restrict__ fixed, const double* __restrict__ lms,
-                                                    const double* __restrict__ xp, const double* __restrict__ zeta,
-                                                    const double* __restrict__ W, const double* __restrict__ bl,
-                                                    double* __restrict__ lms_trial, double* __restrict__ part,
-                                                    const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                    FinArgs fin, const double* __restrict__ Ainv, SpecArgs sp) {
+__device__ __forceinline__ void d_update(const unsigned bx, const UpdArgs& a) {
     // LIN: a lane's first edge waits here for the landmark sums (lin_park); the finisher workgroup stages the trial poses in it
     __shared__ double lds[LIN ? (kBlock / 64) * kWaveLds : 3 * 1024];
     static_assert((kBlock / 64) * kWaveLds >= 3 * 1024, "the finisher's pose stage");
-    if (fin.enabled && (int)bx == fin.nblk) {
-        finish_trial(fin, part, lambda, lds);
+    if (a.fin.enabled && (int)bx == a.fin.nblk) {
+        finish_trial(a.fin, a.part, a.lambda, lds);
         return;
     }
     // The kernel is a chain of dependent loads (controller / CSR bounds -> edge records -> pose gathers) around very
@@ -1658,22 +1675,25 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
     // beside the controller block, and for the first two edges of a lane (a landmark has 6 observations on average, a
     // lane takes every 8th) ALL operands of both passes - W_e and x_p for the back-substitution, the pose, measurement and
     // information for the robust chi^2 - before the first use.  Lanes with more edges take the rest in the old two-pass form.
+    const double *poses = a.poses, *lms = a.lms, *zeta = a.zeta, *W = a.W, *bl = a.bl, *Ainv = a.Ainv;
+    double* lms_trial = a.lms_trial;
+    double lambda = a.lambda;
     const int gid = bx * kBlock + threadIdx.x;
     const int l = gid / kGroup, sub = gid % kGroup;
     int beg = 0, end = 0;
-    if (l < L) {
-        beg = lm_ptr[l];
-        end = lm_ptr[l + 1];
+    if (l < a.L) {
+        beg = a.lm_ptr[l];
+        end = a.lm_ptr[l + 1];
     }
-    if (ctl) {   // (poses, lms) / lms_trial are the "a" / "b" buffers: the controller says which holds the estimate
-        if (ctl->done) return;
-        if (ctl->sel) {
+    if (a.ctl) {   // (poses, lms) / lms_trial are the "a" / "b" buffers: the controller says which holds the estimate
+        if (a.ctl->done) return;
+        if (a.ctl->sel) {
             const double* t = lms; lms = lms_trial; lms_trial = const_cast<double*>(t);
-            poses = poses_b;
+            poses = a.poses_b;
         }
-        lambda = ctl->lambda;
+        lambda = a.ctl->lambda;
     }
-    const bool step = xp != nullptr;
+    const bool step = a.xp != nullptr;
     // LIN: if this trial is accepted and lambda falls to lambda / 3 (lm_lambda_spec: every gain ratio >= 0.937), the next slot
     // linearises the very state this pass evaluates - same poses, landmarks, edges and lane mapping.  So the pass writes
     // that linearisation's records into the other record set; the finisher knows whether the guess held (lm_records_advance)
@@ -1682,12 +1702,12 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
     bool spec = false;
     double lambda_spec = 0;
     RecSet wr{};
-    if (LIN && ctl && step) {
-        spec = ctl->it + 1 < ctl->iters;
-        lambda_spec = lm_lambda_spec(lambda, ctl->mode);
-        const int rs = ctl->rec_sel;
-        const RecSet rd = sp.set[rs];
-        wr = sp.set[rs ^ 1];
+    if (LIN && a.ctl && step) {
+        spec = a.ctl->it + 1 < a.ctl->iters;
+        lambda_spec = lm_lambda_spec(lambda, a.ctl->mode);
+        const int rs = a.ctl->rec_sel;
+        const RecSet rd = a.sp.set[rs];
+        wr = a.sp.set[rs ^ 1];
         W = rd.W; zeta = rd.zeta; bl = rd.bl; Ainv = rd.Ainv;
     }
     double* keep = lds;
@@ -1705,25 +1725,25 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
         const int e = beg + sub + k * kGroup;
         ev[k] = e < end;
         const int ec = ev[k] ? e : max(end - 1, 0);   // (a landmark without edges loads edge 0 of the array: harmless)
-        const bool has = l < L && end > beg;
-        ekf[k] = has ? e_kf[ec] : 0;
+        const bool has = l < a.L && end > beg;
+        ekf[k] = has ? a.e_kf[ec] : 0;
 #pragma unroll
         for (int i = 0; i < 9; ++i) ey[k][i] = (has && step) ? W[(size_t)ec * 9 + i] : 0.0;
-        euv[k][0] = has ? e_uv[2 * (size_t)ec] : 0.0;
-        euv[k][1] = has ? e_uv[2 * (size_t)ec + 1] : 0.0;
+        euv[k][0] = has ? a.e_uv[2 * (size_t)ec] : 0.0;
+        euv[k][1] = has ? a.e_uv[2 * (size_t)ec + 1] : 0.0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) ew[k][i] = has ? e_info[3 * (size_t)ec + i] : 0.0;
+        for (int i = 0; i < 3; ++i) ew[k][i] = has ? a.e_info[3 * (size_t)ec + i] : 0.0;
     }
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
         const int kf = ekf[k];
         epose[k][0] = poses[3 * kf]; epose[k][1] = poses[3 * kf + 1]; epose[k][2] = poses[3 * kf + 2];
-        efix[k] = fixed[kf] != 0;
+        efix[k] = a.fixed[kf] != 0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) ep[k][i] = step ? xp[3 * kf + i] : 0.0;
+        for (int i = 0; i < 3; ++i) ep[k][i] = step ? a.xp[3 * kf + i] : 0.0;
     }
     double lw0[3] = {0, 0, 0}, zz[3] = {0, 0, 0}, blv[3] = {0, 0, 0}, av[6] = {0, 0, 0, 0, 0, 0};
-    if (l < L) {
+    if (l < a.L) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             lw0[c] = lms[(size_t)l * 3 + c];
@@ -1734,7 +1754,7 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
             for (int c = 0; c < 6; ++c) av[c] = Ainv[(size_t)l * 6 + c];
         }
     }
-    if (l < L && step) {
+    if (l < a.L && step) {
 #pragma unroll
         for (int k = 0; k < KS; ++k)
             if (ev[k]) {
@@ -1742,22 +1762,22 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
                 for (int c = 0; c < 3; ++c) x[c] -= ey[k][c] * ep[k][0] + ey[k][3 + c] * ep[k][1] + ey[k][6 + c] * ep[k][2];
             }
         for (int e = beg + sub + KS * kGroup; e < end; e += kGroup) {
-            const int kf = e_kf[e];
+            const int kf = a.e_kf[e];
             const double* y = W + (size_t)e * 9;
-            const double p0 = xp[3 * kf], p1 = xp[3 * kf + 1], p2 = xp[3 * kf + 2];
+            const double p0 = a.xp[3 * kf], p1 = a.xp[3 * kf + 1], p2 = a.xp[3 * kf + 2];
 #pragma unroll
             for (int c = 0; c < 3; ++c) x[c] -= y[c] * p0 + y[3 + c] * p1 + y[6 + c] * p2;
         }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) x[c] = group_sum(x[c]);
-    if (l < L && step) {   // x holds -sum_e W_e^T dp_e:  x_l = A^T (zeta + x)
+    if (l < a.L && step) {   // x holds -sum_e W_e^T dp_e:  x_l = A^T (zeta + x)
         const double t0 = zz[0] + x[0], t1 = zz[1] + x[1], t2 = zz[2] + x[2];
         x[0] = av[0] * t0 + av[1] * t1 + av[3] * t2;
         x[1] = av[2] * t1 + av[4] * t2;
         x[2] = av[5] * t2;
     }
-    if (l < L) {
+    if (l < a.L) {
         double lw[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) lw[c] = lw0[c] + x[c];
@@ -1777,26 +1797,26 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
             }
             if (LIN && spec) {
                 double hpl[9], hpp[6], bpe[3], r0;
-                lin_edge(cam, px, py, pth, lw[0], lw[1], lw[2], u, v, w0, w1, w2, !fx, hll, bsum, hpl, hpp, bpe, r0);
+                lin_edge(a.cam, px, py, pth, lw[0], lw[1], lw[2], u, v, w0, w1, w2, !fx, hll, bsum, hpl, hpp, bpe, r0);
                 chi += r0;
-                lin_park<true>(e == beg + sub, e, hpl, hpp, bpe, keep, wr.W, sp.Hpp_e, sp.bp_e);
+                lin_park<true>(e == beg + sub, e, hpl, hpp, bpe, keep, wr.W, a.sp.Hpp_e, a.sp.bp_e);
                 return;
             }
             double e0, e1;
-            se2xyz<false>(cam, px, py, pth, lw[0], lw[1], lw[2], u, v, e0, e1, nullptr, nullptr);
+            se2xyz<false>(a.cam, px, py, pth, lw[0], lw[1], lw[2], u, v, e0, e1, nullptr, nullptr);
             double r0, r1;
-            huber(e0 * (w0 * e0 + w1 * e1) + e1 * (w1 * e0 + w2 * e1), cam.huber, r0, r1);
+            huber(e0 * (w0 * e0 + w1 * e1) + e1 * (w1 * e0 + w2 * e1), a.cam.huber, r0, r1);
             chi += r0;
         };
 #pragma unroll
         for (int k = 0; k < KS; ++k)
             if (ev[k]) edge_chi(beg + sub + k * kGroup, epose[k][0], epose[k][1], epose[k][2], efix[k], ep[k], euv[k][0], euv[k][1], ew[k][0], ew[k][1], ew[k][2]);
         for (int e = beg + sub + KS * kGroup; e < end; e += kGroup) {
-            const int kf = e_kf[e];
+            const int kf = a.e_kf[e];
             double dp[3] = {0, 0, 0};
-            if (step) { dp[0] = xp[3 * kf]; dp[1] = xp[3 * kf + 1]; dp[2] = xp[3 * kf + 2]; }
-            edge_chi(e, poses[3 * kf], poses[3 * kf + 1], poses[3 * kf + 2], fixed[kf] != 0, dp, e_uv[2 * e], e_uv[2 * e + 1],
-                     e_info[3 * e], e_info[3 * e + 1], e_info[3 * e + 2]);
+            if (step) { dp[0] = a.xp[3 * kf]; dp[1] = a.xp[3 * kf + 1]; dp[2] = a.xp[3 * kf + 2]; }
+            edge_chi(e, poses[3 * kf], poses[3 * kf + 1], poses[3 * kf + 2], a.fixed[kf] != 0, dp, a.e_uv[2 * e], a.e_uv[2 * e + 1],
+                     a.e_info[3 * e], a.e_info[3 * e + 1], a.e_info[3 * e + 2]);
         }
     }
     chi = wave_sum(chi);
@@ -1807,35 +1827,25 @@ __device__ __forceinline__ void d_update(const unsigned bx, CamDev cam, int L, d
     if (threadIdx.x == 0) {
         double c = 0, s = 0;
         for (int i = 0; i < kBlock / 64; ++i) { c += sm[0][i]; s += sm[1][i]; }
-        if (fin.enabled) {   // write-through stores, landed before the counter moves (the finisher may sit behind another L2)
-            store_agent(part + 2 * bx, d2_t{c, s});
+        if (a.fin.enabled) {   // write-through stores, landed before the counter moves (the finisher may sit behind another L2)
+            store_agent(a.part + 2 * bx, d2_t{c, s});
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(fin.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(a.fin.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-            part[2 * bx] = c;
-            part[2 * bx + 1] = s;
+            a.part[2 * bx] = c;
+            a.part[2 * bx + 1] = s;
         }
     }
     // The records come last: chi^2 and the gain denominator are out, so the finisher sums, decides and posts while the landmark
     // workgroups write the next linearisation (nothing below reads the controller).
     if (LIN && spec)
-        lin_landmark<true>(l, sub, beg, end, L, hll, bsum, lambda_spec, keep, wr.W, sp.Hpp_e, sp.bp_e, wr.Hll, wr.bl, wr.Ainv,
+        lin_landmark<true>(l, sub, beg, end, a.L, hll, bsum, lambda_spec, keep, wr.W, a.sp.Hpp_e, a.sp.bp_e, wr.Hll, wr.bl, wr.Ainv,
                            wr.zeta, wr.Dg);
 }
 template <bool LIN>
-__global__ __launch_bounds__(kBlock) void k_update(CamDev cam, int L, double lambda, const int* __restrict__ lm_ptr,
-                                                    const int* __restrict__ e_kf, const double* __restrict__ e_uv,
-                                                    const double* __restrict__ e_info,
-                                                    const double* __restrict__ poses,
-                                                    const uint8_t* __restrict__ fixed, const double* __restrict__ lms,
-                                                    const double* __restrict__ xp, const double* __restrict__ zeta,
-                                                    const double* __restrict__ W, const double* __restrict__ bl,
-                                                    double* __restrict__ lms_trial, double* __restrict__ part,
-                                                    const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                    FinArgs fin, const double* __restrict__ Ainv, SpecArgs sp) {
-    d_update<LIN>(blockIdx.x, cam, L, lambda, lm_ptr, e_kf, e_uv, e_info, poses, fixed, lms, xp, zeta, W, bl, lms_trial, part, ctl, poses_b, fin, Ainv, sp);
+__global__ __launch_bounds__(kBlock) void k_update(UpdArgs a) {
+    d_update<LIN>(blockIdx.x, a);
 }
-
 
 // a dataflow solve timed out and the host switched the handle to the per-column launches: the trial is simply redone
 __global__ void k_ctl_clear_error(BaCtl* __restrict__ ctl) {
@@ -1991,22 +2001,19 @@ __device__ void finish_trial(const FinArgs& fin, const double* part, double lamb
 // part of computeScale().  out[0] = chi2_trial, out[1] = scale (local to this rank), out[2] = factorisation flag (already
 // there).  Single GPU with a controller: also advances the LM state (decide != 0) and posts it when the run has ended
 // or the host asked for it (notify).  step == 0 evaluates the current state (x = 0) and seeds the controller's chi^2.
-__global__ void k_finalize(int nparts, const double* __restrict__ part, int P, double lambda,
-                           const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                           const double* __restrict__ xp, const double* __restrict__ bp, double* __restrict__ poses_trial,
-                           int O, const int* __restrict__ o_i, const int* __restrict__ o_j,
-                           const double* __restrict__ o_meas, const double* __restrict__ o_info, int root,
-                           double* __restrict__ out, volatile double* __restrict__ mail, double seq,
-                           BaCtl* __restrict__ ctl, int step_arg, int decide, int notify,
-                           const volatile int* __restrict__ stop) {
+__global__ void k_finalize(FinArgs fin, int nparts, const double* __restrict__ part, double lambda) {
     __shared__ double sm[2][16];
     __shared__ double sp[3 * 1024];  // trial poses staged for the odometry pass when P <= 1024
     __shared__ int post_s;
-    bool step = xp != nullptr;
+    BaCtl* ctl = fin.ctl;
+    volatile double* mail = fin.mail;
+    const double* poses = fin.poses;
+    double* poses_trial = fin.poses_trial;
+    double* out = fin.out;
+    const bool step = fin.step != 0;
     if (ctl) {
-        step = step_arg != 0;
         if (ctl->done) {   // the run is over: only answer a pending notification (sharded runs: k_lm_decide does)
-            if (decide) end_slot(ctl, mail, notify != 0, threadIdx.x, blockDim.x, step);
+            if (fin.decide) end_slot(ctl, mail, fin.notify != 0, threadIdx.x, blockDim.x, step);
             return;
         }
         if (ctl->sel) { const double* t = poses; poses = poses_trial; poses_trial = const_cast<double*>(t); }
@@ -2017,31 +2024,31 @@ __global__ void k_finalize(int nparts, const double* __restrict__ part, int P, d
         chi += part[2 * i];
         scale += part[2 * i + 1];
     }
-    for (int p = threadIdx.x; p < P; p += blockDim.x) {
+    for (int p = threadIdx.x; p < fin.P; p += blockDim.x) {
         double x = poses[3 * p], y = poses[3 * p + 1], th = poses[3 * p + 2];
-        if (step && !fixed[p]) {
-            const double d0 = xp[3 * p], d1 = xp[3 * p + 1], d2 = xp[3 * p + 2];
+        if (step && !fin.fixed[p]) {
+            const double d0 = fin.xp[3 * p], d1 = fin.xp[3 * p + 1], d2 = fin.xp[3 * p + 2];
             x += d0; y += d1; th = normalize_theta(th + d2);
             // computeScale(): sum_j x_j (lambda x_j + b_j).  bp is this rank's LOCAL pose gradient (its landmark shard's
             // edges, + the odometry edges on the root): every rank contributes x.b_local to the all-reduced sum, the
             // lambda x.x term enters exactly once (root).
-            if (root) scale += d0 * (lambda * d0 + bp[3 * p]) + d1 * (lambda * d1 + bp[3 * p + 1]) + d2 * (lambda * d2 + bp[3 * p + 2]);
-            else scale += d0 * bp[3 * p] + d1 * bp[3 * p + 1] + d2 * bp[3 * p + 2];
+            if (fin.root) scale += d0 * (lambda * d0 + fin.bp[3 * p]) + d1 * (lambda * d1 + fin.bp[3 * p + 1]) + d2 * (lambda * d2 + fin.bp[3 * p + 2]);
+            else scale += d0 * fin.bp[3 * p] + d1 * fin.bp[3 * p + 1] + d2 * fin.bp[3 * p + 2];
         }
         if (step) { poses_trial[3 * p] = x; poses_trial[3 * p + 1] = y; poses_trial[3 * p + 2] = th; }
         if (p < 1024) { sp[3 * p] = x; sp[3 * p + 1] = y; sp[3 * p + 2] = th; }
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < O; k += blockDim.x) {
-        const int i = o_i[k], j = o_j[k];
+    for (int k = threadIdx.x; k < fin.O; k += blockDim.x) {
+        const int i = fin.o_i[k], j = fin.o_j[k];
         double pi[3], pj[3];
         for (int c = 0; c < 3; ++c) {
             pi[c] = (i < 1024) ? sp[3 * i + c] : (step ? poses_trial[3 * i + c] : poses[3 * i + c]);
             pj[c] = (j < 1024) ? sp[3 * j + c] : (step ? poses_trial[3 * j + c] : poses[3 * j + c]);
         }
         double e[3], A[9], B[9];
-        pre_se2(pi, pj, o_meas + 3 * k, e, A, B);
-        const double* W = o_info + 9 * k;
+        pre_se2(pi, pj, fin.o_meas + 3 * k, e, A, B);
+        const double* W = fin.o_info + 9 * k;
         for (int r = 0; r < 3; ++r) chi += e[r] * (W[r * 3] * e[0] + W[r * 3 + 1] * e[1] + W[r * 3 + 2] * e[2]);
     }
     chi = wave_sum(chi);
@@ -2059,27 +2066,27 @@ __global__ void k_finalize(int nparts, const double* __restrict__ part, int P, d
         out[0] = sm[0][0]; out[1] = sm[1][0]; out[3] = 0;
         if (!step) out[2] = 0;
         post_s = 0;
-        if (ctl && decide) {
+        if (ctl && fin.decide) {
             if (!step) {   // evaluation of the starting state
                 ctl->current_chi = ctl->chi2_init = ctl->chi2_final = sm[0][0];
-                if (stop && *stop) { ctl->stopped = 1; ctl->done = 1; }
+                if (fin.stop && *fin.stop) { ctl->stopped = 1; ctl->done = 1; }
                 if (ctl->iters <= 0) ctl->done = 1;
             } else {
                 const double sc[3] = {sm[0][0], sm[1][0], out[2]};
-                lm_advance(ctl, sc, stop && *stop);
+                lm_advance(ctl, sc, fin.stop && *fin.stop);
             }
-            post_s = (ctl->done || notify) && mail;
+            post_s = (ctl->done || fin.notify) && mail;
         } else if (mail && !ctl) {  // synchronous callers (se2gpu_ba_chi2): the three scalars
             mail[0] = sm[0][0];
             mail[1] = sm[1][0];
             mail[2] = step ? out[2] : 0.0;
             __threadfence_system();
-            mail[3] = seq;
+            mail[3] = fin.seq;
         }
     }
-    if (ctl && decide) {
+    if (ctl && fin.decide) {
         __syncthreads();
-        end_slot(ctl, mail, post_s != 0, threadIdx.x, blockDim.x, step != 0);
+        end_slot(ctl, mail, post_s != 0, threadIdx.x, blockDim.x, step);
     }
 }
 
@@ -2108,9 +2115,14 @@ __global__ void k_lm_decide(BaCtl* __restrict__ ctl, const double* __restrict__ 
 // start of an optimize(): everything is reset but the handle's own counters and the sel bit (which of the two estimate
 // buffers is current: it follows from the runs before, the host only mirrors it) - nothing here changes from one run to
 // the next, so the whole optimize() can be replayed as a hipGraph
-__device__ __forceinline__ void d_ctl_init(const unsigned bx, BaCtl* __restrict__ ctl, int iters, int mode) {
+struct CtlInitArgs {
+    BaCtl* ctl;
+    int iters, mode;
+};
+__device__ __forceinline__ void d_ctl_init(const unsigned bx, const CtlInitArgs& a) {
     constexpr int kWords = (int)(offsetof(BaCtl, seq) / 8);
     __shared__ int sel_s;
+    BaCtl* ctl = a.ctl;
     if (threadIdx.x == 0) sel_s = ctl->sel;
     __syncthreads();
     double* w = reinterpret_cast<double*>(ctl);
@@ -2119,12 +2131,12 @@ __device__ __forceinline__ void d_ctl_init(const unsigned bx, BaCtl* __restrict_
     if (threadIdx.x == 0) {
         ctl->ni = 2;
         ctl->sel = sel_s;
-        ctl->iters = iters;
-        ctl->mode = mode;
+        ctl->iters = a.iters;
+        ctl->mode = a.mode;
     }
 }
-__global__ void k_ctl_init(BaCtl* __restrict__ ctl, int iters, int mode) {
-    d_ctl_init(blockIdx.x, ctl, iters, mode);
+__global__ void k_ctl_init(CtlInitArgs a) {
+    d_ctl_init(blockIdx.x, a);
 }
 
 // lambda_0 = 1e-5 * max |diag H| (computeLambdaInit); src holds the maximum (one entry), or one slot per rank
@@ -4630,6 +4642,63 @@ RecSet rec_twin(const se2gpu_ba* h) {
 }
 int ba_reserve_twin(se2gpu_ba* h) { return h->rec_twin.reserve(21 * (size_t)h->E + 18 * (size_t)h->L + 6); }
 
+// The argument structs of the multi-launch SE(2) kernels, one builder each: every launch site and every batch plan entry
+// calls it, and what differs between the sites is a parameter.  B = bufs(h, ctl): with the controller the kernels pick the
+// estimate buffer, lambda and the record set from its block; `alt` = the twin record set (rec_twin) or RecSet{}.
+inline double* ba_scal(se2gpu_ba* h) { return h->red + (size_t)h->ld * h->ld; }   // 4 trailing scalars of the fused buffer
+inline dim3 upd_grid(const se2gpu_ba* h) { return grid1((size_t)h->L * kGroup, kBlock); }   // landmark workgroups of k_linearize / k_update
+inline dim3 reduce2_grid(const se2gpu_ba* h) { return dim3(((h->P + 1 + 7) & ~7) + ((h->nwg_off + 7) & ~7)); }
+LinArgs lin_args(se2gpu_ba* h, const Bufs& B, double lambda, const RecSet& alt) {
+    return LinArgs{h->cam, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p, h->Hpp_e.p,
+                   h->bp_e.p, h->Hll.p, h->bl.p, lambda, h->Dinv.p, h->z.p, h->Dg.p, B.c, B.pb, B.lb, alt};
+}
+// (with the controller the estimate's buffer is the controller's to name: a captured graph must not carry the host's idea of it)
+OdoArgs odo_args(se2gpu_ba* h, const double* poses, bool ctl) {
+    const Bufs B = bufs(h, ctl);
+    return OdoArgs{h->O, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, ctl ? B.pa : poses, h->fixed.p, h->Oii.p, h->Ojj.p, h->Oij.p,
+                   h->obi.p, h->obj.p, B.c, ctl ? B.pb : nullptr};
+}
+PoseReduceArgs pose_reduce_args(se2gpu_ba* h) {
+    return PoseReduceArgs{h->P, h->pose_ptr.p, h->pose_edges.p, h->Hpp_e.p, h->bp_e.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p,
+                          h->Ojj.p, h->obi.p, h->obj.p, h->Hpp.p, h->bp.p};
+}
+// pose diagonals: dpp values per pose in h->diag3, or (stride9) the 3 x 3 blocks of k_pose_reduce in h->Hpp
+MaxdiagArgs maxdiag_args(se2gpu_ba* h, int dpp, int stride9, BaCtl* ctl) {
+    return MaxdiagArgs{h->L, h->Hll.p, h->P, stride9 ? h->Hpp.p : h->diag3.p, h->fixed.p, h->scal.p, dpp, stride9, ctl};
+}
+Reduce2Args reduce2_args(se2gpu_ba* h, const Bufs& B, double lambda, const RecSet& alt) {
+    return Reduce2Args{h->P, h->ld, h->nwg_off, lambda, h->root, h->grp.p, h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p,
+                       h->blk_odo.p, h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p, h->pose_edges.p, h->podo_ptr.p, h->podo_item.p,
+                       h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, B.pa, h->red, h->bp.p, B.c, B.pb, &h->ctl.p->epoch,
+                       h->pose_off.p, h->nsys, alt.W, alt.Dg};
+}
+// the dataflow solve of h->red into h->xp.  skip: SE2GPU_BA_CHOL_FAULT (ba_solve); head: the task counter, or nullptr (the grid fits);
+// verify: the launch is k_chol_tiles<true>'s (SE2GPU_BA_CHOL_VERIFY=1)
+CholArgs chol_args(se2gpu_ba* h, const BaCtl* ctl, int skip, unsigned long long* head, bool verify) {
+    const int n = h->nsys, ld = h->ld;   // D * P, or the padded order of the permuted system (solve_plan_choose)
+    const int nt = ld / kNB, nbc = (n + kNB - 1) / kNB;   // tile rows of A (incl. the rhs / padding tile row), block columns to factor
+    double* YU = h->Rinv.p + 2 * (size_t)nt * nbc * kSlabs * kSlabDoubles;   // behind the publish buffer
+    unsigned* flagA = h->chol_flags.p;
+    return CholArgs{h->red, h->Rinv.p, YU, ld, n, nbc, h->chol_tasks.p + skip, h->chol_deps.p, h->chol_neager.p + skip, h->col_src.p,
+                    flagA, flagA + kSlabs * (size_t)nt * nbc, &h->ctl.p->epoch, ba_scal(h) + 2, h->chol_trace.p, ctl, h->xp.p,
+                    verify ? h->chol_vfy.p : nullptr, head, h->chol_ntask - skip};
+}
+// The end of a trial (finish_trial in k_update's last workgroup, or k_finalize).  With the controller (B.c) it takes the
+// decision when `decide` is set and reads the force-stop word; `lin`: the landmark workgroups are k_update<true>'s; post = false:
+// no mailbox (the scalars of a synchronous sharded evaluation are posted behind the all-reduce, k_post_mail).
+FinArgs fin_args(se2gpu_ba* h, const Bufs& B, const double* xp, int step, int decide, int notify, double seq, bool lin = false,
+                 bool post = true) {
+    return FinArgs{1, (int)upd_grid(h).x, h->P, h->O, h->root, step, decide, notify, h->fixed.p, xp, h->bp.p, B.pa, B.pb,
+                   h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, ba_scal(h), post ? h->d_mail : nullptr, seq, B.c ? h->ctl.p : nullptr,
+                   B.c ? (const volatile int*)h->d_stop : nullptr, h->fin_counter.p, lin ? 1 : 0};
+}
+// xp == nullptr evaluates the state; fin = FinArgs{} when k_finalize ends the trial; lin: k_update<true>'s record sets
+UpdArgs upd_args(se2gpu_ba* h, const Bufs& B, double lambda, const double* xp, const FinArgs& fin, bool lin = false) {
+    return UpdArgs{h->cam, h->L, lambda, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, xp, h->z.p, h->Hpl.p,
+                   h->bl.p, B.lb, h->part.p, B.c, B.pb, fin, h->Dinv.p,
+                   lin ? SpecArgs{{rec_own(h), rec_twin(h)}, h->Hpp_e.p, h->bp_e.p} : SpecArgs{}};
+}
+
 // SE(2) model (whitened records, k_linearize): h->Hpl holds W_e, h->Dinv the inverse Cholesky factors A_l, h->z the zeta_l;
 // h->Y is not used.  The SE3-expmap model keeps Hpl / Y / Dinv / z as named.
 
@@ -4660,14 +4729,10 @@ int ba_linearize(se2gpu_ba* h, double fuse_lambda, bool ctl = false) {
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
     }
-    if (fuse_lambda >= 0.0)
-        SE2_LAUNCH(h->prof, st, "k_linearize", (k_linearize<true>), grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0,
-                   h->cam, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p,
-                   h->Hpp_e.p, h->bp_e.p, h->Hll.p, h->bl.p, fuse_lambda, h->Dinv.p, h->z.p, h->Dg.p, B.c, B.pb, B.lb, rec_twin(h));
-    else
-        SE2_LAUNCH(h->prof, st, "k_linearize0", (k_linearize<false>), grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0,
-                   h->cam, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p,
-                   h->Hpp_e.p, h->bp_e.p, h->Hll.p, h->bl.p, 0.0, h->Dinv.p, h->z.p, h->Dg.p, B.c, B.pb, B.lb, rec_twin(h));
+    const dim3 lg = upd_grid(h);
+    const LinArgs la = lin_args(h, B, fuse_lambda >= 0.0 ? fuse_lambda : 0.0, rec_twin(h));
+    if (fuse_lambda >= 0.0) SE2_LAUNCH(h->prof, st, "k_linearize", (k_linearize<true>), lg, dim3(kBlock), 0, la);
+    else SE2_LAUNCH(h->prof, st, "k_linearize0", (k_linearize<false>), lg, dim3(kBlock), 0, la);
     SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
 }
@@ -4676,22 +4741,9 @@ int ba_linearize(se2gpu_ba* h, double fuse_lambda, bool ctl = false) {
 // un-reduced pose blocks Hpp / bp (only needed for lambda_0 = 1e-5 max diag H and by the odometry fallback)
 int ba_pose_blocks(se2gpu_ba* h, const double* poses, bool ctl = false, bool odometry_only = false) {
     hipStream_t st = h->stream;
-    if (h->O) {
-        // with the device-side controller the estimate's buffer is the controller's to name (a captured graph must not
-        // carry the host's idea of it)
-        if (ctl)
-            SE2_LAUNCH(h->prof, st, "k_odometry", k_odometry, grid1(h->O, 64), dim3(64), 0, h->O, h->o_i.p, h->o_j.p,
-                       h->o_meas.p, h->o_info.p, h->poses_a.p, h->fixed.p, h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p,
-                       (const BaCtl*)h->ctl.p, (const double*)h->poses_b.p);
-        else
-            SE2_LAUNCH(h->prof, st, "k_odometry", k_odometry, grid1(h->O, 64), dim3(64), 0, h->O, h->o_i.p, h->o_j.p,
-                       h->o_meas.p, h->o_info.p, poses, h->fixed.p, h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p,
-                       (const BaCtl*)nullptr, (const double*)nullptr);
-    }
+    if (h->O) SE2_LAUNCH(h->prof, st, "k_odometry", k_odometry, grid1(h->O, 64), dim3(64), 0, odo_args(h, poses, ctl));
     if (!odometry_only)   // (k_lambda0 does the pose blocks itself)
-        SE2_LAUNCH(h->prof, st, "k_pose_reduce", k_pose_reduce, grid1((size_t)h->P * 64, kBlock), dim3(kBlock), 0, h->P,
-                   h->pose_ptr.p, h->pose_edges.p, h->Hpp_e.p, h->bp_e.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p,
-                   h->Ojj.p, h->obi.p, h->obj.p, h->Hpp.p, h->bp.p);
+        SE2_LAUNCH(h->prof, st, "k_pose_reduce", k_pose_reduce, grid1((size_t)h->P * 64, kBlock), dim3(kBlock), 0, pose_reduce_args(h));
     SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
 }
@@ -4719,17 +4771,11 @@ int ba_reduce(se2gpu_ba* h, double lambda, int schur, bool ctl = false) {
     // the per-edge records depend on lambda: a new damping on the same linearisation (first trial after lambda_0, a retry
     // the host knows about) runs the fused linearisation again - same estimate, same code, identical blocks
     if (schur) SE2_CHECK(ba_linearize(h, lambda, ctl));
-    SE2_LAUNCH(h->prof, st, "k_reduce2", k_reduce2, dim3(((h->P + 1 + 7) & ~7) + ((h->nwg_off + 7) & ~7)), dim3(kBlock), 0, h->P, h->ld, h->nwg_off,
-               lambda, h->root, h->grp.p, h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p, h->blk_odo.p,
-               h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p, h->pose_edges.p,
-               h->podo_ptr.p, h->podo_item.p, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, B.pa, S, h->bp.p, B.c, B.pb,
-               &h->ctl.p->epoch, (const int*)h->pose_off.p, h->nsys, (const double*)rec_twin(h).W, (const double*)rec_twin(h).Dg);
+    SE2_LAUNCH(h->prof, st, "k_reduce2", k_reduce2, reduce2_grid(h), dim3(kBlock), 0, reduce2_args(h, B, lambda, rec_twin(h)));
     if (h->O && h->odo_fallback) {
         // PreEdgeSE2 edges the plan cannot carry (self loops, duplicates): blocks from the estimate, added atomically.  Only
         // reachable with a host-known estimate pointer, so such graphs run in synchronous mode (ba_needs_sync).
-        SE2_LAUNCH(h->prof, st, "k_odometry", k_odometry, grid1(h->O, 64), dim3(64), 0, h->O, h->o_i.p, h->o_j.p,
-                   h->o_meas.p, h->o_info.p, h->poses, h->fixed.p, h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p,
-                   (const BaCtl*)nullptr, (const double*)nullptr);
+        SE2_LAUNCH(h->prof, st, "k_odometry", k_odometry, grid1(h->O, 64), dim3(64), 0, odo_args(h, h->poses, false));
         SE2_LAUNCH(h->prof, st, "k_reduce_odo", k_reduce_odo, grid1((size_t)h->O * 9, 256), dim3(256), 0, h->O, h->ld,
                    h->o_i.p, h->o_j.p, h->Oij.p, S, (const int*)h->pose_off.p);
     }
@@ -4836,28 +4882,20 @@ __global__ void k_post_mail(const double* __restrict__ scal, volatile double* __
 int ba_evaluate(se2gpu_ba* h, const double* xp, double lambda) {
     SE2_CHECK(ba_join(h));
     hipStream_t st = h->stream;
-    double* scal = h->red + (size_t)h->ld * h->ld;  // 4 trailing scalars of the fused buffer
+    double* scal = ba_scal(h);
     const bool use_mail = h->d_mail && !(h->allreduce && h->world > 1) && !h->comm;
     const double seq = (double)(++h->mail_seq);
-    const dim3 ug = grid1((size_t)h->L * kGroup, kBlock);
+    const dim3 ug = upd_grid(h);
+    const Bufs B = bufs(h, false);
     if (use_mail) {   // single GPU: the trial ends inside k_update (FinArgs)
-        FinArgs fin{1, (int)ug.x, h->P, h->O, h->root, xp ? 1 : 0, 0, 0, h->fixed.p, xp, h->bp.p, h->poses, h->poses_t,
-                    h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, scal, h->d_mail, seq, (BaCtl*)nullptr,
-                    (const volatile int*)nullptr, h->fin_counter.p};
-        SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, dim3(ug.x + 1), dim3(kBlock), 0, h->cam, h->L, lambda, h->lm_ptr.p,
-                   h->e_kf.p, h->e_uv.p, h->e_info.p, h->poses, h->fixed.p, h->lms, xp, h->z.p, (const double*)h->Hpl.p, h->bl.p, h->lms_t,
-                   h->part.p, (const BaCtl*)nullptr, (const double*)nullptr, fin, (const double*)h->Dinv.p, SpecArgs{});
+        SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, dim3(ug.x + 1), dim3(kBlock), 0,
+                   upd_args(h, B, lambda, xp, fin_args(h, B, xp, xp ? 1 : 0, 0, 0, seq)));
         SE2_HIP(hipGetLastError());
         return ba_wait_mail(h, seq);
     }
-    SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, ug, dim3(kBlock), 0, h->cam, h->L,
-               lambda, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, h->poses, h->fixed.p, h->lms, xp, h->z.p,
-               (const double*)h->Hpl.p, h->bl.p, h->lms_t, h->part.p, (const BaCtl*)nullptr, (const double*)nullptr, FinArgs{}, (const double*)h->Dinv.p,
-               SpecArgs{});
-    SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, h->L ? h->nparts : 0, h->part.p, h->P,
-               lambda, h->poses, h->fixed.p, xp, h->bp.p, h->poses_t, h->O, h->o_i.p, h->o_j.p, h->o_meas.p,
-               h->o_info.p, h->root, scal, (volatile double*)nullptr, seq, (BaCtl*)nullptr, xp ? 1 : 0, 0, 0,
-               (const volatile int*)nullptr);
+    SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, ug, dim3(kBlock), 0, upd_args(h, B, lambda, xp, FinArgs{}));
+    SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, fin_args(h, B, xp, xp ? 1 : 0, 0, 0, seq, false, /*post=*/false),
+               h->L ? h->nparts : 0, (const double*)h->part.p, lambda);
     SE2_HIP(hipGetLastError());
     SE2_CHECK(ba_allreduce(h, scal, 4));
     if (h->d_mail) {
@@ -4878,7 +4916,7 @@ int ba_solve(se2gpu_ba* h, bool ctl = false) {
     const int n = h->nsys;   // D * P, or the padded order of the permuted system (solve_plan_choose)
     const int ld = h->ld;
     double* A = h->red;
-    double* fail = h->red + (size_t)ld * ld + 2;
+    double* fail = ba_scal(h) + 2;
     const BaCtl* c = ctl ? h->ctl.p : nullptr;
     if (h->host_solve) {
         SE2_HIP(hipMemcpyAsync(h->h_red.p, A, (size_t)(n + 1) * ld * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4913,22 +4951,15 @@ int ba_solve(se2gpu_ba* h, bool ctl = false) {
         SE2_LAUNCH(h->prof, st, "k_chol_apply", k_chol_apply, dim3((n + 3) / 4), dim3(256), 0, A, Rm, ld, n, h->xp.p, c,
                    (const int*)h->col_src.p);
     } else {
-        double* YU = Rm + 2 * (size_t)nt * nbc * kSlabs * kSlabDoubles;   // behind the publish buffer
-        unsigned* flagA = h->chol_flags.p;
-        unsigned* flagR = flagA + kSlabs * (size_t)nt * nbc;
         // SE2GPU_BA_CHOL_FAULT=1 (tests): the first dataflow solve of a handle runs without its first task, so that every
         // other task times out - exercises the fallback to k_chol_step in ba_run_step
         static const bool fault = env_flag("SE2GPU_BA_CHOL_FAULT", false);
         const int skip = (fault && !h->chol_faulted && h->chol_ntask > 1) ? 1 : 0;
         h->chol_faulted = true;
-        if (h->chol_vfy.p)
-            SE2_LAUNCH(h->prof, st, "k_chol_tiles", k_chol_tiles<true>, dim3(h->chol_ntask - skip), dim3(256), 0, A, Rm, YU, ld, n, nbc,
-                       h->chol_tasks.p + skip, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p + skip, (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
-                       fail, h->chol_trace.p, c, h->xp.p, h->chol_vfy.p, head, h->chol_ntask - skip);
-        else
-            SE2_LAUNCH(h->prof, st, "k_chol_tiles", k_chol_tiles<false>, dim3(h->chol_ntask - skip), dim3(256), 0, A, Rm, YU, ld, n, nbc,
-                       h->chol_tasks.p + skip, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p + skip, (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
-                       fail, h->chol_trace.p, c, h->xp.p, (unsigned long long*)nullptr, head, h->chol_ntask - skip);
+        const bool verify = h->chol_vfy.p != nullptr;
+        const CholArgs ca = chol_args(h, c, skip, head, verify);
+        if (verify) SE2_LAUNCH(h->prof, st, "k_chol_tiles", k_chol_tiles<true>, dim3(ca.ntask), dim3(256), 0, ca);
+        else SE2_LAUNCH(h->prof, st, "k_chol_tiles", k_chol_tiles<false>, dim3(ca.ntask), dim3(256), 0, ca);
     }
     SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
@@ -4942,8 +4973,7 @@ int ba_lambda_init(se2gpu_ba* h) {
         SE2_LAUNCH(h->prof, st, "k3_pose_diag", k3_pose_diag, grid1((size_t)h->P * 64, kBlock), dim3(kBlock), 0, h->P,
                    h->pose_ptr.p, h->pose_edges.p, h->Hpp_e.p, h->fixed.p, h->prior_has.p,
                    h->model == 2 ? h->ph.p : h->prior_info.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p, h->Ojj.p, h->diag3.p);
-        SE2_LAUNCH(h->prof, st, "k_maxdiag", k_maxdiag, dim3(1), dim3(1024), 0, h->L, h->Hll.p, h->P, h->diag3.p,
-                   h->fixed.p, h->scal.p, 6, 0, h->ctl.p);
+        SE2_LAUNCH(h->prof, st, "k_maxdiag", k_maxdiag, dim3(1), dim3(1024), 0, maxdiag_args(h, 6, 0, h->ctl.p));
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
     }
@@ -4968,8 +4998,7 @@ int ba_lambda_init(se2gpu_ba* h) {
         SE2_CHECK(ba_allreduce(h, h->red, nd));
         SE2_HIP(hipMemcpyAsync(h->diag3.p, h->red, nd * 8, hipMemcpyDeviceToDevice, st));
     }
-    SE2_LAUNCH(h->prof, st, "k_maxdiag", k_maxdiag, dim3(1), dim3(1024), 0, h->L, h->Hll.p, h->P, h->diag3.p,
-               h->fixed.p, h->scal.p, 3, 0, (BaCtl*)nullptr);
+    SE2_LAUNCH(h->prof, st, "k_maxdiag", k_maxdiag, dim3(1), dim3(1024), 0, maxdiag_args(h, 3, 0, nullptr));
     if (sharded) {
         // max over ranks through the SUM all-reduce: every rank deposits its local max in its own slot
         SE2_REQUIRE(h->world <= 1024, SE2GPU_ERR_INVALID, "world size %d > 1024", h->world);
@@ -4991,7 +5020,7 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
     hipStream_t st = h->stream;
     const bool lm = h->run_mode == SE2GPU_BA_LM;
     const bool sharded = h->allreduce != nullptr;
-    double* scal = h->red + (size_t)h->ld * h->ld;
+    double* scal = ba_scal(h);
     const Bufs B = bufs(h, true);
     auto evaluate = [&](bool step, bool note) -> int {
         if (h->model == 2) {
@@ -5017,33 +5046,21 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
             SE2_HIP(hipGetLastError());
             return SE2GPU_OK;
         }
-        const dim3 ug = grid1((size_t)h->L * kGroup, kBlock);
+        const dim3 ug = upd_grid(h);
+        const double* xp = step ? h->xp.p : nullptr;
         if (!sharded) {   // the trial ends inside k_update (FinArgs): no kernel boundary before the controller's decision
             // a step of a speculating run also linearises the trial state (k_update<true>); the evaluation of the start does not
             const bool lin = step && h->run_spec;
-            FinArgs fin{1, (int)ug.x, h->P, h->O, h->root, step ? 1 : 0, 1, note ? 1 : 0, h->fixed.p, h->xp.p, h->bp.p, B.pa,
-                        B.pb, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, scal, h->d_mail, seq, h->ctl.p,
-                        (const volatile int*)h->d_stop, h->fin_counter.p, lin ? 1 : 0};
-            if (lin)
-                SE2_LAUNCH(h->prof, st, "k_update_lin", k_update<true>, dim3(ug.x + 1), dim3(kBlock), 0, h->cam, h->L, 0.0, h->lm_ptr.p,
-                           h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, (const double*)h->xp.p,
-                           h->z.p, (const double*)h->Hpl.p, h->bl.p, B.lb, h->part.p, B.c, B.pb, fin, (const double*)h->Dinv.p,
-                           SpecArgs{{rec_own(h), rec_twin(h)}, h->Hpp_e.p, h->bp_e.p});
-            else
-                SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, dim3(ug.x + 1), dim3(kBlock), 0, h->cam, h->L, 0.0, h->lm_ptr.p,
-                           h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, step ? h->xp.p : (const double*)nullptr,
-                           h->z.p, (const double*)h->Hpl.p, h->bl.p, B.lb, h->part.p, B.c, B.pb, fin, (const double*)h->Dinv.p, SpecArgs{});
+            const UpdArgs ua = upd_args(h, B, 0.0, xp, fin_args(h, B, h->xp.p, step ? 1 : 0, 1, note ? 1 : 0, seq, lin), lin);
+            if (lin) SE2_LAUNCH(h->prof, st, "k_update_lin", k_update<true>, dim3(ug.x + 1), dim3(kBlock), 0, ua);
+            else SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, dim3(ug.x + 1), dim3(kBlock), 0, ua);
             SE2_HIP(hipGetLastError());
             return SE2GPU_OK;
         }
-        SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, ug, dim3(kBlock), 0, h->cam, h->L,
-                   0.0, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la,
-                   step ? h->xp.p : (const double*)nullptr, h->z.p, (const double*)h->Hpl.p, h->bl.p, B.lb, h->part.p, B.c, B.pb, FinArgs{},
-                   (const double*)h->Dinv.p, SpecArgs{});
-        SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, h->L ? h->nparts : 0, h->part.p, h->P,
-                   0.0, B.pa, h->fixed.p, h->xp.p, h->bp.p, B.pb, h->O, h->o_i.p, h->o_j.p, h->o_meas.p,
-                   h->o_info.p, h->root, scal, h->d_mail, seq, h->ctl.p, step ? 1 : 0, sharded ? 0 : 1, note ? 1 : 0,
-                   (const volatile int*)h->d_stop);
+        SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, ug, dim3(kBlock), 0, upd_args(h, B, 0.0, xp, FinArgs{}));
+        // (the decision of a sharded run is k_lm_decide's, behind the all-reduce)
+        SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, fin_args(h, B, h->xp.p, step ? 1 : 0, 0, note ? 1 : 0, seq),
+                   h->L ? h->nparts : 0, (const double*)h->part.p, 0.0);
         if (sharded) {
             SE2_CHECK(ba_allreduce(h, scal, 4));
             hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), 0, st, h->ctl.p, scal, step ? 1 : 0, note ? 1 : 0,
@@ -5078,22 +5095,24 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
 // Lock-step batches: ONE launch per stage for ALL windows of se2gpu_ba_optimize_batch.
 // N windows on N streams are 4 N dependent launches per LM iteration and saturate the command processor at ~157 k
 // launches / s (39 k it/s at 64 windows, > 99 % of the chip idle).  Every model-0 kernel body is a __device__ function
-// of (block index, arguments); k_batched runs it for a whole batch from per-window argument packs in device memory:
+// of (block index, argument struct); k_batched runs it for a whole batch from the windows' argument structs in device memory:
 // blockIdx.y = window, blockIdx.x = the window's block.  The windows keep their own controller (BaCtl), mailbox, solver
 // flags and buffers - a window whose trial was rejected redoes its lambda part in the next slot while its neighbours
 // linearise, a finished window's blocks return at once - so the results are bit-identical to one-by-one runs.  Within a
 // window the dispatch order of the 2-D grid (x fastest) is the order the dataflow solve and the finisher of k_update rely on.
 // =============================================================================================
-template <typename... A>
+template <typename Args>
 struct Packed {
     int nblk;
-    std::tuple<A...> args;
+    Args args;
 };
-template <auto Body, int BS, typename... A>
-__global__ __launch_bounds__(BS) void k_batched(const Packed<A...>* __restrict__ p) {
-    const Packed<A...>& x = p[blockIdx.y];
-    if ((int)blockIdx.x >= x.nblk) return;
-    std::apply([&](const A&... a) { Body(blockIdx.x, a...); }, x.args);
+// (the body gets a COPY of the window's arguments: it stores through pointers that may alias the array in global memory for all
+// the compiler knows, and would reload a member after every store through a reference into it)
+template <typename Args, void (*Body)(unsigned, const Args&), int BS>
+__global__ __launch_bounds__(BS) void k_batched(const Packed<Args>* __restrict__ p) {
+    if ((int)blockIdx.x >= p[blockIdx.y].nblk) return;
+    const Args a = p[blockIdx.y].args;
+    Body(blockIdx.x, a);
 }
 // The same with every window pinned to ONE XCD (round 4).  Workgroups are dealt to the 8 XCDs round-robin in dispatch order
 // (linear id mod 8), each XCD has its own 4 MB L2, and a kernel that re-reads a window's records (k_reduce2: every W_e is an
@@ -5102,8 +5121,8 @@ __global__ __launch_bounds__(BS) void k_batched(const Packed<A...>* __restrict__
 // other: the k-th workgroup of XCD x (k = linear id / 8) is block k mod nb of window 8 (k / nb) + x.  gridDim.x = nb is a
 // multiple of 8; windows beyond the last full eight take the plain mapping.  Inside a window the blocks are still
 // dispatched in increasing order.
-template <auto Body, int BS, typename... A>
-__global__ __launch_bounds__(BS) void k_batched_xcd(const Packed<A...>* __restrict__ p) {
+template <typename Args, void (*Body)(unsigned, const Args&), int BS>
+__global__ __launch_bounds__(BS) void k_batched_xcd(const Packed<Args>* __restrict__ p) {
     const unsigned nb = gridDim.x, nw8 = gridDim.y & ~7u;
     unsigned w = blockIdx.y, bx = blockIdx.x;
     if (w < nw8) {
@@ -5111,12 +5130,12 @@ __global__ __launch_bounds__(BS) void k_batched_xcd(const Packed<A...>* __restri
         w = 8 * (k / nb) + (lin & 7);
         bx = k % nb;
     }
-    const Packed<A...>& x = p[w];
-    if ((int)bx >= x.nblk) return;
-    std::apply([&](const A&... a) { Body(bx, a...); }, x.args);
+    if ((int)bx >= p[w].nblk) return;
+    const Args a = p[w].args;
+    Body(bx, a);
 }
 
-// the argument packs of one kernel for all windows of a batch; they live in the plan's arena (one upload per plan)
+// the arguments of one kernel for all windows of a batch; they live in the plan's arena (one upload per plan)
 struct BatchArena {
     std::vector<uint8_t> host;
     DevBuf<uint8_t> dev;
@@ -5127,22 +5146,21 @@ struct BatchArena {
         return off;
     }
 };
-template <auto Body, int BS>
-struct BatchKernel;
-template <typename... A, void (*Body)(unsigned, A...), int BS>
-struct BatchKernel<Body, BS> {
-    using P = Packed<std::remove_cv_t<A>...>;
+template <typename Args, void (*Body)(unsigned, const Args&), int BS>
+struct BatchKernel {
+    using P = Packed<Args>;
+    static_assert(std::is_trivially_copyable_v<P>, "the arena copies the entries with memcpy");
     std::vector<P> packs;
     size_t off = 0;
     int maxblk = 0;
-    void add(int nblk, A... a) {
-        packs.push_back(P{nblk, std::tuple<std::remove_cv_t<A>...>(a...)});
+    void add(int nblk, const Args& a) {
+        packs.push_back(P{nblk, a});
         maxblk = std::max(maxblk, nblk);
     }
     void commit(BatchArena& ar) { off = ar.add(packs.data(), packs.size() * sizeof(P)); }
     void launch(const BatchArena& ar, hipStream_t st, int block = BS, size_t shmem = 0) const {
         if (packs.empty() || maxblk <= 0) return;
-        hipLaunchKernelGGL((k_batched<Body, BS, std::remove_cv_t<A>...>), dim3((unsigned)maxblk, (unsigned)packs.size()), dim3(block),
+        hipLaunchKernelGGL((k_batched<Args, Body, BS>), dim3((unsigned)maxblk, (unsigned)packs.size()), dim3(block),
                            shmem, st, reinterpret_cast<const P*>(ar.dev.p + off));
     }
     void launch_xcd(const BatchArena& ar, hipStream_t st) const {   // every window on one XCD (k_batched_xcd)
@@ -5154,10 +5172,9 @@ struct BatchKernel<Body, BS> {
             return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && n == 8;
         }();
         if (!eight) { launch(ar, st); return; }
-        hipLaunchKernelGGL((k_batched_xcd<Body, BS, std::remove_cv_t<A>...>), dim3((unsigned)((maxblk + 7) & ~7), (unsigned)packs.size()),
+        hipLaunchKernelGGL((k_batched_xcd<Args, Body, BS>), dim3((unsigned)((maxblk + 7) & ~7), (unsigned)packs.size()),
                            dim3(BS), 0, st, reinterpret_cast<const P*>(ar.dev.p + off));
     }
-    static const void* kernel() { return (const void*)k_batched<Body, BS, std::remove_cv_t<A>...>; }
 };
 
 struct BatchPlan {
@@ -5167,16 +5184,16 @@ struct BatchPlan {
     int iters = -1, mode = -1;
     BatchArena arena;
     hipStream_t stream = nullptr;
-    BatchKernel<d_ctl_init, 64> ctl_init;
-    BatchKernel<d_update<false>, kBlock> eval0, step, step_notify;   // (the lock-step slot does not speculate)
-    BatchKernel<d_linearize<false>, kBlock> lin0;
-    BatchKernel<d_linearize<true>, kBlock> lin;
-    BatchKernel<d_odometry, 64> odo;
-    BatchKernel<d_pose_reduce, kBlock> pose_reduce;
-    BatchKernel<d_maxdiag, 1024> maxdiag;
-    BatchKernel<d_reduce2, kBlock> reduce2;
-    BatchKernel<d_chol_tiles<false>, 256> chol;
-    BatchKernel<d_chol_tiles<true>, 256> chol_v;     // SE2GPU_BA_CHOL_VERIFY=1
+    BatchKernel<CtlInitArgs, d_ctl_init, 64> ctl_init;
+    BatchKernel<UpdArgs, d_update<false>, kBlock> eval0, step, step_notify;   // (the lock-step slot does not speculate)
+    BatchKernel<LinArgs, d_linearize<false>, kBlock> lin0;
+    BatchKernel<LinArgs, d_linearize<true>, kBlock> lin;
+    BatchKernel<OdoArgs, d_odometry, 64> odo;
+    BatchKernel<PoseReduceArgs, d_pose_reduce, kBlock> pose_reduce;
+    BatchKernel<MaxdiagArgs, d_maxdiag, 1024> maxdiag;
+    BatchKernel<Reduce2Args, d_reduce2, kBlock> reduce2;
+    BatchKernel<CholArgs, d_chol_tiles<false>, 256> chol;
+    BatchKernel<CholArgs, d_chol_tiles<true>, 256> chol_v;     // SE2GPU_BA_CHOL_VERIFY=1
     bool verify = false;
     std::vector<hipEvent_t> events;
     ~BatchPlan() {
@@ -5254,54 +5271,21 @@ int ba_build_batch_plan(BatchPlan& bp, se2gpu_ba** hs, int count, int iters, int
         bp.serials[w] = h->init_serial;
         bp.streams[w] = h->stream;
         const Bufs B = bufs(h, true);
-        double* scal = h->red + (size_t)h->ld * h->ld;
-        const dim3 ug = grid1((size_t)h->L * kGroup, kBlock);
-        bp.ctl_init.add(1, h->ctl.p, iters, mode);
-        auto fin = [&](int step, int notify) {
-            return FinArgs{1, (int)ug.x, h->P, h->O, h->root, step, 1, notify, h->fixed.p, h->xp.p, h->bp.p, B.pa, B.pb, h->o_i.p,
-                           h->o_j.p, h->o_meas.p, h->o_info.p, scal, h->d_mail, 0.0, h->ctl.p, (const volatile int*)h->d_stop,
-                           h->fin_counter.p};
-        };
-        auto upd = [&](auto& k, int step, int notify) {
-            k.add((int)ug.x + 1, h->cam, h->L, 0.0, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la,
-                  step ? h->xp.p : (const double*)nullptr, h->z.p, (const double*)h->Hpl.p, h->bl.p, B.lb, h->part.p, B.c, B.pb, fin(step, notify),
-                  (const double*)h->Dinv.p, SpecArgs{});
-        };
-        upd(bp.eval0, 0, 0);
-        upd(bp.step, 1, 0);
-        upd(bp.step_notify, 1, 1);
-        bp.lin0.add((int)ug.x, h->cam, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p,
-                    h->Hpp_e.p, h->bp_e.p, h->Hll.p, h->bl.p, 0.0, h->Dinv.p, h->z.p, h->Dg.p, B.c, B.pb, B.lb, RecSet{});
-        bp.lin.add((int)ug.x, h->cam, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p,
-                   h->Hpp_e.p, h->bp_e.p, h->Hll.p, h->bl.p, 0.0, h->Dinv.p, h->z.p, h->Dg.p, B.c, B.pb, B.lb, RecSet{});
-        bp.odo.add(h->O ? (int)grid1(h->O, 64).x : 0, h->O, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, h->poses_a.p, h->fixed.p,
-                   h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p, (const BaCtl*)h->ctl.p, (const double*)h->poses_b.p);
-        bp.pose_reduce.add((int)grid1((size_t)h->P * 64, kBlock).x, h->P, h->pose_ptr.p, h->pose_edges.p, h->Hpp_e.p, h->bp_e.p,
-                           h->podo_ptr.p, h->podo_item.p, h->Oii.p, h->Ojj.p, h->obi.p, h->obj.p, h->Hpp.p, h->bp.p);
-        bp.maxdiag.add(1, h->L, h->Hll.p, h->P, h->Hpp.p, h->fixed.p, h->scal.p, 3, 1, h->ctl.p);
-        bp.reduce2.add(((h->P + 1 + 7) & ~7) + ((h->nwg_off + 7) & ~7), h->P, h->ld, h->nwg_off, 0.0, h->root, h->grp.p, h->blk_a.p,
-                       h->blk_b.p, h->pair_i.p, h->pair_j.p, h->blk_odo.p, h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p,
-                       h->pose_edges.p, h->podo_ptr.p, h->podo_item.p, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, B.pa, h->red,
-                       h->bp.p, B.c, B.pb, &h->ctl.p->epoch, (const int*)h->pose_off.p, h->nsys, (const double*)nullptr,
-                       (const double*)nullptr);
-        {
-            const int n = h->nsys, ld = h->ld;
-            const int nt = ld / kNB, nbc = (n + kNB - 1) / kNB;
-            double* Rm = h->Rinv.p;
-            double* YU = Rm + 2 * (size_t)nt * nbc * kSlabs * kSlabDoubles;
-            unsigned* flagA = h->chol_flags.p;
-            unsigned* flagR = flagA + kSlabs * (size_t)nt * nbc;
-            double* fail = h->red + (size_t)ld * ld + 2;
-            bp.verify = hs[0]->chol_vfy.p != nullptr;
-            if (bp.verify)
-                bp.chol_v.add(h->chol_ntask, (const double*)h->red, Rm, YU, ld, n, nbc, h->chol_tasks.p, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p,
-                              (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
-                              fail, h->chol_trace.p, (const BaCtl*)h->ctl.p, h->xp.p, h->chol_vfy.p, h->chol_head.p, h->chol_ntask);
-            else
-                bp.chol.add(h->chol_ntask, (const double*)h->red, Rm, YU, ld, n, nbc, h->chol_tasks.p, (const int*)h->chol_deps.p, (const int*)h->chol_neager.p,
-                            (const int*)h->col_src.p, flagA, flagR, &h->ctl.p->epoch,
-                            fail, h->chol_trace.p, (const BaCtl*)h->ctl.p, h->xp.p, (unsigned long long*)nullptr, h->chol_head.p, h->chol_ntask);
-        }
+        const int ug = (int)upd_grid(h).x;
+        bp.ctl_init.add(1, CtlInitArgs{h->ctl.p, iters, mode});
+        bp.eval0.add(ug + 1, upd_args(h, B, 0.0, nullptr, fin_args(h, B, h->xp.p, 0, 1, 0, 0.0)));
+        bp.step.add(ug + 1, upd_args(h, B, 0.0, h->xp.p, fin_args(h, B, h->xp.p, 1, 1, 0, 0.0)));
+        bp.step_notify.add(ug + 1, upd_args(h, B, 0.0, h->xp.p, fin_args(h, B, h->xp.p, 1, 1, 1, 0.0)));
+        bp.lin0.add(ug, lin_args(h, B, 0.0, RecSet{}));
+        bp.lin.add(ug, lin_args(h, B, 0.0, RecSet{}));
+        bp.odo.add(h->O ? (int)grid1(h->O, 64).x : 0, odo_args(h, nullptr, true));
+        bp.pose_reduce.add((int)grid1((size_t)h->P * 64, kBlock).x, pose_reduce_args(h));
+        bp.maxdiag.add(1, maxdiag_args(h, 3, 1, h->ctl.p));
+        bp.reduce2.add((int)reduce2_grid(h).x, reduce2_args(h, B, 0.0, RecSet{}));
+        bp.verify = hs[0]->chol_vfy.p != nullptr;
+        const CholArgs ca = chol_args(h, h->ctl.p, 0, h->chol_head.p, bp.verify);
+        if (bp.verify) bp.chol_v.add(ca.ntask, ca);
+        else bp.chol.add(ca.ntask, ca);
     }
     bp.ctl_init.commit(bp.arena); bp.eval0.commit(bp.arena); bp.step.commit(bp.arena); bp.step_notify.commit(bp.arena);
     bp.lin0.commit(bp.arena); bp.lin.commit(bp.arena); bp.odo.commit(bp.arena); bp.pose_reduce.commit(bp.arena);
@@ -6226,7 +6210,7 @@ int ba_run_begin(se2gpu_ba* h, int iters, int mode, const volatile uint8_t* stop
     if (h->run_spec) SE2_CHECK(ba_reserve_twin(h));   // (before a capture begins; a no-op from the second run on)
     const int n0 = h->run_sync ? 1 : std::max(iters, 1);
     auto enqueue_all = [&]() -> int {
-        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(64), 0, h->stream, h->ctl.p, iters, mode);
+        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(64), 0, h->stream, CtlInitArgs{h->ctl.p, iters, mode});
         SE2_HIP(hipGetLastError());
         for (int k = 0; k < n0; ++k) SE2_CHECK(ba_enqueue_trial(h, k == 0, h->run_sync ? 0 : -1, k == n0 - 1, 0.0));
         return SE2GPU_OK;
