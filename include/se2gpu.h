@@ -532,6 +532,7 @@ int se2gpu_ba_shard_landmarks(int L, int E, const int32_t* e_kf, const int32_t* 
  *                                            (KeyFrame::ComputeBoW, src/KeyFrame.cpp:244-254; Localizer.cpp:195-205, 323-335)
  *   score(v1, v2)                            Thirdparty/DBoW2/DBoW2/ScoringObject.cpp
  *   the candidate loop of DetectLoopClose    src/GlobalMapper.cpp:201-254, src/Localizer.cpp:337-391
+ *   create(training_features, k, L, ..)      Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:573-1020   (se2gpu_voc_train)
  * Every output equals the host mirror include/se2lam_amd/ORBVocabulary.h bit for bit: word ids, node ids, feature indices,
  * BowVector values and scores (all floating-point sums are added in ascending word id, as the mirror adds them).
  * Scoring / weighting constants are DBoW2's: scoring 0 L1_NORM, 1 L2_NORM, 2 CHI_SQUARE, 3 KL, 4 BHATTACHARYYA,
@@ -556,6 +557,38 @@ int se2gpu_voc_k(const se2gpu_voc* v);
 int se2gpu_voc_L(const se2gpu_voc* v);
 int se2gpu_voc_scoring(const se2gpu_voc* v);
 int se2gpu_voc_weighting(const se2gpu_voc* v);
+/* Every se2gpu_voc - loaded, created or trained - keeps its records in host memory as well (about 60 bytes per node, 65 MB
+ * for a vocabulary of ORBvoc's size), which is what the two calls below read. */
+/* the records back, in the layout se2gpu_voc_create takes (the root at index 0, weights as the file's floats widened);
+ * SE2GPU_ERR_CAPACITY when the buffers hold fewer than se2gpu_voc_nodes entries */
+int se2gpu_voc_export(const se2gpu_voc* v, int cap_nodes, int32_t* parent, uint8_t* desc, double* weight, uint8_t* leaf);
+/* the file TemplatedVocabulary::saveToBinaryFile writes (and se2gpu_voc_load reads) */
+int se2gpu_voc_save(const se2gpu_voc* v, const char* path);
+
+/* Training - TemplatedVocabulary::create (TemplatedVocabulary.h:573-1020): hierarchical k-means++ over the descriptors of
+ * nframes documents, on the device, level by level (csrc/voc_train.hip).  The algorithm, its draws and its documented
+ * deviations from the reference are specified in include/se2lam_amd/VocabularyTrain.h; the result equals the host mirror
+ * ORBVocabulary::create bit for bit, statistics included.  desc: nframes * cap * 32 bytes, counts: nframes ints clamped to
+ * 0..cap - the layout se2gpu_orb_extract_batch_device writes and se2gpu_bow_transform_batch_device reads; host memory, or
+ * device memory when on_device != 0 (desc then 16-byte aligned).  Refused with SE2GPU_ERR_INVALID: k outside 2..32, L outside
+ * 1..10, a scoring / weighting se2gpu_voc_create refuses, no descriptor at all, a document with more than 4096 descriptors.
+ * Synchronous, on a stream of its own; every scratch buffer is released before it returns. */
+typedef struct {
+    int32_t k, L, scoring, weighting, max_iters; /* max_iters 0 = 1000 */
+    uint64_t seed;
+} se2gpu_voc_train_params;
+typedef struct {
+    int32_t nodes, words, kmeans_nodes, trivial_nodes, lloyd_iters_total, lloyd_iters_max, short_seeded_nodes, empty_clusters,
+        capped_nodes, zero_weight_words;
+} se2gpu_voc_train_stats;
+int se2gpu_voc_train(const se2gpu_voc_train_params* params, const uint8_t* desc, const int32_t* counts, int cap, int nframes,
+                     int on_device, se2gpu_voc** out, se2gpu_voc_train_stats* stats /* may be NULL */);
+/* per-kernel times of the training calls that start after this call (HIP events around every launch: serialises that call).
+ * The switch is process-wide; every training call times into a table of its own and publishes it when it ends, so calls on
+ * several threads do not disturb each other.  _get walks the table of the call that ended last, SE2GPU_ERR_INVALID past its
+ * end. */
+int se2gpu_voc_train_profile(int enable);
+int se2gpu_voc_train_profile_get(int idx, const char** name, double* ms, int64_t* launches);
 
 /* A per-thread context: its stream and scratch for batches of up to max_batch frames of up to max_features (<= 4096)
  * features.  Not thread-safe; several contexts may share one vocabulary. */

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ORBmatcher.h"   // FeatureVectorView
+#include "VocabularyTrain.h"
 #include "VocabularyTree.h"
 
 namespace se2lam_amd {
@@ -82,29 +83,81 @@ public:
         clear();
         VocabularyTree t;
         if (!t.loadFromBinaryFile(filename)) return false;
-        m_k = t.k; m_L = t.L;
-        m_scoring = (ScoringType)t.scoring; m_weighting = (WeightingType)t.weighting;
-        m_parent.swap(t.parent); m_child_ptr.swap(t.child_ptr); m_child.swap(t.child); m_word.swap(t.word);
-        m_desc.swap(t.desc); m_leaf.swap(t.leaf); m_weight.swap(t.weight); m_words.swap(t.words);
+        adopt(t);
         return true;
+    }
+
+    // create(training_features, k, L, weighting, scoring)   (TemplatedVocabulary.h:573-1020) - the algorithm is stated in
+    // VocabularyTrain.h; this is its straight depth-first restatement with value semantics, single thread, and what the
+    // device path (se2gpu_voc_train) equals bit for bit.  desc: the documents' descriptors concatenated, counts[ndocs] (a
+    // negative count is an empty document).
+    // false (and empty) when the parameters are refused.  The weights are rounded to float, so the result is what create
+    // followed by saveToBinaryFile and loadFromBinaryFile gives.
+    bool create(const uint8_t* desc, const int32_t* counts, int ndocs, int k, int L, int weighting, int scoring, uint64_t seed,
+                TrainStats* stats = nullptr, int max_iters = 0) {
+        clear();
+        if (stats) *stats = TrainStats();
+        if (!voctrain::paramsOk(k, L, scoring, weighting) || ndocs < 1 || !counts || max_iters < 0) return false;
+        int64_t total = 0;
+        std::vector<int32_t> cnt(ndocs);   // a negative count is an empty document, as se2gpu_voc_train clamps it
+        for (int d = 0; d < ndocs; ++d) {
+            cnt[d] = counts[d] > 0 ? counts[d] : 0;
+            if (cnt[d] > voctrain::kMaxDocFeatures) return false;
+            total += cnt[d];
+        }
+        if (total == 0 || total > INT32_MAX || !desc) return false;
+        Trainer tr;
+        tr.feat = desc; tr.k = k; tr.L = L; tr.max_iters = max_iters > 0 ? max_iters : voctrain::kDefaultMaxIters;
+        tr.parent.push_back(0);
+        tr.desc.assign(kDescBytes, 0);
+        std::vector<int32_t> all((size_t)total);
+        for (int32_t i = 0; i < (int32_t)total; ++i) all[i] = i;
+        tr.step(0, all, 1, voctrain::rootKey(seed));
+        const uint32_t N = (uint32_t)tr.parent.size();
+        std::vector<uint8_t> leaf(N, 1);
+        for (uint32_t id = 1; id < N; ++id) leaf[tr.parent[id]] = 0;
+        leaf[0] = 0;
+        std::vector<double> w(N, 0.0);
+        for (uint32_t id = 1; id < N; ++id) w[id] = leaf[id] ? 1.0 : 0.0;
+        VocabularyTree t;
+        if (!t.assign(k, L, scoring, weighting, N, tr.parent.data(), tr.desc.data(), w.data(), leaf.data())) return false;
+        adopt(t);
+        if (weighting == TF_IDF || weighting == IDF) {   // setNodeWeights: a real walk of every training descriptor
+            std::vector<int32_t> ni(m_words.size(), 0), last_doc(m_words.size(), -1);
+            const uint8_t* f = desc;
+            for (int d = 0; d < ndocs; ++d)
+                for (int i = 0; i < cnt[d]; ++i, f += kDescBytes) {
+                    WordId id; WordValue wv;
+                    transform(f, id, wv);
+                    if (last_doc[id] != d) { last_doc[id] = d; ++ni[id]; }
+                }
+            for (size_t wd = 0; wd < m_words.size(); ++wd) m_weight[m_words[wd]] = (double)voctrain::idfWeight(ndocs, ni[wd]);
+        }
+        tr.stats.nodes = (int32_t)N;
+        tr.stats.words = (int32_t)m_words.size();
+        for (uint32_t id : m_words) tr.stats.zero_weight_words += !(m_weight[id] > 0);
+        if (stats) *stats = tr.stats;
+        return true;
+    }
+
+    // the reference's call line - create(training_features, k, L, weighting, scoring) with training_features a
+    // std::vector<std::vector<cv::Mat>> of 1 x 32 rows - plus the seed that replaces DBoW2's global rand() stream
+    template <class Row>
+    bool create(const std::vector<std::vector<Row>>& training_features, int k, int L, int weighting, int scoring, uint64_t seed,
+                TrainStats* stats = nullptr, int max_iters = 0) {
+        std::vector<uint8_t> rows;
+        std::vector<int32_t> counts;
+        for (const auto& doc : training_features) {
+            counts.push_back((int32_t)doc.size());
+            for (const auto& r : doc) rows.insert(rows.end(), r.data, r.data + kDescBytes);
+        }
+        return create(rows.data(), counts.data(), (int)counts.size(), k, L, weighting, scoring, seed, stats, max_iters);
     }
 
     // the file TemplatedVocabulary::saveToBinaryFile (:1526-1546) writes
     bool saveToBinaryFile(const std::string& filename) const {
-        std::FILE* f = std::fopen(filename.c_str(), "wb");
-        if (!f) return false;
-        const uint32_t nb_nodes = nodes(), size_node = 4 + kDescBytes + 4 + 1;
-        const int32_t k = m_k, L = m_L, scoring = (int32_t)m_scoring, weighting = (int32_t)m_weighting;
-        std::fwrite(&nb_nodes, 4, 1, f); std::fwrite(&size_node, 4, 1, f); std::fwrite(&k, 4, 1, f); std::fwrite(&L, 4, 1, f);
-        std::fwrite(&scoring, 4, 1, f); std::fwrite(&weighting, 4, 1, f);
-        for (uint32_t id = 1; id < nb_nodes; ++id) {
-            const int32_t parent = m_parent[id];
-            const float w = (float)m_weight[id];
-            const uint8_t leaf = m_leaf[id];
-            std::fwrite(&parent, 4, 1, f); std::fwrite(&m_desc[(size_t)id * kDescBytes], 1, kDescBytes, f);
-            std::fwrite(&w, 4, 1, f); std::fwrite(&leaf, 1, 1, f);
-        }
-        return std::fclose(f) == 0;
+        return VocabularyTree::writeBinaryFile(filename, m_k, m_L, (int)m_scoring, (int)m_weighting, nodes(), m_parent.data(), m_desc.data(),
+                                               m_weight.data(), m_leaf.data());
     }
 
     // FORB::distance (FORB.cpp:82-102): bits that differ
@@ -238,6 +291,120 @@ public:
     const std::vector<int32_t>& wordOfNode() const { return m_word; }
 
 private:
+    void adopt(VocabularyTree& t) {
+        m_k = t.k; m_L = t.L;
+        m_scoring = (ScoringType)t.scoring; m_weighting = (WeightingType)t.weighting;
+        m_parent.swap(t.parent); m_child_ptr.swap(t.child_ptr); m_child.swap(t.child); m_word.swap(t.word);
+        m_desc.swap(t.desc); m_leaf.swap(t.leaf); m_weight.swap(t.weight); m_words.swap(t.words);
+    }
+
+    // HKmeansStep and what it calls (VocabularyTrain.h); nodes are appended in DBoW2's depth-first id order
+    struct Trainer {
+        const uint8_t* feat = nullptr;
+        int k = 0, L = 0, max_iters = 0;
+        std::vector<int32_t> parent;
+        std::vector<uint8_t> desc;
+        TrainStats stats;
+        typedef std::vector<uint8_t> Centres;   // 32 bytes per cluster
+
+        const uint8_t* f(int32_t i) const { return feat + (size_t)i * kDescBytes; }
+
+        void seed(const std::vector<int32_t>& mem, uint64_t key, Centres& c) const {
+            const int n = (int)mem.size();
+            uint32_t j = 0;
+            const int first = (int)(voctrain::draw(key, j++) * (double)n);
+            c.assign(f(mem[first]), f(mem[first]) + kDescBytes);
+            std::vector<int> md(n);
+            for (int m = 0; m < n; ++m) md[m] = distance(f(mem[m]), c.data());
+            while ((int)c.size() < k * kDescBytes) {
+                const uint8_t* newest = &c[c.size() - kDescBytes];
+                int64_t sum = 0;
+                for (int m = 0; m < n; ++m) {
+                    if (md[m] > 0) { const int d = distance(f(mem[m]), newest); if (d < md[m]) md[m] = d; }
+                    sum += md[m];
+                }
+                if (sum == 0) break;
+                double cut;
+                do cut = voctrain::draw(key, j++) * (double)sum; while (cut == 0.0);
+                int pick = n - 1;
+                int64_t running = 0;
+                for (int m = 0; m < n; ++m) {
+                    running += md[m];
+                    if ((double)running >= cut) { pick = m; break; }
+                }
+                c.insert(c.end(), f(mem[pick]), f(mem[pick]) + kDescBytes);
+            }
+        }
+
+        void step(int32_t parent_id, const std::vector<int32_t>& mem, int level, uint64_t key) {
+            const int n = (int)mem.size();
+            if (n == 0) return;
+            Centres c;
+            std::vector<int> asg(n);
+            int ncl;
+            if (n <= k) {
+                ++stats.trivial_nodes;
+                ncl = n;
+                for (int m = 0; m < n; ++m) { c.insert(c.end(), f(mem[m]), f(mem[m]) + kDescBytes); asg[m] = m; }
+            } else {
+                ++stats.kmeans_nodes;
+                seed(mem, key, c);
+                ncl = (int)c.size() / kDescBytes;
+                if (ncl < k) ++stats.short_seeded_nodes;
+                std::vector<int> cur(n);
+                int iters = 0;
+                for (;;) {
+                    if (iters > 0) {   // the means of the previous assignment; a cluster without members keeps its centre
+                        std::vector<int> bits((size_t)ncl * 256, 0), cnt(ncl, 0);
+                        for (int m = 0; m < n; ++m) {
+                            const uint8_t* p = f(mem[m]);
+                            int* b = &bits[(size_t)asg[m] * 256];
+                            ++cnt[asg[m]];
+                            for (int i = 0; i < kDescBytes; ++i)
+                                for (int q = 0; q < 8; ++q) b[i * 8 + q] += (p[i] >> q) & 1;
+                        }
+                        for (int cl = 0; cl < ncl; ++cl) {
+                            if (!cnt[cl]) continue;
+                            const int need = voctrain::majorityThreshold(cnt[cl]);
+                            for (int i = 0; i < kDescBytes; ++i) {
+                                uint8_t v = 0;
+                                for (int q = 0; q < 8; ++q) v |= (uint8_t)((bits[(size_t)cl * 256 + i * 8 + q] >= need) << q);
+                                c[(size_t)cl * kDescBytes + i] = v;
+                            }
+                        }
+                    }
+                    for (int m = 0; m < n; ++m) {
+                        int best = 0, bd = distance(f(mem[m]), c.data());
+                        for (int cl = 1; cl < ncl; ++cl) {
+                            const int d = distance(f(mem[m]), &c[(size_t)cl * kDescBytes]);
+                            if (d < bd) { bd = d; best = cl; }
+                        }
+                        cur[m] = best;
+                    }
+                    ++iters;
+                    const bool same = iters > 1 && cur == asg;
+                    asg = cur;
+                    if (same) break;
+                    if (iters >= max_iters) { ++stats.capped_nodes; break; }
+                }
+                stats.lloyd_iters_total += iters;
+                if (iters > stats.lloyd_iters_max) stats.lloyd_iters_max = iters;
+            }
+            std::vector<std::vector<int32_t>> groups(ncl);
+            for (int m = 0; m < n; ++m) groups[asg[m]].push_back(mem[m]);
+            std::vector<int32_t> ids(ncl, -1);
+            for (int cl = 0; cl < ncl; ++cl) {
+                if (groups[cl].empty()) { ++stats.empty_clusters; continue; }
+                ids[cl] = (int32_t)parent.size();
+                parent.push_back(parent_id);
+                desc.insert(desc.end(), &c[(size_t)cl * kDescBytes], &c[(size_t)cl * kDescBytes] + kDescBytes);
+            }
+            if (level < L)
+                for (int cl = 0; cl < ncl; ++cl)
+                    if (groups[cl].size() > 1) step(ids[cl], groups[cl], level + 1, voctrain::childKey(key, cl));
+        }
+    };
+
     // KLScoring::score (ScoringObject.cpp:175-222): sum over the words of a; a word b lacks counts with log(eps)
     double scoreKL(const BowVector& a, const BowVector& b) const {
         const double log_eps = std::log(2.220446049250313e-16);   // GeneralScoring::LOG_EPS = log(DBL_EPSILON)

@@ -1,4 +1,5 @@
-// ORBVocabulary on the device: the reference's three call lines (ORBVocabulary.h gives their places in the reference)
+// ORBVocabulary on the device: the reference's call lines (ORBVocabulary.h gives their places in the reference)
+//   create(training_features, k, L, weighting, scoring) [+ seed], saveToBinaryFile(file)
 //   loadFromBinaryFile(strVocFile)
 //   transform(vCurrentDesc, mBowVec, mFeatVec, 4)
 //   score(BowVecCurr, BowVec)
@@ -38,6 +39,53 @@ public:
         m_maxFeatures = maxFeatures;
         return openContext();
     }
+
+    // create(training_features, k, L, weighting, scoring) on the device (se2gpu_voc_train; the algorithm and the seed that
+    // replaces DBoW2's rand() stream: VocabularyTrain.h).  desc: the documents' descriptors concatenated, counts[ndocs] - the
+    // arguments of ORBVocabulary::create, whose result this equals bit for bit.  false when the parameters are refused.
+    bool create(const uint8_t* desc, const int32_t* counts, int ndocs, int k, int L, int weighting, int scoring, uint64_t seed,
+                TrainStats* stats = nullptr, int max_iters = 0, int maxFeatures = 4096) {
+        m_ctx.reset(); m_voc.reset();
+        if (ndocs < 1 || !counts) return false;
+        int cap = 1;
+        for (int d = 0; d < ndocs; ++d) cap = counts[d] > cap ? counts[d] : cap;
+        std::vector<uint8_t> rows((size_t)ndocs * cap * 32, 0);   // the layout of se2gpu_voc_train: ndocs x cap x 32
+        const uint8_t* src = desc;
+        for (int d = 0; d < ndocs; ++d) {
+            if (counts[d] <= 0) continue;   // a negative count is an empty document, on both classes
+            std::memcpy(&rows[(size_t)d * cap * 32], src, (size_t)counts[d] * 32);
+            src += (size_t)counts[d] * 32;
+        }
+        return createPadded(rows.data(), counts, cap, ndocs, false, k, L, weighting, scoring, seed, stats, max_iters, maxFeatures);
+    }
+    // the same from the layout se2gpu_orb_extract_batch_device writes (ndocs x cap x 32 bytes, counts clamped to 0..cap), in
+    // host memory or, with onDevice, where the extractor left it
+    bool createPadded(const uint8_t* desc, const int32_t* counts, int cap, int ndocs, bool onDevice, int k, int L, int weighting, int scoring,
+                      uint64_t seed, TrainStats* stats = nullptr, int max_iters = 0, int maxFeatures = 4096) {
+        m_ctx.reset(); m_voc.reset();
+        se2gpu_voc_train_params p = {k, L, scoring, weighting, max_iters, seed};
+        se2gpu_voc_train_stats st;
+        se2gpu_voc* v = nullptr;
+        if (se2gpu_voc_train(&p, desc, counts, cap, ndocs, onDevice ? 1 : 0, &v, &st) != SE2GPU_OK) return false;
+        static_assert(sizeof(TrainStats) == sizeof(se2gpu_voc_train_stats), "stats layout");
+        if (stats) std::memcpy(static_cast<void*>(stats), &st, sizeof st);
+        m_voc.reset(v, se2gpu_voc_destroy);
+        m_maxFeatures = maxFeatures;
+        return openContext();
+    }
+    template <class Row>
+    bool create(const std::vector<std::vector<Row>>& training_features, int k, int L, int weighting, int scoring, uint64_t seed,
+                TrainStats* stats = nullptr, int max_iters = 0) {
+        std::vector<uint8_t> rows;
+        std::vector<int32_t> counts;
+        for (const auto& doc : training_features) {
+            counts.push_back((int32_t)doc.size());
+            for (const auto& r : doc) rows.insert(rows.end(), r.data, r.data + 32);
+        }
+        return create(rows.data(), counts.data(), (int)counts.size(), k, L, weighting, scoring, seed, stats, max_iters);
+    }
+
+    bool saveToBinaryFile(const std::string& filename) const { return m_voc && se2gpu_voc_save(m_voc.get(), filename.c_str()) == SE2GPU_OK; }
 
     bool empty() const { return !m_voc || se2gpu_voc_words(m_voc.get()) <= 0; }
     unsigned size() const { return m_voc ? (unsigned)se2gpu_voc_words(m_voc.get()) : 0u; }

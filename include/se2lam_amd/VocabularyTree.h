@@ -92,6 +92,27 @@ struct VocabularyTree {
         }
         return assign(k_, L_, scoring_, weighting_, N, p.data(), d.data(), w.data(), lf.data());
     }
+
+    // the file TemplatedVocabulary::saveToBinaryFile (:1526-1546) writes, from per-node arrays (root at index 0, not written);
+    // the one place that writes the format: this struct and ORBVocabulary::saveToBinaryFile both come here
+    static bool writeBinaryFile(const std::string& filename, int k_, int L_, int scoring_, int weighting_, uint32_t nb_nodes,
+                                const int32_t* parent_, const uint8_t* desc_, const double* weight_, const uint8_t* leaf_) {
+        if (nb_nodes < 1) return false;
+        std::FILE* f = std::fopen(filename.c_str(), "wb");
+        if (!f) return false;
+        const uint32_t size_node = kNodeBytes;
+        const int32_t hdr[4] = {k_, L_, scoring_, weighting_};
+        bool ok = std::fwrite(&nb_nodes, 4, 1, f) == 1 && std::fwrite(&size_node, 4, 1, f) == 1 && std::fwrite(hdr, 4, 4, f) == 4;
+        for (uint32_t id = 1; id < nb_nodes && ok; ++id) {
+            const float w = (float)weight_[id];
+            ok = std::fwrite(&parent_[id], 4, 1, f) == 1 && std::fwrite(desc_ + (size_t)id * kDescBytes, 1, kDescBytes, f) == (size_t)kDescBytes &&
+                 std::fwrite(&w, 4, 1, f) == 1 && std::fwrite(&leaf_[id], 1, 1, f) == 1;
+        }
+        return (std::fclose(f) == 0) && ok;
+    }
+    bool saveToBinaryFile(const std::string& filename) const {
+        return writeBinaryFile(filename, k, L, scoring, weighting, (uint32_t)parent.size(), parent.data(), desc.data(), weight.data(), leaf.data());
+    }
 };
 
 }  // namespace se2lam_amd

@@ -30,6 +30,7 @@ PER_FILE = {
     "triangulate.hip": ["-ffp-contract=off"],
     "ransac.hip": ["-ffp-contract=off"],
     "bow.hip": ["-ffp-contract=off"],        # BowVector values and scores equal the host vocabulary's to the bit
+    "voc_train.hip": ["-ffp-contract=off"],  # cut_d = u * sum is one IEEE multiply on host and device
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
 }
 
@@ -57,7 +58,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
     sub = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTree.h")   # the one adapter header a translation unit (bow.hip) includes
-    headers += [sub, os.path.abspath(__file__)]
+    sub2 = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTrain.h")   # voc_train.hip shares its inline functions with the host mirror
+    headers += [sub, sub2, os.path.abspath(__file__)]
     objs = []
     for src in sources():
         obj = os.path.join(OBJDIR, src[:-4] + ".o")

@@ -76,6 +76,16 @@ class MapView(C.Structure):
                 ("mp_kf_ptr", C.c_void_p), ("mp_kf_idx", C.c_void_p)]
 
 
+class VocTrainParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("max_iters", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class VocTrainStats(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("nodes", "words", "kmeans_nodes", "trivial_nodes", "lloyd_iters_total", "lloyd_iters_max",
+                                         "short_seeded_nodes", "empty_clusters", "capped_nodes", "zero_weight_words")]
+
+
 class BaStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("terminated", C.c_int32),
                 ("stopped", C.c_int32), ("chi2_init", C.c_double), ("chi2_final", C.c_double),
@@ -213,6 +223,11 @@ SYMBOLS = {
     "se2gpu_voc_L": (_I, [_VP]),
     "se2gpu_voc_scoring": (_I, [_VP]),
     "se2gpu_voc_weighting": (_I, [_VP]),
+    "se2gpu_voc_export": (_I, [_VP, _I, _VP, _VP, _VP, _VP]),
+    "se2gpu_voc_save": (_I, [_VP, C.c_char_p]),
+    "se2gpu_voc_train": (_I, [_VP, _VP, _VP, _I, _I, _I, C.POINTER(_VP), _VP]),
+    "se2gpu_voc_train_profile": (_I, [_I]),
+    "se2gpu_voc_train_profile_get": (_I, [_I, C.POINTER(C.c_char_p), _PD, C.POINTER(C.c_int64)]),
     "se2gpu_bow_create": (_I, [_VP, _I, _I, C.POINTER(_VP)]),
     "se2gpu_bow_destroy": (None, [_VP]),
     "se2gpu_bow_set_stream": (_I, [_VP, _VP]),

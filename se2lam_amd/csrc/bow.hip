@@ -327,6 +327,7 @@ struct se2gpu_voc {
     DevBuf<uint4> desc;      // 2 per child slot
     DevBuf<int4> meta;       // per child slot
     DevBuf<double> word_weight;
+    se2lam_amd::VocabularyTree tree;   // the records on the host: se2gpu_voc_export, se2gpu_voc_save
 };
 
 struct se2gpu_bow {
@@ -373,7 +374,7 @@ struct se2gpu_bowdb {
 
 namespace {
 
-int voc_upload(const se2lam_amd::VocabularyTree& t, se2gpu_voc** out) {
+int voc_upload(se2lam_amd::VocabularyTree& t, se2gpu_voc** out) {
     std::unique_ptr<se2gpu_voc> v(new (std::nothrow) se2gpu_voc);
     SE2_REQUIRE(v, SE2GPU_ERR_INVALID, "voc: out of memory");
     v->k = t.k; v->L = t.L; v->scoring = t.scoring; v->weighting = t.weighting;
@@ -402,6 +403,7 @@ int voc_upload(const se2lam_amd::VocabularyTree& t, se2gpu_voc** out) {
         SE2_HIP(hipMemcpy(v->meta.p, meta.data(), meta.size() * sizeof(int4), hipMemcpyHostToDevice));
     }
     if (!ww.empty()) SE2_HIP(hipMemcpy(v->word_weight.p, ww.data(), ww.size() * sizeof(double), hipMemcpyHostToDevice));
+    v->tree = std::move(t);
     *out = v.release();
     return SE2GPU_OK;
 }
@@ -535,6 +537,23 @@ int se2gpu_voc_k(const se2gpu_voc* v) { return v ? v->k : SE2GPU_ERR_INVALID; }
 int se2gpu_voc_L(const se2gpu_voc* v) { return v ? v->L : SE2GPU_ERR_INVALID; }
 int se2gpu_voc_scoring(const se2gpu_voc* v) { return v ? v->scoring : SE2GPU_ERR_INVALID; }
 int se2gpu_voc_weighting(const se2gpu_voc* v) { return v ? v->weighting : SE2GPU_ERR_INVALID; }
+
+int se2gpu_voc_export(const se2gpu_voc* v, int cap_nodes, int32_t* parent, uint8_t* desc, double* weight, uint8_t* leaf) {
+    SE2_REQUIRE(v && parent && desc && weight && leaf, SE2GPU_ERR_INVALID, "voc_export: NULL argument");
+    SE2_REQUIRE(cap_nodes >= v->nodes, SE2GPU_ERR_CAPACITY, "voc_export: the vocabulary has %d nodes, the buffers hold %d", v->nodes, cap_nodes);
+    const se2lam_amd::VocabularyTree& t = v->tree;
+    std::copy(t.parent.begin(), t.parent.end(), parent);
+    std::copy(t.desc.begin(), t.desc.end(), desc);
+    std::copy(t.weight.begin(), t.weight.end(), weight);
+    std::copy(t.leaf.begin(), t.leaf.end(), leaf);
+    return SE2GPU_OK;
+}
+
+int se2gpu_voc_save(const se2gpu_voc* v, const char* path) {
+    SE2_REQUIRE(v && path, SE2GPU_ERR_INVALID, "voc_save: NULL argument");
+    SE2_REQUIRE(v->tree.saveToBinaryFile(path), SE2GPU_ERR_INVALID, "voc_save: %s cannot be written", path);
+    return SE2GPU_OK;
+}
 
 // ---- se2gpu_bow ------------------------------------------------------------------------------------------------------
 int se2gpu_bow_create(const se2gpu_voc* voc, int max_features, int max_batch, se2gpu_bow** out) {

@@ -5,7 +5,8 @@ Reference interface: se2lam::ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TD
     transform(features, BowVector, FeatureVector, 4)    KeyFrame.cpp:251, Localizer.cpp:195-205
     score(v1, v2) over every key frame                  GlobalMapper.cpp:201-254, Localizer.cpp:337-391
 Three handles: Vocabulary (the tree on the device, immutable, shareable), BowContext (a thread's stream and scratch:
-transform), BowDatabase (the key frames' BowVectors on the device: query).  All compute happens in libse2gpu.so (HIP).
+transform), BowDatabase (the key frames' BowVectors on the device: query).  Vocabulary.train makes a vocabulary from
+descriptors (create).  All compute happens in libse2gpu.so (HIP).
 """
 from __future__ import annotations
 
@@ -34,6 +35,9 @@ class Vocabulary:
             assert len(desc) == 32 * n and len(weight) == n and len(leaf) == n
             capi.check(capi.lib().se2gpu_voc_create(int(k), int(L), int(scoring), int(weighting), n, parent.ctypes.data,
                                                     desc.ctypes.data, weight.ctypes.data, leaf.ctypes.data, C.byref(self._h)))
+        self._read_header()
+
+    def _read_header(self):
         l = capi.lib()
         self.k, self.L = l.se2gpu_voc_k(self._h), l.se2gpu_voc_L(self._h)
         self.scoring, self.weighting = l.se2gpu_voc_scoring(self._h), l.se2gpu_voc_weighting(self._h)
@@ -42,6 +46,42 @@ class Vocabulary:
     @classmethod
     def load(cls, path):
         return cls(path=path)
+
+    @classmethod
+    def train(cls, desc, counts, k, L, weighting=TF_IDF, scoring=L1_NORM, seed=0, max_iters=0, cap=None, nframes=None):
+        """TemplatedVocabulary::create on the device (se2gpu_voc_train; the algorithm: include/se2lam_amd/VocabularyTrain.h).
+        desc (nframes, cap, 32) uint8 and counts (nframes,) as numpy arrays, or device pointers (capi.DeviceArray.ptr) with
+        cap and nframes given.  The statistics of the run are left in `.train_stats` (a dict)."""
+        on_device = cap is not None
+        if not on_device:
+            desc = np.ascontiguousarray(desc, np.uint8)
+            assert desc.ndim == 3 and desc.shape[2] == 32
+            nframes, cap = desc.shape[:2]
+            counts = np.ascontiguousarray(counts, np.int32)
+            assert len(counts) == nframes
+            pd, pc = desc.ctypes.data, counts.ctypes.data
+        else:
+            pd, pc = desc, counts
+        par = capi.VocTrainParams(int(k), int(L), int(scoring), int(weighting), int(max_iters), int(seed) & ((1 << 64) - 1))
+        st = capi.VocTrainStats()
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        capi.check(capi.lib().se2gpu_voc_train(C.addressof(par), pd, pc, int(cap), int(nframes), int(on_device), C.byref(self._h), C.addressof(st)))
+        self._read_header()
+        self.train_stats = {n: int(getattr(st, n)) for n, _ in capi.VocTrainStats._fields_}
+        return self
+
+    def export(self):
+        """-> parent (n,) int32, desc (n, 32) uint8, weight (n,) float64 (the file's floats widened), leaf (n,) bool; root at 0"""
+        n = self.nodes
+        parent, desc = np.zeros(n, np.int32), np.zeros((n, 32), np.uint8)
+        weight, leaf = np.zeros(n, np.float64), np.zeros(n, np.uint8)
+        capi.check(capi.lib().se2gpu_voc_export(self._h, n, parent.ctypes.data, desc.ctypes.data, weight.ctypes.data, leaf.ctypes.data))
+        return parent, desc, weight, leaf.astype(bool)
+
+    def save(self, path):
+        """the file saveToBinaryFile writes"""
+        capi.check(capi.lib().se2gpu_voc_save(self._h, str(path).encode()))
 
     def __del__(self):
         try:
