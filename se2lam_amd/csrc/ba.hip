@@ -1606,14 +1606,29 @@ __global__ __launch_bounds__(256) void k_chol_apply(const double* __restrict__ A
     if (lane == 0 && dst >= 0) x[dst] = acc;
 }
 
-// The end of a trial without a kernel boundary (single GPU): k_update gets ONE extra workgroup, launched last, that does
-// what k_finalize does - oplus of the poses, odometry chi^2 at the trial poses, the pose part of computeScale() - while
-// the landmark workgroups run, then waits until their partials have all arrived (an agent-scope counter; it was
-// dispatched after every one of them, so the wait cannot deadlock), sums them in a fixed order and advances the
-// Levenberg-Marquardt controller.  k_finalize stays for the sharded (multi-GPU) runs, whose scalars go through an
-// all-reduce between the two steps.
+// What the end of a trial needs whichever kernel runs it (trial_open / trial_decide below; the host fills it in trial_end):
+// where the scalars and the controller block go, and what this slot is.
+struct TrialEnd {
+    double* out;              // {chi2_trial, scale, factorisation flag, 0}
+    volatile double* mail;
+    double seq;               // without a controller: the sequence number the scalars are posted with
+    BaCtl* ctl;
+    const volatile int* stop;
+    int step;                 // the slot evaluates a trial step (0: the starting state)
+    int decide;               // this kernel takes the decision (0: k_lm_decide does, behind the all-reduce)
+    int notify;               // the host waits for this slot's block
+    int spec;                 // the landmark workgroups are k_update<true>'s: they linearise the trial state (SpecArgs)
+};
+
+// The end of an SE(2) trial: oplus of the poses (VertexSE2::oplusImpl: additive x, y; theta = normalize_theta(theta +
+// dtheta)), the odometry chi^2 at the trial poses, the pose part of computeScale(), the sum of the landmark workgroups'
+// partials, the decision.  Single GPU: no kernel boundary - k_update gets ONE extra workgroup, launched last
+// (finish_trial), that does the pose part while the landmark workgroups run, then waits until their partials have all
+// arrived (an agent-scope counter; it was dispatched after every one of them, so the wait cannot deadlock) and sums
+// them in a fixed order.  Sharded (multi-GPU) runs and the two-launch form of ba_evaluate: k_finalize, a single block
+// behind k_update, whose scalars (local to the rank) go through an all-reduce in front of the decision (k_lm_decide).
 struct FinArgs {
-    int enabled, nblk, P, O, root, step, decide, notify;
+    int enabled, nblk, P, O, root;
     const uint8_t* fixed;
     const double* xp;
     const double* bp;
@@ -1623,13 +1638,8 @@ struct FinArgs {
     const int* o_j;
     const double* o_meas;
     const double* o_info;
-    double* out;              // {chi2_trial, scale, factorisation flag, 0}
-    volatile double* mail;
-    double seq;
-    BaCtl* ctl;
-    const volatile int* stop;
     unsigned* counter;        // landmark workgroups that have published their partials (reset by the finisher)
-    int spec;                 // the landmark workgroups are k_update<true>'s: they linearise the trial state (SpecArgs)
+    TrialEnd te;
 };
 __device__ void finish_trial(const FinArgs& fin, const double* part, double lambda, double* fsp);
 
@@ -1880,33 +1890,98 @@ __device__ inline void end_slot(BaCtl* ctl, volatile double* mail, bool post, in
     }
 }
 
-// the finisher workgroup of k_update (kBlock threads): see FinArgs
-__device__ void finish_trial(const FinArgs& fin, const double* part, double lambda, double* fsp) {
-    __shared__ double fsm[2][kBlock / 64];
-    // fsp (3 * 1024 doubles of the caller's LDS): trial poses staged for the odometry pass when P <= 1024
-    __shared__ int fpost;
-    BaCtl* ctl = fin.ctl;
-    const volatile double* cmail = fin.mail;
-    volatile double* mail = fin.mail;
-    (void)cmail;
-    const double* poses = fin.poses;
-    double* poses_trial = fin.poses_trial;
-    const bool step = fin.step != 0;
-    int stopped = 0;
-    double failflag = 0;
+// ---- The end of a trial, for every pose model and launch shape: finish_trial (the last workgroup of k_update), k_finalize,
+// k3_finalize, k4_finalize and k_lm_decide differ in how they come by (chi^2, scale) and are the same from there on.
+//   trial_open    all threads, first: the run is over -> answer a pending notification, leave; else who holds the estimate, lambda
+//   block_sum2    the block's two sums, in thread 0
+//   trial_decide  thread 0: out[0..3], then lm_begin / lm_advance on the controller or, without one, the scalars to the mailbox
+//   trial_close   all threads: the slot counter and, when trial_decide says so, the controller block to the mailbox
+
+// live = false: the run is over.  est_b: the "b" pose buffer holds the estimate (and "a" the trial state); lambda: the controller's,
+// or the caller's without one.  (Returned as values: buffers swapped through reference parameters kept both pointers and lambda in
+// vector registers all through k_finalize, 12 VGPRs and one wave per SIMD more than picking them at the call.)
+struct TrialState { bool live, est_b; double lambda; };
+__device__ __forceinline__ TrialState trial_open(const TrialEnd& t, double lambda) {
+    BaCtl* ctl = t.ctl;
+    bool est_b = false;
     if (ctl) {
-        if (ctl->done) {   // the run is over: only answer a pending notification
-            end_slot(ctl, mail, fin.notify != 0, threadIdx.x, blockDim.x, fin.step != 0);
-            return;
+        if (ctl->done) {   // only answer a pending notification (where the decision is k_lm_decide's, it does)
+            if (t.decide) end_slot(ctl, t.mail, t.notify != 0, threadIdx.x, blockDim.x, t.step != 0);
+            return TrialState{false, false, lambda};
         }
-        if (ctl->sel) { const double* t = poses; poses = poses_trial; poses_trial = const_cast<double*>(t); }
+        est_b = ctl->sel != 0;
         lambda = ctl->lambda;
     }
-    if (threadIdx.x == 0) {   // the two slow reads of the decision (mapped host memory; the solver's flag) start now
-        stopped = (fin.stop && *fin.stop) ? 1 : 0;
-        failflag = step ? fin.out[2] : 0.0;
+    return TrialState{true, est_b, lambda};
+}
+
+// The two slow reads of the decision, as values: the force-stop word (mapped host memory) and the solver's flag.
+__device__ __forceinline__ bool trial_stopped(const TrialEnd& t) { return t.ctl && t.decide && t.stop && *t.stop; }
+__device__ __forceinline__ double trial_fail(const TrialEnd& t) { return t.step ? t.out[2] : 0.0; }
+
+// (chi, scale) summed over the block, valid in thread 0: wave sums, one LDS slot per wave and sum (sm: 2 * blockDim.x / 64 doubles
+// of the CALLER's - an array declared in an inlined body once cost k_window_lm 18 SGPR spills), thread 0 adds the
+// waves in ascending order: a fixed order, so the sums are deterministic.
+__device__ __forceinline__ void block_sum2(double& chi, double& scale, double* sm) {
+    const int w0 = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    chi = wave_sum(chi);
+    scale = wave_sum(scale);
+    if ((threadIdx.x & 63) == 0) {
+        sm[w0] = chi;
+        sm[nw + w0] = scale;
     }
-    double chi = 0, scale = 0;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < nw; ++w) {
+            chi += sm[w];
+            scale += sm[nw + w];
+        }
+}
+
+// Thread 0, with the trial's sums, the factorisation flag and the stop word as values.  `records`: the landmark workgroups keep
+// the linearisation records (k_update of the single-GPU SE(2) run), so the speculation's bookkeeping follows lm_advance.
+// Returns whether the controller block goes to the mailbox (trial_close).
+__device__ __forceinline__ bool trial_decide(const TrialEnd& t, double chi, double scale, double fail, bool stopped, bool records) {
+    BaCtl* ctl = t.ctl;
+    volatile double* mail = t.mail;
+    t.out[0] = chi; t.out[1] = scale; t.out[3] = 0;
+    if (!t.step) t.out[2] = 0;
+    if (ctl && t.decide) {
+        if (!t.step) {   // evaluation of the starting state
+            lm_begin(ctl, chi, stopped);
+        } else {
+            const double sc[3] = {chi, scale, fail};
+            const int sel0 = ctl->sel;
+            const bool speculated = t.spec && ctl->it + 1 < ctl->iters;   // d_update<true>'s own test
+            const double lambda_spec = lm_lambda_spec(ctl->lambda, ctl->mode);
+            lm_advance(ctl, sc, stopped);
+            if (records && !ctl->error) lm_records_advance(ctl, speculated, sel0, lambda_spec);
+        }
+        return (ctl->done || t.notify) && mail;
+    }
+    if (mail && !ctl) {  // synchronous callers (se2gpu_ba_chi2, the host controller): the three scalars
+        mail[0] = chi;
+        mail[1] = scale;
+        mail[2] = fail;
+        __threadfence_system();
+        mail[3] = t.seq;
+    }
+    return false;
+}
+
+// All threads, last; *post: an LDS word of the caller's holding trial_decide's answer.
+__device__ __forceinline__ void trial_close(const TrialEnd& t, const int* post) {
+    if (!(t.ctl && t.decide)) return;
+    __syncthreads();
+    end_slot(t.ctl, t.mail, *post != 0, threadIdx.x, blockDim.x, t.step != 0);
+}
+
+// SE(2) pose stage (all threads of the block): with a step oplus into the trial buffer and the pose part of computeScale(),
+// sum_j x_j (lambda x_j + b_j).  bp is this rank's LOCAL pose gradient (its landmark shard's edges, + the odometry edges on the
+// root): every rank contributes x.b_local to the all-reduced sum, the lambda x.x term enters exactly once (root).  The first
+// 1,024 poses of the evaluated state are staged in sp (3 * 1024 doubles of the caller's LDS) for se2_odometry_chi2.
+__device__ __forceinline__ void se2_pose_stage(const FinArgs& fin, const double* poses, double* poses_trial, double lambda,
+                                               bool step, double* sp, double& scale) {
     for (int p = threadIdx.x; p < fin.P; p += blockDim.x) {
         double x = poses[3 * p], y = poses[3 * p + 1], th = poses[3 * p + 2];
         if (step && !fin.fixed[p]) {
@@ -1917,21 +1992,49 @@ __device__ void finish_trial(const FinArgs& fin, const double* part, double lamb
             else scale += d0 * bp[3 * p] + d1 * bp[3 * p + 1] + d2 * bp[3 * p + 2];
         }
         if (step) { poses_trial[3 * p] = x; poses_trial[3 * p + 1] = y; poses_trial[3 * p + 2] = th; }
-        if (p < 1024) { fsp[3 * p] = x; fsp[3 * p + 1] = y; fsp[3 * p + 2] = th; }
+        if (p < 1024) { sp[3 * p] = x; sp[3 * p + 1] = y; sp[3 * p + 2] = th; }
     }
     __syncthreads();
+}
+
+// chi^2 of the odometry edges at the staged poses (beyond the 1,024th: from the trial buffer with a step, the estimate without)
+__device__ __forceinline__ void se2_odometry_chi2(const FinArgs& fin, const double* poses, const double* poses_trial, bool step,
+                                                  const double* sp, double& chi) {
     for (int k = threadIdx.x; k < fin.O; k += blockDim.x) {
         const int i = fin.o_i[k], j = fin.o_j[k];
         double pi[3], pj[3];
         for (int c = 0; c < 3; ++c) {
-            pi[c] = (i < 1024) ? fsp[3 * i + c] : (step ? poses_trial[3 * i + c] : poses[3 * i + c]);
-            pj[c] = (j < 1024) ? fsp[3 * j + c] : (step ? poses_trial[3 * j + c] : poses[3 * j + c]);
+            pi[c] = (i < 1024) ? sp[3 * i + c] : (step ? poses_trial[3 * i + c] : poses[3 * i + c]);
+            pj[c] = (j < 1024) ? sp[3 * j + c] : (step ? poses_trial[3 * j + c] : poses[3 * j + c]);
         }
         double e[3], A[9], B[9];
         pre_se2(pi, pj, fin.o_meas + 3 * k, e, A, B);
         const double* W = fin.o_info + 9 * k;
         for (int r = 0; r < 3; ++r) chi += e[r] * (W[r * 3] * e[0] + W[r * 3 + 1] * e[1] + W[r * 3 + 2] * e[2]);
     }
+}
+
+// the finisher workgroup of k_update (kBlock threads): see FinArgs.  fsp: 3 * 1024 doubles of the caller's LDS (the pose stage)
+__device__ void finish_trial(const FinArgs& fin, const double* part, double lambda, double* fsp) {
+    __shared__ double fsm[2 * (kBlock / 64)];
+    __shared__ int fpost;
+    const TrialEnd& te = fin.te;
+    const TrialState ts = trial_open(te, lambda);
+    if (!ts.live) return;
+    lambda = ts.lambda;
+    const double* poses = fin.poses;
+    double* poses_trial = fin.poses_trial;
+    if (ts.est_b) { const double* x = poses; poses = poses_trial; poses_trial = const_cast<double*>(x); }
+    const bool step = te.step != 0;
+    bool stopped = false;
+    double failflag = 0;
+    if (threadIdx.x == 0) {   // the two slow reads of the decision (mapped host memory; the solver's flag) start now
+        stopped = trial_stopped(te);
+        failflag = trial_fail(te);
+    }
+    double chi = 0, scale = 0;
+    se2_pose_stage(fin, poses, poses_trial, lambda, step, fsp, scale);
+    se2_odometry_chi2(fin, poses, poses_trial, step, fsp, chi);
     // the landmark workgroups' partials
     if (threadIdx.x == 0) {
         const long long t0 = wall_clock64();
@@ -1952,163 +2055,48 @@ __device__ void finish_trial(const FinArgs& fin, const double* part, double lamb
         for (int u = 0; u < 4; ++u)
             if (i0 + u * (int)blockDim.x < fin.nblk) { chi += v[u].x; scale += v[u].y; }
     }
-    chi = wave_sum(chi);
-    scale = wave_sum(scale);
-    if ((threadIdx.x & 63) == 0) {
-        fsm[0][threadIdx.x >> 6] = chi;
-        fsm[1][threadIdx.x >> 6] = scale;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {   // fixed order: deterministic
-            fsm[0][0] += fsm[0][w];
-            fsm[1][0] += fsm[1][w];
-        }
-        double* out = fin.out;
-        out[0] = fsm[0][0]; out[1] = fsm[1][0]; out[3] = 0;
-        if (!step) out[2] = 0;
-        fpost = 0;
-        if (ctl && fin.decide) {
-            if (!step) {   // evaluation of the starting state
-                ctl->current_chi = ctl->chi2_init = ctl->chi2_final = fsm[0][0];
-                if (stopped) { ctl->stopped = 1; ctl->done = 1; }
-                if (ctl->iters <= 0) ctl->done = 1;
-            } else {
-                const double sc[3] = {fsm[0][0], fsm[1][0], failflag};
-                const int sel0 = ctl->sel;
-                const bool speculated = fin.spec && ctl->it + 1 < ctl->iters;   // d_update<true>'s own test
-                const double lambda_spec = lm_lambda_spec(ctl->lambda, ctl->mode);
-                lm_advance(ctl, sc, stopped != 0);
-                if (!ctl->error) lm_records_advance(ctl, speculated, sel0, lambda_spec);
-            }
-            fpost = (ctl->done || fin.notify) && mail;
-        } else if (mail && !ctl) {  // synchronous callers (se2gpu_ba_chi2, the host controller): the three scalars
-            mail[0] = fsm[0][0];
-            mail[1] = fsm[1][0];
-            mail[2] = step ? failflag : 0.0;
-            __threadfence_system();
-            mail[3] = fin.seq;
-        }
-    }
-    if (ctl && fin.decide) {
-        __syncthreads();
-        end_slot(ctl, mail, fpost != 0, threadIdx.x, blockDim.x, step);
-    }
+    block_sum2(chi, scale, fsm);
+    if (threadIdx.x == 0) fpost = trial_decide(te, chi, scale, failflag, stopped, /*records=*/true);
+    trial_close(te, &fpost);
 }
 
-// k_finalize: single block.  Sums the k_update partials, applies oplus to the poses (VertexSE2::oplusImpl:
-// additive x,y; theta = normalize_theta(theta + dtheta)), adds the odometry chi^2 at the trial poses and the pose
-// part of computeScale().  out[0] = chi2_trial, out[1] = scale (local to this rank), out[2] = factorisation flag (already
-// there).  Single GPU with a controller: also advances the LM state (decide != 0) and posts it when the run has ended
-// or the host asked for it (notify).  step == 0 evaluates the current state (x = 0) and seeds the controller's chi^2.
+// k_finalize: single block of 1,024 behind k_update (see FinArgs).  out[0] = chi2_trial, out[1] = scale (local to this rank),
+// out[2] = factorisation flag (already there).  With a controller and decide != 0 it also advances the LM state and posts it
+// when the run has ended or the host asked for it (notify).  step == 0 evaluates the current state (x = 0).
 __global__ void k_finalize(FinArgs fin, int nparts, const double* __restrict__ part, double lambda) {
-    __shared__ double sm[2][16];
-    __shared__ double sp[3 * 1024];  // trial poses staged for the odometry pass when P <= 1024
+    __shared__ double sm[2 * 16];
+    __shared__ double sp[3 * 1024];
     __shared__ int post_s;
-    BaCtl* ctl = fin.ctl;
-    volatile double* mail = fin.mail;
+    const TrialEnd& te = fin.te;
+    const TrialState ts = trial_open(te, lambda);
+    if (!ts.live) return;
+    lambda = ts.lambda;
     const double* poses = fin.poses;
     double* poses_trial = fin.poses_trial;
-    double* out = fin.out;
-    const bool step = fin.step != 0;
-    if (ctl) {
-        if (ctl->done) {   // the run is over: only answer a pending notification (sharded runs: k_lm_decide does)
-            if (fin.decide) end_slot(ctl, mail, fin.notify != 0, threadIdx.x, blockDim.x, step);
-            return;
-        }
-        if (ctl->sel) { const double* t = poses; poses = poses_trial; poses_trial = const_cast<double*>(t); }
-        lambda = ctl->lambda;
-    }
+    if (ts.est_b) { const double* x = poses; poses = poses_trial; poses_trial = const_cast<double*>(x); }
+    const bool step = te.step != 0;
     double chi = 0, scale = 0;
     for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
         chi += part[2 * i];
         scale += part[2 * i + 1];
     }
-    for (int p = threadIdx.x; p < fin.P; p += blockDim.x) {
-        double x = poses[3 * p], y = poses[3 * p + 1], th = poses[3 * p + 2];
-        if (step && !fin.fixed[p]) {
-            const double d0 = fin.xp[3 * p], d1 = fin.xp[3 * p + 1], d2 = fin.xp[3 * p + 2];
-            x += d0; y += d1; th = normalize_theta(th + d2);
-            // computeScale(): sum_j x_j (lambda x_j + b_j).  bp is this rank's LOCAL pose gradient (its landmark shard's
-            // edges, + the odometry edges on the root): every rank contributes x.b_local to the all-reduced sum, the
-            // lambda x.x term enters exactly once (root).
-            if (fin.root) scale += d0 * (lambda * d0 + fin.bp[3 * p]) + d1 * (lambda * d1 + fin.bp[3 * p + 1]) + d2 * (lambda * d2 + fin.bp[3 * p + 2]);
-            else scale += d0 * fin.bp[3 * p] + d1 * fin.bp[3 * p + 1] + d2 * fin.bp[3 * p + 2];
-        }
-        if (step) { poses_trial[3 * p] = x; poses_trial[3 * p + 1] = y; poses_trial[3 * p + 2] = th; }
-        if (p < 1024) { sp[3 * p] = x; sp[3 * p + 1] = y; sp[3 * p + 2] = th; }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < fin.O; k += blockDim.x) {
-        const int i = fin.o_i[k], j = fin.o_j[k];
-        double pi[3], pj[3];
-        for (int c = 0; c < 3; ++c) {
-            pi[c] = (i < 1024) ? sp[3 * i + c] : (step ? poses_trial[3 * i + c] : poses[3 * i + c]);
-            pj[c] = (j < 1024) ? sp[3 * j + c] : (step ? poses_trial[3 * j + c] : poses[3 * j + c]);
-        }
-        double e[3], A[9], B[9];
-        pre_se2(pi, pj, fin.o_meas + 3 * k, e, A, B);
-        const double* W = fin.o_info + 9 * k;
-        for (int r = 0; r < 3; ++r) chi += e[r] * (W[r * 3] * e[0] + W[r * 3 + 1] * e[1] + W[r * 3 + 2] * e[2]);
-    }
-    chi = wave_sum(chi);
-    scale = wave_sum(scale);
-    if ((threadIdx.x & 63) == 0) {
-        sm[0][threadIdx.x >> 6] = chi;
-        sm[1][threadIdx.x >> 6] = scale;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {   // fixed order: deterministic
-            sm[0][0] += sm[0][w];
-            sm[1][0] += sm[1][w];
-        }
-        out[0] = sm[0][0]; out[1] = sm[1][0]; out[3] = 0;
-        if (!step) out[2] = 0;
-        post_s = 0;
-        if (ctl && fin.decide) {
-            if (!step) {   // evaluation of the starting state
-                ctl->current_chi = ctl->chi2_init = ctl->chi2_final = sm[0][0];
-                if (fin.stop && *fin.stop) { ctl->stopped = 1; ctl->done = 1; }
-                if (ctl->iters <= 0) ctl->done = 1;
-            } else {
-                const double sc[3] = {sm[0][0], sm[1][0], out[2]};
-                lm_advance(ctl, sc, fin.stop && *fin.stop);
-            }
-            post_s = (ctl->done || fin.notify) && mail;
-        } else if (mail && !ctl) {  // synchronous callers (se2gpu_ba_chi2): the three scalars
-            mail[0] = sm[0][0];
-            mail[1] = sm[1][0];
-            mail[2] = step ? out[2] : 0.0;
-            __threadfence_system();
-            mail[3] = fin.seq;
-        }
-    }
-    if (ctl && fin.decide) {
-        __syncthreads();
-        end_slot(ctl, mail, post_s != 0, threadIdx.x, blockDim.x, step);
-    }
+    se2_pose_stage(fin, poses, poses_trial, lambda, step, sp, scale);
+    se2_odometry_chi2(fin, poses, poses_trial, step, sp, chi);
+    block_sum2(chi, scale, sm);
+    if (threadIdx.x == 0) post_s = trial_decide(te, chi, scale, trial_fail(te), trial_stopped(te), /*records=*/false);
+    trial_close(te, &post_s);
 }
 
-// Sharded (multi-GPU) runs: k_finalize leaves this rank's partial scalars in the fused buffer, the all-reduce sums them,
-// and this kernel takes the LM decision - identically on every rank, since the summed scalars are identical.
-__global__ void k_lm_decide(BaCtl* __restrict__ ctl, const double* __restrict__ sc, int step, int notify,
-                            volatile double* __restrict__ mail, double seq, const volatile int* __restrict__ stop) {
+// Sharded (multi-GPU) runs: k_finalize leaves this rank's partial scalars in the fused buffer (te.out), the all-reduce sums
+// them, and this kernel takes the LM decision - identically on every rank, since the summed scalars are identical.  A run that
+// is over posts its block from every remaining slot (k_finalize left the answer to this kernel).
+__global__ void k_lm_decide(TrialEnd te) {
     __shared__ int post_s;
     if (threadIdx.x == 0) {
-        if (!ctl->done) {
-            if (!step) {
-                ctl->current_chi = ctl->chi2_init = ctl->chi2_final = sc[0];
-                if (stop && *stop) { ctl->stopped = 1; ctl->done = 1; }
-                if (ctl->iters <= 0) ctl->done = 1;
-            } else {
-                lm_advance(ctl, sc, stop && *stop);
-            }
-        }
-        post_s = (ctl->done || notify) && mail;
+        if (te.ctl->done) post_s = te.mail != nullptr;
+        else post_s = trial_decide(te, te.out[0], te.out[1], trial_fail(te), trial_stopped(te), /*records=*/false);
     }
-    __syncthreads();
-    end_slot(ctl, mail, post_s != 0, threadIdx.x, blockDim.x, step != 0);
+    trial_close(te, &post_s);
 }
 
 // start of an optimize() call: fresh controller block
@@ -2625,32 +2613,34 @@ __global__ __launch_bounds__(kBlock) void k3_update(Cam3 cam, int L, double lamb
     }
 }
 
+// the pose part of computeScale() of the 6-DoF models (SE3-expmap, pose graph): scale += x_p (lambda x_p + b_p) of one free
+// pose, term by term into the caller's running sum
+__device__ inline void scale6(const double* xp, const double* bp, double lambda, size_t p, double& scale) {
+    for (int r = 0; r < 6; ++r) scale += xp[6 * p + r] * (lambda * xp[6 * p + r] + bp[6 * p + r]);
+}
+
 // single block: sums the k3_update partials, adds the prior and odometry chi^2 at the trial poses and the pose part of
-// computeScale(), advances the LM controller (structure of k_finalize)
+// computeScale(), advances the LM controller (the end of a trial: trial_open ... trial_close)
 __global__ void k3_finalize(int nparts, const double* __restrict__ part, int P, const double* __restrict__ poses_a,
                             const double* __restrict__ poses_b, const uint8_t* __restrict__ fixed, const double* __restrict__ xp,
                             const double* __restrict__ bp, const uint8_t* __restrict__ prior_has,
                             const double* __restrict__ prior_meas, const double* __restrict__ prior_info, int O,
                             const int* __restrict__ o_i, const int* __restrict__ o_j, const double* __restrict__ o_meas,
-                            const double* __restrict__ o_info, double* __restrict__ out, volatile double* __restrict__ mail,
-                            double seq, BaCtl* __restrict__ ctl, int step, int notify, const volatile int* __restrict__ stop) {
-    __shared__ double sm[2][16];
+                            const double* __restrict__ o_info, TrialEnd te) {
+    __shared__ double sm[2 * 16];
     __shared__ int post_s;
-    if (ctl->done) {
-        end_slot(ctl, mail, notify != 0, threadIdx.x, blockDim.x, step != 0);
-        return;
-    }
-    const bool est_b = ctl->sel != 0;
-    const double* poses = (est_b != (step != 0)) ? poses_b : poses_a;   // trial poses with a step, the estimate without
-    const double lambda = ctl->lambda;
+    const TrialState ts = trial_open(te, 0.0);
+    if (!ts.live) return;
+    const double lambda = ts.lambda;
+    const bool step = te.step != 0;
+    const double* poses = (ts.est_b != step) ? poses_b : poses_a;   // k3_oplus has made the trial poses
     double chi = 0, scale = 0;
     for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
         chi += part[2 * i];
         scale += part[2 * i + 1];
     }
     for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        if (step && !fixed[p])
-            for (int r = 0; r < 6; ++r) scale += xp[6 * (size_t)p + r] * (lambda * xp[6 * (size_t)p + r] + bp[6 * (size_t)p + r]);
+        if (step && !fixed[p]) scale6(xp, bp, lambda, p, scale);
         if (prior_has[p]) {
             double e[6];
             se3_log(se3_mul(se3_load(prior_meas + 12 * (size_t)p), se3_inv(se3_load(poses + 12 * (size_t)p))), e);
@@ -2673,32 +2663,9 @@ __global__ void k3_finalize(int nparts, const double* __restrict__ part, int P, 
             chi += e[r] * v;
         }
     }
-    chi = wave_sum(chi);
-    scale = wave_sum(scale);
-    if ((threadIdx.x & 63) == 0) {
-        sm[0][threadIdx.x >> 6] = chi;
-        sm[1][threadIdx.x >> 6] = scale;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-            sm[0][0] += sm[0][w];
-            sm[1][0] += sm[1][w];
-        }
-        out[0] = sm[0][0]; out[1] = sm[1][0]; out[3] = 0;
-        if (!step) {
-            out[2] = 0;
-            ctl->current_chi = ctl->chi2_init = ctl->chi2_final = sm[0][0];
-            if (stop && *stop) { ctl->stopped = 1; ctl->done = 1; }
-            if (ctl->iters <= 0) ctl->done = 1;
-        } else {
-            const double sc[3] = {sm[0][0], sm[1][0], out[2]};
-            lm_advance(ctl, sc, stop && *stop);
-        }
-        post_s = (ctl->done || notify) && mail;
-    }
-    __syncthreads();
-    end_slot(ctl, mail, post_s != 0, threadIdx.x, blockDim.x, step != 0);
+    block_sum2(chi, scale, sm);
+    if (threadIdx.x == 0) post_s = trial_decide(te, chi, scale, trial_fail(te), trial_stopped(te), /*records=*/false);
+    trial_close(te, &post_s);
 }
 
 // =============================================================================================
@@ -2819,30 +2786,23 @@ __device__ inline double quad6(const double* W, const double* e) {
 }
 
 // chi^2 of the priors and of every EdgeSE3 at the trial poses (the estimate without a step), pose part of computeScale(),
-// LM decision.  edge_chi2 (nullable): chi2() per edge, in slot order.
+// LM decision.  edge_chi2 (nullable): chi2() per edge, in slot order; without a controller that is all the kernel gives.
 __global__ void k4_finalize(int P, int nedge, const double* __restrict__ poses_a, const double* __restrict__ poses_b,
                             const uint8_t* __restrict__ fixed, const double* __restrict__ xp, const double* __restrict__ bp,
                             const uint8_t* __restrict__ prior_has, const double* __restrict__ prior_meas,
                             const double* __restrict__ prior_info, const int* __restrict__ e_i, const int* __restrict__ e_j,
-                            const double* __restrict__ e_meas, const double* __restrict__ e_info, double* __restrict__ out,
-                            volatile double* __restrict__ mail, double seq, BaCtl* __restrict__ ctl, int step, int notify,
-                            const volatile int* __restrict__ stop, double* __restrict__ edge_chi2) {
-    __shared__ double sm[2][16];
+                            const double* __restrict__ e_meas, const double* __restrict__ e_info, TrialEnd te,
+                            double* __restrict__ edge_chi2) {
+    __shared__ double sm[2 * 16];
     __shared__ int post_s;
-    const double* poses = poses_a;
-    double lambda = 0;
-    if (ctl) {
-        if (ctl->done) {
-            end_slot(ctl, mail, notify != 0, threadIdx.x, blockDim.x, step != 0);
-            return;
-        }
-        poses = ((ctl->sel != 0) != (step != 0)) ? poses_b : poses_a;
-        lambda = ctl->lambda;
-    }
+    const TrialState ts = trial_open(te, 0.0);
+    if (!ts.live) return;
+    const double lambda = ts.lambda;
+    const bool step = te.step != 0;
+    const double* poses = (ts.est_b != step) ? poses_b : poses_a;   // k4_oplus has made the trial poses
     double chi = 0, scale = 0;
     for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        if (step && !fixed[p])
-            for (int r = 0; r < 6; ++r) scale += xp[6 * (size_t)p + r] * (lambda * xp[6 * (size_t)p + r] + bp[6 * (size_t)p + r]);
+        if (step && !fixed[p]) scale6(xp, bp, lambda, p, scale);
         if (prior_has[p]) {
             double e[6];
             to_mqt(iso_mul(se3_inv(se3_load(prior_meas + 12 * (size_t)p)), se3_load(poses + 12 * (size_t)p)), e);
@@ -2857,33 +2817,10 @@ __global__ void k4_finalize(int P, int nedge, const double* __restrict__ poses_a
         if (edge_chi2) edge_chi2[k] = c2;
         chi += c2;
     }
-    if (!ctl) return;
-    chi = wave_sum(chi);
-    scale = wave_sum(scale);
-    if ((threadIdx.x & 63) == 0) {
-        sm[0][threadIdx.x >> 6] = chi;
-        sm[1][threadIdx.x >> 6] = scale;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-            sm[0][0] += sm[0][w];
-            sm[1][0] += sm[1][w];
-        }
-        out[0] = sm[0][0]; out[1] = sm[1][0]; out[3] = 0;
-        if (!step) {
-            out[2] = 0;
-            ctl->current_chi = ctl->chi2_init = ctl->chi2_final = sm[0][0];
-            if (stop && *stop) { ctl->stopped = 1; ctl->done = 1; }
-            if (ctl->iters <= 0) ctl->done = 1;
-        } else {
-            const double sc[3] = {sm[0][0], sm[1][0], out[2]};
-            lm_advance(ctl, sc, stop && *stop);
-        }
-        post_s = (ctl->done || notify) && mail;
-    }
-    __syncthreads();
-    end_slot(ctl, mail, post_s != 0, threadIdx.x, blockDim.x, step != 0);
+    if (!te.ctl) return;
+    block_sum2(chi, scale, sm);
+    if (threadIdx.x == 0) post_s = trial_decide(te, chi, scale, trial_fail(te), trial_stopped(te), /*records=*/false);
+    trial_close(te, &post_s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4683,14 +4620,17 @@ CholArgs chol_args(se2gpu_ba* h, const BaCtl* ctl, int skip, unsigned long long*
                     flagA, flagA + kSlabs * (size_t)nt * nbc, &h->ctl.p->epoch, ba_scal(h) + 2, h->chol_trace.p, ctl, h->xp.p,
                     verify ? h->chol_vfy.p : nullptr, head, h->chol_ntask - skip};
 }
-// The end of a trial (finish_trial in k_update's last workgroup, or k_finalize).  With the controller (B.c) it takes the
-// decision when `decide` is set and reads the force-stop word; `lin`: the landmark workgroups are k_update<true>'s; post = false:
-// no mailbox (the scalars of a synchronous sharded evaluation are posted behind the all-reduce, k_post_mail).
-FinArgs fin_args(se2gpu_ba* h, const Bufs& B, const double* xp, int step, int decide, int notify, double seq, bool lin = false,
-                 bool post = true) {
-    return FinArgs{1, (int)upd_grid(h).x, h->P, h->O, h->root, step, decide, notify, h->fixed.p, xp, h->bp.p, B.pa, B.pb,
-                   h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, ba_scal(h), post ? h->d_mail : nullptr, seq, B.c ? h->ctl.p : nullptr,
-                   B.c ? (const volatile int*)h->d_stop : nullptr, h->fin_counter.p, lin ? 1 : 0};
+// The end of a trial, whichever kernel runs it (TrialEnd).  With the controller (B.c) the kernel takes the decision when
+// `decide` is set and reads the force-stop word; `lin`: the landmark workgroups are k_update<true>'s; post = false: no mailbox
+// (the scalars of a synchronous sharded evaluation are posted behind the all-reduce, k_post_mail).
+TrialEnd trial_end(se2gpu_ba* h, const Bufs& B, int step, int decide, int notify, double seq, bool lin = false, bool post = true) {
+    return TrialEnd{ba_scal(h), post ? h->d_mail : nullptr, seq, B.c ? h->ctl.p : nullptr,
+                    B.c ? (const volatile int*)h->d_stop : nullptr, step, decide, notify, lin ? 1 : 0};
+}
+// The end of an SE(2) trial (finish_trial in k_update's last workgroup, or k_finalize)
+FinArgs fin_args(se2gpu_ba* h, const Bufs& B, const double* xp, const TrialEnd& te) {
+    return FinArgs{1, (int)upd_grid(h).x, h->P, h->O, h->root, h->fixed.p, xp, h->bp.p, B.pa, B.pb,
+                   h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, h->fin_counter.p, te};
 }
 // xp == nullptr evaluates the state; fin = FinArgs{} when k_finalize ends the trial; lin: k_update<true>'s record sets
 UpdArgs upd_args(se2gpu_ba* h, const Bufs& B, double lambda, const double* xp, const FinArgs& fin, bool lin = false) {
@@ -4889,13 +4829,14 @@ int ba_evaluate(se2gpu_ba* h, const double* xp, double lambda) {
     const Bufs B = bufs(h, false);
     if (use_mail) {   // single GPU: the trial ends inside k_update (FinArgs)
         SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, dim3(ug.x + 1), dim3(kBlock), 0,
-                   upd_args(h, B, lambda, xp, fin_args(h, B, xp, xp ? 1 : 0, 0, 0, seq)));
+                   upd_args(h, B, lambda, xp, fin_args(h, B, xp, trial_end(h, B, xp ? 1 : 0, 0, 0, seq))));
         SE2_HIP(hipGetLastError());
         return ba_wait_mail(h, seq);
     }
     SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, ug, dim3(kBlock), 0, upd_args(h, B, lambda, xp, FinArgs{}));
-    SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, fin_args(h, B, xp, xp ? 1 : 0, 0, 0, seq, false, /*post=*/false),
-               h->L ? h->nparts : 0, (const double*)h->part.p, lambda);
+    SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0,
+               fin_args(h, B, xp, trial_end(h, B, xp ? 1 : 0, 0, 0, seq, false, /*post=*/false)), h->L ? h->nparts : 0,
+               (const double*)h->part.p, lambda);
     SE2_HIP(hipGetLastError());
     SE2_CHECK(ba_allreduce(h, scal, 4));
     if (h->d_mail) {
@@ -5023,13 +4964,13 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
     double* scal = ba_scal(h);
     const Bufs B = bufs(h, true);
     auto evaluate = [&](bool step, bool note) -> int {
+        auto te = [&](int decide, bool lin = false) { return trial_end(h, B, step ? 1 : 0, decide, note ? 1 : 0, seq, lin); };
         if (h->model == 2) {
             if (step)
                 SE2_LAUNCH(h->prof, st, "k4_oplus", k4_oplus, grid1(h->P, 64), dim3(64), 0, h->P, B.pa, h->fixed.p, h->xp.p, B.pb, B.c);
             SE2_LAUNCH(h->prof, st, "k4_finalize", k4_finalize, dim3(1), dim3(1024), 0, h->P, h->pg_edges, B.pa, B.pb, h->fixed.p,
                        h->xp.p, h->bp.p, h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->pe_i.p, h->pe_j.p, h->pe_meas.p,
-                       h->pe_info.p, scal, h->d_mail, seq, h->ctl.p, step ? 1 : 0, note ? 1 : 0, (const volatile int*)h->d_stop,
-                       (double*)nullptr);
+                       h->pe_info.p, te(1), (double*)nullptr);
             SE2_HIP(hipGetLastError());
             return SE2GPU_OK;
         }
@@ -5041,8 +4982,7 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
                        B.lb, h->part.p, B.c, step ? 1 : 0, (double*)nullptr);
             SE2_LAUNCH(h->prof, st, "k3_finalize", k3_finalize, dim3(1), dim3(1024), 0, h->L ? h->nparts : 0, h->part.p, h->P,
                        B.pa, B.pb, h->fixed.p, h->xp.p, h->bp.p, h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->O,
-                       h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, scal, h->d_mail, seq, h->ctl.p, step ? 1 : 0, note ? 1 : 0,
-                       (const volatile int*)h->d_stop);
+                       h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, te(1));
             SE2_HIP(hipGetLastError());
             return SE2GPU_OK;
         }
@@ -5051,7 +4991,7 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
         if (!sharded) {   // the trial ends inside k_update (FinArgs): no kernel boundary before the controller's decision
             // a step of a speculating run also linearises the trial state (k_update<true>); the evaluation of the start does not
             const bool lin = step && h->run_spec;
-            const UpdArgs ua = upd_args(h, B, 0.0, xp, fin_args(h, B, h->xp.p, step ? 1 : 0, 1, note ? 1 : 0, seq, lin), lin);
+            const UpdArgs ua = upd_args(h, B, 0.0, xp, fin_args(h, B, h->xp.p, te(1, lin)), lin);
             if (lin) SE2_LAUNCH(h->prof, st, "k_update_lin", k_update<true>, dim3(ug.x + 1), dim3(kBlock), 0, ua);
             else SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, dim3(ug.x + 1), dim3(kBlock), 0, ua);
             SE2_HIP(hipGetLastError());
@@ -5059,12 +4999,11 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
         }
         SE2_LAUNCH(h->prof, st, "k_update", k_update<false>, ug, dim3(kBlock), 0, upd_args(h, B, 0.0, xp, FinArgs{}));
         // (the decision of a sharded run is k_lm_decide's, behind the all-reduce)
-        SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, fin_args(h, B, h->xp.p, step ? 1 : 0, 0, note ? 1 : 0, seq),
+        SE2_LAUNCH(h->prof, st, "k_finalize", k_finalize, dim3(1), dim3(1024), 0, fin_args(h, B, h->xp.p, te(0)),
                    h->L ? h->nparts : 0, (const double*)h->part.p, 0.0);
         if (sharded) {
             SE2_CHECK(ba_allreduce(h, scal, 4));
-            hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), 0, st, h->ctl.p, scal, step ? 1 : 0, note ? 1 : 0,
-                               h->d_mail, seq, (const volatile int*)h->d_stop);
+            hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(256), 0, st, te(1));
         }
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
@@ -5273,9 +5212,9 @@ int ba_build_batch_plan(BatchPlan& bp, se2gpu_ba** hs, int count, int iters, int
         const Bufs B = bufs(h, true);
         const int ug = (int)upd_grid(h).x;
         bp.ctl_init.add(1, CtlInitArgs{h->ctl.p, iters, mode});
-        bp.eval0.add(ug + 1, upd_args(h, B, 0.0, nullptr, fin_args(h, B, h->xp.p, 0, 1, 0, 0.0)));
-        bp.step.add(ug + 1, upd_args(h, B, 0.0, h->xp.p, fin_args(h, B, h->xp.p, 1, 1, 0, 0.0)));
-        bp.step_notify.add(ug + 1, upd_args(h, B, 0.0, h->xp.p, fin_args(h, B, h->xp.p, 1, 1, 1, 0.0)));
+        bp.eval0.add(ug + 1, upd_args(h, B, 0.0, nullptr, fin_args(h, B, h->xp.p, trial_end(h, B, 0, 1, 0, 0.0))));
+        bp.step.add(ug + 1, upd_args(h, B, 0.0, h->xp.p, fin_args(h, B, h->xp.p, trial_end(h, B, 1, 1, 0, 0.0))));
+        bp.step_notify.add(ug + 1, upd_args(h, B, 0.0, h->xp.p, fin_args(h, B, h->xp.p, trial_end(h, B, 1, 1, 1, 0.0))));
         bp.lin0.add(ug, lin_args(h, B, 0.0, RecSet{}));
         bp.lin.add(ug, lin_args(h, B, 0.0, RecSet{}));
         bp.odo.add(h->O ? (int)grid1(h->O, 64).x : 0, odo_args(h, nullptr, true));
@@ -5731,8 +5670,7 @@ int se2gpu_ba_edge_chi2(se2gpu_ba* h, double* chi2, int cap) {
         if (!NE) return SE2GPU_OK;
         hipLaunchKernelGGL(k4_finalize, dim3(1), dim3(1024), 0, st, h->P, NE, h->poses, h->poses_t, h->fixed.p, h->xp.p, h->bp.p,
                            h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->pe_i.p, h->pe_j.p, h->pe_meas.p, h->pe_info.p,
-                           (double*)nullptr, (volatile double*)nullptr, 0.0, (BaCtl*)nullptr, 0, 0, (const volatile int*)nullptr,
-                           h->edge_chi2.p);
+                           trial_end(h, bufs(h, false), 0, 0, 0, 0.0, false, /*post=*/false), h->edge_chi2.p);
         SE2_HIP(hipGetLastError());
         std::vector<double> tmp(NE);
         SE2_HIP(hipMemcpyAsync(tmp.data(), h->edge_chi2.p, (size_t)NE * 8, hipMemcpyDeviceToHost, st));

@@ -167,6 +167,15 @@ __device__ inline void pre_se2(const double* pi, const double* pj, const double*
     B[0] = c; B[1] = s; B[3] = -s; B[4] = c; B[8] = 1;
 }
 
+// The evaluation of the starting state, in front of the first trial (computeActiveErrors + activeRobustChi2 before iteration 0),
+// by the thread that will run lm_advance: its chi^2 is the run's current, initial and - if no iteration follows - final cost; a
+// raised force-stop flag or a run of zero iterations ends the run here.
+__device__ inline void lm_begin(BaCtl* c, double chi, bool stopped) {
+    c->current_chi = c->chi2_init = c->chi2_final = chi;
+    if (stopped) { c->stopped = 1; c->done = 1; }
+    if (c->iters <= 0) c->done = 1;
+}
+
 // One step of g2o's OptimizationAlgorithmLevenberg::solve / OptimizationAlgorithmGaussNewton on the controller block, run
 // by ONE thread after the (all-reduced) scalars of a trial are known:  sc = {chi2 of the trial state, computeScale()
 // denominator, factorisation flag}.  Mirrors, statement for statement, the host loop this replaces

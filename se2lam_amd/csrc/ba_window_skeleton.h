@@ -499,9 +499,7 @@ __device__ __forceinline__ void window_lm(const typename M::Args& a, WindowShare
             for (int i = tid; i < n; i += NT) dm = fmax(dm, fabs(xs[i]));
         wg_reduce<NT>(red, chi, sc, dm);
         if (tid == 0) {
-            ctl.current_chi = ctl.chi2_init = ctl.chi2_final = chi;
-            if (s_stop) { ctl.stopped = 1; ctl.done = 1; }
-            if (ctl.iters <= 0) ctl.done = 1;
+            lm_begin(&ctl, chi, s_stop != 0);
             if (lm && !ctl.done) { ctl.lambda = 1e-5 * dm; ctl.ni = 2; }
         }
         __syncthreads();

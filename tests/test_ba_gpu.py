@@ -199,13 +199,16 @@ def test_landmark_sharded_lm_schedule_on_a_start_that_rejects(synth):
     _sharded_equals_single(_kidnapped(synth, *case), 10, trials)
 
 
-def _sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None):
+def _sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None, stop=None):
     """`world` landmark shards as `world` handles on `world` threads of ONE GPU; the all-reduce callback (no caller-owned
     buffer, so the library hands it the PACKED exchange: the lower-triangular tiles of [S; b^T], se2gpu_ba_exchange_doubles)
-    sums the ranks' buffers on the host.  Same collective pattern as the RCCL path, which takes this buffer too."""
+    sums the ranks' buffers on the host.  Same collective pattern as the RCCL path, which takes this buffer too.
+    `stop`: a force-stop flag every handle polls (a raised one ends the runs before any system is exchanged).  Returns the single
+    handle and the ranks' (stats, estimates)."""
     from se2lam_amd import capi
     from se2lam_amd.optimizer import SlamOptimizer
     single = _opt(g)
+    single.setForceStopFlag(stop)
     single.optimize(iters)
     if trials is not None:
         assert single.stats["trials_hist"] == trials
@@ -246,6 +249,7 @@ def _sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None):
             o.set_allreduce(make_cb(rank))
             o.load(g.shard(rank, world))
             o.initializeOptimization(0)
+            o.setForceStopFlag(stop)
             assert o.exchange_doubles() == packed     # every rank chose the single handle's order
             if debug_lam is not None:                 # the debug entry points are collectives too
                 dbg[rank] = (o.reduced_system(debug_lam), o.solve(debug_lam))
@@ -268,7 +272,7 @@ def _sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None):
         assert np.allclose(poses, single.estimates()[0], rtol=1e-8, atol=1e-8)
         assert np.array_equal(poses, results[0][1][0])  # replicated poses stay bit-identical across the ranks
         # the system exchange went through the packed triangle (the other exchanges are 4 scalars / world slots / 3P diagonals)
-        assert packed in counts[r] and (packed >= rect or debug_lam is not None or not any(c >= rect for c in counts[r])), sorted(counts[r])
+        assert stop is not None or packed in counts[r] and (packed >= rect or debug_lam is not None or not any(c >= rect for c in counts[r])), sorted(counts[r])
     if debug_lam is not None:   # se2gpu_ba_debug_reduced_system / _solve on a sharded handle whose poses were re-ordered
         fresh = _opt(g)
         S0, b0 = fresh.reduced_system(debug_lam)
@@ -284,6 +288,7 @@ def _sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None):
         own = g.shard_landmarks(r, world)
         lms[own] = results[r][1][1]
     assert np.allclose(lms, single.estimates()[1], rtol=1e-8, atol=1e-6)
+    return single, results
 
 
 @pytest.mark.gpu
