@@ -190,6 +190,35 @@ int se2gpu_search_by_bow(se2gpu_matcher* h,
                          const uint8_t* has_mp2,
                          int mp_only, float nnratio, int check_orientation, int32_t* matches12, int* n_matches);
 
+/* Batched device-resident SearchByBoW over `npairs` independent key-frame pairs: pair p is SearchByBoW(frame a[p],
+ * frame b[p], .., mp_only) with ORBmatcher(nnratio, check_orientation).  Every pointer is device memory.  The frame arrays
+ * are the ones se2gpu_orb_extract_batch_device writes (d_kps from f * cap, d_desc from f * cap * 32, d_counts[f]); the
+ * feature vectors are the CSR se2gpu_bow_transform_batch_device writes (d_fv_nodes from f * cap, ascending; d_fv_ptr from
+ * f * (cap + 1); d_fv_idx from f * cap; d_fv_nn[f]).  d_has_mp: nframes * cap bytes, 1 = the feature has a non-null map
+ * point; read only when mp_only != 0 and may be NULL otherwise.  Row p of d_matches12 holds cap ints: entry i < counts[a[p]]
+ * is the index into frame b[p] or -1, every entry from counts[a[p]] on is -1; d_nmatches[p] is the reference's return value.
+ * The kernels never index outside the arrays, whatever the arrays hold: counts and nn are clamped to 0..cap, ptr values to
+ * 0..cap, a segment whose end lies before its start is empty, a feature index outside the frame is skipped, and a pair that
+ * names a frame outside 0..nframes-1 gives an all -1 row and count 0.
+ * Asynchronous on the matcher's stream, as se2gpu_match_window_batch_device is: no read-back and no synchronise inside the
+ * call; se2gpu_matcher_sync waits for it.  Ordering against the transform that writes the feature vectors is the caller's
+ * job: se2gpu_matcher_set_stream(h, se2gpu_bow_stream(ctx)) puts both on one stream, or sync the context first.
+ * The scratch (node pairs, their number, rotation bins and the 30 histogram counters of every pair) lives in the handle,
+ * grows from npairs and cap alone and is reused by the next call.
+ * SE2GPU_ERR_INVALID: a NULL handle or required pointer, npairs / cap / nframes < 1, mp_only != 0 without d_has_mp.
+ * SE2GPU_ERR_CAPACITY: cap > 65536 - the vbMatched2 flags of a vocabulary node, one LDS byte per feature of frame b, take
+ * `cap` rounded up to 64 bytes of the 64 KiB a workgroup gets without opting in (the transform's own limit is 4096); or
+ * npairs > 65535, the pairs being one dimension of a launch. */
+int se2gpu_search_by_bow_batch_device(se2gpu_matcher* h,
+                                      const se2gpu_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_counts, int cap,
+                                      int nframes,
+                                      const int32_t* d_fv_nodes, const int32_t* d_fv_ptr, const int32_t* d_fv_idx,
+                                      const int32_t* d_fv_nn,
+                                      const uint8_t* d_has_mp,
+                                      const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs,
+                                      int mp_only, float nnratio, int check_orientation,
+                                      int32_t* d_matches12, int32_t* d_nmatches);
+
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by
  *   LocalMapper::localBA          /root/reference/src/LocalMapper.cpp:232-302
@@ -601,7 +630,7 @@ void* se2gpu_bow_stream(se2gpu_bow* h);
 /* transform(.., levelsup) of nframes frames whose descriptors lie where se2gpu_orb_extract_batch_device wrote them
  * (d_desc: nframes * cap * 32 bytes, 16-byte aligned; d_counts: nframes ints, clamped to 0..cap).  Outputs of frame f, all
  * device memory: the BowVector d_bow_word (u32) / d_bow_value (f64) from f * cap, ascending word id, d_bow_n[f] words; the
- * FeatureVector as the CSR se2gpu_search_by_bow takes - d_fv_nodes from f * cap (ascending node ids of the file), d_fv_ptr
+ * FeatureVector as the CSR se2gpu_search_by_bow takes (se2gpu_search_by_bow_batch_device reads it where it lies) - d_fv_nodes from f * cap (ascending node ids of the file), d_fv_ptr
  * from f * (cap + 1), d_fv_idx from f * cap (ascending within a node), d_fv_nn[f] nodes.  A feature on a word of weight 0
  * is in neither vector; the node of a feature is its ancestor at level L - levelsup (the root when that is not positive,
  * the leaf when the leaf lies above that level); an empty frame gives empty vectors.  Asynchronous on the context's stream. */

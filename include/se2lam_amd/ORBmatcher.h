@@ -5,6 +5,8 @@
 //   int MatchByProjection(pNewKF, localMPs, winSize, levelOffset, vMatchesIdxMP)                  (:73-74)
 //   int SearchByBoW(pKF1, pKF2, mapIdxMatches12, bIfMPOnly=true)                                 (:55)
 //   void ComputeThreeMaxima(histo, L, ind1, ind2, ind3)                                          (:57)
+// and, with no counterpart in the reference, SearchByBoWBatchDevice: SearchByBoW for a batch of pairs of key frames that lie
+// in device memory (DeviceFrameSet / DeviceFeatureVectorSet below).
 // Frame / KeyFrame / MapPoint are pointer-graph classes of the reference's data model (out of scope); the adapters
 // take the POD content the matchers actually read from them (FrameView / MapPointView below) - INTEGRATION.md shows
 // the three-line glue that fills the views from the reference's classes.
@@ -34,6 +36,23 @@ struct FeatureVectorView {               // DBoW2::FeatureVector (std::map<NodeI
     const int32_t* idx = nullptr;            // feature indices
     int numNodes = 0;
     const uint8_t* hasMapPoint = nullptr;    // per feature: GetMapPointMatches()[i] non-null (read only if bIfMPOnly)
+};
+
+// A batch of key frames in device memory, as se2gpu_orb_extract_batch_device writes them (SearchByBoWBatchDevice)
+struct DeviceFrameSet {
+    const KeyPoint* kps = nullptr;           // frame f from f * cap
+    const uint8_t* desc = nullptr;           // frame f from f * cap * 32
+    const int32_t* counts = nullptr;         // nframes
+    int cap = 0, nframes = 0;
+};
+
+// Their DBoW2::FeatureVectors in device memory, as se2gpu_bow_transform_batch_device writes them
+struct DeviceFeatureVectorSet {
+    const int32_t* nodes = nullptr;          // frame f from f * cap, ascending node ids
+    const int32_t* ptr = nullptr;            // frame f from f * (cap + 1)
+    const int32_t* idx = nullptr;            // frame f from f * cap
+    const int32_t* nn = nullptr;             // nframes: nodes of frame f
+    const uint8_t* hasMapPoint = nullptr;    // nframes * cap bytes (read only if bIfMPOnly; may stay null otherwise)
 };
 
 struct MapPointView {                    // what MatchByProjection reads from localMPs[i]
@@ -115,6 +134,22 @@ public:
             if (dense[i] >= 0) mapIdxMatches12[i] = dense[i];
         return n;
     }
+
+    // SearchByBoW(frame a[p], frame b[p], .., bIfMPOnly) for npairs pairs of device-resident key frames
+    // (se2gpu_search_by_bow_batch_device): d_matches12 gets npairs rows of frames.cap ints, d_nmatches the npairs return
+    // values.  Every pointer is device memory; asynchronous on the matcher's stream - sync() before the outputs are read,
+    // setStream(the vocabulary context's stream) to run behind the transform that writes the feature vectors.
+    void SearchByBoWBatchDevice(const DeviceFrameSet& frames, const DeviceFeatureVectorSet& fvs, const int32_t* d_pair_a,
+                                const int32_t* d_pair_b, int npairs, int32_t* d_matches12, int32_t* d_nmatches,
+                                bool bIfMPOnly = true) {
+        check(se2gpu_search_by_bow_batch_device(h_, reinterpret_cast<const se2gpu_keypoint*>(frames.kps), frames.desc,
+                                                frames.counts, frames.cap, frames.nframes, fvs.nodes, fvs.ptr, fvs.idx, fvs.nn, fvs.hasMapPoint, d_pair_a, d_pair_b,
+                                                npairs, bIfMPOnly ? 1 : 0, mfNNratio, mbCheckOrientation ? 1 : 0,
+                                                d_matches12, d_nmatches),
+              "ORBmatcher::SearchByBoWBatchDevice");
+    }
+    void sync() { check(se2gpu_matcher_sync(h_), "ORBmatcher::sync"); }
+    void setStream(void* hipStream) { check(se2gpu_matcher_set_stream(h_, hipStream), "ORBmatcher::setStream"); }
 
     // void ComputeThreeMaxima(std::vector<int>* histo, const int L, int& ind1, int& ind2, int& ind3) (ORBmatcher.h:57): a
     // public member in the reference; the device resolve kernels run the same function (se2gpu_three_maxima)

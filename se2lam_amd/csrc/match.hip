@@ -702,24 +702,24 @@ __global__ __launch_bounds__(1024) void k_resolve_projection(const se2gpu_keypoi
 // (idx1 in list order; best / second best over the still unmatched idx2 of the node by wave-ballot arg-min);
 // nodes run in parallel.  The rotation histogram is global (30 atomic counters).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_bow_match(const int2* __restrict__ node_pairs, const int* __restrict__ ptr1,
-                                                   const int* __restrict__ idx1s, const int* __restrict__ ptr2,
-                                                   const int* __restrict__ idx2s, const se2gpu_keypoint* __restrict__ kps1,
-                                                   const uint8_t* __restrict__ desc1, const uint8_t* __restrict__ has1,
-                                                   const se2gpu_keypoint* __restrict__ kps2,
-                                                   const uint8_t* __restrict__ desc2, const uint8_t* __restrict__ has2,
-                                                   int mp_only, float nnratio, int check_ori, int* __restrict__ matches12,
-                                                   int* __restrict__ bin_of, int* __restrict__ hist) {
-    extern __shared__ unsigned char matched2[];   // vbMatched2 of this node's features: sized by the host to the largest node
+// The reference's loop over one pair of equal nodes (ORBmatcher.cpp:168-240), run by one wave: the features [a0, a1) of
+// idx1s against the features [b0, b1) of idx2s.  matched2 = vbMatched2 of this node's features in LDS, b1 - b0 bytes.
+// A feature index outside 0..n1-1 / 0..n2-1 is skipped, so the function never reads outside the frames' arrays.
+__device__ __forceinline__ void bow_match_node(int a0, int a1, int b0, int b1, const int* __restrict__ idx1s,
+                                               const int* __restrict__ idx2s, const se2gpu_keypoint* __restrict__ kps1,
+                                               const uint8_t* __restrict__ desc1, const uint8_t* __restrict__ has1, int n1,
+                                               const se2gpu_keypoint* __restrict__ kps2, const uint8_t* __restrict__ desc2,
+                                               const uint8_t* __restrict__ has2, int n2, int mp_only, float nnratio,
+                                               int check_ori, int* __restrict__ matches12, int* __restrict__ bin_of,
+                                               int* __restrict__ hist, unsigned char* matched2) {
     const int lane = threadIdx.x;
-    const int2 np = node_pairs[blockIdx.x];
-    const int a0 = ptr1[np.x], a1 = ptr1[np.x + 1], b0 = ptr2[np.y], b1 = ptr2[np.y + 1];
     const int m2 = b1 - b0;
     for (int i = lane; i < m2; i += 64) matched2[i] = 0;
     __syncthreads();
     const float factor = (float)kHisto / 360.0f;
     for (int i1 = a0; i1 < a1; ++i1) {
         const int idx1 = idx1s[i1];
+        if ((unsigned)idx1 >= (unsigned)n1) continue;
         if (mp_only && !has1[idx1]) continue;
         const uint8_t* d1 = desc1 + 32 * (size_t)idx1;
         Best2 b{INT_MAX, -1, INT_MAX, -1};
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(64) void k_bow_match(const int2* __restrict__ node_
             int dist = 0;
             if (pos < m2) {
                 const int idx2 = idx2s[b0 + pos];
-                valid = !(mp_only && !has2[idx2]) && !matched2[pos];
+                valid = (unsigned)idx2 < (unsigned)n2 && !(mp_only && !has2[idx2]) && !matched2[pos];
                 if (valid) dist = hamming256(d1, desc2 + 32 * (size_t)idx2);
             }
             const int l1 = wave_argmin(valid, dist);
@@ -749,7 +749,7 @@ __global__ __launch_bounds__(64) void k_bow_match(const int2* __restrict__ node_
                     int bin = (int)roundf(rot * factor);
                     if (bin == kHisto) bin = 0;
                     bin_of[idx1] = bin;
-                    atomicAdd(&hist[bin], 1);
+                    if ((unsigned)bin < (unsigned)kHisto) atomicAdd(&hist[bin], 1);   // (angles outside 0..360: no counter)
                 }
             }
         }
@@ -757,8 +757,11 @@ __global__ __launch_bounds__(64) void k_bow_match(const int2* __restrict__ node_
     }
 }
 
-__global__ void k_bow_finish(int n1, int check_ori, const int* __restrict__ bin_of, const int* __restrict__ hist,
-                             int* __restrict__ matches12, int* __restrict__ nmatches) {
+// The end of SearchByBoW (ORBmatcher.cpp:255-275), run by one workgroup: the matches outside the three fullest rotation
+// bins are erased, the rest counted.
+__device__ __forceinline__ void bow_finish(int n1, int check_ori, const int* __restrict__ bin_of,
+                                           const int* __restrict__ hist, int* __restrict__ matches12,
+                                           int* __restrict__ nmatches) {
     __shared__ int s_ind[3];
     __shared__ int s_cnt;
     if (threadIdx.x == 0) {
@@ -779,6 +782,125 @@ __global__ void k_bow_finish(int n1, int check_ori, const int* __restrict__ bin_
     atomicAdd(&s_cnt, cnt);
     __syncthreads();
     if (threadIdx.x == 0) nmatches[0] = s_cnt;
+}
+
+// host-buffer path (se2gpu_search_by_bow): one wave per pair of equal nodes, the list merged on the host
+__global__ __launch_bounds__(64) void k_bow_match(const int2* __restrict__ node_pairs, const int* __restrict__ ptr1,
+                                                   const int* __restrict__ idx1s, const int* __restrict__ ptr2,
+                                                   const int* __restrict__ idx2s, const se2gpu_keypoint* __restrict__ kps1,
+                                                   const uint8_t* __restrict__ desc1, const uint8_t* __restrict__ has1, int n1,
+                                                   const se2gpu_keypoint* __restrict__ kps2,
+                                                   const uint8_t* __restrict__ desc2, const uint8_t* __restrict__ has2, int n2,
+                                                   int mp_only, float nnratio, int check_ori, int* __restrict__ matches12,
+                                                   int* __restrict__ bin_of, int* __restrict__ hist) {
+    extern __shared__ unsigned char matched2[];   // vbMatched2 of this node's features: sized by the host to the largest node
+    const int2 np = node_pairs[blockIdx.x];
+    bow_match_node(ptr1[np.x], ptr1[np.x + 1], ptr2[np.y], ptr2[np.y + 1], idx1s, idx2s, kps1, desc1, has1, n1, kps2, desc2,
+                   has2, n2, mp_only, nnratio, check_ori, matches12, bin_of, hist, matched2);
+}
+
+__global__ void k_bow_finish(int n1, int check_ori, const int* __restrict__ bin_of, const int* __restrict__ hist,
+                             int* __restrict__ matches12, int* __restrict__ nmatches) {
+    bow_finish(n1, check_ori, bin_of, hist, matches12, nmatches);
+}
+
+// ---------------------------------------------------------------------------------------------
+// SearchByBoW over a batch of key-frame pairs whose frames and feature vectors lie in HBM
+// (se2gpu_search_by_bow_batch_device).  Three launches, none waits on another workgroup:
+//   k_bow_pair_nodes    one workgroup per pair: the merge of the two ascending node lists (a binary search per node of
+//                       frame a) -> the pair's list of equal nodes; clears the pair's outputs and scratch
+//   k_bow_match_batch   grid (kBowWaves, npairs), one wave each: wave w takes node pairs w, w + kBowWaves, ..
+//   k_bow_finish_batch  one workgroup per pair: three maxima of the pair's histogram, erase, count
+// Whatever the device arrays hold, no kernel indexes outside them: counts and nn are clamped to 0..cap, ptr values to
+// 0..cap with a descending segment taken as empty, feature indices outside the frame are skipped (bow_match_node), and a
+// pair that names a frame outside 0..nframes-1 gets no node pairs and n1 = 0.
+// ---------------------------------------------------------------------------------------------
+constexpr int kBowWaves = 128;     // waves per key-frame pair: the reference's levelsup = 4 gives about 100 node pairs
+constexpr int kBowHistStride = 32; // the 30 counters of a pair, padded
+
+struct BowFrames {   // the device-resident frame set and its feature vectors, as the extractor and the transform write them
+    const se2gpu_keypoint* kps;
+    const uint8_t* desc;
+    const int* counts;
+    const int* fv_nodes;
+    const int* fv_ptr;
+    const int* fv_idx;
+    const int* fv_nn;
+    const uint8_t* has_mp;   // NULL unless mp_only
+    int cap, nframes;
+};
+
+__device__ __forceinline__ int clamp_cap(int v, int cap) { return min(max(v, 0), cap); }
+
+__global__ __launch_bounds__(256) void k_bow_pair_nodes(BowFrames fr, const int* __restrict__ pair_a,
+                                                        const int* __restrict__ pair_b, int2* __restrict__ node_pairs,
+                                                        int* __restrict__ n_node_pairs, int* __restrict__ matches12,
+                                                        int* __restrict__ bin_of, int* __restrict__ hist) {
+    __shared__ int s_n;
+    const int p = blockIdx.x, tid = threadIdx.x, cap = fr.cap;
+    const size_t row = (size_t)p * cap;
+    for (int i = tid; i < cap; i += blockDim.x) {
+        matches12[row + i] = -1;
+        bin_of[row + i] = -1;
+    }
+    if (tid < kBowHistStride) hist[(size_t)p * kBowHistStride + tid] = 0;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    const int fa = pair_a[p], fb = pair_b[p];
+    if ((unsigned)fa < (unsigned)fr.nframes && (unsigned)fb < (unsigned)fr.nframes) {
+        const int nna = clamp_cap(fr.fv_nn[fa], cap), nnb = clamp_cap(fr.fv_nn[fb], cap);
+        const int* na = fr.fv_nodes + (size_t)fa * cap;
+        const int* nb = fr.fv_nodes + (size_t)fb * cap;
+        for (int i = tid; i < nna; i += blockDim.x) {
+            const int node = na[i];
+            int lo = 0, hi = nnb;   // first j with nb[j] >= node
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (nb[mid] < node) lo = mid + 1; else hi = mid;
+            }
+            if (lo < nnb && nb[lo] == node) node_pairs[row + atomicAdd(&s_n, 1)] = make_int2(i, lo);   // at most nna <= cap hits
+        }
+    }
+    __syncthreads();
+    if (tid == 0) n_node_pairs[p] = s_n;
+}
+
+__global__ __launch_bounds__(64) void k_bow_match_batch(BowFrames fr, const int* __restrict__ pair_a,
+                                                         const int* __restrict__ pair_b, const int2* __restrict__ node_pairs,
+                                                         const int* __restrict__ n_node_pairs, int mp_only, float nnratio,
+                                                         int check_ori, int* __restrict__ matches12, int* __restrict__ bin_of,
+                                                         int* __restrict__ hist) {
+    extern __shared__ unsigned char matched2[];   // vbMatched2 of one node's features: a node holds at most cap of them
+    const int p = blockIdx.y, cap = fr.cap;
+    const int nnp = min(n_node_pairs[p], cap);
+    if ((int)blockIdx.x >= nnp) return;
+    const int fa = pair_a[p], fb = pair_b[p];     // inside 0..nframes-1: the pair has node pairs
+    const int n1 = clamp_cap(fr.counts[fa], cap), n2 = clamp_cap(fr.counts[fb], cap);
+    const int* ptr1 = fr.fv_ptr + (size_t)fa * (cap + 1);
+    const int* ptr2 = fr.fv_ptr + (size_t)fb * (cap + 1);
+    const size_t row = (size_t)p * cap;
+    for (int k = blockIdx.x; k < nnp; k += gridDim.x) {
+        const int2 np = node_pairs[row + k];
+        const int a0 = clamp_cap(ptr1[np.x], cap), a1 = max(a0, clamp_cap(ptr1[np.x + 1], cap));
+        const int b0 = clamp_cap(ptr2[np.y], cap), b1 = max(b0, clamp_cap(ptr2[np.y + 1], cap));
+        bow_match_node(a0, a1, b0, b1, fr.fv_idx + (size_t)fa * cap, fr.fv_idx + (size_t)fb * cap,
+                       fr.kps + (size_t)fa * cap, fr.desc + (size_t)fa * cap * 32, mp_only ? fr.has_mp + (size_t)fa * cap : nullptr,
+                       n1, fr.kps + (size_t)fb * cap, fr.desc + (size_t)fb * cap * 32,
+                       mp_only ? fr.has_mp + (size_t)fb * cap : nullptr, n2, mp_only, nnratio, check_ori, matches12 + row,
+                       bin_of + row, hist + (size_t)p * kBowHistStride, matched2);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bow_finish_batch(BowFrames fr, const int* __restrict__ pair_a,
+                                                          const int* __restrict__ pair_b, int check_ori,
+                                                          const int* __restrict__ bin_of, const int* __restrict__ hist,
+                                                          int* __restrict__ matches12, int* __restrict__ nmatches) {
+    const int p = blockIdx.x;
+    const int fa = pair_a[p], fb = pair_b[p];
+    const bool ok = (unsigned)fa < (unsigned)fr.nframes && (unsigned)fb < (unsigned)fr.nframes;
+    const int n1 = ok ? clamp_cap(fr.counts[fa], fr.cap) : 0;
+    const size_t row = (size_t)p * fr.cap;
+    bow_finish(n1, check_ori, bin_of + row, hist + (size_t)p * kBowHistStride, matches12 + row, nmatches + p);
 }
 
 Bounds make_bounds(const se2gpu_frame_bounds& b) {
@@ -804,6 +926,7 @@ struct se2gpu_matcher {
     DevBuf<uint8_t> desc, mp_desc, mp_skip, kf_obs, has1, has2;
     DevBuf<int> fvp1, fvi1, fvp2, fvi2, bin_of, hist;
     DevBuf<int2> node_pairs;
+    DevBuf<int> n_node_pairs;     // se2gpu_search_by_bow_batch_device: equal nodes per key-frame pair
     // single-call paths (host buffers in, host buffers out): one packed block each way
     PinBuf<uint8_t> stage_h;
     DevBuf<uint8_t> stage_d;
@@ -1208,7 +1331,7 @@ int se2gpu_search_by_bow(se2gpu_matcher* h, const se2gpu_keypoint* kps1, const u
     SE2_HIP(hipMemsetAsync(h->hist.p, 0, 32 * sizeof(int), st));
     if (!pairs.empty())
         hipLaunchKernelGGL(k_bow_match, dim3((unsigned)pairs.size()), dim3(64), (size_t)((max_node2 + 63) & ~63), st, h->node_pairs.p, h->fvp1.p, h->fvi1.p,
-                           h->fvp2.p, h->fvi2.p, h->kps.p, h->desc.p, h->has1.p, d_k2, d_d2, h->has2.p, mp_only, nnratio,
+                           h->fvp2.p, h->fvi2.p, h->kps.p, h->desc.p, h->has1.p, n1, d_k2, d_d2, h->has2.p, n2, mp_only, nnratio,
                            check_orientation, h->matches.p, h->bin_of.p, h->hist.p);
     hipLaunchKernelGGL(k_bow_finish, dim3(1), dim3(256), 0, st, n1, check_orientation, h->bin_of.p, h->hist.p, h->matches.p,
                        h->nmatches.p);
@@ -1216,6 +1339,37 @@ int se2gpu_search_by_bow(se2gpu_matcher* h, const se2gpu_keypoint* kps1, const u
     SE2_HIP(hipMemcpyAsync(matches12, h->matches.p, (size_t)n1 * sizeof(int), hipMemcpyDeviceToHost, st));
     SE2_HIP(hipMemcpyAsync(n_matches, h->nmatches.p, sizeof(int), hipMemcpyDeviceToHost, st));
     SE2_HIP(hipStreamSynchronize(st));
+    return SE2GPU_OK;
+}
+
+int se2gpu_search_by_bow_batch_device(se2gpu_matcher* h, const se2gpu_keypoint* d_kps, const uint8_t* d_desc,
+                                      const int32_t* d_counts, int cap, int nframes, const int32_t* d_fv_nodes,
+                                      const int32_t* d_fv_ptr, const int32_t* d_fv_idx, const int32_t* d_fv_nn,
+                                      const uint8_t* d_has_mp, const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs,
+                                      int mp_only, float nnratio, int check_orientation, int32_t* d_matches12,
+                                      int32_t* d_nmatches) {
+    SE2_REQUIRE(h && d_kps && d_desc && d_counts && d_fv_nodes && d_fv_ptr && d_fv_idx && d_fv_nn && d_pair_a && d_pair_b &&
+                    d_matches12 && d_nmatches,
+                SE2GPU_ERR_INVALID, "search_by_bow_batch: NULL argument");
+    SE2_REQUIRE(npairs >= 1 && cap >= 1 && nframes >= 1, SE2GPU_ERR_INVALID, "search_by_bow_batch: bad sizes");
+    SE2_REQUIRE(!mp_only || d_has_mp, SE2GPU_ERR_INVALID, "search_by_bow_batch: mp_only without d_has_mp");
+    // vbMatched2 of a node: one LDS byte per feature, at most cap of them, within the 64 KiB a workgroup gets without opting in
+    SE2_REQUIRE(cap <= 64 * 1024, SE2GPU_ERR_CAPACITY, "search_by_bow_batch: cap %d exceeds the limit %d", cap, 64 * 1024);
+    SE2_REQUIRE(npairs <= 65535, SE2GPU_ERR_CAPACITY, "search_by_bow_batch: %d pairs exceed the 65535 of one launch", npairs);
+    SE2_CHECK(h->node_pairs.reserve((size_t)npairs * cap));
+    SE2_CHECK(h->n_node_pairs.reserve((size_t)npairs));
+    SE2_CHECK(h->bin_of.reserve((size_t)npairs * cap));
+    SE2_CHECK(h->hist.reserve((size_t)npairs * kBowHistStride));
+    hipStream_t st = h->stream;
+    const BowFrames fr{d_kps, d_desc, d_counts, d_fv_nodes, d_fv_ptr, d_fv_idx, d_fv_nn, mp_only ? d_has_mp : nullptr, cap, nframes};
+    hipLaunchKernelGGL(k_bow_pair_nodes, dim3(npairs), dim3(256), 0, st, fr, d_pair_a, d_pair_b, h->node_pairs.p,
+                       h->n_node_pairs.p, d_matches12, h->bin_of.p, h->hist.p);
+    hipLaunchKernelGGL(k_bow_match_batch, dim3(kBowWaves, npairs), dim3(64), (size_t)((cap + 63) & ~63), st, fr, d_pair_a,
+                       d_pair_b, (const int2*)h->node_pairs.p, (const int*)h->n_node_pairs.p, mp_only, nnratio,
+                       check_orientation, d_matches12, h->bin_of.p, h->hist.p);
+    hipLaunchKernelGGL(k_bow_finish_batch, dim3(npairs), dim3(256), 0, st, fr, d_pair_a, d_pair_b, check_orientation,
+                       (const int*)h->bin_of.p, (const int*)h->hist.p, d_matches12, d_nmatches);
+    SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
 }
 

@@ -104,8 +104,24 @@ class ORBmatcher:
                                                                minLevel, maxLevel, self.mfNNratio, d_matches12,
                                                                d_nmatches))
 
+    def search_by_bow_batch_device(self, d_kps, d_desc, d_counts, cap, nframes, d_fv_nodes, d_fv_ptr, d_fv_idx, d_fv_nn,
+                                   d_has_mp, d_pair_a, d_pair_b, npairs, d_matches12, d_nmatches, bIfMPOnly=True,
+                                   checkOri=True):
+        """se2gpu_search_by_bow_batch_device: SearchByBoW(frame a[p], frame b[p], .., bIfMPOnly) for npairs pairs of the
+        frames se2gpu_orb_extract_batch_device wrote and the feature vectors se2gpu_bow_transform_batch_device wrote, all
+        device pointers (d_has_mp may be None when bIfMPOnly is false).  Asynchronous on the matcher's stream: sync()
+        before the outputs are read; set_stream(ctx.stream()) orders it behind the transform."""
+        capi.check(capi.lib().se2gpu_search_by_bow_batch_device(self._h, d_kps, d_desc, d_counts, cap, nframes, d_fv_nodes,
+                                                                d_fv_ptr, d_fv_idx, d_fv_nn, d_has_mp, d_pair_a, d_pair_b,
+                                                                npairs, int(bIfMPOnly), self.mfNNratio, int(checkOri),
+                                                                d_matches12, d_nmatches))
+
     def sync(self):
         capi.check(capi.lib().se2gpu_matcher_sync(self._h))
+
+    def set_stream(self, hip_stream):
+        """se2gpu_matcher_set_stream: run this matcher's calls on `hip_stream` (None = its own stream again)"""
+        capi.check(capi.lib().se2gpu_matcher_set_stream(self._h, hip_stream))
 
     def stream(self):
         return capi.lib().se2gpu_matcher_stream(self._h)
