@@ -477,6 +477,49 @@ int se2gpu_track_fundamental_mask(se2gpu_track* h, const float* pt1, const float
 int se2gpu_track_remove_outliers(se2gpu_track* h, const se2gpu_keypoint* kps1, int n1, const se2gpu_keypoint* kps2,
                                  int n2, int32_t* matches, int* n_inliers);
 int se2gpu_track_last_ransac(const se2gpu_track* h, int info[4]);
+/* The handle's calls run on its own stream, or on `hip_stream` (NULL -> its own stream again), which the caller keeps alive
+ * and has to have drained before it changes streams.  se2gpu_track_sync waits for the stream in use. */
+int se2gpu_track_set_stream(se2gpu_track* h, void* hip_stream);
+void* se2gpu_track_stream(se2gpu_track* h);
+int se2gpu_track_sync(se2gpu_track* h);
+
+/* Loop verification: what both VerifyLoopClose of the reference run behind SearchByBoW (GlobalMapper.cpp:256-326 with
+ * RemoveMatchOutlierRansac :1207-1248 and RemoveKPMatch :1251-1276; Localizer.cpp:394-431 with :571-612) for npairs pairs of
+ * key frames at once.  Every pointer is device memory in the layouts of se2gpu_search_by_bow_batch_device; d_matches12 is the
+ * array that call writes.  The x, y of d_kps are the positions tested (the reference passes keyPointsUn).
+ * For pair p, a = pair_a[p], b = pair_b[p], counts clamped to 0..cap:
+ *   raw matches   entries i < counts[a] of row p with a value in 0..counts[b]-1; every other entry counts as -1.  Their
+ *                 points are taken in ascending i, the order of the reference's std::map<int,int>.
+ *   filter        fewer than 10 raw matches: nothing survives (numMinMatch).  Otherwise the mask of cv::findFundamentalMat
+ *                 exactly as se2gpu_track_fundamental_mask computes it for those points (LMedS for 10..14, RANSAC from 15
+ *                 on, all 0 when no model exists).
+ *   d_matches_good   row p = the input row with the non-survivors at -1, and -1 from counts[a] on
+ *   d_matches_mp     the same, without the entries where has_mp[a][i] or has_mp[b][m] is 0 (RemoveKPMatch); may be NULL
+ *   d_info[p * 8 ..] = {n_raw, n_good, n_good_mp, n_mps_a, path, best sample, best model, iterations}
+ *                 n_good_mp: 0 without d_has_mp.   path: 0 skipped, 1 LMedS, 2 RANSAC.  The last three have the meaning
+ *                 of se2gpu_track_last_ransac and are -1, -1, 0 on path 0.  n_mps_a (getAllObsMPs().size() in the reference's
+ *                 ratio): d_num_mps[a] when d_num_mps is given, else the number of set flags among the first counts[a] of
+ *                 has_mp[a], else 0.
+ * A pair naming a frame outside 0..nframes-1 is a skipped pair without matches: rows of -1, info {0, 0, 0, 0, 0, -1, -1, 0}.
+ * Nothing is indexed outside the arrays, whatever they hold.  The outputs must not overlap the inputs.
+ * Asynchronous on the handle's stream: nothing is read back and nothing waits, so with se2gpu_track_set_stream(h,
+ * se2gpu_matcher_stream(m)) the matcher's batch call and this one follow each other without the host in between.  (The first
+ * call on a handle allocates the scratch and copies an 32 KiB table of random numbers to the device, which blocks.)  The
+ * scratch - per pair 1000 x 27 doubles of models, 3000 scores, 7000 sample indices, 21 bytes per feature - lives in the
+ * handle and is reused by the next call; it is capped at 64 MiB whatever npairs is (about 230 pairs at cap = 1024): a larger
+ * batch runs as equal slices of at most that many pairs, one after the other on the same stream.
+ * SE2GPU_ERR_INVALID: a NULL handle or required pointer, npairs / cap / nframes < 1, d_matches_mp without d_has_mp.
+ * SE2GPU_ERR_CAPACITY: cap > 65536 or npairs > 65535, the limits of se2gpu_search_by_bow_batch_device.
+ * The argument checks come first and use neither the handle nor a device. */
+int se2gpu_track_loop_verify_batch_device(se2gpu_track* h,
+                                          const se2gpu_keypoint* d_kps, const int32_t* d_counts, int cap, int nframes,
+                                          const uint8_t* d_has_mp /* nframes*cap, may be NULL */,
+                                          const int32_t* d_num_mps /* nframes, may be NULL */,
+                                          const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs,
+                                          const int32_t* d_matches12 /* npairs*cap */,
+                                          int32_t* d_matches_good /* npairs*cap, out */,
+                                          int32_t* d_matches_mp /* npairs*cap, out; may be NULL */,
+                                          int32_t* d_info /* npairs*8, out */);
 /* se2gpu_triangulate (below) on the workspace of the tracking thread: one packed upload / download, no allocation */
 int se2gpu_track_triangulate(se2gpu_track* h, int n, const se2gpu_keypoint* kps_ref, const se2gpu_keypoint* kps_cur,
                              int n_cur, int32_t* match_idx, const uint8_t* has_observation, const float* P_ref,

@@ -30,6 +30,8 @@
 
 #include <algorithm>
 
+#include "fm_subsets.h"
+
 namespace se2gpu {
 namespace {
 
@@ -218,11 +220,10 @@ __host__ __device__ inline int fm_update_num_iters(double p, double ep, int mode
     return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
 }
 
-__global__ __launch_bounds__(64) void k_fm_models(const float2* __restrict__ m1, const float2* __restrict__ m2,
-                                                   const int* __restrict__ subsets, int niters,
-                                                   double* __restrict__ F, int* __restrict__ nmodels) {
-    const int it = blockIdx.x * blockDim.x + threadIdx.x;
-    if (it >= niters) return;
+// one thread per sample `it` of one point set
+__device__ inline void fm_models_sample(const float2* __restrict__ m1, const float2* __restrict__ m2,
+                                        const int* __restrict__ subsets, int it, double* __restrict__ F,
+                                        int* __restrict__ nmodels) {
     int idx[7];
     for (int i = 0; i < 7; ++i) idx[i] = subsets[it * 7 + i];
     double Fl[27];
@@ -232,13 +233,20 @@ __global__ __launch_bounds__(64) void k_fm_models(const float2* __restrict__ m1,
     for (int i = 0; i < 27; ++i) F[(size_t)it * 27 + i] = Fl[i];
 }
 
+__global__ __launch_bounds__(64) void k_fm_models(const float2* __restrict__ m1, const float2* __restrict__ m2,
+                                                   const int* __restrict__ subsets, int niters,
+                                                   double* __restrict__ F, int* __restrict__ nmodels) {
+    const int it = blockIdx.x * blockDim.x + threadIdx.x;
+    if (it >= niters) return;
+    fm_models_sample(m1, m2, subsets, it, F, nmodels);
+}
+
 // score[it*3 + k]: RANSAC - number of correspondences with error <= thr (as double); LMedS - the median error.
 // Models that do not exist score -1 (RANSAC) / +inf (LMedS).
-__global__ __launch_bounds__(256) void k_fm_score(const float2* __restrict__ m1, const float2* __restrict__ m2, int n,
-                                                   const double* __restrict__ F, const int* __restrict__ nmodels,
-                                                   int niters, int lmeds, float thr, double* __restrict__ score) {
-    const int w = blockIdx.x * 4 + threadIdx.x / 64;
-    const int lane = threadIdx.x & 63;
+// one wave per (sample, model) w of one point set
+__device__ inline void fm_score_wave(const float2* __restrict__ m1, const float2* __restrict__ m2, int n,
+                                     const double* __restrict__ F, const int* __restrict__ nmodels, int niters, int lmeds,
+                                     float thr, double* __restrict__ score, int w, int lane) {
     if (w >= niters * 3) return;
     const int it = w / 3, k = w - 3 * it;
     const int nm = nmodels[it];
@@ -250,6 +258,7 @@ __global__ __launch_bounds__(256) void k_fm_score(const float2* __restrict__ m1,
     for (int i = 0; i < 9; ++i) Fm[i] = F[(size_t)it * 27 + 9 * k + i];
     if (!lmeds) {
         int good = 0;
+#pragma unroll 1
         for (int i = lane; i < n; i += 64) good += fm_error(Fm, m1[i], m2[i]) <= thr;
         for (int s = 1; s < 64; s <<= 1) good += __shfl_xor(good, s);
         if (lane == 0) score[w] = (double)good;
@@ -275,12 +284,18 @@ __global__ __launch_bounds__(256) void k_fm_score(const float2* __restrict__ m1,
     if (lane == 0) score[w] = median;
 }
 
+__global__ __launch_bounds__(256) void k_fm_score(const float2* __restrict__ m1, const float2* __restrict__ m2, int n,
+                                                   const double* __restrict__ F, const int* __restrict__ nmodels,
+                                                   int niters, int lmeds, float thr, double* __restrict__ score) {
+    fm_score_wave(m1, m2, n, F, nmodels, niters, lmeds, thr, score, blockIdx.x * 4 + threadIdx.x / 64, threadIdx.x & 63);
+}
+
 // Replays RANSACPointSetRegistrator::run / LMeDSPointSetRegistrator::run over the per-model scores and writes the mask.
 // out_mask[n], out_info = {inliers, best sample, best model, iterations the reference would have run}
-__global__ __launch_bounds__(256) void k_fm_select(const float2* __restrict__ m1, const float2* __restrict__ m2, int n,
-                                                    const double* __restrict__ F, const double* __restrict__ score,
-                                                    int niters, int lmeds, uint8_t* __restrict__ out_mask,
-                                                    int* __restrict__ out_info) {
+// The 256 threads of one workgroup call it together; out_mask and out_info are theirs to read after a __syncthreads().
+__device__ inline void fm_select_block(const float2* __restrict__ m1, const float2* __restrict__ m2, int n,
+                                       const double* __restrict__ F, const double* __restrict__ score, int niters,
+                                       int lmeds, uint8_t* __restrict__ out_mask, int* out_info) {
     __shared__ double s_F[9];
     __shared__ float s_thr;
     __shared__ int s_best, s_iters, s_count;
@@ -363,6 +378,187 @@ __global__ __launch_bounds__(256) void k_fm_select(const float2* __restrict__ m1
     }
 }
 
+__global__ __launch_bounds__(256) void k_fm_select(const float2* __restrict__ m1, const float2* __restrict__ m2, int n,
+                                                    const double* __restrict__ F, const double* __restrict__ score,
+                                                    int niters, int lmeds, uint8_t* __restrict__ out_mask,
+                                                    int* __restrict__ out_info) {
+    fm_select_block(m1, m2, n, F, score, niters, lmeds, out_mask, out_info);
+}
+
+// ---- loop verification: RemoveMatchOutlierRansac over a batch of key-frame pairs that lie in HBM -----------------------------
+// (GlobalMapper.cpp:1207-1276, Localizer.cpp:571-612 of the reference; se2gpu_track_loop_verify_batch_device).  The point
+// count of a pair is known on the device only, so everything the single-pair path decides on the host - LMedS or RANSAC, the
+// number of samples, the samples themselves - is decided per pair by the kernels, from lv_meta.  Five launches per slice of
+// pairs, none waits on another workgroup:
+//   k_lv_gather   one workgroup per pair: ordered compaction of the match row (ballot prefix count, ascending feature index
+//                 = the order of the reference's std::map) into the two point lists; slot[i] = position of feature i's match
+//                 in them or -1, which is what the last kernel needs to write the rows back without a scatter
+//   k_lv_draw     one wave per pair: the 7-point samples for its n (fm_subsets.h)
+//   k_lv_models / k_lv_score / k_lv_select   k_fm_models / k_fm_score / k_fm_select with the pair as a grid dimension; the
+//                 arithmetic is the same __device__ functions, so a pair's mask equals se2gpu_track_fundamental_mask's
+//                 bit for bit.  k_lv_select also writes the output rows and info.
+constexpr size_t kLvScratchCeiling = (size_t)64 << 20;   // bytes of slice scratch a handle ever holds (lv_raw not counted)
+constexpr int kLvMinMatch = 10;                          // numMinMatch of RemoveMatchOutlierRansac
+constexpr int kLvMeta = 4;                               // {n_raw, path, n_mps_a, samples to run}
+
+inline size_t lv_pair_bytes(int cap) {
+    return (size_t)kMaxIters * (27 * sizeof(double) + 3 * sizeof(double) + sizeof(int) + 7 * sizeof(int)) +
+           (size_t)cap * (2 * sizeof(float2) + sizeof(int) + 1) + kLvMeta * sizeof(int);
+}
+
+struct LvBatch {
+    const se2gpu_keypoint* kps;
+    const int32_t* counts;
+    const uint8_t* has_mp;
+    const int32_t* num_mps;
+    const int32_t *pair_a, *pair_b;
+    const int32_t* matches12;
+    int cap, nframes;
+};
+
+__device__ inline int lv_count(const LvBatch& b, int f) { return min(max(b.counts[f], 0), b.cap); }
+
+__global__ __launch_bounds__(256) void k_lv_gather(LvBatch b, int p0, int lmeds_iters, float2* __restrict__ pts,
+                                                    int* __restrict__ slot, int* __restrict__ meta) {
+    __shared__ int s_wave[4];
+    __shared__ int s_flags;
+    const int s = blockIdx.x, p = p0 + s, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int cap = b.cap;
+    float2* m1 = pts + (size_t)s * 2 * cap;
+    float2* m2 = m1 + cap;
+    int* sl = slot + (size_t)s * cap;
+    const int fa = b.pair_a[p], fb = b.pair_b[p];
+    const bool ok = fa >= 0 && fa < b.nframes && fb >= 0 && fb < b.nframes;
+    const int na = ok ? lv_count(b, fa) : 0, nb = ok ? lv_count(b, fb) : 0;
+    const int32_t* row = b.matches12 + (size_t)p * cap;
+    const se2gpu_keypoint* ka = b.kps + (size_t)(ok ? fa : 0) * cap;
+    const se2gpu_keypoint* kb = b.kps + (size_t)(ok ? fb : 0) * cap;
+    const bool count_flags = ok && !b.num_mps && b.has_mp;
+    if (tid == 0) s_flags = 0;
+    int base = 0, flags = 0;
+    for (int c0 = 0; c0 < cap; c0 += 256) {
+        const int i = c0 + tid;
+        int m = -1;
+        if (i < na) {
+            m = row[i];
+            if (m < 0 || m >= nb) m = -1;
+            if (count_flags) flags += b.has_mp[(size_t)fa * cap + i] != 0;
+        }
+        const unsigned long long bal = __ballot(m >= 0);
+        if (lane == 0) s_wave[wv] = __popcll(bal);
+        __syncthreads();
+        int off = base, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wv) off += s_wave[w];
+            total += s_wave[w];
+        }
+        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
+        if (i < cap) sl[i] = m >= 0 ? pos : -1;
+        if (m >= 0) {
+            m1[pos] = make_float2(ka[i].x, ka[i].y);
+            m2[pos] = make_float2(kb[m].x, kb[m].y);
+        }
+        base += total;
+        __syncthreads();
+    }
+    for (int d = 1; d < 64; d <<= 1) flags += __shfl_xor(flags, d);
+    if (lane == 0 && flags) atomicAdd(&s_flags, flags);
+    __syncthreads();
+    if (tid == 0) {
+        const int path = base < kLvMinMatch ? 0 : base < 15 ? 1 : 2;
+        meta[s * kLvMeta + 0] = base;
+        meta[s * kLvMeta + 1] = path;
+        meta[s * kLvMeta + 2] = !ok ? 0 : b.num_mps ? b.num_mps[fa] : s_flags;
+        meta[s * kLvMeta + 3] = path == 0 ? 0 : path == 1 ? lmeds_iters : kMaxIters;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_lv_draw(const int* __restrict__ meta, const uint32_t* __restrict__ raw,
+                                                 uint64_t raw_state, int* __restrict__ subsets) {
+    const int s = blockIdx.x;
+    if (meta[s * kLvMeta + 1] == 0) return;
+    fm_draw_subsets(raw, kFmRawTable, raw_state, meta[s * kLvMeta + 0], meta[s * kLvMeta + 3],
+                    subsets + (size_t)s * kMaxIters * 7, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void k_lv_models(const int* __restrict__ meta, int cap, const float2* __restrict__ pts,
+                                                   const int* __restrict__ subsets, double* __restrict__ F,
+                                                   int* __restrict__ nmodels) {
+    const int s = blockIdx.y, it = blockIdx.x * blockDim.x + threadIdx.x;
+    if (it >= meta[s * kLvMeta + 3]) return;   // 0 samples on path 0
+    const float2* m1 = pts + (size_t)s * 2 * cap;
+    fm_models_sample(m1, m1 + cap, subsets + (size_t)s * kMaxIters * 7, it, F + (size_t)s * kMaxIters * 27,
+                     nmodels + (size_t)s * kMaxIters);
+}
+
+__global__ __launch_bounds__(256) void k_lv_score(const int* __restrict__ meta, int cap, const float2* __restrict__ pts,
+                                                   const double* __restrict__ F, const int* __restrict__ nmodels,
+                                                   float thr, double* __restrict__ score) {
+    const int s = blockIdx.y;
+    const int path = __builtin_amdgcn_readfirstlane(meta[s * kLvMeta + 1]);
+    if (path == 0) return;
+    const int n = __builtin_amdgcn_readfirstlane(meta[s * kLvMeta + 0]);
+    const int niters = __builtin_amdgcn_readfirstlane(meta[s * kLvMeta + 3]);
+    const float2* m1 = pts + (size_t)s * 2 * cap;
+    fm_score_wave(m1, m1 + cap, n, F + (size_t)s * kMaxIters * 27, nmodels + (size_t)s * kMaxIters, niters, path == 1, thr,
+                  score + (size_t)s * kMaxIters * 3, blockIdx.x * 4 + threadIdx.x / 64, threadIdx.x & 63);
+}
+
+// info[p] = {n_raw, n_good, n_good_mp, n_mps_a, path, best sample, best model, iterations}
+__global__ __launch_bounds__(256) void k_lv_select(LvBatch b, int p0, const float2* __restrict__ pts, const int* slot,
+                                                    const int* __restrict__ meta, const double* __restrict__ F,
+                                                    const double* __restrict__ score, uint8_t* mask, int32_t* good,
+                                                    int32_t* good_mp, int32_t* __restrict__ info) {
+    __shared__ int s_info[4];
+    __shared__ int s_mp;
+    const int s = blockIdx.x, p = p0 + s, tid = threadIdx.x, lane = tid & 63;
+    const int cap = b.cap;
+    const int n = meta[s * kLvMeta + 0], path = meta[s * kLvMeta + 1];
+    const float2* m1 = pts + (size_t)s * 2 * cap;
+    uint8_t* mk = mask + (size_t)s * cap;
+    if (tid == 0) {
+        s_mp = 0;
+        s_info[0] = 0; s_info[1] = s_info[2] = -1; s_info[3] = 0;
+    }
+    __syncthreads();
+    if (path != 0)
+        fm_select_block(m1, m1 + cap, n, F + (size_t)s * kMaxIters * 27, score + (size_t)s * kMaxIters * 3,
+                        meta[s * kLvMeta + 3], path == 1, mk, s_info);
+    __syncthreads();
+    // a pair on path 1 or 2 names two frames inside the arrays: k_lv_gather found matches in it
+    const int fa = path != 0 ? b.pair_a[p] : 0, fb = path != 0 ? b.pair_b[p] : 0;
+    const int32_t* row = b.matches12 + (size_t)p * cap;
+    const int* sl = slot + (size_t)s * cap;
+    int n_mp = 0;
+    for (int i = tid; i < cap; i += 256) {
+        int v = -1;
+        if (path != 0) {
+            const int j = sl[i];
+            if (j >= 0 && mk[j]) v = row[i];   // slot >= 0: the entry was in 0..counts[b]-1 when k_lv_gather read it
+        }
+        good[(size_t)p * cap + i] = v;
+        if (b.has_mp) {   // RemoveKPMatch
+            if (v >= 0 && !(v < cap && b.has_mp[(size_t)fa * cap + i] && b.has_mp[(size_t)fb * cap + v])) v = -1;
+            if (good_mp) good_mp[(size_t)p * cap + i] = v;
+            n_mp += v >= 0;
+        }
+    }
+    for (int d = 1; d < 64; d <<= 1) n_mp += __shfl_xor(n_mp, d);
+    if (lane == 0 && n_mp) atomicAdd(&s_mp, n_mp);
+    __syncthreads();
+    if (tid == 0) {
+        int32_t* o = info + (size_t)p * 8;
+        o[0] = n;
+        o[1] = s_info[0];
+        o[2] = s_mp;
+        o[3] = meta[s * kLvMeta + 2];
+        o[4] = path;
+        o[5] = s_info[1];
+        o[6] = s_info[2];
+        o[7] = s_info[3];
+    }
+}
+
 struct CvRng {   // cv::RNG (multiply-with-carry), seeded with (uint64)-1 by both registrators
     uint64_t state;
     explicit CvRng(uint64_t s) : state(s ? s : 0xffffffffull) {}
@@ -383,23 +579,39 @@ extern "C" int se2gpu_track_create(se2gpu_track** out) {
     *out = nullptr;
     SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
     se2gpu_track* h = new se2gpu_track();
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
         delete h;
         return SE2GPU_ERR_HIP;
     }
+    h->stream = h->own_stream;
     *out = h;
     return SE2GPU_OK;
 }
 
 extern "C" void se2gpu_track_destroy(se2gpu_track* h) {
     if (!h) return;
-    if (h->stream) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipStreamDestroy(h->stream);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->own_stream) {
+        if (h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
+        (void)hipStreamDestroy(h->own_stream);
     }
     delete h;
+}
+
+extern "C" int se2gpu_track_set_stream(se2gpu_track* h, void* s) {
+    SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "track handle is NULL");
+    h->stream = s ? (hipStream_t)s : h->own_stream;
+    return SE2GPU_OK;
+}
+
+extern "C" void* se2gpu_track_stream(se2gpu_track* h) { return h ? (void*)h->stream : nullptr; }
+
+extern "C" int se2gpu_track_sync(se2gpu_track* h) {
+    SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "track handle is NULL");
+    SE2_HIP(hipStreamSynchronize(h->stream));
+    return SE2GPU_OK;
 }
 
 extern "C" int se2gpu_track_fundamental_mask(se2gpu_track* h, const float* pt1, const float* pt2, int n, uint8_t* mask,
@@ -508,5 +720,57 @@ extern "C" int se2gpu_track_remove_outliers(se2gpu_track* h, const se2gpu_keypoi
 extern "C" int se2gpu_track_last_ransac(const se2gpu_track* h, int info[4]) {
     SE2_REQUIRE(h && info, SE2GPU_ERR_INVALID, "last_ransac: NULL argument");
     std::memcpy(info, h->last_info, sizeof(h->last_info));
+    return SE2GPU_OK;
+}
+
+extern "C" int se2gpu_track_loop_verify_batch_device(se2gpu_track* h, const se2gpu_keypoint* d_kps, const int32_t* d_counts,
+                                                     int cap, int nframes, const uint8_t* d_has_mp,
+                                                     const int32_t* d_num_mps, const int32_t* d_pair_a,
+                                                     const int32_t* d_pair_b, int npairs, const int32_t* d_matches12,
+                                                     int32_t* d_matches_good, int32_t* d_matches_mp, int32_t* d_info) {
+    // the argument checks touch neither the handle nor a device
+    SE2_REQUIRE(h && d_kps && d_counts && d_pair_a && d_pair_b && d_matches12 && d_matches_good && d_info,
+                SE2GPU_ERR_INVALID, "loop_verify_batch: NULL argument");
+    SE2_REQUIRE(npairs >= 1 && cap >= 1 && nframes >= 1, SE2GPU_ERR_INVALID, "loop_verify_batch: bad sizes");
+    SE2_REQUIRE(!d_matches_mp || d_has_mp, SE2GPU_ERR_INVALID, "loop_verify_batch: d_matches_mp without d_has_mp");
+    SE2_REQUIRE(cap <= 64 * 1024, SE2GPU_ERR_CAPACITY, "loop_verify_batch: cap %d exceeds the limit %d", cap, 64 * 1024);
+    SE2_REQUIRE(npairs <= 65535, SE2GPU_ERR_CAPACITY, "loop_verify_batch: %d pairs exceed the limit 65535", npairs);
+    if (!h->lv_raw.p) {   // once per handle, blocking: the table is in place whichever stream the calls run on
+        std::vector<uint32_t> raw(kFmRawTable);
+        h->lv_raw_state = fm_raw_fill(raw.data(), kFmRawTable);
+        SE2_CHECK(h->lv_raw.reserve(kFmRawTable));
+        SE2_HIP(hipMemcpy(h->lv_raw.p, raw.data(), raw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    // as few slices as the ceiling allows, of equal size: every slice pays the latency of the five launches once
+    const int fit = (int)std::min<size_t>((size_t)npairs, std::max<size_t>(1, kLvScratchCeiling / lv_pair_bytes(cap)));
+    const int nslices = (npairs + fit - 1) / fit;
+    const int slice = (npairs + nslices - 1) / nslices;
+    SE2_CHECK(h->lv_pts.reserve((size_t)slice * 2 * cap));
+    SE2_CHECK(h->lv_slot.reserve((size_t)slice * cap));
+    SE2_CHECK(h->lv_mask.reserve((size_t)slice * cap));
+    SE2_CHECK(h->lv_meta.reserve((size_t)slice * kLvMeta));
+    SE2_CHECK(h->lv_sub.reserve((size_t)slice * kMaxIters * 7));
+    SE2_CHECK(h->lv_F.reserve((size_t)slice * kMaxIters * 27));
+    SE2_CHECK(h->lv_nm.reserve((size_t)slice * kMaxIters));
+    SE2_CHECK(h->lv_score.reserve((size_t)slice * kMaxIters * 3));
+    const int lmeds_iters = std::max(fm_update_num_iters(kConfidence, kLmedsOutlierRatio, kModelPoints, kMaxIters), 3);
+    const LvBatch b{d_kps, d_counts, d_has_mp, d_num_mps, d_pair_a, d_pair_b, d_matches12, cap, nframes};
+    hipStream_t st = h->stream;
+    for (int p0 = 0; p0 < npairs; p0 += slice) {   // the slices follow each other on the stream and share the scratch
+        const int np = std::min(slice, npairs - p0);
+        hipLaunchKernelGGL(k_lv_gather, dim3(np), dim3(256), 0, st, b, p0, lmeds_iters, h->lv_pts.p, h->lv_slot.p,
+                           h->lv_meta.p);
+        hipLaunchKernelGGL(k_lv_draw, dim3(np), dim3(64), 0, st, (const int*)h->lv_meta.p, (const uint32_t*)h->lv_raw.p,
+                           h->lv_raw_state, h->lv_sub.p);
+        hipLaunchKernelGGL(k_lv_models, dim3((kMaxIters + 63) / 64, np), dim3(64), 0, st, (const int*)h->lv_meta.p, cap,
+                           (const float2*)h->lv_pts.p, (const int*)h->lv_sub.p, h->lv_F.p, h->lv_nm.p);
+        hipLaunchKernelGGL(k_lv_score, dim3((kMaxIters * 3 + 3) / 4, np), dim3(256), 0, st, (const int*)h->lv_meta.p, cap,
+                           (const float2*)h->lv_pts.p, (const double*)h->lv_F.p, (const int*)h->lv_nm.p,
+                           (float)(kThreshold * kThreshold), h->lv_score.p);
+        hipLaunchKernelGGL(k_lv_select, dim3(np), dim3(256), 0, st, b, p0, (const float2*)h->lv_pts.p,
+                           (const int*)h->lv_slot.p, (const int*)h->lv_meta.p, (const double*)h->lv_F.p,
+                           (const double*)h->lv_score.p, h->lv_mask.p, d_matches_good, d_matches_mp, d_info);
+    }
+    SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
 }

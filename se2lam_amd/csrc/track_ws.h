@@ -1,9 +1,10 @@
-// Device workspace of one tracking thread, shared by ransac.hip (removeOutliers) and triangulate.hip (doTriangulate).
+// Device workspace of one tracking thread, shared by ransac.hip (removeOutliers, the batched loop verification) and
+// triangulate.hip (doTriangulate).
 #pragma once
 #include "common.h"
 
 struct se2gpu_track {
-    hipStream_t stream = nullptr;
+    hipStream_t own_stream = nullptr, stream = nullptr;   // stream: own_stream, or the one se2gpu_track_set_stream lent
     se2gpu::PinBuf<uint8_t> h_in, h_out;
     se2gpu::DevBuf<uint8_t> d_in, d_out;
     se2gpu::DevBuf<double> d_F, d_score;
@@ -14,4 +15,15 @@ struct se2gpu_track {
     std::vector<int> idx;
     std::vector<uint8_t> mask;
     int last_info[4] = {0, -1, -1, 0};
+    // se2gpu_track_loop_verify_batch_device: the scratch of one slice of pairs (ransac.hip, LvScratch)
+    se2gpu::DevBuf<uint32_t> lv_raw;    // head of cv::RNG(-1)'s raw stream, uploaded by the first call
+    uint64_t lv_raw_state = 0;          // generator state behind lv_raw
+    se2gpu::DevBuf<float2> lv_pts;      // slice x 2 x cap: the matched positions of frame a, then of frame b
+    se2gpu::DevBuf<int> lv_slot;        // slice x cap: position of feature i's match in the point lists, -1 = no match
+    se2gpu::DevBuf<int> lv_meta;        // slice x 4: {n_raw, path, n_mps_a, samples to run}
+    se2gpu::DevBuf<int> lv_sub;         // slice x 1000 x 7 sample indices
+    se2gpu::DevBuf<double> lv_F;        // slice x 1000 x 27
+    se2gpu::DevBuf<int> lv_nm;          // slice x 1000
+    se2gpu::DevBuf<double> lv_score;    // slice x 3000
+    se2gpu::DevBuf<uint8_t> lv_mask;    // slice x cap
 };

@@ -2,6 +2,8 @@
 
     Track.removeOutliers(kp1, kp2, matches)   Track.cpp:308-344   cv::findFundamentalMat RANSAC mask on the device
     Track.doTriangulate(...)                  Track.cpp:378-419   see matcher.doTriangulate
+    Track.loop_verify_batch_device(...)       GlobalMapper.cpp:1207-1276, Localizer.cpp:571-612   RemoveMatchOutlierRansac and
+                                              RemoveKPMatch behind SearchByBoW, for a batch of key-frame pairs in HBM
 
 Everything is computed by libse2gpu (csrc/ransac.hip, csrc/triangulate.hip); there is no CPU fallback.
 """
@@ -12,6 +14,10 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+
+
+# the 8 ints se2gpu_track_loop_verify_batch_device writes per pair
+LOOP_VERIFY_INFO = ("n_raw", "n_good", "n_good_mp", "n_mps_a", "path", "sample", "model", "iterations")
 
 
 class Track:
@@ -53,6 +59,26 @@ class Track:
         info = np.zeros(4, np.int32)
         capi.check(capi.lib().se2gpu_track_last_ransac(self._h, info.ctypes.data))
         return dict(inliers=int(info[0]), sample=int(info[1]), model=int(info[2]), iterations=int(info[3]))
+
+    def loop_verify_batch_device(self, d_kps, d_counts, cap, nframes, d_has_mp, d_num_mps, d_pair_a, d_pair_b, npairs,
+                                 d_matches12, d_matches_good, d_matches_mp, d_info):
+        """se2gpu_track_loop_verify_batch_device: the fundamental-matrix filter of both VerifyLoopClose on the match rows
+        ORBmatcher.search_by_bow_batch_device wrote, all device pointers (d_has_mp, d_num_mps and d_matches_mp may be None).
+        d_info gets 8 ints per pair, LOOP_VERIFY_INFO.  Asynchronous on this handle's stream: sync() before the outputs are
+        read; set_stream(matcher.stream()) orders it behind the matcher."""
+        capi.check(capi.lib().se2gpu_track_loop_verify_batch_device(self._h, d_kps, d_counts, cap, nframes, d_has_mp, d_num_mps,
+                                                                    d_pair_a, d_pair_b, npairs, d_matches12, d_matches_good,
+                                                                    d_matches_mp, d_info))
+
+    def sync(self):
+        capi.check(capi.lib().se2gpu_track_sync(self._h))
+
+    def set_stream(self, hip_stream):
+        """se2gpu_track_set_stream: run this handle's calls on `hip_stream` (None = its own stream again)"""
+        capi.check(capi.lib().se2gpu_track_set_stream(self._h, hip_stream))
+
+    def stream(self):
+        return capi.lib().se2gpu_track_stream(self._h)
 
     def doTriangulate(self, kps_ref, kps_cur, match_idx, has_observation, P_ref, P_cur, Ocam, lower_depth, upper_depth,
                       min_degree=2):
