@@ -310,6 +310,37 @@ int se2gpu_sparsify_se3xyz(int npairs, const double* kf12, const int32_t* mp_ptr
                            const int32_t* m_ptr, const int32_t* m_kf, const int32_t* m_mp, const double* m_info,
                            double* z_out12, double* info_out36);
 
+/* GlobalMapper::CreateFeatEdge (/root/reference/src/GlobalMapper.cpp:737-843) for a batch of key-frame pairs: the bundle
+ * adjustment of the two key frames and their common map points - OptKFPair (:847-927: key frame 0 fixed, 15 iterations) or
+ * OptKFPairMatch (:929-1032: both free, 30 iterations, then every point with an edge chi2 above 5.0 is dropped) - followed on
+ * the device by Sparsifier::DoMarginalizeSE3XYZ on the optimised poses and the surviving points.  The graph is g2o's
+ * VertexSE3 (T_w_c) with the EdgeSE3Prior of addVertexSE3PlaneMotion (built here from the INPUT pose, Tbc and the three
+ * informations, as se2gpu_plane_motion_prior_iso3 does), marginalised VertexPointXYZ, and one EdgeSE3PointXYZ per point and
+ * key frame (offset = identity, Huber huber_delta), Levenberg-Marquardt.  One wave per pair; host buffers.
+ * Pair p: kf12[p] (2 x 12), its points mp_xyz[mp_ptr[p] .. mp_ptr[p+1]) (start values), per point m_z (2 x 3: the point in
+ * key frame 0's camera, then in key frame 1's: KeyFrame::mViewMPs) and m_info (2 x 9, row-major: mViewMPsInfo).
+ * Outputs: kf12_out (optimised T_w_c), mp_xyz_out, outlier (per point; always 0 in COVIS mode or with outlier_chi2 <= 0),
+ * edge_chi2 (per point x 2, not robustified), stats (per pair, may be NULL), z_out12 / info_out36 as
+ * se2gpu_sparsify_se3xyz, and info4 per pair = {status, points, outliers, points handed to the sparsifier}:
+ *   status 0  constraint written
+ *   status 1  fewer than min_points points (counted before the rejection, as :790 does): nothing is run, kf12_out and
+ *             mp_xyz_out are the input, z_out12 / info_out36 / stats zero
+ *   status 2  a non-finite result: z_out12 / info_out36 zero
+ * SE2GPU_ERR_INVALID: a NULL required pointer, a mode other than the two, mp_ptr not starting at 0 or decreasing, iters
+ * outside 1..64 (the histories of se2gpu_ba_stats).  SE2GPU_ERR_CAPACITY: npairs >= 65536.  All before any device use. */
+#define SE2GPU_FEAT_EDGE_COVIS 0   /* OptKFPair:      KF0 fixed, no rejection; reference: 15 iterations, >= 10 points */
+#define SE2GPU_FEAT_EDGE_MATCH 1   /* OptKFPairMatch: both free, chi2 rejection; reference: 30 iterations, >= 3 matches */
+int se2gpu_feat_edge_batch(int npairs, int mode, int iters, int min_points,
+        const double* kf12,            /* npairs x 2 x 12, T_w_c */
+        const double* Tbc12, double xrot_info, double yrot_info, double z_info,
+        const int32_t* mp_ptr, const double* mp_xyz,          /* CSR over pairs; start values of the points */
+        const double* m_z, const double* m_info,              /* per point: 2 x 3 and 2 x 9 (KF0 then KF1) */
+        double huber_delta, double outlier_chi2,
+        double* kf12_out, double* mp_xyz_out, uint8_t* outlier, double* edge_chi2 /* per point x 2 */,
+        int32_t* info4 /* per pair: status, points, outliers, points handed to the sparsifier */,
+        se2gpu_ba_stats* stats /* per pair, may be NULL */,
+        double* z_out12, double* info_out36);
+
 /* Map::loadLocalGraph(SlamOptimizer&) (/root/reference/src/Map.cpp:891-1022) as ONE call on a POD view of the local
  * window - SURVEY.md section 8f.1.  The caller flattens its pointer graph once per key frame (INTEGRATION.md shows the
  * 30 lines that do it with one hash map instead of the reference's std::find per observation); the library applies

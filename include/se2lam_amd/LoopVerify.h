@@ -4,7 +4,8 @@
 //   Localizer::VerifyLoopClose      src/Localizer.cpp:394-431 of the reference (RemoveMatchOutlierRansac :571-612)
 // for a batch of key-frame pairs whose frames and match rows lie in device memory (ORBmatcher::SearchByBoWBatchDevice writes
 // the rows).  The reference verifies one candidate at a time on the host; here every pair of the batch goes through the same
-// five launches and the host sees 8 ints per pair.  CreateFeatEdge and Map::mergeLoopClose stay with the caller.
+// five launches and the host sees 8 ints per pair.  The verified pairs' CreateFeatEdge is CreateFeatEdgeMatchBatch of FeatEdge.h;
+// Map::mergeLoopClose stays with the caller.
 #pragma once
 #include <cstdint>
 

@@ -167,6 +167,8 @@ SYMBOLS = {
     "se2gpu_ba_edge_chi2": (_I, [_VP, _PD, _I]),
     "se2gpu_map_update_local_graph": (_I, [C.POINTER(MapView), _I, _I, _VP, C.POINTER(_I), _VP, C.POINTER(_I), _VP, C.POINTER(_I)]),
     "se2gpu_sparsify_se3xyz": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "se2gpu_feat_edge_batch": (_I, [_I, _I, _I, _I, _VP, _VP, _D, _D, _D, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP,
+                                    _VP, _VP, _VP]),
     "se2gpu_ba_initialize": (_I, [_VP]),
     "se2gpu_ba_set_edge_level": (_I, [_VP, _I, _I]),
     "se2gpu_ba_reset_estimates": (_I, [_VP]),

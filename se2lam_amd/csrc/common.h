@@ -20,6 +20,13 @@ bool have_device();
 int comm_allreduce(se2gpu_comm* c, void* dev_ptr, size_t count, void* hip_stream);
 int comm_rank(const se2gpu_comm* c);
 int comm_world(const se2gpu_comm* c);
+// k_sparsify (sparsify.hip) on device arrays, on `stream`: what se2gpu_sparsify_se3xyz launches after its host preparation
+// (measurements grouped by point: d_mm_ptr / d_m_kf / d_m_info; d_ord_ptr / d_ord: the order they were given in; scratch of
+// 36 doubles per measurement and 144 per point).  d_mp_cnt, when not NULL, gives the number of points at the head of every
+// pair's row that count (rows compacted on the device, feat_edge.hip); the measurements are then listed point by point.
+int launch_sparsify(hipStream_t stream, int npairs, const double* d_kf12, const int* d_mp_ptr, const double* d_mp_xyz,
+                    const int* d_mm_ptr, const int* d_m_kf, const double* d_m_info, const int* d_ord_ptr, const int* d_ord,
+                    double* d_kf_blk, double* d_schur, const int* d_mp_cnt, double* d_z_out, double* d_info_out);
 
 // The SE2GPU_* environment switches (README) are read through these; an unset variable gives `dflt`.  A flag is on for a
 // value that starts with '1', off for one that starts with '0', `dflt` for anything else; env_is compares the whole value.

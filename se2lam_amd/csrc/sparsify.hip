@@ -195,18 +195,24 @@ __device__ void clamp_spectrum6(double* I) {
 // point on the host); m_kf in {0, 1}; ord: the grouped slots of pair p's measurements, [ord_ptr[p], ord_ptr[p+1]), in the order
 // the caller gave them.  Scratch: 36 doubles per MEASUREMENT (its 6x6 key-frame block of J' W J) and 144 per POINT (its Schur
 // term), so that the sums can be taken in exactly the reference's order whatever lane computed a point.
+// mp_cnt (optional): pair p has only the first mp_cnt[p] points of its row [mp_ptr[p], mp_ptr[p+1]) - a row compacted on the
+// device, with slack behind it (feat_edge.hip).  The pair's measurements must then be listed point by point, so that the
+// first points' measurements are the head of its ord row.
 __global__ __launch_bounds__(64) void k_sparsify(int npairs, const double* __restrict__ kf12, const int* __restrict__ mp_ptr,
                                                  const double* __restrict__ mp_xyz, const int* __restrict__ mm_ptr,
                                                  const int* __restrict__ m_kf, const double* __restrict__ m_info,
                                                  const int* __restrict__ ord_ptr, const int* __restrict__ ord,
                                                  double* __restrict__ kf_blk, double* __restrict__ schur,
-                                                 double* __restrict__ z_out, double* __restrict__ info_out) {
+                                                 const int* __restrict__ mp_cnt, double* __restrict__ z_out,
+                                                 double* __restrict__ info_out) {
     const int p = blockIdx.x;
     if (p >= npairs) return;
     const int lane = threadIdx.x;
     const Q3 KF0 = from_pose12(kf12 + 24 * (size_t)p), KF1 = from_pose12(kf12 + 24 * (size_t)p + 12);
     __shared__ double h11s[144];
-    for (int j = mp_ptr[p] + lane; j < mp_ptr[p + 1]; j += 64) {
+    const int j_begin = mp_ptr[p], j_end = mp_cnt ? j_begin + mp_cnt[p] : mp_ptr[p + 1];
+    const int q_begin = ord_ptr[p], q_end = mp_cnt ? q_begin + (mm_ptr[j_end] - mm_ptr[j_begin]) : ord_ptr[p + 1];
+    for (int j = j_begin + lane; j < j_end; j += 64) {
         // this point's Schur term of H11 (12 x 12); the key-frame blocks of J' W J go to their measurement's slot
         double* acc = schur + (size_t)j * 144;
         for (int i = 0; i < 144; ++i) acc[i] = 0.0;
@@ -253,13 +259,13 @@ __global__ __launch_bounds__(64) void k_sparsify(int npairs, const double* __res
         double hsum = 0.0;
         if (c / 6 == k) {
             const int e = 6 * (r - 6 * k) + (c - 6 * k);
-            for (int q = ord_ptr[p]; q < ord_ptr[p + 1]; ++q) {
+            for (int q = q_begin; q < q_end; ++q) {
                 const int t = ord[q];
                 if (m_kf[t] == k) hsum += kf_blk[36 * (size_t)t + e];
             }
         }
         if (i % 13 == 0) hsum += 1e-6;
-        for (int j = mp_ptr[p]; j < mp_ptr[p + 1]; ++j) hsum -= schur[(size_t)j * 144 + i];
+        for (int j = j_begin; j < j_end; ++j) hsum -= schur[(size_t)j * 144 + i];
         h11s[i] = hsum;
     }
     __syncthreads();
@@ -301,6 +307,19 @@ __global__ __launch_bounds__(64) void k_sparsify(int npairs, const double* __res
 }
 
 }  // namespace
+
+namespace se2gpu {
+
+int launch_sparsify(hipStream_t st, int npairs, const double* d_kf12, const int* d_mp_ptr, const double* d_mp_xyz, const int* d_mm_ptr,
+                    const int* d_m_kf, const double* d_m_info, const int* d_ord_ptr, const int* d_ord, double* d_kf_blk,
+                    double* d_schur, const int* d_mp_cnt, double* d_z_out, double* d_info_out) {
+    hipLaunchKernelGGL(k_sparsify, dim3(npairs), dim3(64), 0, st, npairs, d_kf12, d_mp_ptr, d_mp_xyz, d_mm_ptr, d_m_kf, d_m_info,
+                       d_ord_ptr, d_ord, d_kf_blk, d_schur, d_mp_cnt, d_z_out, d_info_out);
+    SE2_HIP(hipGetLastError());
+    return SE2GPU_OK;
+}
+
+}  // namespace se2gpu
 
 extern "C" {
 
@@ -369,9 +388,8 @@ int se2gpu_sparsify_se3xyz(int npairs, const double* kf12, const int32_t* mp_ptr
     SE2_CHECK(d_schur.reserve((size_t)std::max(NP, 1) * 144));
     SE2_CHECK(d_z.reserve(12 * (size_t)npairs));
     SE2_CHECK(d_out.reserve(36 * (size_t)npairs));
-    hipLaunchKernelGGL(k_sparsify, dim3(npairs), dim3(64), 0, st, npairs, d_kf.p, d_mpp.p, d_mp.p, d_mmp.p, d_mkf.p, d_info.p,
-                       d_ordp.p, d_ord.p, d_blk.p, d_schur.p, d_z.p, d_out.p);
-    SE2_HIP(hipGetLastError());
+    SE2_CHECK(launch_sparsify(st, npairs, d_kf.p, d_mpp.p, d_mp.p, d_mmp.p, d_mkf.p, d_info.p, d_ordp.p, d_ord.p, d_blk.p, d_schur.p,
+                              nullptr, d_z.p, d_out.p));
     SE2_HIP(hipMemcpyAsync(z_out12, d_z.p, 12 * (size_t)npairs * 8, hipMemcpyDeviceToHost, st));
     SE2_HIP(hipMemcpyAsync(info_out36, d_out.p, 36 * (size_t)npairs * 8, hipMemcpyDeviceToHost, st));
     SE2_HIP(hipStreamSynchronize(st));

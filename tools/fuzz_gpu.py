@@ -18,7 +18,7 @@ from se2lam_amd.optimizer import SlamOptimizer  # noqa: E402
 from se2lam_amd.orb import ORBextractor  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(12))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path
+KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(13))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
 tex = synth.texture()
@@ -280,6 +280,34 @@ while time.time() < t_end:
             if not ok or path != 2:
                 print(got, want, ref["trials_hist"][:n])
                 sys.exit(1)
+        continue
+    if kind == 12:   # GlobalMapper::CreateFeatEdge: random N, mode and perturbation; the comparison is tests/test_feat_edge_gpu.py's
+        tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+        if tests_dir not in sys.path:
+            sys.path.insert(0, tests_dir)
+        import feat_edge_cases as fc
+        import feat_edge_model as fm
+        from se2lam_amd import feat_edge as fe
+        mode = int(rng.integers(0, 2))
+        lo = fe.COVIS_MIN_POINTS if mode == fe.COVIS else fe.MATCH_MIN_POINTS
+        spec = [dict(N=int(rng.integers(lo, 200)), seed=int(rng.integers(0, 10**6)), kf_sigma=(float(rng.uniform(1, 40)), float(rng.uniform(5e-4, 1e-2))),
+                     mp_sigma=float(rng.uniform(1, 80))) for _ in range(int(rng.integers(1, 9)))]
+        for sp in spec:
+            sp["n_outliers"] = int(rng.integers(0, sp["N"] // 6 + 1)) if mode == fe.MATCH else 0
+        cases = [fc.make_pair(**sp) for sp in spec]
+        got = fe.CreateFeatEdgeBatch([fc.as_tuple(c) for c in cases], mode)
+        for sp, c, r in zip(spec, cases, got):
+            m = fm.optimize(fm.Problem(c["kf"], c["mp"], c["z"], c["info"], mode), fe.COVIS_ITERS if mode == fe.COVIS else fe.MATCH_ITERS)
+            if not fm.inputs_ok(m, mode):   # an edge at the rejection threshold, or fewer than 10 comparable iterations: not a case
+                print(f"featedge mode {mode} {sp}: skipped (the model's conditions on the inputs do not hold)")
+                continue
+            try:
+                fm.check_against_model(r, c, m, mode, oracle, f"featedge mode {mode} N {sp['N']} seed {sp['seed']}")
+            except AssertionError:
+                import traceback
+                traceback.print_exc()
+                fail(f"featedge mode {mode} {sp}")
+        print(f"featedge mode {mode} {len(spec)} pairs: ok")
         continue
     if kind == 1:
         W, H = int(rng.integers(160, 900)), int(rng.integers(120, 700))
