@@ -176,6 +176,21 @@ int se2gpu_match_projection(se2gpu_matcher* h, const se2gpu_frame_bounds* bounds
                             const se2gpu_keypoint* kps, const uint8_t* desc, const uint8_t* kf_observed, int n,
                             int win_size, int level_offset, float nnratio, int32_t* match_idx_mp, int* n_matches);
 
+/* se2gpu_match_projection with every array in device memory, where se2gpu_mappoint_main_batch_device (d_mp_desc,
+ * d_mp_octave) and the extractor (d_kps, d_desc of one frame) left them; Tcw (12 host floats) and the intrinsics travel by
+ * value.  d_match_idx_mp: n ints, d_n_matches: one int, both device memory.  The same three launches as the host-buffer
+ * call, asynchronous on the matcher's stream: no staging copy, no read-back and no wait; se2gpu_matcher_sync waits for it.
+ * n == 0 only clears *d_n_matches.  The spill flag of the call (a query with more than 128 candidates) stays in the handle
+ * until the next se2gpu_matcher_sync, which adds it to se2gpu_matcher_spill_calls; calls between two syncs count once.
+ * SE2GPU_ERR_INVALID: a NULL handle, bounds, Tcw, d_n_matches or needed array; SE2GPU_ERR_CAPACITY: n > max_features. */
+int se2gpu_match_projection_device(se2gpu_matcher* h, const se2gpu_frame_bounds* bounds,
+                                   const float* d_mp_pos, const uint8_t* d_mp_desc, const int32_t* d_mp_octave,
+                                   const uint8_t* d_mp_skip, int m,
+                                   const float* Tcw, float fx, float fy, float cx, float cy,
+                                   const se2gpu_keypoint* d_kps, const uint8_t* d_desc, const uint8_t* d_kf_observed, int n,
+                                   int win_size, int level_offset, float nnratio,
+                                   int32_t* d_match_idx_mp, int32_t* d_n_matches);
+
 /* SearchByBoW(pKF1, pKF2, mapMatches12, bIfMPOnly) with ORBmatcher(nnratio, checkOri) - ORBmatcher.cpp:128-276.
  * The DBoW2::FeatureVector of each key frame (std::map<NodeId, std::vector<unsigned>>, computed by the host
  * vocabulary) is passed as CSR: fv_nodes[nn] ascending node ids, fv_ptr[nn+1], fv_idx[fv_ptr[nn]] feature indices.
@@ -218,6 +233,50 @@ int se2gpu_search_by_bow_batch_device(se2gpu_matcher* h,
                                       const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs,
                                       int mp_only, float nnratio, int check_orientation,
                                       int32_t* d_matches12, int32_t* d_nmatches);
+
+/* MapPoint::updateMainKFandDescriptor (src/MapPoint.cpp:228-292 of the reference) for a batch of m map points whose
+ * observations lie in the frame arrays se2gpu_orb_extract_batch_device writes (d_kps from f * cap, d_desc from f * cap * 32,
+ * d_counts[f]; descriptors 8-byte aligned).  Every pointer is device memory except scale_factors.
+ *   d_frame_null   nframes bytes or NULL: 1 = KeyFrame::isNull() (:242)
+ *   d_view_pos     nframes * cap * 3 floats or NULL: KeyFrame::mViewMPs[idx] (:287); NULL writes no distances
+ *   scale_factors  HOST array of nlevels floats, mvScaleFactors (:286, :291); read during the call, needed with d_view_pos
+ *   d_mp_ptr (m + 1), d_obs_frame / d_obs_ftr (nobs each): the observations in CSR form, point p owns entries
+ *                  d_mp_ptr[p] .. d_mp_ptr[p + 1] - 1.  ORDER MATTERS: list a point's observations in the order the caller's
+ *                  container iterates them (the reference's std::map<PtrKeyFrame, int>, include/se2lam/MapPoint.h:86,
+ *                  iterates in the order of the shared pointers' addresses).  On equal medians the earliest observation of the list wins, as `median < bestMedian`
+ *                  (:272) lets the first one iterated win; another order can pick another main key frame.
+ *   d_prev_main_frame  m ints or NULL: the frame of the point's mMainKF before the call, -1 = none (:280)
+ * Per point: an observation is valid when its frame lies in 0..nframes-1, the frame is not null and its feature lies in
+ * 0..min(counts, cap)-1; the others are skipped (nothing is indexed outside the arrays whatever they hold; d_mp_ptr values
+ * are clamped to 0..nobs and a descending segment is empty).  Over the N valid ones in list order, D[i][j] = 256-bit Hamming
+ * distance, median of row i = element (N-1)/2 of the row sorted ascending (self-distance 0 included), main observation =
+ * the first i whose median is strictly smaller than every earlier one.
+ *   d_info[4p..]       {place of the main observation in the point's list (skipped entries counted), its median, N, changed};
+ *                      {-1, 0, 0, 0} and nothing else written when N == 0
+ *   d_main_desc[32p..] its descriptor, always (:278);  d_main_frame[p] its frame
+ *   changed            bit 0: the frame differs from d_prev_main_frame[p] (or that array is NULL).  Only then (:280 returns
+ *                      early otherwise and the old values stay):
+ *   d_main_octave[p]   = kps.octave (:285)
+ *   d_dist[2p..]       = {mMinDist, mMaxDist} (:290-291): dist = (float)sqrt((double)x*x + (double)y*y + (double)z*z) with a
+ *                      correctly rounded FP64 square root, max = dist * scale_factors[octave], min = max /
+ *                      scale_factors[nlevels - 1], in float.  An octave outside 0..nlevels-1 leaves them untouched and sets
+ *                      bit 1 of changed (with or without d_view_pos).
+ * A point's outputs depend on its own list only: not on the batch, its place in it or the run.
+ * Asynchronous on the matcher's stream: nothing is read back and nothing waits; se2gpu_matcher_sync waits for it.  The call
+ * needs no scratch memory.
+ * The argument checks come first and touch neither the handle nor a device:
+ * SE2GPU_ERR_INVALID: a NULL handle, d_kps, d_desc, d_counts, d_mp_ptr or output (d_dist only with d_view_pos); nobs > 0
+ *   without d_obs_frame / d_obs_ftr; m < 0, nobs < 0, cap < 1, nframes < 1, nlevels < 1; d_view_pos without scale_factors.
+ * SE2GPU_ERR_CAPACITY: nlevels > 32 (the factors are kernel arguments); nframes * cap > 2^31 - 1.
+ * m == 0 is SE2GPU_OK and launches nothing. */
+int se2gpu_mappoint_main_batch_device(se2gpu_matcher* h,
+                                      const se2gpu_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_counts, int cap,
+                                      int nframes, const uint8_t* d_frame_null, const float* d_view_pos,
+                                      const float* scale_factors, int nlevels,
+                                      const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr,
+                                      int m, int nobs, const int32_t* d_prev_main_frame,
+                                      int32_t* d_info, uint8_t* d_main_desc, int32_t* d_main_frame, int32_t* d_main_octave,
+                                      float* d_dist);
 
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by

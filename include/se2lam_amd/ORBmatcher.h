@@ -148,6 +148,21 @@ public:
                                                 d_matches12, d_nmatches),
               "ORBmatcher::SearchByBoWBatchDevice");
     }
+    // MatchByProjection with every array in device memory (se2gpu_match_projection_device): localMPs.mainDescriptor and
+    // .mainOctave may be the arrays MapPointTable::updateMainBatchDevice (MapPointMain.h) has just written on this matcher's
+    // stream; newKF.keyPointsUn / descriptors / observed are device pointers, newKF.Tcw and the intrinsics host values.
+    // d_vMatchesIdxMP: newKF.N ints, d_nmatches: one int.  Asynchronous: sync() before they are read.
+    void MatchByProjectionDevice(const FrameView& newKF, const MapPointView& localMPs, const int winSize, const int levelOffset,
+                                 int32_t* d_vMatchesIdxMP, int32_t* d_nmatches) {
+        se2gpu_frame_bounds b{newKF.minXUn, newKF.minYUn, newKF.maxXUn, newKF.maxYUn};
+        check(se2gpu_match_projection_device(h_, &b, localMPs.pos, localMPs.mainDescriptor, localMPs.mainOctave, localMPs.skip,
+                                             localMPs.M, newKF.Tcw, newKF.fx, newKF.fy, newKF.cx, newKF.cy,
+                                             reinterpret_cast<const se2gpu_keypoint*>(newKF.keyPointsUn), newKF.descriptors,
+                                             newKF.observed, newKF.N, winSize, levelOffset, mfNNratio, d_vMatchesIdxMP,
+                                             d_nmatches),
+              "ORBmatcher::MatchByProjectionDevice");
+    }
+    se2gpu_matcher* handle() const { return h_; }   // for the batch calls that run on a matcher (MapPointMain.h)
     void sync() { check(se2gpu_matcher_sync(h_), "ORBmatcher::sync"); }
     void setStream(void* hipStream) { check(se2gpu_matcher_set_stream(h_, hipStream), "ORBmatcher::setStream"); }
 

@@ -31,6 +31,7 @@ PER_FILE = {
     "ransac.hip": ["-ffp-contract=off"],
     "bow.hip": ["-ffp-contract=off"],        # BowVector values and scores equal the host vocabulary's to the bit
     "voc_train.hip": ["-ffp-contract=off"],  # cut_d = u * sum is one IEEE multiply on host and device
+    "mappoint.hip": ["-ffp-contract=off"],   # mMinDist / mMaxDist are IEEE operations, equal to the host's to the bit
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
 }
 

@@ -142,6 +142,10 @@ SYMBOLS = {
                                                _VP, _VP]),
     "se2gpu_match_projection": (_I, [_VP, C.POINTER(FrameBounds), _VP, _VP, _VP, _VP, _I, _VP, _F, _F, _F, _F,
                                      _VP, _VP, _VP, _I, _I, _I, _F, _VP, C.POINTER(_I)]),
+    "se2gpu_match_projection_device": (_I, [_VP, C.POINTER(FrameBounds), _VP, _VP, _VP, _VP, _I, _VP, _F, _F, _F, _F,
+                                            _VP, _VP, _VP, _I, _I, _I, _F, _VP, _VP]),
+    "se2gpu_mappoint_main_batch_device": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP,
+                                               _VP, _VP, _VP, _VP, _VP]),
     # BA
     "se2gpu_ba_create": (_I, [C.POINTER(_VP)]),
     "se2gpu_ba_reserve": (_I, [_I, _I, _I]),

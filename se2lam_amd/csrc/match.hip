@@ -927,6 +927,7 @@ struct se2gpu_matcher {
     DevBuf<int> fvp1, fvi1, fvp2, fvi2, bin_of, hist;
     DevBuf<int2> node_pairs;
     DevBuf<int> n_node_pairs;     // se2gpu_search_by_bow_batch_device: equal nodes per key-frame pair
+    DevBuf<int> proj_n;           // se2gpu_match_projection_device: the key frame's feature count where k_grid_order reads it
     // single-call paths (host buffers in, host buffers out): one packed block each way
     PinBuf<uint8_t> stage_h;
     DevBuf<uint8_t> stage_d;
@@ -1008,6 +1009,45 @@ int window_batch(se2gpu_matcher* h, const Bounds& bd, const se2gpu_keypoint* d_k
                        d_pair_b, h->cand.p, h->ncand.p, nnratio, cand_lds, d_matches12, d_prev, d_nmatches, d_overflow, bd, d_desc,
                        (const uint32_t*)h->sorted.p, (const int*)h->n_grid.p, win, level_offset, min_level, max_level, h->spill.p,
                        spill_cap, h->spill_place.p);
+    SE2_HIP(hipGetLastError());
+    return SE2GPU_OK;
+}
+
+// MatchByProjection of m map points into one key frame of n >= 1 features, every array in device memory: the three launches
+// se2gpu_match_projection and se2gpu_match_projection_device share.  d_n holds n (k_grid_order reads its count from memory).
+int projection_launch(se2gpu_matcher* h, const Bounds& bd, const ProjCam& cam, const float* d_mp_pos, const uint8_t* d_mp_desc,
+                      const int* d_mp_octave, const uint8_t* d_mp_skip, int m, const se2gpu_keypoint* d_kps,
+                      const uint8_t* d_desc, const uint8_t* d_kf_obs, int n, const int* d_n, int win_size, int level_offset,
+                      float nnratio, int* d_match_idx, int* d_nmatches, int* d_overflow) {
+    hipStream_t st = h->stream;
+    const int mm = std::max(m, 1);
+    SE2_CHECK(h->sorted.reserve((size_t)n));
+    SE2_CHECK(h->n_grid.reserve(kGridRec));
+    SE2_CHECK(h->cand.reserve((size_t)mm * kMaxCand));
+    SE2_CHECK(h->ncand.reserve((size_t)mm));
+    SE2_CHECK(h->proj_xy.reserve(2 * (size_t)mm));
+    const int chunk = 1024;
+    constexpr size_t kLdsBudget = kResolveLds;
+    const size_t nE = ((size_t)n + 3) & ~(size_t)3;
+    const size_t fixed_lds = (3 * nE + 6 * (size_t)chunk + 8) * sizeof(int);
+    SE2_REQUIRE(fixed_lds + 4096 <= kLdsBudget, SE2GPU_ERR_CAPACITY, "%d key-frame features need %zu B of LDS", n, fixed_lds);
+    const int cand_lds = (int)((kLdsBudget - 1024 - fixed_lds) / sizeof(int));
+    const int spill_cap = 16 * std::max(n, 1024);   // per chunk of 1024 map points
+    SE2_CHECK(h->spill.reserve((size_t)spill_cap));
+    SE2_CHECK(h->spill_place.reserve((size_t)mm));
+    SE2_CHECK(lds_attributes());
+    hipLaunchKernelGGL(k_grid_order, dim3(1), dim3(256), 0, st, bd, d_kps, d_n, (const int*)nullptr, n, h->sorted.p,
+                       h->n_grid.p);
+    if (m) {
+        const int qpb = kCandQueriesSingle;
+        hipLaunchKernelGGL(k_cand_projection, dim3((m + qpb - 1) / qpb), dim3(256), (size_t)n * 16, st, bd, cam, d_mp_pos,
+                           d_mp_desc, d_mp_octave, d_mp_skip, m, d_kps, d_desc, d_kf_obs, h->sorted.p, h->n_grid.p, win_size,
+                           level_offset, h->cand.p, h->ncand.p, n, qpb, h->proj_xy.p);
+    }
+    hipLaunchKernelGGL(k_resolve_projection, dim3(1), dim3(1024), fixed_lds + (size_t)cand_lds * sizeof(int), st, d_kps, n, m,
+                       h->cand.p, h->ncand.p, nnratio, chunk, cand_lds, d_match_idx, d_nmatches, d_overflow, bd, d_desc,
+                       d_kf_obs, (const uint32_t*)h->sorted.p, (const int*)h->n_grid.p, (const float*)h->proj_xy.p, d_mp_desc,
+                       d_mp_octave, win_size, level_offset, h->spill.p, spill_cap, h->spill_place.p);
     SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
 }
@@ -1188,11 +1228,6 @@ int se2gpu_match_projection(se2gpu_matcher* h, const se2gpu_frame_bounds* bounds
                 SE2GPU_ERR_INVALID, "match_projection: NULL buffer");
     hipStream_t st = h->stream;
     const int mm = std::max(m, 1);
-    SE2_CHECK(h->sorted.reserve((size_t)n));
-    SE2_CHECK(h->n_grid.reserve(kGridRec));
-    SE2_CHECK(h->cand.reserve((size_t)mm * kMaxCand));
-    SE2_CHECK(h->ncand.reserve((size_t)mm));
-    SE2_CHECK(h->proj_xy.reserve(2 * (size_t)mm));
     // one block both ways: [match_idx (n) | nmatches, overflow, count | kps | desc | kf_obs | mp_pos | mp_octave | mp_desc | mp_skip]
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_m = 0, o_sc = up16((size_t)n * sizeof(int)), o_kps = o_sc + 16;
@@ -1216,40 +1251,13 @@ int se2gpu_match_projection(se2gpu_matcher* h, const se2gpu_frame_bounds* bounds
         std::memcpy(hs + o_skip, mp_skip, (size_t)m);
     }
     SE2_HIP(hipMemcpyAsync(ds + o_sc, hs + o_sc, total - o_sc, hipMemcpyHostToDevice, st));
-    const se2gpu_keypoint* d_kps = (const se2gpu_keypoint*)(ds + o_kps);
     int* d_sc = (int*)(ds + o_sc);
-    const Bounds bd = make_bounds(*bounds);
     ProjCam cam;
     std::memcpy(cam.T, Tcw, sizeof(cam.T));
     cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
-    hipLaunchKernelGGL(k_grid_order, dim3(1), dim3(256), 0, st, bd, d_kps, d_sc + 2, (const int*)nullptr, n, h->sorted.p,
-                       h->n_grid.p);
-    if (m) {
-        SE2_CHECK(lds_attributes());
-        const int qpb = kCandQueriesSingle;
-        hipLaunchKernelGGL(k_cand_projection, dim3((m + qpb - 1) / qpb), dim3(256), (size_t)n * 16, st, bd, cam,
-                           (const float*)(ds + o_pos), ds + o_mdesc, (const int*)(ds + o_oct), ds + o_skip, m, d_kps,
-                           ds + o_desc, ds + o_obs, h->sorted.p, h->n_grid.p, win_size, level_offset, h->cand.p, h->ncand.p,
-                           n, qpb, h->proj_xy.p);
-    }
-    {
-        const int chunk = 1024;
-        constexpr size_t kLdsBudget = kResolveLds;
-        const size_t nE = ((size_t)n + 3) & ~(size_t)3;
-        const size_t fixed_lds = (3 * nE + 6 * (size_t)chunk + 8) * sizeof(int);
-        SE2_REQUIRE(fixed_lds + 4096 <= kLdsBudget, SE2GPU_ERR_CAPACITY, "%d key-frame features need %zu B of LDS", n, fixed_lds);
-        SE2_CHECK(lds_attributes());
-        const int cand_lds = (int)((kLdsBudget - 1024 - fixed_lds) / sizeof(int));
-        const int spill_cap = 16 * std::max(n, 1024);   // per chunk of 1024 map points
-        SE2_CHECK(h->spill.reserve((size_t)spill_cap));
-        SE2_CHECK(h->spill_place.reserve((size_t)std::max(m, 1)));
-        hipLaunchKernelGGL(k_resolve_projection, dim3(1), dim3(1024), fixed_lds + (size_t)cand_lds * sizeof(int), st, d_kps,
-                           n, m, h->cand.p, h->ncand.p, nnratio, chunk, cand_lds, (int*)(ds + o_m), d_sc, d_sc + 1, bd,
-                           (const uint8_t*)(ds + o_desc), (const uint8_t*)(ds + o_obs), (const uint32_t*)h->sorted.p,
-                           (const int*)h->n_grid.p, (const float*)h->proj_xy.p, (const uint8_t*)(ds + o_mdesc),
-                           (const int*)(ds + o_oct), win_size, level_offset, h->spill.p, spill_cap, h->spill_place.p);
-    }
-    SE2_HIP(hipGetLastError());
+    SE2_CHECK(projection_launch(h, make_bounds(*bounds), cam, (const float*)(ds + o_pos), ds + o_mdesc, (const int*)(ds + o_oct),
+                                ds + o_skip, m, (const se2gpu_keypoint*)(ds + o_kps), ds + o_desc, ds + o_obs, n, d_sc + 2,
+                                win_size, level_offset, nnratio, (int*)(ds + o_m), d_sc, d_sc + 1));
     SE2_HIP(hipMemcpyAsync(hs, ds, o_kps, hipMemcpyDeviceToHost, st));
     SE2_HIP(hipStreamSynchronize(st));
     const int* r = (const int*)(hs + o_sc);
@@ -1257,6 +1265,34 @@ int se2gpu_match_projection(se2gpu_matcher* h, const se2gpu_frame_bounds* bounds
     *n_matches = r[0];
     if (r[1]) ++h->spill_calls;
     return SE2GPU_OK;
+}
+
+// se2gpu_match_projection with every array where it lies in device memory: no staging block, no read-back, no wait.  The
+// spill flag goes to the handle's counter word, which the next se2gpu_matcher_sync folds into se2gpu_matcher_spill_calls.
+int se2gpu_match_projection_device(se2gpu_matcher* h, const se2gpu_frame_bounds* bounds, const float* d_mp_pos,
+                                   const uint8_t* d_mp_desc, const int32_t* d_mp_octave, const uint8_t* d_mp_skip, int m,
+                                   const float* Tcw, float fx, float fy, float cx, float cy, const se2gpu_keypoint* d_kps,
+                                   const uint8_t* d_desc, const uint8_t* d_kf_observed, int n, int win_size,
+                                   int level_offset, float nnratio, int32_t* d_match_idx_mp, int32_t* d_n_matches) {
+    SE2_REQUIRE(h && bounds && d_n_matches && Tcw, SE2GPU_ERR_INVALID, "match_projection_device: NULL argument");
+    SE2_REQUIRE(n >= 0 && n <= h->max_features && m >= 0, SE2GPU_ERR_CAPACITY,
+                "match_projection_device: %d features exceed %d", n, h->max_features);
+    SE2_REQUIRE(n == 0 || (d_kps && d_desc && d_kf_observed && d_match_idx_mp &&
+                           (m == 0 || (d_mp_pos && d_mp_desc && d_mp_octave && d_mp_skip))),
+                SE2GPU_ERR_INVALID, "match_projection_device: NULL buffer");
+    hipStream_t st = h->stream;
+    if (n == 0) {
+        SE2_HIP(hipMemsetAsync(d_n_matches, 0, sizeof(int32_t), st));
+        return SE2GPU_OK;
+    }
+    SE2_CHECK(h->proj_n.reserve(1));
+    SE2_HIP(hipMemsetD32Async((hipDeviceptr_t)h->proj_n.p, n, 1, st));
+    ProjCam cam;
+    std::memcpy(cam.T, Tcw, sizeof(cam.T));
+    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
+    return projection_launch(h, make_bounds(*bounds), cam, d_mp_pos, d_mp_desc, d_mp_octave, d_mp_skip, m, d_kps, d_desc,
+                             d_kf_observed, n, h->proj_n.p, win_size, level_offset, nnratio, d_match_idx_mp, d_n_matches,
+                             h->overflow.p);
 }
 
 int se2gpu_search_by_bow(se2gpu_matcher* h, const se2gpu_keypoint* kps1, const uint8_t* desc1, int n1,

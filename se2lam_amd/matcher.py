@@ -116,6 +116,20 @@ class ORBmatcher:
                                                                 npairs, int(bIfMPOnly), self.mfNNratio, int(checkOri),
                                                                 d_matches12, d_nmatches))
 
+    def match_projection_device(self, d_mp_pos, d_mp_desc, d_mp_octave, d_mp_skip, m, Tcw, K4, d_kps, d_desc,
+                                d_kf_observed, n, winSize, levelOffset, d_match_idx_mp, d_n_matches, frame_bounds=None):
+        """se2gpu_match_projection_device: MatchByProjection with every array a device pointer (d_mp_desc / d_mp_octave may
+        be what mappoint.update_main_batch_device has just written on this matcher's stream); Tcw and K4 = (fx, fy, cx, cy)
+        are host values.  Asynchronous: sync() before d_match_idx_mp (n ints) and d_n_matches (one int) are read; the
+        spill counter moves at that sync."""
+        fb = frame_bounds or bounds()
+        Tcw = np.ascontiguousarray(Tcw, np.float32).reshape(-1)[:12].copy()
+        fx, fy, cx, cy = [float(v) for v in K4]
+        capi.check(capi.lib().se2gpu_match_projection_device(self._h, C.byref(fb), d_mp_pos, d_mp_desc, d_mp_octave,
+                                                             d_mp_skip, m, Tcw.ctypes.data, fx, fy, cx, cy, d_kps, d_desc,
+                                                             d_kf_observed, n, winSize, levelOffset, self.mfNNratio,
+                                                             d_match_idx_mp, d_n_matches))
+
     def sync(self):
         capi.check(capi.lib().se2gpu_matcher_sync(self._h))
 

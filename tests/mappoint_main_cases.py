@@ -1,0 +1,59 @@
+"""The frame set and observation lists the tests of se2gpu_mappoint_main_batch_device share (numpy only): 136 frames of up to
+16 features whose descriptors are noisy copies of 50 landmark descriptors, so that a random list mixes small and large
+distances and equal medians occur."""
+import numpy as np
+
+NFRAMES, CAP, NLEVELS = 136, 16, 8
+KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+               ("class_id", "<i4")])
+SCALE = (np.float32(1.2) ** np.arange(NLEVELS)).astype(np.float32)
+# the observation counts of the issue: every sub-wave group edge (8, 16, 32), the wave (64) and the tile edge, one past each
+BATCH_N = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 130)
+
+
+class FrameSet:
+    def __init__(self, seed=7):
+        rng = np.random.default_rng(seed)
+        n = NFRAMES * CAP
+        self.counts = rng.integers(10, CAP + 1, NFRAMES).astype(np.int32)
+        self.counts[:4] = (CAP, CAP + 3, 10, 0)              # a count beyond cap is clamped; an empty frame
+        self.kps = np.zeros(n, KP)
+        self.kps["octave"] = rng.integers(0, NLEVELS, n)
+        land = rng.integers(0, 256, (50, 32), dtype=np.uint8)
+        noise = np.packbits(rng.random((n, 256)) < 0.04, axis=1)
+        self.desc = land[rng.integers(0, 50, n)] ^ noise
+        self.view = (rng.standard_normal((n, 3)) * 4).astype(np.float32)
+        self.null = np.zeros(NFRAMES, np.uint8)
+        self.pairs = np.array([(f, k) for f in range(NFRAMES) for k in range(min(int(self.counts[f]), CAP))], np.int32)
+
+    def pick(self, rng, n):
+        """n distinct valid observations in random order -> (frames, features)"""
+        sel = self.pairs[rng.choice(len(self.pairs), n, replace=False)]
+        return sel[:, 0].copy(), sel[:, 1].copy()
+
+    def model_args(self, null=None, view=True):
+        return dict(kps=self.kps, desc=self.desc, counts=self.counts, cap=CAP, nframes=NFRAMES,
+                    frame_null=self.null if null is None else null, view_pos=self.view if view else None, scale_factors=SCALE,
+                    nlevels=NLEVELS)
+
+
+def first_batch(fs, seed=11):
+    """two points of every count in BATCH_N, a point without observations and three more: 40 lists"""
+    rng = np.random.default_rng(seed)
+    lists = [fs.pick(rng, n) for n in BATCH_N for _ in range(2)]
+    lists.insert(5, (np.zeros(0, np.int32), np.zeros(0, np.int32)))
+    lists += [fs.pick(rng, n) for n in (6, 12, 40)]
+    return lists
+
+
+def csr(lists):
+    ptr = np.zeros(len(lists) + 1, np.int32)
+    ptr[1:] = np.cumsum([len(f) for f, _ in lists])
+    cat = lambda j: np.concatenate([np.asarray(l[j], np.int32) for l in lists] + [np.zeros(0, np.int32)]).astype(np.int32)
+    return ptr, cat(0), cat(1)
+
+
+def sentinels(m):
+    return dict(info=np.full((m, 4), -9, np.int32), main_desc=np.full((m, 32), 0xAB, np.uint8),
+                main_frame=np.full(m, -55, np.int32), main_octave=np.full(m, -77, np.int32),
+                dist=np.full((m, 2), -1.0, np.float32))

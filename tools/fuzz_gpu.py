@@ -18,7 +18,7 @@ from se2lam_amd.optimizer import SlamOptimizer  # noqa: E402
 from se2lam_amd.orb import ORBextractor  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(13))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints
+KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(14))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints; 13 = map points' main key frame
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
 tex = synth.texture()
@@ -308,6 +308,43 @@ while time.time() < t_end:
                 traceback.print_exc()
                 fail(f"featedge mode {mode} {sp}")
         print(f"featedge mode {mode} {len(spec)} pairs: ok")
+        continue
+    if kind == 13:   # MapPoint::updateMainKFandDescriptor: random observation lists, planted duplicate descriptors, against the numpy model
+        tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+        if tests_dir not in sys.path:
+            sys.path.insert(0, tests_dir)
+        import mappoint_main_model as mm
+        from se2lam_amd import capi, mappoint as mpt
+        nf, cap, nl = int(rng.integers(1, 200)), int(rng.integers(1, 33)), int(rng.integers(1, 9))
+        n = nf * cap
+        counts = rng.integers(0, cap + 3, nf).astype(np.int32)
+        kps = np.zeros(n, capi.KP_DTYPE)
+        kps["octave"] = rng.integers(-1, nl + 1, n)
+        ndist = int(rng.choice([1, 2, 3, 8, 50, n]))     # few distinct descriptors: many rows share the least median
+        desc = rng.integers(0, 256, (ndist, 32), dtype=np.uint8)[rng.integers(0, ndist, n)]
+        desc ^= np.packbits(rng.random((n, 256)) < float(rng.choice([0.0, 0.0, 0.02, 0.2])), axis=1)
+        view = (rng.standard_normal((n, 3)) * float(rng.uniform(0.1, 100))).astype(np.float32)
+        null = (rng.random(nf) < float(rng.choice([0.0, 0.1, 0.9]))).astype(np.uint8)
+        sf = (np.float32(rng.uniform(1.05, 1.5)) ** np.arange(nl)).astype(np.float32)
+        m = int(rng.integers(1, 300))
+        lens = np.where(rng.random(m) < 0.03, rng.integers(60, 400, m), np.minimum(rng.geometric(1 / 6.0, m) - 1, 70))
+        lists = [(rng.integers(-1, nf + 1, L).astype(np.int32), rng.integers(-1, cap + 1, L).astype(np.int32)) for L in lens]
+        prev = rng.integers(-1, nf, m).astype(np.int32) if rng.random() < 0.7 else None
+        with_view = bool(rng.random() < 0.8)
+        frames = mpt.DeviceFrames(kps, desc, counts, cap, null, view)
+        batch = mpt.MainBatch(lists, prev)
+        mt = ORBmatcher()
+        batch.run(mt, frames, sf, with_view)
+        got = batch.download(mt)
+        ptr, fr, ft = mpt.csr(lists)
+        want = mm.update_main_batch(kps, desc, counts, cap, nf, null, view if with_view else None, sf, nl, ptr, fr, ft, prev,
+                                    mpt.sentinels(m))
+        ok = all(np.array_equal(got[k], want[k]) for k in ("info", "main_desc", "main_frame", "main_octave")) and \
+            np.array_equal(got["dist"].view(np.uint32), want["dist"].view(np.uint32))
+        print(f"mappoint main {nf} frames x {cap}, {m} points, {len(fr)} observations (longest {int(lens.max())}), {ndist} descriptors: "
+              f"{int((want['info'][:, 0] >= 0).sum())} with a main {'ok' if ok else ''}")
+        if not ok:
+            fail("mappoint main")
         continue
     if kind == 1:
         W, H = int(rng.integers(160, 900)), int(rng.integers(120, 700))
