@@ -278,6 +278,113 @@ int se2gpu_mappoint_main_batch_device(se2gpu_matcher* h,
                                       int32_t* d_info, uint8_t* d_main_desc, int32_t* d_main_frame, int32_t* d_main_octave,
                                       float* d_dist);
 
+/* MapPoint::updateParallax (src/MapPoint.cpp:124-185 of the reference), the rule every MapPoint::addObservation runs, for a
+ * batch of m map points.  The sibling of se2gpu_mappoint_main_batch_device: the same frame layout and the same observation
+ * CSR (d_mp_ptr, d_obs_frame, d_obs_ftr in the caller's container order).  Every pointer is device memory.
+ *   d_kps_un       nframes * cap: keyPointsUn (x, y are read); may be the extractor's d_kps itself
+ *   d_counts       nframes
+ *   d_frame_Tcw, d_frame_Twc, d_frame_P   nframes x 12 floats each: rows 0-2 (row-major) of Tcw, of cvu::inv(Tcw) and of
+ *                  Kcam * Tcw.  The inverse and the projection come from the caller; the camera centre is column 3 of Twc
+ *   d_frame_idkf   nframes ints: mIdKF
+ *   d_good_prl     m bytes: mbGoodParallax before the call
+ *   d_new_frame    m ints: the frame of pKF, the observation just added
+ *   fx, lower_depth, upper_depth   Config::fxCam, LOWER_DEPTH, UPPER_DEPTH
+ *   d_kf_observed  nframes * cap bytes or NULL, in/out: KeyFrame::hasObservation(idx)
+ * Per point p: an entry is valid when its frame lies in 0..nframes-1 and its feature in 0..min(counts, cap)-1; the others
+ * are skipped and not counted (a null key frame is NOT skipped: the reference does not skip it here).  N = valid entries.
+ *   status 0, nothing done: d_good_prl[p] set, N <= 2 (:125), or no valid entry of d_new_frame[p] (pKF = the first one).
+ *   pKF0 = the valid entry with the smallest idkf among those with idkf(pKF) - idkf(entry) <= 6, the first in list order on
+ *          equal ids (:129-139).
+ *   pKF0's frame is pKF's: status 3 (the reference triangulates a ray against itself, fails the parallax test, age 0).
+ *   Otherwise (:142-153) posW = cvu::triangulate(pt0, pt1, P0, P1) - rows in float, one-sided Jacobi in FP64, dehomogenised
+ *   in float, as se2gpu_triangulate -, pos0 / pos1 = cvu::se3map, Config::acceptDepth on both depths, cvu::checkParallax
+ *   against 0.9994f.
+ *   status 1, promoted (:154-177): d_pos[3p..] = posW; (info0, info1) = Track::calcSE3toXYZInfo(pos0, Tcw0, Tcw1) (float
+ *          arithmetic in the reference's order, norms, cv::Rodrigues and matrix sums in double, asinf; 3x3 row-major floats);
+ *          xyzinfoW = Rcw0^T info0 Rcw0.  For every valid entry e (index into the CSR arrays) d_obs_view[3e..] /
+ *          d_obs_info[9e..]: pKF0 gets pos0 / info0, pKF pos1 / info1, every other entry se3map(Tcw_k, posW) and
+ *          Rcw_k xyzinfoW Rcw_k^T, except an entry with the idkf of pKF or pKF0, which is left alone (:169).
+ *   status 2, abandoned (:182-184): not promoted and idkf(pKF) - idkf(pKF0) >= 6.  With d_kf_observed the byte of every
+ *          valid entry is cleared (MapPoint::setNull, :68-78).
+ *   status 3: not promoted, younger.
+ *   d_status[p], d_pkf0_place[p] (place of pKF0 in the point's list, skipped entries counted, -1 with status 0): always
+ *   written.  Nothing else is written for a point that is not promoted.
+ * A point's outputs depend on its own list only.  One thread per point, no atomics, no scratch memory.
+ * Asynchronous on the matcher's stream: nothing is read back; se2gpu_matcher_sync waits for it.
+ * The argument checks come first and touch neither the handle nor a device:
+ * SE2GPU_ERR_INVALID: a NULL handle, frame array, d_frame_idkf, d_mp_ptr, d_good_prl, d_new_frame, d_status, d_pkf0_place
+ *   or d_pos; nobs > 0 without d_obs_frame / d_obs_ftr / d_obs_view / d_obs_info; m < 0, nobs < 0, cap < 1, nframes < 1.
+ * SE2GPU_ERR_CAPACITY: nframes * cap > 2^31 - 1.   m == 0 is SE2GPU_OK and launches nothing. */
+int se2gpu_mappoint_parallax_batch_device(se2gpu_matcher* h,
+                                          const se2gpu_keypoint* d_kps_un, const int32_t* d_counts, int cap, int nframes,
+                                          const float* d_frame_Tcw, const float* d_frame_Twc, const float* d_frame_P,
+                                          const int32_t* d_frame_idkf,
+                                          const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr,
+                                          int m, int nobs, const uint8_t* d_good_prl, const int32_t* d_new_frame,
+                                          float fx, float lower_depth, float upper_depth, uint8_t* d_kf_observed,
+                                          int32_t* d_status, int32_t* d_pkf0_place, float* d_pos, float* d_obs_view,
+                                          float* d_obs_info);
+
+/* The three passes of LocalMapper::findCorrespd (src/LocalMapper.cpp:87-170) for a batch of B new key frames: which feature
+ * of the new key frame becomes an observation, with its KeyFrame::mViewMPs[idx] and mViewMPsInfo[idx].  The frame arrays,
+ * pose tables and d_kf_observed (required here) are those of se2gpu_mappoint_parallax_batch_device; d_view_pos is the
+ * mViewMPs table of se2gpu_mappoint_main_batch_device (nframes * cap * 3 floats).  Every pointer is device memory.
+ * Job b:  d_job_prev[b], d_job_new[b]  frame slots of the previous and the new key frame (different, in range; another job
+ *                                       is left with kind 0 everywhere).  THE 2 B SLOTS OF A BATCH MUST BE PAIRWISE DISTINCT:
+ *                                       a job reads and writes the kf_observed bytes of its two frames, and two jobs that
+ *                                       share a frame would do so in no defined order.  The call cannot see the slots (they
+ *                                       are device memory) and does not check this; key frames that follow one another (the
+ *                                       new one of a job being the previous one of the next) go into successive calls
+ *         d_Tcr, d_Trc (B x 12)        mNewKF->Tcr and its inverse, rows 0-2
+ *         d_matched12 (B * cap)        vMatched12 as doTriangulate left it, feature i of prev -> feature of new or -1
+ *         d_local_pos (B * cap * 3)    localMPs, in the previous key frame
+ *         d_match_idx_mp (B * cap)     the row se2gpu_match_projection_device wrote for this key frame (index into the
+ *                                       map-point table, -1 = none); needed with pass 2
+ * Map-point table (m points): d_mp_main_frame / d_mp_main_ftr / d_mp_main_octave (the main observation), d_mp_normal (m x 3,
+ * mNormalVector), d_mp_dist (m x 2, {mMinDist, mMaxDist} as se2gpu_mappoint_main_batch_device writes them).
+ * passes: bit 0, 1, 2 = pass 1, 2, 3.
+ * First inv[j] = i is built from the matched12 row into d_inv (B * cap ints, work space and output): -1 where no i with
+ * i < counts[prev] and matched12[i] in 0..counts[new]-1 points at j, the greatest such i otherwise; d_counts_out[5b + 4]
+ * counts the claims beyond the first.  The reference's input is injective after the RANSAC: a non-zero count says it was not.
+ * Then one thread per feature j < min(counts[new], cap), the passes in this order, the first that applies wins:
+ *   pass 1 (:95-107)   i = inv[j] >= 0 and kf_observed[prev][i]:  view = se3map(Tcr, mViewMPs_prev[i]), info = the second
+ *                      output of calcSE3toXYZInfo(mViewMPs_prev[i], I, Tcr).  kind 1, src = i.
+ *   pass 2 (:119-141)  kf_observed[new][j] clear on entry and q = match_idx_mp[j] in 0..m-1 with a valid main observation:
+ *                      x3d = cvu::triangulate(kps_un[main], kps_un[new][j], P_main, P_new), posNewKF = se3map(Tcw_new, x3d);
+ *                      if MapPoint::acceptNewObserve (0.866f, |octave difference| <= 2, min <= dist <= max) and
+ *                      lower_depth <= z <= upper_depth: view = posNewKF, info = the first output of
+ *                      calcSE3toXYZInfo(posNewKF, Tcw_new, Tcw_main).  kind 2, src = q.
+ *   pass 3 (:145-168)  kf_observed[new][j] clear on entry, i = inv[j] >= 0 and kf_observed[prev][i] clear:
+ *                      view = se3map(Tcr, local_pos[i]), (info_prev, info) = calcSE3toXYZInfo(local_pos[i], Tcw_prev,
+ *                      Tcw_new); d_new_pos_w[3(b cap + j)..] = se3map(Twc_prev, local_pos[i]), d_info_prev[9(b cap + j)..].
+ *                      kind 3, src = i.  (vbGoodPrl[i] was decided by doTriangulate; the caller passes it on.)
+ * Outputs per (b, j), j < cap: d_kind (byte, 0 = none) and d_src (-1 for kind 0) always; d_view (3 floats) and d_info (9,
+ * row-major) for kinds 1-3.  d_counts_out[5b + k], k = 0..3: features of kind k.  kf_observed[new][j] is set for kinds 1-3
+ * and kf_observed[prev][i] for kind 3; a thread writes only bytes it owns.  Integer atomics only: with pairwise distinct
+ * frame slots the outputs are the same in every run and wherever a job stands in the batch.
+ * A point abandoned by updateParallax inside pass 1 frees its feature before MatchByProjection looks at it
+ * (MapPoint.cpp:73-74, ORBmatcher.cpp:417), so the faithful order is: passes = 1, se2gpu_mappoint_parallax_batch_device
+ * over the tracked points that are not yet good parallax, the main descriptors, MatchByProjection, passes = 6.
+ * passes = 7 in one call is for callers with no such point pending.
+ * Asynchronous on the matcher's stream (two memsets, two launches); se2gpu_matcher_sync waits for it.
+ * The argument checks come first and touch neither the handle nor a device:
+ * SE2GPU_ERR_INVALID: a NULL handle, frame array, d_kf_observed, d_job_prev, d_job_new, d_Tcr, d_matched12, d_inv or
+ *   output; d_view_pos / d_Trc NULL with pass 1, d_match_idx_mp (or, with m > 0, the map-point table) NULL with pass 2,
+ *   d_local_pos / d_new_pos_w / d_info_prev NULL with pass 3; B < 0, m < 0, cap < 1, nframes < 1; passes outside 1..7.
+ * SE2GPU_ERR_CAPACITY: nframes * cap or B * cap > 2^31 - 1, B > 65535.   B == 0 is SE2GPU_OK and launches nothing. */
+int se2gpu_kf_correspd_batch_device(se2gpu_matcher* h,
+                                    const se2gpu_keypoint* d_kps_un, const int32_t* d_counts, int cap, int nframes,
+                                    const float* d_frame_Tcw, const float* d_frame_Twc, const float* d_frame_P,
+                                    uint8_t* d_kf_observed, const float* d_view_pos,
+                                    const int32_t* d_job_prev, const int32_t* d_job_new, const float* d_Tcr,
+                                    const float* d_Trc, const int32_t* d_matched12, const float* d_local_pos,
+                                    const int32_t* d_match_idx_mp, int B,
+                                    const int32_t* d_mp_main_frame, const int32_t* d_mp_main_ftr,
+                                    const int32_t* d_mp_main_octave, const float* d_mp_normal, const float* d_mp_dist, int m,
+                                    float fx, float lower_depth, float upper_depth, int passes,
+                                    int32_t* d_inv, uint8_t* d_kind, int32_t* d_src, float* d_view, float* d_info,
+                                    float* d_new_pos_w, float* d_info_prev, int32_t* d_counts_out);
+
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by
  *   LocalMapper::localBA          /root/reference/src/LocalMapper.cpp:232-302

@@ -1,0 +1,207 @@
+// The observations of a new key frame - header-only mirror, C++17, of
+//   Track::calcSE3toXYZInfo      src/Track.cpp:259-306        calcSE3toXYZInfo(...)
+//   MapPoint::acceptNewObserve   src/MapPoint.cpp:202-209     acceptNewObserve(...)
+//   MapPoint::updateParallax     src/MapPoint.cpp:124-185     updateParallax(...)
+// on plain data in HOST memory, one item per call: the CPU stand-in where no device copy exists and the baseline
+// tools/new_kf_bench.py times.  They run the very text the kernels run (include/se2lam_amd/view_info.h, which compiles for
+// host and device), so the definitions cannot drift apart; compile with -ffp-contract=off to get the kernels' roundings.
+//   NewKeyFrameTable             LocalMapper::findCorrespd (src/LocalMapper.cpp:87-170) for batches of new key frames in
+//                                device memory: trackedBatchDevice (pass 1), promoteBatchDevice (updateParallax of the
+//                                tracked points), observeBatchDevice (passes 2 and 3, or any set of passes)
+// Poses are rows 0-2 of a 4x4 matrix, row-major, 12 floats; the inverse poses and Kcam * Tcw come from the caller.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "../se2gpu.h"
+#include "ORBmatcher.h"
+#include "types.h"
+#include "view_info.h"
+
+namespace se2lam_amd {
+
+// Track::calcSE3toXYZInfo(xyz1, Tcw1, Tcw2, info1, info2) with Twc1 = cvu::inv(Tcw1), Twc2 = cvu::inv(Tcw2) supplied.
+// info1 / info2: 3x3 row-major floats (the reference widens them to Eigen::Matrix3d); xyz2 (optional): the point in camera 2.
+inline void calcSE3toXYZInfo(const Point3f& xyz1, const float Twc1[12], const float Tcw2[12], const float Twc2[12], float fxCam,
+                             float info1[9], float info2[9], Point3f* xyz2 = nullptr) {
+    const float p[3] = {xyz1.x, xyz1.y, xyz1.z};
+    float q[3];
+    se2gpu::se3_to_xyz_info(p, Twc1, Tcw2, Twc2, fxCam, info1, info2, q);
+    if (xyz2) *xyz2 = Point3f{q[0], q[1], q[2]};
+}
+
+// MapPoint::acceptNewObserve(posKF, kp) of a point with mNormalVector, the octave of its main observation, mMinDist, mMaxDist
+inline bool acceptNewObserve(const Point3f& posKF, const Point3f& mNormalVector, int mainOctave, int kpOctave, float mMinDist,
+                             float mMaxDist) {
+    const float p[3] = {posKF.x, posKF.y, posKF.z}, n[3] = {mNormalVector.x, mNormalVector.y, mNormalVector.z};
+    return se2gpu::accept_new_observe(p, n, mainOctave, kpOctave, mMinDist, mMaxDist);
+}
+
+// The pose side of a frame set: HOST arrays for updateParallax, device arrays for NewKeyFrameTable
+struct FramePoseSet {
+    const float* Tcw = nullptr;      // nframes x 12: rows 0-2 of Tcw
+    const float* Twc = nullptr;      // nframes x 12: rows 0-2 of cvu::inv(Tcw)
+    const float* P = nullptr;        // nframes x 12: Config::Kcam * Tcw.rowRange(0, 3)
+    const int32_t* idKF = nullptr;   // nframes: mIdKF
+};
+
+struct ParallaxUpdate {
+    int32_t status = 0;      // 0 nothing done, 1 promoted, 2 abandoned (MapPoint::setNull), 3 neither
+    int32_t pKF0Place = -1;  // place of pKF0 in the list
+};
+
+// MapPoint::updateParallax(pKF) of one point.  frames (keyPointsUn in kps): HOST arrays; obsFrame / obsFtr: its n
+// observations in container order; newFrame: the frame of pKF.  On promotion pos (mPos), obsView[i] / obsInfo[9 i..]
+// (mViewMPs / mViewMPsInfo of observation i) are written under the rules of se2gpu_mappoint_parallax_batch_device; on
+// abandonment the bytes of its features in kfObserved (nframes * cap, may be null) are cleared.
+inline ParallaxUpdate updateParallax(const DeviceFrameSet& frames, const FramePoseSet& poses, const int32_t* obsFrame,
+                                     const int32_t* obsFtr, int n, bool mbGoodParallax, int newFrame, float fxCam,
+                                     float lowerDepth, float upperDepth, uint8_t* kfObserved, Point3f* pos, Point3f* obsView,
+                                     float* obsInfo) {
+    using namespace se2gpu;
+    ParallaxUpdate r;
+    auto offset = [&](int i) -> long {
+        const int f = obsFrame[i], k = obsFtr[i];
+        if (f < 0 || f >= frames.nframes) return -1;
+        if (k < 0 || k >= std::min(frames.counts[f], frames.cap)) return -1;
+        return (long)f * frames.cap + k;
+    };
+    if (mbGoodParallax) return r;                                          // :125
+    int N = 0, place1 = -1;
+    for (int i = 0; i < n; ++i) {
+        if (offset(i) < 0) continue;
+        ++N;
+        if (obsFrame[i] == newFrame && place1 < 0) place1 = i;
+    }
+    if (N <= 2 || place1 < 0) return r;
+    const long long id1 = poses.idKF[newFrame];
+    long long id0 = 0;
+    int place0 = -1;
+    for (int i = 0; i < n; ++i) {                                          // :129-139
+        if (offset(i) < 0) continue;
+        const long long id = poses.idKF[obsFrame[i]];
+        if (id1 - id > 6) continue;
+        if (place0 < 0 || id < id0) { place0 = i; id0 = id; }
+    }
+    r.pKF0Place = place0;
+    r.status = 3;
+    const int f0 = obsFrame[place0];
+    if (f0 == newFrame) return r;
+    const float *Tcw0 = poses.Tcw + 12 * (size_t)f0, *Tcw1 = poses.Tcw + 12 * (size_t)newFrame;
+    const float *Twc0 = poses.Twc + 12 * (size_t)f0, *Twc1 = poses.Twc + 12 * (size_t)newFrame;
+    const KeyPoint &k0 = frames.kps[offset(place0)], &k1 = frames.kps[offset(place1)];
+    const float pt0[2] = {k0.pt.x, k0.pt.y}, pt1[2] = {k1.pt.x, k1.pt.y};
+    float posW[3], pos0[3], pos1[3];
+    triangulate_dlt(pt0, pt1, poses.P + 12 * (size_t)f0, poses.P + 12 * (size_t)newFrame, posW);   // :142-146
+    se3map(Tcw0, posW, pos0);
+    se3map(Tcw1, posW, pos1);
+    bool good = false;
+    if (pos0[2] >= lowerDepth && pos0[2] <= upperDepth && pos1[2] >= lowerDepth && pos1[2] <= upperDepth) {   // :150
+        const float O0[3] = {Twc0[3], Twc0[7], Twc0[11]}, O1[3] = {Twc1[3], Twc1[7], Twc1[11]};
+        good = cos_parallax(O0, O1, posW) < 0.9994f;                       // :153
+    }
+    if (!good) {
+        if (id1 - id0 >= 6) {                                              // :182-184
+            r.status = 2;
+            if (kfObserved)
+                for (int i = 0; i < n; ++i)
+                    if (offset(i) >= 0) kfObserved[offset(i)] = 0;
+        }
+        return r;
+    }
+    r.status = 1;
+    *pos = Point3f{posW[0], posW[1], posW[2]};                             // :154
+    float info0[9], info1[9], infoW[9], R[9];
+    se3_to_xyz_info(pos0, Twc0, Tcw1, Twc1, fxCam, info0, info1, nullptr); // :159
+    rot_of(Tcw0, R);
+    mat3_at_m_a(R, info0, infoW);                                          // :163-164
+    for (int i = 0; i < n; ++i) {
+        if (offset(i) < 0) continue;
+        const float* v;
+        const float* I;
+        float posk[3], infok[9];
+        if (i == place0) {
+            v = pos0; I = info0;
+        } else if (i == place1) {
+            v = pos1; I = info1;
+        } else {
+            const long long id = poses.idKF[obsFrame[i]];
+            if (id == id1 || id == id0) continue;                          // :169
+            const float* Tk = poses.Tcw + 12 * (size_t)obsFrame[i];
+            se3map(Tk, posW, posk);
+            rot_of(Tk, R);
+            mat3_a_m_at(R, infoW, infok);
+            v = posk; I = infok;
+        }
+        obsView[i] = Point3f{v[0], v[1], v[2]};
+        for (int k = 0; k < 9; ++k) obsInfo[9 * (size_t)i + k] = I[k];
+    }
+    return r;
+}
+
+// LocalMapper::findCorrespd for B new key frames at once.  Every pointer is device memory owned by the caller; the layouts
+// are those of se2gpu_kf_correspd_batch_device and se2gpu_mappoint_parallax_batch_device (include/se2gpu.h).
+struct NewKeyFrameTable {
+    // the frame set
+    DeviceFrameSet framesUn;                 // keyPointsUn (desc is not read)
+    FramePoseSet poses;
+    uint8_t* kfObserved = nullptr;           // nframes * cap: KeyFrame::hasObservation(idx), in/out
+    const Point3f* viewMPs = nullptr;        // nframes * cap: KeyFrame::mViewMPs
+    float fxCam = 0, lowerDepth = 0, upperDepth = 0;   // Config::fxCam, LOWER_DEPTH, UPPER_DEPTH
+    // the jobs
+    int B = 0;
+    const int32_t* jobPrev = nullptr;        // B: the frame of mpMap->getCurrentKF() (:92)
+    const int32_t* jobNew = nullptr;         // B: the frame of mNewKF
+                                             //    (the 2 B slots of jobPrev and jobNew pairwise distinct: se2gpu.h)
+    const float* Tcr = nullptr;              // B x 12: mNewKF->Tcr
+    const float* Trc = nullptr;              // B x 12: its inverse
+    const int32_t* vMatched12 = nullptr;     // B * cap
+    const Point3f* localMPs = nullptr;       // B * cap
+    const int32_t* vMatchedIdxMPs = nullptr; // B * cap: what MatchByProjectionDevice wrote (:118), needed by pass 2
+    // the map points pass 2 looks at (MapPointTable of MapPointMain.h holds the same arrays)
+    int M = 0;
+    const int32_t* mainFrame = nullptr;      // M: mMainKF
+    const int32_t* mainFtr = nullptr;        // M: mObservations[mMainKF]
+    const int32_t* mainOctave = nullptr;     // M: mMainOctave
+    const Point3f* normalVector = nullptr;   // M: mNormalVector
+    const float* minMaxDist = nullptr;       // M x 2: {mMinDist, mMaxDist}
+    // work space and outputs, B * cap each (counts: B x 5)
+    int32_t* inv = nullptr;                  // feature of prev matched to feature j of new, -1 = none
+    uint8_t* kind = nullptr;                 // 0 none, 1 tracked (:95-107), 2 matched map point (:119-141), 3 new point (:145-168)
+    int32_t* src = nullptr;                  // i of prev (kinds 1, 3) or the map point (kind 2)
+    Point3f* view = nullptr;                 // setViewMP's position of feature j of mNewKF (:103, :138, :155)
+    float* info = nullptr;                   // x 9: its information
+    Point3f* newPosW = nullptr;              // kind 3: posW (:150)
+    float* infoPrev = nullptr;               // x 9, kind 3: xyzinfo0 for pPrefKF (:156)
+    int32_t* counts = nullptr;               // per job: features of kind 0..3, duplicated matches
+
+    void observeBatchDevice(ORBmatcher& matcher, int passes) {
+        check(se2gpu_kf_correspd_batch_device(
+                  matcher.handle(), reinterpret_cast<const se2gpu_keypoint*>(framesUn.kps), framesUn.counts, framesUn.cap,
+                  framesUn.nframes, poses.Tcw, poses.Twc, poses.P, kfObserved, reinterpret_cast<const float*>(viewMPs), jobPrev,
+                  jobNew, Tcr, Trc, vMatched12, reinterpret_cast<const float*>(localMPs), vMatchedIdxMPs, B, mainFrame, mainFtr,
+                  mainOctave, reinterpret_cast<const float*>(normalVector), minMaxDist, M, fxCam, lowerDepth, upperDepth, passes,
+                  inv, kind, src, reinterpret_cast<float*>(view), info, reinterpret_cast<float*>(newPosW), infoPrev, counts),
+              "NewKeyFrameTable::observeBatchDevice");
+    }
+    // pass 1 alone: the tracked map points (:95-107)
+    void trackedBatchDevice(ORBmatcher& matcher) { observeBatchDevice(matcher, 1); }
+
+    // MapPoint::updateParallax for m points whose lists (CSR, container order) already hold the observation just added;
+    // kfObserved loses the features of the abandoned ones.  Asynchronous like the passes; the order of LocalMapper.cpp is
+    // trackedBatchDevice, promoteBatchDevice, MapPointTable::updateMainBatchDevice, MatchByProjectionDevice,
+    // observeBatchDevice(matcher, 6).
+    void promoteBatchDevice(ORBmatcher& matcher, const int32_t* mpPtr, const int32_t* obsFrame, const int32_t* obsFtr, int m,
+                            int nobs, const uint8_t* goodPrl, const int32_t* newFrame, int32_t* status, int32_t* pKF0Place,
+                            Point3f* pos, Point3f* obsView, float* obsInfo) {
+        check(se2gpu_mappoint_parallax_batch_device(
+                  matcher.handle(), reinterpret_cast<const se2gpu_keypoint*>(framesUn.kps), framesUn.counts, framesUn.cap,
+                  framesUn.nframes, poses.Tcw, poses.Twc, poses.P, poses.idKF, mpPtr, obsFrame, obsFtr, m, nobs, goodPrl,
+                  newFrame, fxCam, lowerDepth, upperDepth, kfObserved, status, pKF0Place, reinterpret_cast<float*>(pos),
+                  reinterpret_cast<float*>(obsView), obsInfo),
+              "NewKeyFrameTable::promoteBatchDevice");
+    }
+};
+
+}  // namespace se2lam_amd

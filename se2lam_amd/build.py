@@ -32,6 +32,7 @@ PER_FILE = {
     "bow.hip": ["-ffp-contract=off"],        # BowVector values and scores equal the host vocabulary's to the bit
     "voc_train.hip": ["-ffp-contract=off"],  # cut_d = u * sum is one IEEE multiply on host and device
     "mappoint.hip": ["-ffp-contract=off"],   # mMinDist / mMaxDist are IEEE operations, equal to the host's to the bit
+    "new_kf.hip": ["-ffp-contract=off"],     # view_info.h: float arithmetic in the reference's order, equal to the host mirror's
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
 }
 
@@ -60,7 +61,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     headers += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
     sub = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTree.h")   # the one adapter header a translation unit (bow.hip) includes
     sub2 = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTrain.h")   # voc_train.hip shares its inline functions with the host mirror
-    headers += [sub, sub2, os.path.abspath(__file__)]
+    sub3 = os.path.join(INCLUDE, "se2lam_amd", "view_info.h")         # triangulate.hip / new_kf.hip share it with FindCorrespd.h
+    headers += [sub, sub2, sub3, os.path.abspath(__file__)]
     objs = []
     for src in sources():
         obj = os.path.join(OBJDIR, src[:-4] + ".o")

@@ -146,6 +146,11 @@ SYMBOLS = {
                                             _VP, _VP, _VP, _I, _I, _I, _F, _VP, _VP]),
     "se2gpu_mappoint_main_batch_device": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP,
                                                _VP, _VP, _VP, _VP, _VP]),
+    "se2gpu_mappoint_parallax_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP,
+                                                   _F, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "se2gpu_kf_correspd_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                             _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _F, _F, _F, _I, _VP, _VP, _VP, _VP, _VP,
+                                             _VP, _VP, _VP]),
     # BA
     "se2gpu_ba_create": (_I, [C.POINTER(_VP)]),
     "se2gpu_ba_reserve": (_I, [_I, _I, _I]),

@@ -12,69 +12,10 @@
 // iteration is unpinned (OpenCV is not installed), expected ~1e-5 relative.
 // Compiled with -ffp-contract=off like the matchers.
 #include "track_ws.h"
+#include "view_info.h"
 
 namespace se2gpu {
 namespace {
-
-// smallest right singular vector of the 4x4 matrix a (row-major); v4 = that vector (unnormalised sign)
-__device__ inline void smallest_right_singular_vector(const double a_in[16], double v4[4]) {
-    double At[4][4], Vt[4][4], W[4];   // At: rows = columns of A (one-sided Jacobi works on A^T), Vt: accumulates V^T
-    for (int i = 0; i < 4; ++i)
-        for (int k = 0; k < 4; ++k) {
-            At[i][k] = a_in[k * 4 + i];
-            Vt[i][k] = i == k ? 1.0 : 0.0;
-        }
-    for (int i = 0; i < 4; ++i) {
-        double sd = 0;
-        for (int k = 0; k < 4; ++k) sd += At[i][k] * At[i][k];
-        W[i] = sd;
-    }
-    const double eps = 2.220446049250313e-16 * 10;
-    for (int iter = 0; iter < 30; ++iter) {
-        bool changed = false;
-        for (int i = 0; i < 3; ++i)
-            for (int j = i + 1; j < 4; ++j) {
-                double a = W[i], p = 0, b = W[j];
-                for (int k = 0; k < 4; ++k) p += At[i][k] * At[j][k];
-                if (fabs(p) <= eps * sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = sqrt(p * p + beta * beta);
-                double c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = sqrt(delta / gamma);
-                    c = p / (gamma * s * 2);
-                } else {
-                    c = sqrt((gamma + beta) / (gamma * 2));
-                    s = p / (gamma * c * 2);
-                }
-                a = 0;
-                b = 0;
-                for (int k = 0; k < 4; ++k) {
-                    const double t0 = c * At[i][k] + s * At[j][k];
-                    const double t1 = -s * At[i][k] + c * At[j][k];
-                    At[i][k] = t0;
-                    At[j][k] = t1;
-                    a += t0 * t0;
-                    b += t1 * t1;
-                }
-                W[i] = a;
-                W[j] = b;
-                changed = true;
-                for (int k = 0; k < 4; ++k) {
-                    const double t0 = c * Vt[i][k] + s * Vt[j][k];
-                    const double t1 = -s * Vt[i][k] + c * Vt[j][k];
-                    Vt[i][k] = t0;
-                    Vt[j][k] = t1;
-                }
-            }
-        if (!changed) break;
-    }
-    int m = 0;
-    for (int i = 1; i < 4; ++i)
-        if (W[i] < W[m]) m = i;   // first minimum
-    for (int k = 0; k < 4; ++k) v4[k] = Vt[m][k];
-}
 
 __global__ void k_triangulate(int n, const se2gpu_keypoint* __restrict__ kps_ref,
                               const se2gpu_keypoint* __restrict__ kps_cur, int n_cur, int* __restrict__ match_idx,
@@ -91,18 +32,10 @@ __global__ void k_triangulate(int n, const se2gpu_keypoint* __restrict__ kps_ref
         atomicAdd(&counters[1], 1);
         return;
     }
-    const float x1 = kps_ref[i].x, y1 = kps_ref[i].y, x2 = kps_cur[mi].x, y2 = kps_cur[mi].y;
-    double A[16];
-    for (int c = 0; c < 4; ++c) {   // rows in float as cv::Mat arithmetic does, then widened
-        A[0 + c] = (double)(x1 * P1[8 + c] - P1[0 + c]);
-        A[4 + c] = (double)(y1 * P1[8 + c] - P1[4 + c]);
-        A[8 + c] = (double)(x2 * P2[8 + c] - P2[0 + c]);
-        A[12 + c] = (double)(y2 * P2[8 + c] - P2[4 + c]);
-    }
-    double v[4];
-    smallest_right_singular_vector(A, v);
-    const float w = (float)v[3];
-    const float px = (float)v[0] / w, py = (float)v[1] / w, pz = (float)v[2] / w;
+    const float pt1[2] = {kps_ref[i].x, kps_ref[i].y}, pt2[2] = {kps_cur[mi].x, kps_cur[mi].y};
+    float x3d[3];
+    triangulate_dlt(pt1, pt2, P1, P2, x3d);   // view_info.h
+    const float px = x3d[0], py = x3d[1], pz = x3d[2];
     if (pz >= lower && pz <= upper) {
         pos[3 * i] = px;       // mLocalMPs[i] = pos only for an accepted depth (Track.cpp:407-408); zero elsewhere
         pos[3 * i + 1] = py;

@@ -1,0 +1,96 @@
+// The host functions of include/se2lam_amd/FindCorrespd.h on cases dumped by tests/test_new_kf_model.py.
+//   line "I <47 words>"  xyz1 (3), Twc1 (12), Tcw2 (12), Twc2 (12), fx, normal (3) as float bits; two octaves; min / max dist
+//                        -> info1 (9), info2 (9), xyz2 (3) as float bits, acceptNewObserve(xyz1, normal, ...)
+//   line "P ..."         a frame set and a batch of observation lists -> per point: status, place, pos; per observation: view
+//                        (3) and info (9); then the hasObservation bytes.  Floats the functions leave alone hold -7.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "se2lam_amd/FindCorrespd.h"
+
+using namespace se2lam_amd;
+
+static float f_of(long long bits) {
+    const uint32_t u = (uint32_t)bits;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+static unsigned bits_of(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+
+struct Reader {
+    std::istringstream in;
+    explicit Reader(const std::string& s) : in(s) {}
+    long long i() { long long v = 0; in >> v; return v; }
+    float f() { return f_of(i()); }
+    void floats(float* dst, size_t n) { for (size_t k = 0; k < n; ++k) dst[k] = f(); }
+    template <typename T> void ints(std::vector<T>& dst, size_t n) { dst.resize(n); for (size_t k = 0; k < n; ++k) dst[k] = (T)i(); }
+};
+
+int main(int argc, char** argv) {
+    if (argc < 2) return 2;
+    std::ifstream file(argv[1]);
+    std::string line;
+    while (std::getline(file, line)) {
+        if (line.size() < 2) continue;
+        Reader r(line.substr(2));
+        if (line[0] == 'I') {
+            float xyz1[3], Twc1[12], Tcw2[12], Twc2[12], n[3], info1[9], info2[9];
+            r.floats(xyz1, 3); r.floats(Twc1, 12); r.floats(Tcw2, 12); r.floats(Twc2, 12);
+            const float fx = r.f();
+            r.floats(n, 3);
+            const int o1 = (int)r.i(), o2 = (int)r.i();
+            const float mind = r.f(), maxd = r.f();
+            Point3f xyz2;
+            calcSE3toXYZInfo(Point3f{xyz1[0], xyz1[1], xyz1[2]}, Twc1, Tcw2, Twc2, fx, info1, info2, &xyz2);
+            for (float v : info1) std::printf("%u ", bits_of(v));
+            for (float v : info2) std::printf("%u ", bits_of(v));
+            std::printf("%u %u %u ", bits_of(xyz2.x), bits_of(xyz2.y), bits_of(xyz2.z));
+            std::printf("%d\n", (int)acceptNewObserve(Point3f{xyz1[0], xyz1[1], xyz1[2]}, Point3f{n[0], n[1], n[2]}, o1, o2, mind, maxd));
+        } else if (line[0] == 'P') {
+            const int nframes = (int)r.i(), cap = (int)r.i(), m = (int)r.i(), nobs = (int)r.i();
+            std::vector<int32_t> counts, idkf, ptr, of, ok, nw;
+            std::vector<uint8_t> good, observed;
+            r.ints(counts, nframes); r.ints(idkf, nframes);
+            std::vector<float> Tcw(12 * nframes), Twc(12 * nframes), P(12 * nframes), x((size_t)nframes * cap), y((size_t)nframes * cap);
+            r.floats(Tcw.data(), Tcw.size()); r.floats(Twc.data(), Twc.size()); r.floats(P.data(), P.size());
+            r.floats(x.data(), x.size()); r.floats(y.data(), y.size());
+            r.ints(ptr, m + 1); r.ints(of, nobs); r.ints(ok, nobs); r.ints(good, m); r.ints(nw, m);
+            const float fx = r.f(), lower = r.f(), upper = r.f();
+            r.ints(observed, (size_t)nframes * cap);
+            std::vector<KeyPoint> kps((size_t)nframes * cap);
+            for (size_t k = 0; k < kps.size(); ++k) { kps[k].pt.x = x[k]; kps[k].pt.y = y[k]; }
+            DeviceFrameSet fs;
+            fs.kps = kps.data(); fs.counts = counts.data(); fs.cap = cap; fs.nframes = nframes;
+            FramePoseSet ps;
+            ps.Tcw = Tcw.data(); ps.Twc = Twc.data(); ps.P = P.data(); ps.idKF = idkf.data();
+            std::vector<Point3f> view(nobs + 1, Point3f{-7.f, -7.f, -7.f});
+            std::vector<float> info(9 * (size_t)nobs + 9, -7.f);
+            for (int p = 0; p < m; ++p) {
+                Point3f pos{-7.f, -7.f, -7.f};
+                const int s = ptr[p], n = ptr[p + 1] - ptr[p];
+                const ParallaxUpdate u = updateParallax(fs, ps, of.data() + s, ok.data() + s, n, good[p] != 0, nw[p], fx, lower, upper,
+                                                        observed.data(), &pos, view.data() + s, info.data() + 9 * (size_t)s);
+                std::printf("%d %d %u %u %u\n", u.status, u.pKF0Place, bits_of(pos.x), bits_of(pos.y), bits_of(pos.z));
+            }
+            for (int e = 0; e < nobs; ++e) {
+                std::printf("%u %u %u", bits_of(view[e].x), bits_of(view[e].y), bits_of(view[e].z));
+                for (int k = 0; k < 9; ++k) std::printf(" %u", bits_of(info[9 * (size_t)e + k]));
+                std::printf("\n");
+            }
+            for (uint8_t b : observed) std::printf("%d ", (int)b);
+            std::printf("\n");
+        }
+    }
+    return 0;
+}

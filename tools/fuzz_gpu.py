@@ -18,7 +18,7 @@ from se2lam_amd.optimizer import SlamOptimizer  # noqa: E402
 from se2lam_amd.orb import ORBextractor  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(14))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints; 13 = map points' main key frame
+KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(15))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints; 13 = map points' main key frame; 14 = a new key frame's observations
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
 tex = synth.texture()
@@ -345,6 +345,48 @@ while time.time() < t_end:
               f"{int((want['info'][:, 0] >= 0).sum())} with a main {'ok' if ok else ''}")
         if not ok:
             fail("mappoint main")
+        continue
+    if kind == 14:   # updateParallax and findCorrespd: the scenes of tests/new_kf_cases.py under a random seed, against the FP64 model
+        tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+        if tests_dir not in sys.path:
+            sys.path.insert(0, tests_dir)
+        import new_kf_cases as nc
+        import new_kf_model as nk
+        from se2lam_amd import newkf
+        seed = int(rng.integers(1, 10**6))
+        try:
+            pc, cc = nc.ParallaxCases(seed), nc.CorrespdCases(seed, abandoned=bool(rng.random() < 0.5))
+        except AssertionError as e:     # a scene in which some named case finds no draw with its margins
+            print(f"new key frame seed {seed}: skipped ({e})")
+            continue
+        e_pos, e_mat = nc.restatement_errors(pc, [cc])
+        bound = 4 * max(e_pos, e_mat)
+        mt = ORBmatcher()
+        fr = pc.sc.fr
+        poses = newkf.DevicePoses(fr.kps, fr.counts, fr.cap, fr.Tcw, fr.Twc, fr.P, fr.idkf, pc.observed)
+        got = newkf.promote_batch_device(mt, poses, pc.ptr, pc.obs_frame, pc.obs_ftr, pc.good, pc.new, nc.FX, nc.LOWER, nc.UPPER)
+        want = pc.run(nk.L64)
+        w = want["obs_view"][:, 0] != nk.SENT
+        ok = np.array_equal(got["status"], want["status"]) and np.array_equal(got["place"], want["place"]) and \
+            np.array_equal(poses.observed(), want["kf_observed"]) and \
+            np.array_equal(got["obs_view"][:, 0] != np.float32(nk.SENT), w) and \
+            nk.rel_err_pos(got["obs_view"][w], want["obs_view"][w]).max() <= bound and \
+            nk.rel_err_mat(got["obs_info"][w], want["obs_info"][w]).max() <= bound
+        passes = int(rng.integers(1, 8))
+        fr = cc.sc.fr
+        poses = newkf.DevicePoses(fr.kps, fr.counts, fr.cap, fr.Tcw, fr.Twc, fr.P, fr.idkf, cc.observed, cc.view_pos)
+        got = newkf.observe_batch_device(mt, poses, cc.job_prev, cc.job_new, cc.Tcr, cc.Trc, cc.matched12, cc.local_pos,
+                                         cc.match_idx_mp, cc.mp, nc.FX, nc.LOWER, nc.UPPER, passes)
+        want = cc.run(nk.L64, passes)
+        w = want["kind"] > 0
+        ok = ok and all(np.array_equal(got[k], want[k]) for k in ("inv", "kind", "src", "counts")) and \
+            np.array_equal(poses.observed(), want["kf_observed"]) and \
+            (not w.any() or (nk.rel_err_pos(got["view"][w], want["view"][w]).max() <= bound and
+                             nk.rel_err_mat(got["info"][w], want["info"][w]).max() <= bound))
+        print(f"new key frame seed {seed}: {int((pc.run(nk.L64)['status'] == 1).sum())} promoted, passes {passes} kinds "
+              f"{want['counts'][:, 1:4].sum(0).tolist()}, bound {bound:.2g} {'ok' if ok else ''}")
+        if not ok:
+            fail("new key frame")
         continue
     if kind == 1:
         W, H = int(rng.integers(160, 900)), int(rng.integers(120, 700))
