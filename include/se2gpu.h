@@ -385,6 +385,81 @@ int se2gpu_kf_correspd_batch_device(se2gpu_matcher* h,
                                     int32_t* d_inv, uint8_t* d_kind, int32_t* d_src, float* d_view, float* d_info,
                                     float* d_new_pos_w, float* d_info_prev, int32_t* d_counts_out);
 
+/* Covisibility: Map::compareViewMPs (src/Map.cpp:354-400 of the reference, both overloads) for batches, on the observation
+ * CSR of se2gpu_mappoint_parallax_batch_device.  The observation sets live in a caller-supplied bit matrix d_bits of
+ * (nframes + 2) rows of W = ceil(m / 64) 64-bit words, bit p & 63 of word p / 64 = point p:
+ *   row f < nframes   key frame slot f's mObservations over the m points
+ *   row nframes       point is not null               (what getAllObsMPs(false) keeps, KeyFrame.cpp:152)
+ *   row nframes + 1   not null and good parallax      (what getAllObsMPs() keeps: checkParallax defaults to true, KeyFrame.h:69)
+ * Bits past m are zero.  se2gpu_covis_bits_words (host only, no device) returns the number of words, (nframes + 2) * W, or
+ * -1 with nframes < 1 or m < 0.
+ *
+ * se2gpu_covis_build_device fills d_bits and d_size_obs from the CSR.  Every pointer is device memory.
+ *   THE CSR MUST DESCRIBE THE KEY FRAME'S SIDE: point p lists frame f iff pKF_f->mObservations holds p.  compareViewMPs reads
+ *   only that side (getAllObsMPs, hasObservation(pMP), getSizeObsMP are KeyFrame members), never MapPoint::mObservations.
+ *   d_mp_null    m bytes or NULL (none is null): MapPoint::isNull()
+ *   d_good_prl   m bytes or NULL (all good): MapPoint::isGoodPrl()
+ *   Bit (f, p) is set iff point p's list holds at least one valid entry of frame f.  Validity is the rule of
+ *   se2gpu_mappoint_parallax_batch_device: the frame lies in 0..nframes-1 and the feature in 0..min(counts, cap)-1; a null key
+ *   frame is not skipped.  d_mp_ptr values are clamped to 0..nobs and a descending segment is empty.  A frame that appears
+ *   twice in one list counts once.
+ *   d_size_obs[f] (nframes ints) = the popcount of row f = KeyFrame::getSizeObsMP() (KeyFrame.cpp:122-125): mObservations.size()
+ *   counts null points too.
+ *   A memset of the key-frame rows, one thread per point (64-bit integer atomicOr; the two point rows by ballot), one wave per
+ *   row for the sizes: the memset is inside the call, so a second build gives the same bits.  m == 0 launches nothing and
+ *   leaves d_size_obs alone (se2gpu_covis_pairs_device counts the rows itself and needs no d_size_obs).
+ *
+ * se2gpu_covis_pairs_device: Point2f Map::compareViewMPs(pKF1, pKF2, spMPs) (:354-369) for npairs pairs of slots
+ * (d_pair_a[p], d_pair_b[p]) = (pKF1, pKF2), one wave per pair.
+ *   d_pair_out[4p..]   {n_same, size_a, size_b, flags}: n_same = popcount(row a & row b & not-null row) (:358-365; the null
+ *                      points are dropped from the numerator and not from the sizes), size = popcount of the row
+ *   d_pair_ratio[2p..] {(float)n_same / (float)size_a, (float)n_same / (float)size_b} (:367-368), one IEEE division each;
+ *                      0 / 0 is NaN as in the reference
+ *   flags bit 0        (float)n_same > ratio_f * (float)size_a: Map::updateCovisibility's test with 0.3f (:794), one float
+ *                      multiply and a compare in float
+ *   flags bit 1        (double)n_same > ratio_d * (double)size_a: Localizer::UpdateCovisKFCurr's with 0.1 (Localizer.cpp:683)
+ *   A pair with a slot outside 0..nframes-1 gets {-1, 0, 0, 0}; its ratios and its list are left untouched.  a == b is legal.
+ *   With m == 0 every in-range pair gets {0, 0, 0, 0} and NaN ratios.  A pair's outputs depend on that pair alone.
+ *   Optional list, with d_common != NULL (then d_counts, cap, d_mp_ptr, d_obs_frame, d_obs_ftr, nobs of the build are
+ *   required, whatever list_cap is; without d_common they are not read and may be NULL / 0, and list_cap is ignored):
+ *   d_common[3 (p * list_cap + i)..] = {point, e_a, e_b} for the first list_cap common points in ascending point index - the
+ *   spMPs GlobalMapper::CreateFeatEdge turns into vPtrMPs (GlobalMapper.cpp:741-750).  e_a / e_b are the CSR entry indices of
+ *   the first valid entry of frames a / b in that point's list (-1 if the CSR no longer holds one): gather mp_xyz, m_z and
+ *   m_info for se2gpu_feat_edge_batch from d_obs_view / d_obs_info with them.  Truncation shows as n_same > list_cap; entries
+ *   from min(n_same, list_cap) on are left untouched.  The order is fixed by a prefix sum over the wave, without atomics.
+ *
+ * se2gpu_covis_refset_device: double Map::compareViewMPs(pKFNow, spKFsRef, spMPsRet, k) (:373-400) for njobs jobs, one wave
+ * per job: key frame slot d_job_kf[j] against the slots d_ref_idx[d_ref_ptr[j] .. d_ref_ptr[j + 1] - 1] (d_ref_ptr: njobs + 1
+ * ints, clamped to 0..nref, a descending segment is empty).
+ *   all = popcount(row kf & good-parallax row) (:376); cnt = the points of that set observed by at least k of the listed
+ *   reference frames (:381-396).  Entries outside 0..nframes-1 are skipped.  A SLOT LISTED TWICE COUNTS TWICE: the reference's
+ *   std::set has no duplicates, and keeping the list free of them is the caller's duty.  The job's own slot counts if listed.
+ *   d_job_out[3j..] = {cnt, all, redundant}; d_job_ratio[j] = (double)cnt * 1.0 / (double)all (:398), -1.0 with all == 0
+ *   (:377-379); redundant = ratio >= thresh, Map::pruneRedundantKF's test with 0.8 (:196), 0 with all == 0.
+ *   A job slot out of range gives {-1, 0, 0} and leaves its ratio untouched.  k in 1..7: the count is kept in three bit planes.
+ *
+ * All three are asynchronous on the matcher's stream: nothing is read back; se2gpu_matcher_sync waits for them.  No scratch
+ * memory.  Integer atomics only: the same words in every run.
+ * The argument checks come first and touch neither the handle nor a device; se2gpu_last_error names the argument:
+ * SE2GPU_ERR_INVALID: a NULL handle, d_bits, required array (d_counts, d_mp_ptr; d_obs_frame / d_obs_ftr with nobs > 0;
+ *   d_pair_a, d_pair_b; d_job_kf, d_ref_ptr; d_ref_idx with nref > 0) or output; m < 0, nobs < 0, npairs < 0, njobs < 0,
+ *   nref < 0, nframes < 1, cap < 1 (where the CSR is read), list_cap < 0; d_common without the CSR arrays.
+ * SE2GPU_ERR_CAPACITY: (nframes + 2) * W > 2^31 - 1; nframes * cap > 2^31 - 1 (where the CSR is read); npairs or njobs >
+ *   2^26 - 1 = 67108863 (64 threads each, and a launch's threads stay below 2^32); k outside 1..7.
+ * npairs == 0, njobs == 0 and m == 0 at build are SE2GPU_OK and launch nothing. */
+long long se2gpu_covis_bits_words(int nframes, int m);
+int se2gpu_covis_build_device(se2gpu_matcher* h, const int32_t* d_counts, int cap, int nframes,
+                              const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr, int m, int nobs,
+                              const uint8_t* d_mp_null, const uint8_t* d_good_prl, uint64_t* d_bits, int32_t* d_size_obs);
+int se2gpu_covis_pairs_device(se2gpu_matcher* h, const uint64_t* d_bits, int nframes, int m,
+                              const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs, float ratio_f, double ratio_d,
+                              int32_t* d_pair_out, float* d_pair_ratio,
+                              int32_t* d_common, int list_cap, const int32_t* d_counts, int cap,
+                              const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr, int nobs);
+int se2gpu_covis_refset_device(se2gpu_matcher* h, const uint64_t* d_bits, int nframes, int m,
+                               const int32_t* d_job_kf, const int32_t* d_ref_ptr, const int32_t* d_ref_idx, int nref, int njobs,
+                               int k, double thresh, int32_t* d_job_out, double* d_job_ratio);
+
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by
  *   LocalMapper::localBA          /root/reference/src/LocalMapper.cpp:232-302

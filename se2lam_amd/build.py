@@ -33,6 +33,7 @@ PER_FILE = {
     "voc_train.hip": ["-ffp-contract=off"],  # cut_d = u * sum is one IEEE multiply on host and device
     "mappoint.hip": ["-ffp-contract=off"],   # mMinDist / mMaxDist are IEEE operations, equal to the host's to the bit
     "new_kf.hip": ["-ffp-contract=off"],     # view_info.h: float arithmetic in the reference's order, equal to the host mirror's
+    "covis.hip": ["-ffp-contract=off"],      # the ratios and threshold tests are single IEEE operations, as in the reference
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
 }
 

@@ -18,7 +18,7 @@ from se2lam_amd.optimizer import SlamOptimizer  # noqa: E402
 from se2lam_amd.orb import ORBextractor  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(15))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints; 13 = map points' main key frame; 14 = a new key frame's observations
+KINDS = [int(k) for k in sys.argv[3].split(',')] if len(sys.argv) > 3 else list(range(16))   # e.g. 0,4,5: the three BA models only; 11 = the one-workgroup-per-window batch path; 12 = feature constraints; 13 = map points' main key frame; 14 = a new key frame's observations; 15 = covisibility
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
 tex = synth.texture()
@@ -387,6 +387,34 @@ while time.time() < t_end:
               f"{want['counts'][:, 1:4].sum(0).tolist()}, bound {bound:.2g} {'ok' if ok else ''}")
         if not ok:
             fail("new key frame")
+        continue
+    if kind == 15:   # Map::compareViewMPs in both overloads: random maps with planted irregularities, against the set model
+        tests_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+        if tests_dir not in sys.path:
+            sys.path.insert(0, tests_dir)
+        import covis_cases as cvc
+        import covis_model as cvm
+        from se2lam_amd import covis
+        seed, nf, m = int(rng.integers(1, 10**6)), int(rng.integers(1, 90)), int(rng.integers(0, 6000))
+        t = cvc.random_map(seed, nf, m, irregular=bool(rng.random() < 0.8))
+        model = cvm.Model(*cvc.tables(t))
+        mt = ORBmatcher()
+        cv = covis.build_device(mt, *cvc.tables(t))
+        ok = np.array_equal(cv.read_bits(), model.bits()) and (m == 0 or np.array_equal(cv.read_size_obs(), model.size_obs()))
+        pa, pb = cvc.pair_list(seed, nf, int(rng.integers(1, 60)))
+        list_cap = [None, 0, int(rng.integers(1, 50)), m + 1][int(rng.integers(0, 4))]
+        rf, rd = float(rng.choice([0.3, rng.random()])), float(rng.choice([0.1, rng.random()]))
+        got, want = covis.pairs_device(mt, cv, pa, pb, rf, rd, list_cap), model.pairs(pa, pb, rf, rd, list_cap)
+        ok = ok and np.array_equal(got["out"], want["out"]) and cvm.same_floats(got["ratio"], want["ratio"]) and \
+            (list_cap is None or np.array_equal(got["common"], want["common"]))
+        kf, rp, ri = cvc.job_list(seed + 1, nf, int(rng.integers(3, 40)), int(rng.integers(0, 100)))
+        k, th = int(rng.integers(1, 8)), float(rng.choice([0.8, rng.random()]))
+        gotj, wantj = covis.refset_device(mt, cv, kf, rp, ri, k, th), model.refset(kf, rp, ri, k, th)
+        ok = ok and np.array_equal(gotj["out"], wantj["out"]) and cvm.same_floats(gotj["ratio"], wantj["ratio"])
+        print(f"covisibility seed {seed}: {nf} key frames, {m} points, {len(pa)} pairs (list_cap {list_cap}), {len(kf)} jobs k {k} "
+              f"{'ok' if ok else ''}")
+        if not ok:
+            fail("covisibility")
         continue
     if kind == 1:
         W, H = int(rng.integers(160, 900)), int(rng.integers(120, 700))
