@@ -7,8 +7,8 @@
 // written as the reference writes them - a sorted container of points per key frame, one look-up per point and key frame -
 // and share nothing with the kernels' bit matrix.
 //   CovisibilityTable   the same for batches in device memory (se2gpu_covis_build_device / _pairs_device / _refset_device)
-// Key frames are slots 0..nframes-1, map points indices 0..m-1; the observation CSR is that of
-// se2gpu_mappoint_parallax_batch_device and must describe the key frame's side (se2gpu.h).
+// Key frames are slots 0..nframes-1, map points indices 0..m-1; the observation CSR is read by obs_table.h's entry and segment
+// rule (null key frames are not skipped) and must describe the key frame's side (se2gpu.h).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -17,6 +17,7 @@
 
 #include "../se2gpu.h"
 #include "ORBmatcher.h"
+#include "obs_table.h"
 #include "types.h"
 
 namespace se2lam_amd {
@@ -34,12 +35,13 @@ struct CovisHostView {
 
     void index() {
         observations.assign(nframes, std::vector<int32_t>());
-        for (int p = 0; p < m; ++p) {
-            const int s = std::min(std::max(mpPtr[p], 0), nobs), e = std::min(std::max(mpPtr[p + 1], 0), nobs);
-            for (int i = s; i < e; ++i) {
-                const int f = obsFrame[i], k = obsFtr[i];
-                if (f < 0 || f >= nframes || k < 0 || k >= std::min(counts[f], cap)) continue;
-                std::vector<int32_t>& o = observations[f];
+        const se2gpu::FrameSlots slots{counts, nullptr, cap, nframes};
+        const se2gpu::ObsCsr csr{mpPtr, obsFrame, obsFtr, m, nobs};
+        for (int p = 0, s, n; p < m; ++p) {
+            se2gpu::point_segment(csr, p, s, n);
+            for (int i = s; i < s + n; ++i) {
+                if (!se2gpu::entry_valid(slots, obsFrame[i], obsFtr[i])) continue;
+                std::vector<int32_t>& o = observations[obsFrame[i]];
                 if (o.empty() || o.back() != p) o.push_back(p);      // points come in ascending order: a repeat is the last one
             }
         }

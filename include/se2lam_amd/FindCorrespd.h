@@ -16,6 +16,7 @@
 
 #include "../se2gpu.h"
 #include "ORBmatcher.h"
+#include "obs_table.h"
 #include "types.h"
 #include "view_info.h"
 
@@ -61,12 +62,8 @@ inline ParallaxUpdate updateParallax(const DeviceFrameSet& frames, const FramePo
                                      float* obsInfo) {
     using namespace se2gpu;
     ParallaxUpdate r;
-    auto offset = [&](int i) -> long {
-        const int f = obsFrame[i], k = obsFtr[i];
-        if (f < 0 || f >= frames.nframes) return -1;
-        if (k < 0 || k >= std::min(frames.counts[f], frames.cap)) return -1;
-        return (long)f * frames.cap + k;
-    };
+    const FrameSlots slots{frames.counts, nullptr, frames.cap, frames.nframes};   // a null key frame is not skipped
+    auto offset = [&](int i) { return feature_offset(slots, obsFrame[i], obsFtr[i]); };
     if (mbGoodParallax) return r;                                          // :125
     int N = 0, place1 = -1;
     for (int i = 0; i < n; ++i) {

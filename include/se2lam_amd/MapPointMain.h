@@ -16,6 +16,7 @@
 
 #include "../se2gpu.h"
 #include "ORBmatcher.h"
+#include "obs_table.h"
 #include "types.h"
 
 namespace se2lam_amd {
@@ -40,7 +41,8 @@ inline int descriptorDistance256(const uint8_t* a, const uint8_t* b) {   // ORBm
     return d;
 }
 
-// One point.  frames: HOST arrays in the DeviceFrameSet layout; frameNull (nframes bytes), viewMPs (nframes * cap) and
+// One point.  Which observations count is obs_table.h's entry rule, the kernels' own text.  frames: HOST arrays in the
+// DeviceFrameSet layout; frameNull (nframes bytes), viewMPs (nframes * cap) and
 // scaleFactors may be null as in the C ABI.  obsFrame / obsFtr: the point's n observations in container order.
 // prevMainFrame: the frame of mMainKF, -1 = none.  mainDescriptor (32 bytes), mainFrame, mainOctave and minMaxDist (2 floats)
 // are written under the rules of the C ABI (the last two only when the main key frame changed).
@@ -48,17 +50,16 @@ inline MainObservationInfo mainObservation(const DeviceFrameSet& frames, const u
                                            const float* scaleFactors, int nlevels, const int32_t* obsFrame,
                                            const int32_t* obsFtr, int n, int prevMainFrame, uint8_t* mainDescriptor,
                                            int32_t* mainFrame, int32_t* mainOctave, float* minMaxDist) {
+    const se2gpu::FrameSlots slots{frames.counts, frameNull, frames.cap, frames.nframes};
     std::vector<int> vPos;            // vKFs / vDes of :234-246 as places in the list
     std::vector<size_t> vOff;
-    vPos.reserve(n);
-    vOff.reserve(n);
+    vPos.reserve(std::max(n, 0));
+    vOff.reserve(std::max(n, 0));
     for (int i = 0; i < n; ++i) {
-        const int f = obsFrame[i], k = obsFtr[i];
-        if (f < 0 || f >= frames.nframes) continue;
-        if (frameNull && frameNull[f]) continue;                     // :242
-        if (k < 0 || k >= std::min(frames.counts[f], frames.cap)) continue;
+        const int off = se2gpu::feature_offset(slots, obsFrame[i], obsFtr[i]);   // skips the null key frames (:242)
+        if (off < 0) continue;
         vPos.push_back(i);
-        vOff.push_back((size_t)f * frames.cap + k);
+        vOff.push_back((size_t)off);
     }
     if (vOff.empty()) return MainObservationInfo{-1, 0, 0, 0};        // :248
     const int N = (int)vOff.size();

@@ -63,7 +63,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     sub = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTree.h")   # the one adapter header a translation unit (bow.hip) includes
     sub2 = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTrain.h")   # voc_train.hip shares its inline functions with the host mirror
     sub3 = os.path.join(INCLUDE, "se2lam_amd", "view_info.h")         # triangulate.hip / new_kf.hip share it with FindCorrespd.h
-    headers += [sub, sub2, sub3, os.path.abspath(__file__)]
+    sub4 = os.path.join(INCLUDE, "se2lam_amd", "obs_table.h")         # mappoint.hip / new_kf.hip / covis.hip share it with their mirrors
+    headers += [sub, sub2, sub3, sub4, os.path.abspath(__file__)]
     objs = []
     for src in sources():
         obj = os.path.join(OBJDIR, src[:-4] + ".o")

@@ -357,6 +357,29 @@ class DeviceArray:
             pass
 
 
+def dev_ptr(d):
+    """a DeviceArray, a raw device pointer or None -> what ctypes passes for a pointer argument"""
+    return None if d is None else (d.ptr if isinstance(d, DeviceArray) else d)
+
+
+def upload(a, dtype=None) -> DeviceArray:
+    """a host array in device memory; an empty one gets one element (an allocation of 0 bytes has no address)"""
+    a = np.ascontiguousarray(a, dtype)
+    return DeviceArray.from_numpy(a if a.size else np.zeros(1, a.dtype))
+
+
+SENT, ISENT = -7.0, -9   # float / integer outputs start from these: the calls leave alone what they do not compute
+SENTINEL_FRAME, SENTINEL_OCTAVE, SENTINEL_DIST, SENTINEL_DESC = -55, -77, -1.0, 0xAB   # the main-key-frame call's own
+
+
+def csr(lists):
+    """[(frames, features), ...] per point, in container order -> mp_ptr (m + 1), obs_frame, obs_ftr (int32) of obs_table.h"""
+    ptr = np.zeros(len(lists) + 1, np.int32)
+    ptr[1:] = np.cumsum([len(f) for f, _ in lists])
+    cat = lambda j: np.concatenate([np.asarray(l[j], np.int32).ravel() for l in lists] + [np.zeros(0, np.int32)])
+    return ptr, cat(0), cat(1)
+
+
 class PinnedArray:
     """Pinned host allocation (se2gpu_host_alloc) viewed as a numpy array; for the streaming bench."""
 

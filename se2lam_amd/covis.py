@@ -10,18 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
-
-SENT = -7.0   # float outputs start from this value, integer outputs from ISENT: the calls leave alone what they do not compute
-ISENT = -9
-
-
-def _ptr(d):
-    return None if d is None else (d.ptr if isinstance(d, capi.DeviceArray) else d)
-
-
-def _up(a, dtype):
-    a = np.ascontiguousarray(a, dtype)
-    return capi.DeviceArray.from_numpy(a if a.size else np.zeros(1, dtype))   # (an allocation of 0 bytes has no address)
+from .capi import ISENT, SENT, dev_ptr as _ptr, upload as _up
 
 
 class DeviceCovis:

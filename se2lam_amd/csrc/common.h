@@ -66,6 +66,11 @@ inline bool env_is(const char* name, const char* value) {
         }                                     \
     } while (0)
 
+// A required pointer argument, refused by its name; `who` (a const char* in scope) names the call.  _IF: required when `cond`.
+#define SE2_NEED(ptr) SE2_REQUIRE(ptr, SE2GPU_ERR_INVALID, "%s: " #ptr " is NULL", who)
+#define SE2_NEED_IF(cond, ptr) SE2_REQUIRE(!(cond) || (ptr), SE2GPU_ERR_INVALID, "%s: " #ptr " is NULL with " #cond, who)
+#define SE2_NEED_DEVICE() SE2_REQUIRE(::se2gpu::have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)")
+
 // Growable device allocation (never shrinks).  Not copyable.
 template <typename T>
 struct DevBuf {

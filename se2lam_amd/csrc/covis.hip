@@ -11,11 +11,11 @@
 // d_bits is (nframes + 2) rows of W = ceil(m / 64) 64-bit words: row f < nframes = the observation set of key frame slot f, row
 // nframes = point is not null, row nframes + 1 = not null and good parallax.  Bits past m are zero in every row.
 // A thread per point and not per CSR entry: d_mp_ptr is clamped and its segments need not ascend or be disjoint, so an entry has
-// no single owner to search for.  Integer atomics only; every index read from an array is checked before it is used.
+// no single owner to search for.  Integer atomics only; every index read from an array is checked before it is used, the
+// observation lists by obs_table.h's entry and segment rule (a null key frame is not skipped: compareViewMPs does not).
 // Compiled with -ffp-contract=off: the ratios and the threshold tests are single IEEE operations.
-#include <climits>
-
 #include "common.h"
+#include "obs_table.h"
 
 using namespace se2gpu;
 
@@ -31,14 +31,10 @@ struct CsrArgs {
     const int* obs_frame;
     const int* obs_ftr;
     int cap, nframes, m, nobs;
+    // no frame_null: compareViewMPs does not skip a null key frame, and the rule's test folds away
+    __device__ __forceinline__ FrameSlots slots() const { return FrameSlots{counts, nullptr, cap, nframes}; }
+    __device__ __forceinline__ ObsCsr csr() const { return ObsCsr{mp_ptr, obs_frame, obs_ftr, m, nobs}; }
 };
-
-// the validity rule of se2gpu_mappoint_parallax_batch_device: frame in range, feature below min(counts, cap); a null key
-// frame is not skipped
-__device__ __forceinline__ bool entry_valid(const CsrArgs& c, int f, int k) {
-    if ((unsigned)f >= (unsigned)c.nframes) return false;
-    return k >= 0 && k < min(c.counts[f], c.cap);
-}
 
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
@@ -53,11 +49,13 @@ __global__ __launch_bounds__(256) void k_covis_scatter(CsrArgs c, const uint8_t*
     const bool notnull = in && !(mp_null && mp_null[p]);
     const bool good = notnull && (!good_prl || good_prl[p]);
     if (in) {
-        const int s = min(max(c.mp_ptr[p], 0), c.nobs), e = min(max(c.mp_ptr[p + 1], 0), c.nobs);
+        const FrameSlots fs = c.slots();
+        int s, e;
+        point_range(c.csr(), p, s, e);
         const u64 bit = 1ull << (p & 63);
         for (int i = s; i < e; ++i) {
             const int f = c.obs_frame[i];
-            if (entry_valid(c, f, c.obs_ftr[i])) atomicOr(&bits[(size_t)f * W + (p >> 6)], bit);
+            if (entry_valid(fs, f, c.obs_ftr[i])) atomicOr(&bits[(size_t)f * W + (p >> 6)], bit);
         }
     }
     const u64 bn = __ballot(notnull), bg = __ballot(good);
@@ -93,6 +91,7 @@ __global__ __launch_bounds__(64) void k_covis_pairs(PairArgs a) {
     const int p = blockIdx.x, lane = threadIdx.x;
     const int fa = a.pair_a[p], fb = a.pair_b[p];
     const int nframes = a.c.nframes, W = a.W;
+    const FrameSlots fs = a.c.slots();
     int* out = a.out + 4 * (size_t)p;
     if ((unsigned)fa >= (unsigned)nframes || (unsigned)fb >= (unsigned)nframes) {
         if (lane == 0) { out[0] = -1; out[1] = 0; out[2] = 0; out[3] = 0; }
@@ -126,13 +125,10 @@ __global__ __launch_bounds__(64) void k_covis_pairs(PairArgs a) {
                 x &= x - 1;
                 int ea = -1, eb = -1;                                  // the first valid entry of either frame
                 int s = 0, e = 0;
-                if (pt < a.c.m) {                                      // (a d_bits of this m has no bit past it)
-                    s = min(max(a.c.mp_ptr[pt], 0), a.c.nobs);
-                    e = min(max(a.c.mp_ptr[pt + 1], 0), a.c.nobs);
-                }
+                if (pt < a.c.m) point_range(a.c.csr(), pt, s, e);     // (a d_bits of this m has no bit past it)
                 for (int i = s; i < e; ++i) {
                     const int f = a.c.obs_frame[i];
-                    if ((f != fa && f != fb) || !entry_valid(a.c, f, a.c.obs_ftr[i])) continue;
+                    if ((f != fa && f != fb) || !entry_valid(fs, f, a.c.obs_ftr[i])) continue;
                     if (f == fa && ea < 0) ea = i;
                     if (f == fb && eb < 0) eb = i;
                 }
@@ -211,8 +207,6 @@ __global__ __launch_bounds__(64) void k_covis_refset(RefArgs a) {
     }
 }
 
-#define COVIS_NEED(ptr) SE2_REQUIRE(ptr, SE2GPU_ERR_INVALID, "%s: " #ptr " is NULL", who)
-
 long long words_of(int m) { return ((long long)m + 63) / 64; }
 
 int check_bits(const char* who, int nframes, int m) {
@@ -221,19 +215,6 @@ int check_bits(const char* who, int nframes, int m) {
     SE2_REQUIRE(((long long)nframes + 2) * words_of(m) <= INT_MAX, SE2GPU_ERR_CAPACITY,
                 "%s: (nframes + 2) * ceil(m / 64) = %lld words of d_bits exceed the limit %d", who,
                 ((long long)nframes + 2) * words_of(m), INT_MAX);
-    return SE2GPU_OK;
-}
-
-int check_csr(const char* who, const void* d_counts, int cap, int nframes, const void* d_mp_ptr, const void* d_obs_frame,
-              const void* d_obs_ftr, int nobs) {
-    COVIS_NEED(d_counts);
-    COVIS_NEED(d_mp_ptr);
-    SE2_REQUIRE(cap >= 1, SE2GPU_ERR_INVALID, "%s: cap = %d is below 1", who, cap);
-    SE2_REQUIRE(nobs >= 0, SE2GPU_ERR_INVALID, "%s: nobs = %d is negative", who, nobs);
-    SE2_REQUIRE(nobs == 0 || d_obs_frame, SE2GPU_ERR_INVALID, "%s: d_obs_frame is NULL with nobs = %d", who, nobs);
-    SE2_REQUIRE(nobs == 0 || d_obs_ftr, SE2GPU_ERR_INVALID, "%s: d_obs_ftr is NULL with nobs = %d", who, nobs);
-    SE2_REQUIRE((long long)nframes * cap <= INT_MAX, SE2GPU_ERR_CAPACITY, "%s: nframes * cap = %lld exceeds the limit %d", who,
-                (long long)nframes * cap, INT_MAX);
     return SE2GPU_OK;
 }
 
@@ -249,13 +230,13 @@ extern "C" int se2gpu_covis_build_device(se2gpu_matcher* h, const int32_t* d_cou
                                          int nobs, const uint8_t* d_mp_null, const uint8_t* d_good_prl, uint64_t* d_bits,
                                          int32_t* d_size_obs) {
     const char* who = "covis_build";
-    COVIS_NEED(h);
+    SE2_NEED(h);
     SE2_CHECK(check_bits(who, nframes, m));
-    SE2_CHECK(check_csr(who, d_counts, cap, nframes, d_mp_ptr, d_obs_frame, d_obs_ftr, nobs));
-    COVIS_NEED(d_bits);
-    COVIS_NEED(d_size_obs);
+    SE2_CHECK(check_obs_csr(who, d_mp_ptr, d_obs_frame, d_obs_ftr, m, nobs));
+    SE2_CHECK(check_frame_slots(who, d_counts, cap, nframes));
+    SE2_NEED(d_bits); SE2_NEED(d_size_obs);
     if (m == 0) return SE2GPU_OK;
-    SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
+    SE2_NEED_DEVICE();
     const int W = (int)words_of(m);
     hipStream_t st = (hipStream_t)se2gpu_matcher_stream(h);
     SE2_HIP(hipMemsetAsync(d_bits, 0, (size_t)nframes * W * sizeof(u64), st));   // the two point rows are written whole
@@ -273,19 +254,16 @@ extern "C" int se2gpu_covis_pairs_device(se2gpu_matcher* h, const uint64_t* d_bi
                                          const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr,
                                          int nobs) {
     const char* who = "covis_pairs";
-    COVIS_NEED(h);
+    SE2_NEED(h);
     SE2_CHECK(check_bits(who, nframes, m));
-    COVIS_NEED(d_bits);
-    COVIS_NEED(d_pair_a);
-    COVIS_NEED(d_pair_b);
-    COVIS_NEED(d_pair_out);
-    COVIS_NEED(d_pair_ratio);
+    SE2_NEED(d_bits); SE2_NEED(d_pair_a); SE2_NEED(d_pair_b); SE2_NEED(d_pair_out); SE2_NEED(d_pair_ratio);
     SE2_REQUIRE(npairs >= 0, SE2GPU_ERR_INVALID, "%s: npairs = %d is negative", who, npairs);
     SE2_REQUIRE(list_cap >= 0, SE2GPU_ERR_INVALID, "%s: list_cap = %d is negative", who, list_cap);
-    if (d_common) SE2_CHECK(check_csr(who, d_counts, cap, nframes, d_mp_ptr, d_obs_frame, d_obs_ftr, nobs));
+    if (d_common) SE2_CHECK(check_obs_csr(who, d_mp_ptr, d_obs_frame, d_obs_ftr, m, nobs));   // without a list the table is not read
+    if (d_common) SE2_CHECK(check_frame_slots(who, d_counts, cap, nframes));
     SE2_REQUIRE(npairs <= MAX_WAVES, SE2GPU_ERR_CAPACITY, "%s: npairs = %d exceeds the limit %d", who, npairs, MAX_WAVES);
     if (npairs == 0) return SE2GPU_OK;
-    SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
+    SE2_NEED_DEVICE();
     PairArgs a;
     a.c = CsrArgs{d_counts, d_mp_ptr, d_obs_frame, d_obs_ftr, cap, nframes, m, nobs};
     a.bits = (const u64*)d_bits; a.pair_a = d_pair_a; a.pair_b = d_pair_b; a.out = d_pair_out; a.ratio = d_pair_ratio;
@@ -301,20 +279,16 @@ extern "C" int se2gpu_covis_refset_device(se2gpu_matcher* h, const uint64_t* d_b
                                           const int32_t* d_ref_ptr, const int32_t* d_ref_idx, int nref, int njobs, int k,
                                           double thresh, int32_t* d_job_out, double* d_job_ratio) {
     const char* who = "covis_refset";
-    COVIS_NEED(h);
+    SE2_NEED(h);
     SE2_CHECK(check_bits(who, nframes, m));
-    COVIS_NEED(d_bits);
-    COVIS_NEED(d_job_kf);
-    COVIS_NEED(d_ref_ptr);
-    COVIS_NEED(d_job_out);
-    COVIS_NEED(d_job_ratio);
+    SE2_NEED(d_bits); SE2_NEED(d_job_kf); SE2_NEED(d_ref_ptr); SE2_NEED(d_job_out); SE2_NEED(d_job_ratio);
     SE2_REQUIRE(njobs >= 0, SE2GPU_ERR_INVALID, "%s: njobs = %d is negative", who, njobs);
     SE2_REQUIRE(nref >= 0, SE2GPU_ERR_INVALID, "%s: nref = %d is negative", who, nref);
     SE2_REQUIRE(nref == 0 || d_ref_idx, SE2GPU_ERR_INVALID, "%s: d_ref_idx is NULL with nref = %d", who, nref);
     SE2_REQUIRE(k >= 1 && k <= 7, SE2GPU_ERR_CAPACITY, "%s: k = %d is outside 1..7 (three counter planes)", who, k);
     SE2_REQUIRE(njobs <= MAX_WAVES, SE2GPU_ERR_CAPACITY, "%s: njobs = %d exceeds the limit %d", who, njobs, MAX_WAVES);
     if (njobs == 0) return SE2GPU_OK;
-    SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
+    SE2_NEED_DEVICE();
     RefArgs a;
     a.bits = (const u64*)d_bits; a.job_kf = d_job_kf; a.ref_ptr = d_ref_ptr; a.ref_idx = d_ref_idx; a.out = d_job_out;
     a.ratio = d_job_ratio; a.W = (int)words_of(m); a.nframes = nframes; a.nref = nref; a.k = k; a.thresh = thresh;

@@ -14,13 +14,11 @@
 //   k_mappoint_large  points with more than 64 observations, one workgroup per point, its waves taking the rows in turn:
 //                     kRegTiles tiles of 64 observations live in registers (descriptor + distance of the current row), the
 //                     tiles beyond are recomputed from memory in every bisection step - N is bounded by the CSR alone
-// An observation is valid when its frame lies in 0..nframes-1, the frame is not null and its feature lies in
-// 0..min(counts, cap)-1; the rest is skipped as the reference skips null key frames (:242), so nothing is indexed outside the
-// arrays whatever they hold (mp_ptr values are clamped to 0..nobs, a descending segment is empty).
+// Which observations count and where a point's list lies is obs_table.h's entry and segment rule, with the null key frames
+// skipped as the reference skips them (:242).
 // Compiled with -ffp-contract=off: mMinDist / mMaxDist (:287-291) are IEEE operations, equal to the host's to the bit.
-#include <climits>
-
 #include "common.h"
+#include "obs_table.h"
 
 using namespace se2gpu;
 
@@ -32,6 +30,8 @@ constexpr int kLargeWaves = 8;   // k_mappoint_large: waves that share the rows 
 
 typedef unsigned long long u64;
 
+// The table's fields keep the places they had in the kernel arguments before obs_table.h: the kernels fetch them in the same
+// pieces and compile to the same instructions.  slots() and csr() hand them to the shared rules.
 struct MpArgs {
     const se2gpu_keypoint* kps;
     const uint8_t* desc;
@@ -49,16 +49,9 @@ struct MpArgs {
     float* dist;
     int cap, nframes, nlevels, m, nobs;
     float sf[kMaxLevels];
+    __device__ __forceinline__ FrameSlots slots() const { return FrameSlots{counts, frame_null, cap, nframes}; }
+    __device__ __forceinline__ ObsCsr csr() const { return ObsCsr{mp_ptr, obs_frame, obs_ftr, m, nobs}; }
 };
-
-// feature index f * cap + k of a valid observation, -1 of one to skip
-__device__ __forceinline__ int obs_offset(const MpArgs& a, int f, int k) {
-    if ((unsigned)f >= (unsigned)a.nframes) return -1;
-    if (a.frame_null && a.frame_null[f]) return -1;
-    const int c = min(a.counts[f], a.cap);
-    if (k < 0 || k >= c) return -1;
-    return f * a.cap + k;
-}
 
 __device__ __forceinline__ void load_desc(const MpArgs& a, int off, u64 d[4]) {
     const u64* p = (const u64*)(a.desc + 32 * (size_t)off);
@@ -67,13 +60,6 @@ __device__ __forceinline__ void load_desc(const MpArgs& a, int off, u64 d[4]) {
 
 __device__ __forceinline__ int hamming256(const u64 a[4], const u64 b[4]) {
     return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
-}
-
-// the segment of point p in the observation arrays, clamped to them
-__device__ __forceinline__ void point_segment(const MpArgs& a, int p, int& s, int& n) {
-    const int s0 = min(max(a.mp_ptr[p], 0), a.nobs), e0 = min(max(a.mp_ptr[p + 1], 0), a.nobs);
-    s = s0;
-    n = max(e0 - s0, 0);
 }
 
 __device__ __forceinline__ void write_none(const MpArgs& a, int p) {
@@ -119,7 +105,7 @@ __device__ __forceinline__ void group_pass(const MpArgs& a, int G, bool active, 
     u64 d[4] = {0, 0, 0, 0};
     if (active && sub < n) {
         frame = a.obs_frame[s + sub];
-        off = obs_offset(a, frame, a.obs_ftr[s + sub]);
+        off = entry_offset(a.slots(), a.csr(), s + sub);
         if (off >= 0) load_desc(a, off, d);
     }
     const bool valid = off >= 0;
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(256) void k_mappoint_small(MpArgs a) {
     if (p0 >= a.m) return;
     int ps = 0, pn = -1;                                   // lane l < 8: the segment of point p0 + l
     if (lane < 8 && p0 + lane < a.m) {
-        point_segment(a, p0 + lane, ps, pn);
+        point_segment(a.csr(), p0 + lane, ps, pn);
         if (pn == 0) write_none(a, p0 + lane);
     }
     for (int G = 8; G <= 64; G <<= 1) {
@@ -191,7 +177,7 @@ __global__ __launch_bounds__(64 * kLargeWaves) void k_mappoint_large(MpArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int pl = 64 * (int)blockIdx.x + lane;
     int ps = 0, pn = 0;
-    if (pl < a.m) point_segment(a, pl, ps, pn);
+    if (pl < a.m) point_segment(a.csr(), pl, ps, pn);
     for (u64 todo = __ballot(pn > 64); todo; todo &= todo - 1) {
         const int l = __ffsll((long long)todo) - 1;
         const int p = 64 * (int)blockIdx.x + l;
@@ -205,14 +191,14 @@ __global__ __launch_bounds__(64 * kLargeWaves) void k_mappoint_large(MpArgs a) {
             off[r] = -1;
             d[r][0] = d[r][1] = d[r][2] = d[r][3] = 0;
             if (j < n) {
-                off[r] = obs_offset(a, a.obs_frame[s + j], a.obs_ftr[s + j]);
+                off[r] = entry_offset(a.slots(), a.csr(), s + j);
                 if (off[r] >= 0) load_desc(a, off[r], d[r]);
             }
             N += __popcll(__ballot(off[r] >= 0));
         }
         for (int j0 = 64 * kRegTiles; j0 < n; j0 += 64) {
             const int j = j0 + lane;
-            const int o = j < n ? obs_offset(a, a.obs_frame[s + j], a.obs_ftr[s + j]) : -1;
+            const int o = j < n ? entry_offset(a.slots(), a.csr(), s + j) : -1;
             N += __popcll(__ballot(o >= 0));
         }
         if (N == 0) {                                     // (every wave counts the same N)
@@ -233,7 +219,7 @@ __global__ __launch_bounds__(64 * kLargeWaves) void k_mappoint_large(MpArgs a) {
                         for (int w = 0; w < 4; ++w) rd[w] = readlane64(d[r][w], i & 63);
                     }
             } else {
-                ro = obs_offset(a, a.obs_frame[s + i], a.obs_ftr[s + i]);
+                ro = entry_offset(a.slots(), a.csr(), s + i);
                 if (ro >= 0) load_desc(a, ro, rd);
             }
             if (ro < 0) continue;
@@ -250,7 +236,7 @@ __global__ __launch_bounds__(64 * kLargeWaves) void k_mappoint_large(MpArgs a) {
                     const int j = j0 + lane;
                     bool in = false;
                     if (j < n) {
-                        const int o = obs_offset(a, a.obs_frame[s + j], a.obs_ftr[s + j]);
+                        const int o = entry_offset(a.slots(), a.csr(), s + j);
                         if (o >= 0) {
                             u64 dj[4];
                             load_desc(a, o, dj);
@@ -287,20 +273,16 @@ extern "C" int se2gpu_mappoint_main_batch_device(se2gpu_matcher* h, const se2gpu
                                                  const int32_t* d_obs_frame, const int32_t* d_obs_ftr, int m, int nobs,
                                                  const int32_t* d_prev_main_frame, int32_t* d_info, uint8_t* d_main_desc,
                                                  int32_t* d_main_frame, int32_t* d_main_octave, float* d_dist) {
-    SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "mappoint_main_batch: matcher handle is NULL");
-    SE2_REQUIRE(d_kps && d_desc && d_counts && d_mp_ptr && d_info && d_main_desc && d_main_frame && d_main_octave,
-                SE2GPU_ERR_INVALID, "mappoint_main_batch: NULL argument");
-    SE2_REQUIRE(m >= 0 && nobs >= 0 && cap >= 1 && nframes >= 1 && nlevels >= 1, SE2GPU_ERR_INVALID,
-                "mappoint_main_batch: bad sizes (m %d, nobs %d, cap %d, nframes %d, nlevels %d)", m, nobs, cap, nframes, nlevels);
-    SE2_REQUIRE(nobs == 0 || (d_obs_frame && d_obs_ftr), SE2GPU_ERR_INVALID, "mappoint_main_batch: observations are NULL");
-    SE2_REQUIRE(!d_view_pos || (scale_factors && d_dist), SE2GPU_ERR_INVALID,
-                "mappoint_main_batch: view positions need scale_factors and d_dist");
-    SE2_REQUIRE(nlevels <= kMaxLevels, SE2GPU_ERR_CAPACITY, "mappoint_main_batch: %d levels exceed the limit %d", nlevels,
-                kMaxLevels);
-    SE2_REQUIRE((long long)nframes * cap <= INT_MAX, SE2GPU_ERR_CAPACITY,
-                "mappoint_main_batch: nframes * cap = %lld exceeds the limit %d", (long long)nframes * cap, INT_MAX);
+    const char* who = "mappoint_main_batch";
+    SE2_NEED(h); SE2_NEED(d_kps); SE2_NEED(d_desc);
+    SE2_NEED(d_info); SE2_NEED(d_main_desc); SE2_NEED(d_main_frame); SE2_NEED(d_main_octave);
+    SE2_CHECK(check_obs_csr(who, d_mp_ptr, d_obs_frame, d_obs_ftr, m, nobs));
+    SE2_REQUIRE(nlevels >= 1, SE2GPU_ERR_INVALID, "%s: nlevels = %d is below 1", who, nlevels);
+    SE2_REQUIRE(!d_view_pos || (scale_factors && d_dist), SE2GPU_ERR_INVALID, "%s: d_view_pos needs scale_factors and d_dist", who);
+    SE2_CHECK(check_frame_slots(who, d_counts, cap, nframes));   // its nframes * cap refusal is the first of the capacity ones
+    SE2_REQUIRE(nlevels <= kMaxLevels, SE2GPU_ERR_CAPACITY, "%s: %d levels exceed the limit %d", who, nlevels, kMaxLevels);
     if (m == 0) return SE2GPU_OK;
-    SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
+    SE2_NEED_DEVICE();
     MpArgs a;
     a.kps = d_kps; a.desc = d_desc; a.counts = d_counts; a.frame_null = d_frame_null; a.view_pos = d_view_pos;
     a.mp_ptr = d_mp_ptr; a.obs_frame = d_obs_frame; a.obs_ftr = d_obs_ftr; a.prev = d_prev_main_frame;

@@ -11,11 +11,10 @@
 // The arithmetic is view_info.h's, shared with the host mirror (include/se2lam_amd/FindCorrespd.h).  A point's and a
 // feature's outputs are functions of their own inputs alone: integer atomics for the counters, no float atomics.
 // The frame slots of a batch's jobs are pairwise distinct (the caller's duty, se2gpu.h): a job owns the flags of its two frames.
-// Every index read from an array is checked before it is used, so nothing is indexed outside the arrays whatever they hold.
+// Every index read from an array is checked before it is used (obs_table.h; a null key frame is not skipped): nothing is indexed outside them.
 // Compiled with -ffp-contract=off like the matchers and triangulate.hip.
-#include <climits>
-
 #include "common.h"
+#include "obs_table.h"
 #include "view_info.h"
 
 using namespace se2gpu;
@@ -29,15 +28,9 @@ struct FrameArgs {
     const float* Twc;
     const float* P;
     int cap, nframes;
+    // no frame_null: updateParallax and findCorrespd do not skip a null key frame, and the rule's test folds away
+    __device__ __forceinline__ FrameSlots slots() const { return FrameSlots{counts, nullptr, cap, nframes}; }
 };
-
-// feature index f * cap + k of a valid (frame, feature), -1 otherwise (a null frame is valid here: updateParallax does not skip it)
-__device__ __forceinline__ int feature_offset(const FrameArgs& fr, int f, int k) {
-    if ((unsigned)f >= (unsigned)fr.nframes) return -1;
-    const int c = min(fr.counts[f], fr.cap);
-    if (k < 0 || k >= c) return -1;
-    return f * fr.cap + k;
-}
 
 struct PrlArgs {
     FrameArgs fr;
@@ -55,8 +48,8 @@ struct PrlArgs {
     float* obs_info;
     int m, nobs;
     float fx, lower, upper;
+    __device__ __forceinline__ ObsCsr csr() const { return ObsCsr{mp_ptr, obs_frame, obs_ftr, m, nobs}; }
 };
-
 __device__ __forceinline__ void store3(float* dst, const float v[3]) {
     dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2];
 }
@@ -69,15 +62,16 @@ __global__ __launch_bounds__(128) void k_parallax(PrlArgs a) {
     const int p = blockIdx.x * 128 + threadIdx.x;
     if (p >= a.m) return;
     const FrameArgs& fr = a.fr;
-    int status = 0, place0 = -1;
-    const int s = min(max(a.mp_ptr[p], 0), a.nobs), e = min(max(a.mp_ptr[p + 1], 0), a.nobs);
-    const int n = max(e - s, 0);
+    const FrameSlots fs = fr.slots();
+    const ObsCsr csr = a.csr();
+    int status = 0, place0 = -1, s, n;
+    point_segment(csr, p, s, n);
     const int fnew = a.new_frame[p];
     do {
         if (a.good_prl[p]) break;                                      // :125
         int N = 0, place1 = -1, off1 = -1;                             // pKF: the first valid entry of the new frame
         for (int i = 0; i < n; ++i) {
-            const int f = a.obs_frame[s + i], off = feature_offset(fr, f, a.obs_ftr[s + i]);
+            const int f = a.obs_frame[s + i], off = entry_offset(fs, csr, s + i);
             if (off < 0) continue;
             ++N;
             if (f == fnew && place1 < 0) { place1 = i; off1 = off; }
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(128) void k_parallax(PrlArgs a) {
         long long id0 = 0;
         int f0 = -1, off0 = -1;
         for (int i = 0; i < n; ++i) {                                  // :129-139, the oldest key frame of the last six
-            const int f = a.obs_frame[s + i], off = feature_offset(fr, f, a.obs_ftr[s + i]);
+            const int f = a.obs_frame[s + i], off = entry_offset(fs, csr, s + i);
             if (off < 0) continue;
             const long long id = a.idkf[f];
             if (id1 - id > 6) continue;
@@ -114,7 +108,7 @@ __global__ __launch_bounds__(128) void k_parallax(PrlArgs a) {
                 status = 2;
                 if (a.kf_observed)
                     for (int i = 0; i < n; ++i) {
-                        const int off = feature_offset(fr, a.obs_frame[s + i], a.obs_ftr[s + i]);
+                        const int off = entry_offset(fs, csr, s + i);
                         if (off >= 0) a.kf_observed[off] = 0;
                     }
             }
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(128) void k_parallax(PrlArgs a) {
         rot_of(Tcw0, R);
         mat3_at_m_a(R, info0, infoW);                                  // :163-164
         for (int i = 0; i < n; ++i) {                                  // :160-161, :167-177
-            const int f = a.obs_frame[s + i], off = feature_offset(fr, f, a.obs_ftr[s + i]);
+            const int f = a.obs_frame[s + i], off = entry_offset(fs, csr, s + i);
             if (off < 0) continue;
             float* view = a.obs_view + 3 * (size_t)(s + i);
             float* info = a.obs_info + 9 * (size_t)(s + i);
@@ -185,23 +179,24 @@ struct CorArgs {
 __global__ __launch_bounds__(128) void k_invert_match(CorArgs a) {
     const int b = blockIdx.y, i = blockIdx.x * 128 + threadIdx.x;
     const int fp = a.job_prev[b], fn = a.job_new[b];
-    if ((unsigned)fp >= (unsigned)a.fr.nframes || (unsigned)fn >= (unsigned)a.fr.nframes) return;
-    if (i >= min(a.fr.counts[fp], a.fr.cap)) return;
-    const int j = a.matched12[(size_t)b * a.fr.cap + i];
-    if (j < 0 || j >= min(a.fr.counts[fn], a.fr.cap)) return;
-    if (atomicMax(&a.inv[(size_t)b * a.fr.cap + j], i) >= 0) atomicAdd(&a.counts_out[5 * b + 4], 1);
+    const FrameSlots fs = a.fr.slots();
+    if ((unsigned)fp >= (unsigned)fs.nframes || (unsigned)fn >= (unsigned)fs.nframes) return;
+    if (i >= feature_count(fs, fp)) return;
+    const int j = a.matched12[(size_t)b * fs.cap + i];
+    if (j < 0 || j >= feature_count(fs, fn)) return;
+    if (atomicMax(&a.inv[(size_t)b * fs.cap + j], i) >= 0) atomicAdd(&a.counts_out[5 * b + 4], 1);
 }
 
 __global__ __launch_bounds__(128) void k_correspd(CorArgs a) {
     const FrameArgs& fr = a.fr;
     const int b = blockIdx.y, j = blockIdx.x * 128 + threadIdx.x;
-    const int cap = fr.cap;
+    const int cap = fr.cap, nframes = fr.nframes;
     int kind = 0, src = -1;
     bool in_row = false;
     if (j < cap) {
         const int fp = a.job_prev[b], fn = a.job_new[b];
         const size_t row = (size_t)b * cap;
-        if ((unsigned)fp < (unsigned)fr.nframes && (unsigned)fn < (unsigned)fr.nframes && fp != fn && j < min(fr.counts[fn], cap)) {
+        if ((unsigned)fp < (unsigned)nframes && (unsigned)fn < (unsigned)nframes && fp != fn && j < feature_count(fr.slots(), fn)) {
             in_row = true;
             const size_t onew = (size_t)fn * cap + j;
             const bool was_observed = a.kf_observed[onew] != 0;
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(128) void k_correspd(CorArgs a) {
                 const int q = a.match_idx_mp[row + j];
                 if (q >= 0 && q < a.m) {
                     const int fm = a.mp_main_frame[q];
-                    const int om = feature_offset(fr, fm, a.mp_main_ftr[q]);
+                    const int om = feature_offset(fr.slots(), fm, a.mp_main_ftr[q]);
                     if (om >= 0) {
                         const float pt1[2] = {fr.kps_un[om].x, fr.kps_un[om].y};
                         const float pt2[2] = {fr.kps_un[onew].x, fr.kps_un[onew].y};
@@ -275,15 +270,6 @@ __global__ __launch_bounds__(128) void k_correspd(CorArgs a) {
     }
 }
 
-int check_frames(const char* who, const void* kps, const void* counts, const void* Tcw, const void* Twc, const void* P,
-                 int cap, int nframes) {
-    SE2_REQUIRE(kps && counts && Tcw && Twc && P, SE2GPU_ERR_INVALID, "%s: NULL frame array", who);
-    SE2_REQUIRE(cap >= 1 && nframes >= 1, SE2GPU_ERR_INVALID, "%s: bad sizes (cap %d, nframes %d)", who, cap, nframes);
-    SE2_REQUIRE((long long)nframes * cap <= INT_MAX, SE2GPU_ERR_CAPACITY, "%s: nframes * cap = %lld exceeds the limit %d", who,
-                (long long)nframes * cap, INT_MAX);
-    return SE2GPU_OK;
-}
-
 }  // namespace
 
 extern "C" int se2gpu_mappoint_parallax_batch_device(se2gpu_matcher* h, const se2gpu_keypoint* d_kps_un,
@@ -297,21 +283,21 @@ extern "C" int se2gpu_mappoint_parallax_batch_device(se2gpu_matcher* h, const se
                                                      int32_t* d_pkf0_place, float* d_pos, float* d_obs_view,
                                                      float* d_obs_info) {
     const char* who = "mappoint_parallax_batch";
-    SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "%s: matcher handle is NULL", who);
-    SE2_REQUIRE(m >= 0 && nobs >= 0, SE2GPU_ERR_INVALID, "%s: bad sizes (m %d, nobs %d)", who, m, nobs);
-    SE2_CHECK(check_frames(who, d_kps_un, d_counts, d_frame_Tcw, d_frame_Twc, d_frame_P, cap, nframes));
-    SE2_REQUIRE(d_frame_idkf && d_mp_ptr && d_good_prl && d_new_frame && d_status && d_pkf0_place && d_pos,
-                SE2GPU_ERR_INVALID, "%s: NULL argument", who);
-    SE2_REQUIRE(nobs == 0 || (d_obs_frame && d_obs_ftr && d_obs_view && d_obs_info), SE2GPU_ERR_INVALID,
-                "%s: observations are NULL", who);
+    SE2_NEED(h);
+    SE2_CHECK(check_obs_csr(who, d_mp_ptr, d_obs_frame, d_obs_ftr, m, nobs));
+    SE2_NEED(d_kps_un); SE2_NEED(d_frame_Tcw); SE2_NEED(d_frame_Twc); SE2_NEED(d_frame_P);
+    SE2_CHECK(check_frame_slots(who, d_counts, cap, nframes));
+    SE2_NEED(d_frame_idkf); SE2_NEED(d_good_prl); SE2_NEED(d_new_frame);
+    SE2_NEED(d_status); SE2_NEED(d_pkf0_place); SE2_NEED(d_pos);
+    SE2_NEED_IF(nobs > 0, d_obs_view); SE2_NEED_IF(nobs > 0, d_obs_info);
     if (m == 0) return SE2GPU_OK;
-    SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
+    SE2_NEED_DEVICE();
     PrlArgs a;
     a.fr = FrameArgs{d_kps_un, d_counts, d_frame_Tcw, d_frame_Twc, d_frame_P, cap, nframes};
-    a.idkf = d_frame_idkf; a.mp_ptr = d_mp_ptr; a.obs_frame = d_obs_frame; a.obs_ftr = d_obs_ftr;
+    a.idkf = d_frame_idkf; a.mp_ptr = d_mp_ptr; a.obs_frame = d_obs_frame; a.obs_ftr = d_obs_ftr; a.m = m; a.nobs = nobs;
     a.good_prl = d_good_prl; a.new_frame = d_new_frame; a.kf_observed = d_kf_observed;
     a.status = d_status; a.pkf0_place = d_pkf0_place; a.pos = d_pos; a.obs_view = d_obs_view; a.obs_info = d_obs_info;
-    a.m = m; a.nobs = nobs; a.fx = fx; a.lower = lower_depth; a.upper = upper_depth;
+    a.fx = fx; a.lower = lower_depth; a.upper = upper_depth;
     hipStream_t st = (hipStream_t)se2gpu_matcher_stream(h);
     hipLaunchKernelGGL(k_parallax, dim3(((unsigned)m + 127u) / 128u), dim3(128), 0, st, a);
     SE2_HIP(hipGetLastError());
@@ -330,13 +316,13 @@ extern "C" int se2gpu_kf_correspd_batch_device(se2gpu_matcher* h, const se2gpu_k
                                                uint8_t* d_kind, int32_t* d_src, float* d_view, float* d_info,
                                                float* d_new_pos_w, float* d_info_prev, int32_t* d_counts_out) {
     const char* who = "kf_correspd_batch";
-    SE2_REQUIRE(h, SE2GPU_ERR_INVALID, "%s: matcher handle is NULL", who);
+    SE2_NEED(h);
     SE2_REQUIRE(B >= 0 && m >= 0, SE2GPU_ERR_INVALID, "%s: bad sizes (B %d, m %d)", who, B, m);
     SE2_REQUIRE(passes >= 1 && passes <= 7, SE2GPU_ERR_INVALID, "%s: passes = %d is outside 1..7", who, passes);
-    SE2_CHECK(check_frames(who, d_kps_un, d_counts, d_frame_Tcw, d_frame_Twc, d_frame_P, cap, nframes));
-    SE2_REQUIRE(d_kf_observed && d_job_prev && d_job_new && d_Tcr && d_matched12 && d_inv && d_kind && d_src && d_view &&
-                    d_info && d_counts_out,
-                SE2GPU_ERR_INVALID, "%s: NULL argument", who);
+    SE2_NEED(d_kps_un); SE2_NEED(d_frame_Tcw); SE2_NEED(d_frame_Twc); SE2_NEED(d_frame_P);
+    SE2_CHECK(check_frame_slots(who, d_counts, cap, nframes));
+    SE2_NEED(d_kf_observed); SE2_NEED(d_job_prev); SE2_NEED(d_job_new); SE2_NEED(d_Tcr); SE2_NEED(d_matched12);
+    SE2_NEED(d_inv); SE2_NEED(d_kind); SE2_NEED(d_src); SE2_NEED(d_view); SE2_NEED(d_info); SE2_NEED(d_counts_out);
     SE2_REQUIRE(!(passes & 1) || (d_view_pos && d_Trc), SE2GPU_ERR_INVALID, "%s: pass 1 needs d_view_pos and d_Trc", who);
     SE2_REQUIRE(!(passes & 2) || d_match_idx_mp, SE2GPU_ERR_INVALID, "%s: pass 2 needs d_match_idx_mp", who);
     SE2_REQUIRE(!(passes & 2) || m == 0 || (d_mp_main_frame && d_mp_main_ftr && d_mp_main_octave && d_mp_normal && d_mp_dist),
@@ -346,7 +332,7 @@ extern "C" int se2gpu_kf_correspd_batch_device(se2gpu_matcher* h, const se2gpu_k
     SE2_REQUIRE((long long)B * cap <= INT_MAX && B <= 65535, SE2GPU_ERR_CAPACITY,
                 "%s: %d jobs of %d features exceed the limit (65535 jobs, B * cap <= %d)", who, B, cap, INT_MAX);
     if (B == 0) return SE2GPU_OK;
-    SE2_REQUIRE(have_device(), SE2GPU_ERR_NO_DEVICE, "no HIP device visible (libse2gpu has no CPU fallback)");
+    SE2_NEED_DEVICE();
     CorArgs a;
     a.fr = FrameArgs{d_kps_un, d_counts, d_frame_Tcw, d_frame_Twc, d_frame_P, cap, nframes};
     a.kf_observed = d_kf_observed; a.view_pos = d_view_pos; a.job_prev = d_job_prev; a.job_new = d_job_new;

@@ -10,21 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
-
-SENTINEL_FRAME, SENTINEL_OCTAVE, SENTINEL_DIST, SENTINEL_DESC = -55, -77, -1.0, 0xAB
-
-
-def csr(lists):
-    """[(frames, features), ...] per point, in container order -> mp_ptr (m + 1), obs_frame, obs_ftr (int32)"""
-    ptr = np.zeros(len(lists) + 1, np.int32)
-    for i, (f, _) in enumerate(lists):
-        ptr[i + 1] = ptr[i] + len(f)
-    cat = lambda j: (np.concatenate([np.asarray(l[j], np.int32).ravel() for l in lists]) if lists else np.zeros(0, np.int32))
-    return ptr, cat(0).astype(np.int32), cat(1).astype(np.int32)
-
-
-def _ptr(d):
-    return None if d is None else (d.ptr if isinstance(d, capi.DeviceArray) else d)
+from .capi import SENTINEL_DESC, SENTINEL_DIST, SENTINEL_FRAME, SENTINEL_OCTAVE, csr, dev_ptr as _ptr, upload as up
 
 
 def update_main_batch_device(matcher, d_kps, d_desc, d_counts, cap, nframes, d_mp_ptr, d_obs_frame, d_obs_ftr, m, nobs,
@@ -49,12 +35,9 @@ class DeviceFrames:
 
     def __init__(self, kps, desc, counts, cap, frame_null=None, view_pos=None):
         self.cap, self.nframes = int(cap), len(counts)
-        up = capi.DeviceArray.from_numpy
-        self.kps = up(np.ascontiguousarray(kps, capi.KP_DTYPE))
-        self.desc = up(np.ascontiguousarray(desc, np.uint8))
-        self.counts = up(np.ascontiguousarray(counts, np.int32))
-        self.frame_null = None if frame_null is None else up(np.ascontiguousarray(frame_null, np.uint8))
-        self.view_pos = None if view_pos is None else up(np.ascontiguousarray(view_pos, np.float32))
+        self.kps, self.desc, self.counts = up(kps, capi.KP_DTYPE), up(desc, np.uint8), up(counts, np.int32)
+        self.frame_null = None if frame_null is None else up(frame_null, np.uint8)
+        self.view_pos = None if view_pos is None else up(view_pos, np.float32)
 
 
 def sentinels(m):
@@ -72,12 +55,10 @@ class MainBatch:
         self.m = len(lists)
         ptr, fr, ft = csr(lists)
         self.nobs = len(fr)
-        up = capi.DeviceArray.from_numpy
-        pad = lambda a: a if len(a) else np.zeros(1, a.dtype)   # (an allocation of 0 bytes has no address)
-        self.mp_ptr, self.obs_frame, self.obs_ftr = up(ptr), up(pad(fr)), up(pad(ft))
-        self.prev = None if prev_main_frame is None else up(pad(np.ascontiguousarray(prev_main_frame, np.int32)))
+        self.mp_ptr, self.obs_frame, self.obs_ftr = up(ptr), up(fr), up(ft)
+        self.prev = None if prev_main_frame is None else up(prev_main_frame, np.int32)
         init = init or sentinels(max(self.m, 1))
-        self.out = {k: up(np.ascontiguousarray(v)) for k, v in init.items()}
+        self.out = {k: up(v) for k, v in init.items()}
         self._shapes = {k: (v.dtype, v.shape) for k, v in init.items()}
 
     def run(self, matcher, frames: DeviceFrames, scale_factors, with_view=True, nlevels=None):

@@ -168,6 +168,28 @@ def cpp_run(program, path, jobs):
     return out
 
 
+def against_header(program, path, jobs):
+    """cpp_run held to the set model (tests/covis_model.py), exactly; returns the number of calls compared"""
+    import covis_model as cm
+    got = cpp_run(program, path, jobs)
+    i = 0
+    for t, calls in jobs:
+        m = cm.Model(*tables(t))
+        for c in calls:
+            g = got[i]
+            i += 1
+            if c[0] == "pairs":
+                w = m.pairs([c[1]], [c[2]], 0.3, 0.1)
+                assert (g["n_same"], g["size_a"], g["size_b"], g["connect"]) == (*w["out"][0, :3], w["out"][0, 3] & 1), c
+                assert cm.same_floats(g["ratio"], w["ratio"][0]) and g["common"] == m.common(c[1], c[2]), c
+            else:
+                w = m.refset([c[1]], [0, len(c[2])], c[2], c[3], 0.8)
+                assert g["cnt"] == w["out"][0, 0] and cm.same_floats(g["ratio"], w["ratio"][0]), c
+                assert g["common"] == m.refset_points(c[1], c[2], c[3])[0], c
+                assert g["redundant"] == m.refset([c[1]], [0, len(c[2])], c[2], 2, 0.8)["out"][0, 2], c
+    return i
+
+
 # ---- tests/golden/covis_ref.npz: maps built with the reference's own objects and what the compiled reference answered
 # (tools/gen_covis_golden.cpp)
 

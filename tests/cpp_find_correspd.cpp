@@ -78,7 +78,8 @@ int main(int argc, char** argv) {
             std::vector<float> info(9 * (size_t)nobs + 9, -7.f);
             for (int p = 0; p < m; ++p) {
                 Point3f pos{-7.f, -7.f, -7.f};
-                const int s = ptr[p], n = ptr[p + 1] - ptr[p];
+                int s, n;
+                se2gpu::point_segment(se2gpu::ObsCsr{ptr.data(), of.data(), ok.data(), m, nobs}, p, s, n);
                 const ParallaxUpdate u = updateParallax(fs, ps, of.data() + s, ok.data() + s, n, good[p] != 0, nw[p], fx, lower, upper,
                                                         observed.data(), &pos, view.data() + s, info.data() + 9 * (size_t)s);
                 std::printf("%d %d %u %u %u\n", u.status, u.pKF0Place, bits_of(pos.x), bits_of(pos.y), bits_of(pos.z));

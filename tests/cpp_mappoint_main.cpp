@@ -62,7 +62,8 @@ int main(int argc, char** argv) {
         for (auto& b : md) b = 0xAB;
         int32_t frame = -55, octave = -77;
         float dist[2] = {-1.0f, -1.0f};
-        const int s = mp_ptr[p], n = mp_ptr[p + 1] - s;
+        int s, n;
+        se2gpu::point_segment(se2gpu::ObsCsr{mp_ptr.data(), obs_frame.data(), obs_ftr.data(), m, nobs}, p, s, n);
         const MainObservationInfo r = mainObservation(frames, has_null ? null.data() : nullptr, has_view ? view.data() : nullptr,
                                                       sf.data(), nlevels, obs_frame.data() + s, obs_ftr.data() + s, n, prev[p],
                                                       md, &frame, &octave, dist);

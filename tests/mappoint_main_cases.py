@@ -3,6 +3,8 @@
 distances and equal medians occur."""
 import numpy as np
 
+from se2lam_amd.capi import csr  # noqa: F401  (the one builder of the observation CSR; loads no library)
+
 NFRAMES, CAP, NLEVELS = 136, 16, 8
 KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
                ("class_id", "<i4")])
@@ -46,14 +48,58 @@ def first_batch(fs, seed=11):
     return lists
 
 
-def csr(lists):
-    ptr = np.zeros(len(lists) + 1, np.int32)
-    ptr[1:] = np.cumsum([len(f) for f, _ in lists])
-    cat = lambda j: np.concatenate([np.asarray(l[j], np.int32) for l in lists] + [np.zeros(0, np.int32)]).astype(np.int32)
-    return ptr, cat(0), cat(1)
-
-
 def sentinels(m):
     return dict(info=np.full((m, 4), -9, np.int32), main_desc=np.full((m, 32), 0xAB, np.uint8),
                 main_frame=np.full(m, -55, np.int32), main_octave=np.full(m, -77, np.int32),
                 dist=np.full((m, 2), -1.0, np.float32))
+
+
+# ---- the header's host function (include/se2lam_amd/MapPointMain.h) through tests/cpp_mappoint_main.cpp
+
+def cpp_build(outdir):
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++")
+    assert cxx
+    out = os.path.join(str(outdir), "cpp_mappoint_main")
+    libdir = os.path.join(root, "se2lam_amd", "lib")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(root, "include"),
+                           os.path.join(root, "tests", "cpp_mappoint_main.cpp"), "-o", out, "-L", libdir, "-lse2gpu",
+                           "-Wl,-rpath," + libdir])
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+
+
+def cpp_run(program, path, counts, cap, scale, octave, desc, null, view, ptr, fr, ft, prev):
+    """mainObservation for every point of the CSR; null, view and prev may be None.  Returns the arrays of sentinels()."""
+    import subprocess
+    m = len(ptr) - 1
+    vals = [len(counts), cap, len(scale), m, len(fr), int(null is not None), int(view is not None), int(prev is not None)]
+    vals += list(counts)
+    if null is not None:
+        vals += list(null)
+    vals += _bits(scale) + list(octave) + list(np.asarray(desc).ravel())
+    if view is not None:
+        vals += _bits(view)
+    vals += list(ptr) + list(fr) + list(ft)
+    if prev is not None:
+        vals += list(prev)
+    with open(str(path), "w") as f:
+        f.write(" ".join(str(int(v)) for v in vals))
+    r = subprocess.run([program, str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    rows = np.array([[int(v) for v in ln.split()] for ln in r.stdout.splitlines()], np.int64).reshape(m, 40)
+    return dict(info=rows[:, :4].astype(np.int32), main_frame=rows[:, 4].astype(np.int32), main_octave=rows[:, 5].astype(np.int32),
+                dist=rows[:, 6:8].astype(np.uint32).view(np.float32), main_desc=rows[:, 8:].astype(np.uint8))
+
+
+def same(got, want):
+    """every integer output equal, the distances equal to the bit"""
+    for k in ("info", "main_desc", "main_frame", "main_octave"):
+        assert np.array_equal(got[k], want[k]), k
+    assert np.array_equal(got["dist"].view(np.uint32), want["dist"].view(np.uint32)), "dist"

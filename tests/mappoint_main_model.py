@@ -47,10 +47,10 @@ def update_main_batch(kps, desc, counts, cap, nframes, frame_null, view_pos, sca
     None; out: dict of info (m, 4) int32, main_desc (m, 32) uint8, main_frame (m,), main_octave (m,) int32, dist (m, 2) float32
     holding the values before the call.  Returns a new dict of the values after it."""
     o = {k: np.array(v, copy=True) for k, v in out.items()}
-    m = len(mp_ptr) - 1
+    m, nobs = len(mp_ptr) - 1, len(obs_frame)
     for p in range(m):
-        s, e = int(mp_ptr[p]), int(mp_ptr[p + 1])
-        fr, ft = obs_frame[s:e], obs_ftr[s:e]
+        s, e = (min(max(int(v), 0), nobs) for v in (mp_ptr[p], mp_ptr[p + 1]))   # clamped; a descending segment is empty
+        fr, ft = obs_frame[s:max(e, s)], obs_ftr[s:max(e, s)]
         keep = valid_observations(fr, ft, counts, cap, nframes, frame_null)
         if not keep:
             o["info"][p] = (-1, 0, 0, 0)

@@ -6,6 +6,7 @@ is redrawn until that holds, and `margins_of_*` let the CPU test assert it for t
 import numpy as np
 
 import new_kf_model as nk
+from se2lam_amd import capi
 
 CAP, NFRAMES = 64, 9
 FX, CX, CY = 230.0, 160.0, 120.0
@@ -27,14 +28,15 @@ def _rot_y(a):
 class Scene:
     """poses, intrinsics and an empty key-point table; add_point projects a world point into the frames of its list"""
 
-    def __init__(self, seed=1, counts=COUNTS):
+    def __init__(self, seed=1, counts=COUNTS, idkf=IDKF, cap=CAP):
         rng = np.random.default_rng(seed)
+        self.cap = cap
         K = np.array([[FX, 0, CX], [0, FX, CY], [0, 0, 1.0]])
         self.Tcw64 = []
         Tcw, Twc, P = [], [], []
-        for f in range(NFRAMES):
+        for f in range(len(idkf)):
             R = _rot_y(0.02 * rng.standard_normal())
-            c = np.array([STEP * IDKF[f] + (0.03 if f == 3 else 0.0), 0.01 * rng.standard_normal(), 0.02 * rng.standard_normal()])
+            c = np.array([STEP * idkf[f] + (0.03 if f == 3 else 0.0), 0.01 * rng.standard_normal(), 0.02 * rng.standard_normal()])
             T = np.eye(4)
             T[:3, :3], T[:3, 3] = R, -R @ c
             T32 = T.astype(np.float32)                 # what the caller holds; inverse and projection derive from it
@@ -42,11 +44,11 @@ class Scene:
             Tcw.append(T32[:3].ravel())
             Twc.append(np.linalg.inv(T32.astype(np.float64))[:3].astype(np.float32).ravel())
             P.append((K @ T32[:3].astype(np.float64)).astype(np.float32).ravel())
-        self.kps = np.zeros(NFRAMES * CAP, KP)
+        self.kps = np.zeros(len(idkf) * cap, KP)
         self.kps["x"], self.kps["y"] = CX, CY
         self.kps["octave"] = 2
         self.K = K
-        self.fr = nk.Frames(self.kps, counts, CAP, np.array(Tcw), np.array(Twc), np.array(P), IDKF)
+        self.fr = nk.Frames(self.kps, counts, cap, np.array(Tcw), np.array(Twc), np.array(P), idkf)
         self.rng = rng
 
     def world(self, depth, f=NEW, spread=0.25):
@@ -60,17 +62,14 @@ class Scene:
     def put(self, f, k, X, octave=2, noise=0.0):
         pc = self.cam(f, X)
         uv = self.K @ (pc / pc[2])
-        o = f * CAP + k
+        o = f * self.cap + k
         self.kps["x"][o], self.kps["y"][o] = uv[0] + noise * self.rng.standard_normal(), uv[1] + noise * self.rng.standard_normal()
         self.kps["octave"][o] = octave
 
 
 def csr(lists):
-    ptr = np.zeros(len(lists) + 1, np.int32)
-    for i, l in enumerate(lists):
-        ptr[i + 1] = ptr[i] + len(l)
-    flat = [e for l in lists for e in l]
-    return ptr, np.array([e[0] for e in flat], np.int32), np.array([e[1] for e in flat], np.int32)
+    """lists of (frame, feature) pairs per point -> mp_ptr, obs_frame, obs_ftr"""
+    return capi.csr([([e[0] for e in l], [e[1] for e in l]) for l in lists])
 
 
 def _one_point(sc, entries, good=0, new=NEW):
@@ -335,3 +334,57 @@ def restatement_errors(pc, cc_list):
             ep += [nk.rel_err_pos(b["view"][w], a["view"][w]), nk.rel_err_pos(b["new_pos_w"][w3], a["new_pos_w"][w3])]
             em += [nk.rel_err_mat(b["info"][w], a["info"][w]), nk.rel_err_mat(b["info_prev"][w3], a["info_prev"][w3])]
     return float(np.concatenate(ep).max()), float(np.concatenate(em).max())
+
+
+# ---- the header's host functions (include/se2lam_amd/FindCorrespd.h) through tests/cpp_find_correspd.cpp
+
+def cpp_build(outdir):
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = os.path.join(str(outdir), "cpp_find_correspd")
+    libdir = os.path.join(root, "se2lam_amd", "lib")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(root, "include"),
+                           os.path.join(root, "tests", "cpp_find_correspd.cpp"), "-o", out, "-L", libdir, "-lse2gpu",
+                           "-Wl,-rpath," + libdir])
+    return out
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+
+
+def cpp_run_parallax(program, path, fr, ptr, obs_frame, obs_ftr, good, new, observed, fx=FX, lower=LOWER, upper=UPPER, lines=()):
+    """updateParallax for every point of the CSR, after the "I" lines given.  Returns their output rows and the outputs of
+    nk.parallax_batch as float32."""
+    import subprocess
+    m, nobs = len(ptr) - 1, len(obs_frame)
+    head = [fr.nframes, fr.cap, m, nobs] + list(fr.counts) + list(fr.idkf) + bits(fr.Tcw) + bits(fr.Twc) + bits(fr.P) + \
+        bits(fr.kps["x"]) + bits(fr.kps["y"]) + list(ptr) + list(obs_frame) + list(obs_ftr) + list(good) + list(new) + \
+        bits([fx, lower, upper]) + list(observed)
+    with open(str(path), "w") as f:
+        f.write("\n".join(list(lines) + ["P " + " ".join(str(int(v)) for v in head)]) + "\n")
+    r = subprocess.run([program, str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    rows = r.stdout.splitlines()
+    n = len(lines)
+    pts = np.array([[int(x) for x in ln.split()] for ln in rows[n:n + m]], np.int64).reshape(m, 5)
+    ob = np.array([[int(x) for x in ln.split()] for ln in rows[n + m:n + m + nobs]], np.int64).reshape(nobs, 12)
+    ob = ob.astype(np.uint32).view(np.float32)
+    return rows[:n], dict(status=pts[:, 0].astype(np.int32), place=pts[:, 1].astype(np.int32),
+                          pos=pts[:, 2:5].astype(np.uint32).view(np.float32), obs_view=ob[:, :3], obs_info=ob[:, 3:],
+                          kf_observed=np.array([int(x) for x in rows[n + m + nobs].split()], np.uint8))
+
+
+def same_parallax(got, ref):
+    """the host mirror against the float32 restatement: integers exactly, the DLT to the bit (no library call in it), the
+    rest to 4e-6 relative - the two sides differ in asinf / sin / cos of the C library against numpy's alone"""
+    nobs = len(got["obs_view"])
+    assert np.array_equal(got["status"], ref["status"]) and np.array_equal(got["place"], ref["place"])
+    assert np.array_equal(got["pos"].view(np.uint32), ref["pos"].view(np.uint32))
+    w = ref["obs_view"][:nobs, 0] != nk.SENT
+    assert np.array_equal(got["obs_view"][:, 0] != np.float32(nk.SENT), w)
+    assert w.any()
+    assert nk.rel_err_pos(got["obs_view"][w], ref["obs_view"][:nobs][w]).max() < 4e-6
+    assert nk.rel_err_mat(got["obs_info"][w], ref["obs_info"][:nobs][w]).max() < 4e-6
+    assert np.array_equal(got["kf_observed"], ref["kf_observed"])

@@ -70,26 +70,6 @@ def program(tmp_path_factory):
     return cc.cpp_build(tmp_path_factory.mktemp("covis"))
 
 
-def _against_header(program, path, jobs):
-    got = cc.cpp_run(program, path, jobs)
-    i = 0
-    for t, calls in jobs:
-        m = cm.Model(*cc.tables(t))
-        for c in calls:
-            g = got[i]
-            i += 1
-            if c[0] == "pairs":
-                w = m.pairs([c[1]], [c[2]], 0.3, 0.1)
-                assert (g["n_same"], g["size_a"], g["size_b"], g["connect"]) == (*w["out"][0, :3], w["out"][0, 3] & 1), c
-                assert cm.same_floats(g["ratio"], w["ratio"][0]) and g["common"] == m.common(c[1], c[2]), c
-            else:
-                w = m.refset([c[1]], [0, len(c[2])], c[2], c[3], 0.8)
-                assert g["cnt"] == w["out"][0, 0] and cm.same_floats(g["ratio"], w["ratio"][0]), c
-                assert g["common"] == m.refset_points(c[1], c[2], c[3])[0], c
-                assert g["redundant"] == m.refset([c[1]], [0, len(c[2])], c[2], 2, 0.8)["out"][0, 2], c
-    return i
-
-
 def test_header_host_functions_equal_the_model(program, tmp_path):
     jobs = [(t, [call]) for t, call, _ in HAND.values()]
     for seed, (nf, m, irregular) in enumerate([(2, 1, False), (5, 65, True), (5, 129, True), (8, 60, False), (70, 300, True)]):
@@ -100,4 +80,4 @@ def test_header_host_functions_equal_the_model(program, tmp_path):
             for _ in range(3):
                 calls.append(("refset", int(rng.integers(0, nf)), [int(x) for x in rng.integers(-1, nf + 1, rng.integers(0, 12))], k))
         jobs.append((t, calls))
-    assert _against_header(program, tmp_path / "cases.txt", jobs) == len(HAND) + 5 * 25
+    assert cc.against_header(program, tmp_path / "cases.txt", jobs) == len(HAND) + 5 * 25

@@ -265,3 +265,18 @@ def test_chain_projection_on_device_arrays(matcher):
     _same(main, want)
     nm_r, idx_r = matcher.MatchByProjection(mp_pos, main["main_desc"], main["main_octave"], mp_skip, Tcw, K4, kps, desc, kf_obs, 15, 2)
     assert nm_c == nm_r and np.array_equal(idx_c, idx_r) and nm_r > 50
+
+
+def test_the_shared_observation_table(matcher):
+    """the irregular table of tests/obs_table_cases.py, which the parallax and covisibility calls are fed too: planted entries
+    out of range, a null frame, descending and overlapping d_mp_ptr segments (all inside 0..nobs)"""
+    import obs_table_cases as oc
+    from se2lam_amd import capi, mappoint as mpt
+    t = oc.table()
+    want = t.main_model(mm)
+    assert (want["info"][[0, 10, 24], 0] == -1).all() and want["info"][9, 2] > want["info"][11, 2] > 0
+    b = mpt.MainBatch([([e[0] for e in l], [e[1] for e in l]) for l in t.lists], t.prev, mc.sentinels(oc.M))
+    assert b.nobs == t.nobs and 60 <= t.nobs <= 160 and b.m == oc.M
+    b.mp_ptr = capi.upload(t.ptr)                          # the lists as they stand, the pointer array with its planted values
+    b.run(matcher, mpt.DeviceFrames(t.kps, t.desc, oc.COUNTS, oc.CAP, t.frame_null, t.view), mc.SCALE)
+    _same(b.download(matcher), want, "shared table")

@@ -1,16 +1,10 @@
 """MapPoint::updateMainKFandDescriptor without a device: the numpy model (tests/mappoint_main_model.py) against hand-worked
 cases, and the host mirror include/se2lam_amd/MapPointMain.h (tests/cpp_mappoint_main.cpp) against the model, exactly."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import mappoint_main_cases as mc
 import mappoint_main_model as mm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def therm(t):
@@ -52,45 +46,15 @@ def test_distances_are_float32_of_the_float64_norm():
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx
-    out = str(tmp_path_factory.mktemp("mappoint_main") / "cpp_mappoint_main")
-    libdir = os.path.join(ROOT, "se2lam_amd", "lib")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp_mappoint_main.cpp"), "-o", out, "-L", libdir, "-lse2gpu",
-                           "-Wl,-rpath," + libdir])
-    return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+    return mc.cpp_build(tmp_path_factory.mktemp("mappoint_main"))
 
 
 def _run_mirror(program, tmp_path, fs, kps, null, view, lists, prev):
-    ptr, fr, ft = mc.csr(lists)
-    vals = [mc.NFRAMES, mc.CAP, mc.NLEVELS, len(lists), len(fr), int(null is not None), int(view), int(prev is not None)]
-    vals += fs.counts.tolist()
-    if null is not None:
-        vals += null.tolist()
-    vals += _bits(mc.SCALE) + kps["octave"].tolist() + fs.desc.ravel().tolist()
-    if view:
-        vals += _bits(fs.view)
-    vals += ptr.tolist() + fr.tolist() + ft.tolist()
-    if prev is not None:
-        vals += prev.tolist()
-    path = tmp_path / "case.txt"
-    path.write_text(" ".join(str(int(v)) for v in vals))
-    r = subprocess.run([program, str(path)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    rows = np.array([[int(v) for v in ln.split()] for ln in r.stdout.splitlines()], np.int64).reshape(len(lists), 40)
-    return dict(info=rows[:, :4].astype(np.int32), main_frame=rows[:, 4].astype(np.int32), main_octave=rows[:, 5].astype(np.int32),
-                dist=rows[:, 6:8].astype(np.uint32).view(np.float32), main_desc=rows[:, 8:].astype(np.uint8))
+    return mc.cpp_run(program, tmp_path / "case.txt", fs.counts, mc.CAP, mc.SCALE, kps["octave"], fs.desc, null,
+                      fs.view if view else None, *mc.csr(lists), prev)
 
 
-def _same(got, want):
-    for k in ("info", "main_desc", "main_frame", "main_octave"):
-        assert np.array_equal(got[k], want[k]), k
-    assert np.array_equal(got["dist"].view(np.uint32), want["dist"].view(np.uint32)), "dist"
+_same = mc.same
 
 
 def test_host_mirror_equals_the_model(program, tmp_path):

@@ -242,3 +242,23 @@ def test_pass_sequence_with_an_abandoned_point_frees_its_feature(cases, matcher,
     _same_correspd(s6, m6, bound, "passes 6")
     # in one call the feature stays with the tracked point
     assert cca.run(nk.L64, 7, match_idx_mp=mi)["kind"][0, ab["j"]] == 1
+
+
+def test_the_shared_observation_table(matcher, bound):
+    """the irregular table of tests/obs_table_cases.py, which the main-key-frame and covisibility calls are fed too: planted
+    entries out of range, descending and overlapping d_mp_ptr segments (all inside 0..nobs; no entry has two writers)"""
+    import obs_table_cases as oc
+    from se2lam_amd import newkf
+    t = oc.table()
+    want = t.parallax_model(nk.L64)
+    t.check_one_writer(want["status"])
+    assert set(want["status"]) == {0, 1, 2, 3} and want["status"][9] != 0 and want["status"][25] != 0 and 60 <= t.nobs <= 160
+    fr = t.sc.fr
+    poses = newkf.DevicePoses(fr.kps, fr.counts, fr.cap, fr.Tcw, fr.Twc, fr.P, fr.idkf, t.observed)
+    got = newkf.promote_batch_device(matcher, poses, t.ptr, t.obs_frame, t.obs_ftr, t.good, t.new, nc.FX, nc.LOWER, nc.UPPER)
+    assert np.array_equal(got["status"], want["status"]) and np.array_equal(got["place"], want["place"])
+    assert np.array_equal(poses.observed(), want["kf_observed"]) and (want["kf_observed"] != t.observed).any()
+    _close_pos(got["pos"], want["pos"], want["status"] == 1, bound, "shared table mPos")
+    w = want["obs_view"][:, 0] != nk.SENT
+    _close_pos(got["obs_view"], want["obs_view"], w, bound, "shared table mViewMPs")
+    _close_mat(got["obs_info"], want["obs_info"], w, bound, "shared table mViewMPsInfo")

@@ -4,16 +4,12 @@ held to its FP64 layer, the cases' distance from every threshold, and the header
 
 Measured here (float32 restatement against the FP64 layer, cases of tests/new_kf_cases.py): positions 1.1e-6 of their norm,
 informations 2.3e-6 of their largest entry at worst; the device is allowed four times the figure measured in the run."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import new_kf_cases as nc
 import new_kf_model as nk
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EYE = nk.EYE12
 
 
@@ -193,16 +189,10 @@ def test_pass_sequence_of_the_model(cases):
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("find_correspd") / "cpp_find_correspd")
-    libdir = os.path.join(ROOT, "se2lam_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp_find_correspd.cpp"), "-o", out, "-L", libdir, "-lse2gpu",
-                           "-Wl,-rpath," + libdir])
-    return out
+    return nc.cpp_build(tmp_path_factory.mktemp("find_correspd"))
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32).ravel().tolist()
+_bits = nc.bits
 
 
 def test_host_functions_equal_the_restatement(program, tmp_path, cases):
@@ -223,30 +213,15 @@ def test_host_functions_equal_the_restatement(program, tmp_path, cases):
                                          _bits([nc.FX]) + _bits(normal) + octs.tolist() + _bits([mind, maxd]))))
         i1, i2, x2 = nk.L32.se3_to_xyz_info(xyz1, sc.fr.Twc[f1], sc.fr.Tcw[f2], sc.fr.Twc[f2], nc.FX)
         want.append((np.concatenate([i1.ravel(), i2.ravel(), x2]), int(nk.accept_new_observe(nk.L32, xyz1, normal, octs[0], octs[1], mind, maxd))))
-    fr = sc.fr
-    head = [fr.nframes, fr.cap, len(pc.lists), len(pc.obs_frame)] + fr.counts.tolist() + fr.idkf.tolist() + \
-        _bits(fr.Tcw) + _bits(fr.Twc) + _bits(fr.P) + _bits(fr.kps["x"]) + _bits(fr.kps["y"]) + pc.ptr.tolist() + \
-        pc.obs_frame.tolist() + pc.obs_ftr.tolist() + pc.good.tolist() + pc.new.tolist() + _bits([nc.FX, nc.LOWER, nc.UPPER]) + \
-        pc.observed.tolist()
-    path = tmp_path / "cases.txt"
-    path.write_text("\n".join(lines) + "\nP " + " ".join(map(str, head)) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    rows = r.stdout.splitlines()
-    for ln, (w, acc) in zip(rows[:60], want):
+    rows, mirror = nc.cpp_run_parallax(program, tmp_path / "cases.txt", sc.fr, pc.ptr, pc.obs_frame, pc.obs_ftr, pc.good, pc.new,
+                                    pc.observed, lines=lines)
+    assert len(rows) == 60
+    for ln, (w, acc) in zip(rows, want):
         v = ln.split()
         got = np.array([int(x) for x in v[:21]], np.uint32).view(np.float32)
         assert int(v[21]) == acc
         assert nk.rel_err_mat(got[:9], w[:9])[0] < 4e-6 and nk.rel_err_mat(got[9:18], w[9:18])[0] < 4e-6
         assert np.array_equal(got[18:].view(np.uint32), w[18:].astype(np.float32).view(np.uint32))
-    m, nobs = len(pc.lists), len(pc.obs_frame)
     ref = pc.run(nk.L32)
-    pts = np.array([[int(x) for x in ln.split()] for ln in rows[60:60 + m]], np.int64)
-    assert np.array_equal(pts[:, 0], ref["status"]) and np.array_equal(pts[:, 1], ref["place"])
-    pos = pts[:, 2:5].astype(np.uint32).view(np.float32)
-    assert np.array_equal(pos.view(np.uint32), ref["pos"].view(np.uint32))            # the DLT has no library call in it
-    ob = np.array([[int(x) for x in ln.split()] for ln in rows[60 + m:60 + m + nobs]], np.int64).astype(np.uint32).view(np.float32)
-    w = ref["obs_view"][:, 0] != nk.SENT
-    assert np.array_equal(ob[:, 0] != np.float32(nk.SENT), w)
-    assert nk.rel_err_pos(ob[w, :3], ref["obs_view"][w]).max() < 4e-6 and nk.rel_err_mat(ob[w, 3:], ref["obs_info"][w]).max() < 4e-6
-    assert np.array_equal(np.array([int(x) for x in rows[60 + m + nobs].split()], np.uint8), ref["kf_observed"])
+    assert (ref["status"] == 1).sum() >= 10
+    nc.same_parallax(mirror, ref)

@@ -109,7 +109,7 @@ def main():
     mt = ORBmatcher()
     mp = the_map(np.random.default_rng(7))
     cv = covis.DeviceCovis(mp["counts"], CAP, mp["ptr"], mp["obs_frame"], mp["obs_ftr"], mp["null"], mp["good"])
-    lib, up = capi.lib(), lambda x, dt: capi.DeviceArray.from_numpy(np.ascontiguousarray(x, dt))
+    lib, up = capi.lib(), capi.upload
     rows = []
     for J in [int(x) for x in a.sizes.split(",")]:
         new, local, refs = jobs_of(J, np.random.default_rng(11))

@@ -130,7 +130,7 @@ def main():
     from test_mappoint_main_gpu import _scene
     mp_pos, mp_desc, mp_octave, mp_skip, Tcw, K4, skps, sdesc, kf_obs = _scene()
     n, m = len(skps), len(mp_octave)
-    up = capi.DeviceArray.from_numpy
+    up = capi.upload
     dv = [up(x) for x in (mp_pos, mp_desc, mp_octave, mp_skip, skps, sdesc, kf_obs)]
     d_idx, d_nm = up(np.zeros(n, np.int32)), up(np.zeros(1, np.int32))
 

@@ -128,7 +128,7 @@ class Resident:
     """everything of one scene in device memory, and the two calls on it without a transfer"""
 
     def __init__(self, s, mt):
-        up = lambda a, dt: capi.DeviceArray.from_numpy(np.ascontiguousarray(a, dt))
+        up = capi.upload
         self.s, self.mt, self.B = s, mt, len(s["job_prev"])
         self.poses = newkf.DevicePoses(s["kps"], s["counts"], CAP, s["Tcw"], s["Twc"], s["P"], s["idkf"], s["observed"], s["view_pos"])
         n, m, nobs = self.B * CAP, len(s["ptr"]) - 1, len(s["obs_frame"])
