@@ -460,6 +460,84 @@ int se2gpu_covis_refset_device(se2gpu_matcher* h, const uint64_t* d_bits, int nf
                                const int32_t* d_job_kf, const int32_t* d_ref_ptr, const int32_t* d_ref_idx, int nref, int njobs,
                                int k, double thresh, int32_t* d_job_out, double* d_job_ratio);
 
+/* Local window: the covisibility graph KeyFrame::mCovisibleKFs as a bit matrix in device memory, the calls that maintain it,
+ * and Map::updateLocalGraph (src/Map.cpp:285-331 of the reference) on it for batches of current key frames.
+ *
+ * d_adj is supplied by the caller and zeroed by the caller once: nframes rows of WF = ceil(nframes / 64) 64-bit words, bit
+ * b & 63 of word b / 64 of row a = "slot b is in slot a's mCovisibleKFs".  It is directed: the reference's set is per key
+ * frame, and only the callers of addCovisibleKF keep it symmetric.  Bits past nframes are zero.  se2gpu_covis_adj_words (host
+ * only, no device) returns the number of words, nframes * WF, or -1 with nframes < 1.
+ *
+ * se2gpu_covis_connect_device: addCovisibleKF in both directions, one thread per pair (64-bit integer atomicOr), for every
+ * pair (d_pair_a[p], d_pair_b[p]) whose two slots lie in 0..nframes-1 and for which
+ *   d_pair_out == NULL                    the unconditional links of LocalMapper.cpp:66-67, Map.cpp:233-234 and :337-338, or
+ *   d_pair_out[4p + 3] & flag_mask != 0   d_pair_out as se2gpu_covis_pairs_device wrote it; flag_mask = 1 is Map.cpp:794-797.
+ *   a == b sets the one diagonal bit.  No bit is ever cleared.  Pairs out of range are skipped.
+ *
+ * se2gpu_covis_disconnect_device: the covisibility part of KeyFrame::setNull (KeyFrame.cpp:106-114) for the nslots slots of
+ * d_slots.  For every listed slot s in range, bit (b, s) is cleared for every b in row s, then row s is zeroed.  A key frame
+ * that lists s while s does not list it keeps s, as in the reference.  Slots out of range are skipped.
+ *   Two launches on the stream: the first clears the bits (b, s) read from the rows as they stand (one wave per listed slot,
+ *   64-bit integer atomicAnd), the second zeroes the listed rows.  SLOTS LISTED TWICE, AND TWO LISTED SLOTS THAT NAME EACH
+ *   OTHER, GIVE THE RESULT OF THE REFERENCE'S CALLS IN ANY ORDER: a setNull(s) changes other rows only in column s, so before
+ *   its own turn the row of a listed slot s can lose only bits in the columns of other listed slots s' - and those bits decide
+ *   only whether (s', s) is cleared, a bit of row s', which ends as zero whatever the order.  For an unlisted b the bit (b, s)
+ *   is cleared iff b was in row s at the start, in every order; the first launch computes exactly that, and clearing is
+ *   idempotent.
+ *
+ * se2gpu_local_window_batch_device: Map.cpp:285-331 for njobs current key frames d_job_kf[j], one workgroup per job.
+ *   d_bits_kf     the d_bits of se2gpu_covis_build_device (nframes + 2 rows of W = ceil(m / 64) words) built from the key
+ *                 frame's side; serves KeyFrame::getAllObsMPs(false): key-frame row AND the not-null row nframes (:313)
+ *   d_bits_mp     a second such matrix built from the CSR of the points' own side, MapPoint::mObservations, which
+ *                 getObservations() reads (:320); only its rows 0..nframes-1 are read.  WHERE THE TWO SIDES AGREE, AS THEY DO
+ *                 IN A CONSISTENT MAP, PASS THE SAME POINTER TWICE.
+ *   d_frame_null  nframes bytes or NULL (none is null): MapPoint::getObservations skips null key frames (MapPoint.cpp:216)
+ *   d_kf_order, d_mp_order   nframes / m ints or NULL, read only for the lists (below)
+ *   search_level  3 in the reference (:299); any value >= 0
+ *   Per job, with cur = d_job_kf[j] in 0..nframes-1:
+ *   local   {cur}, then search_level times the union with the adjacency rows of all members AS THE SET STOOD AT THE START OF
+ *           THAT ROUND (:300-308 copies the set before it walks it).  Only the members found in the round before are expanded,
+ *           which is the same thing, and the rounds stop when one finds nothing.  A null key frame is not skipped (the
+ *           reference does not skip it).  Adjacency bits past nframes are ignored.
+ *   points  the OR of the d_bits_kf rows of the local key frames, AND the not-null row (:310-315); bits past m are ignored
+ *   ref     every slot f that is not local, not d_frame_null[f], and whose d_bits_mp row meets the point set (:317-326)
+ *   n_obs   the sum of popcount(d_bits_mp row f & points) over the f of local and ref that are not d_frame_null[f]: the number
+ *           of EdgeSE2XYZ Map::loadLocalGraph creates (:1005-1051), to size the graph and to judge whether a window fits the
+ *           resident path before it is loaded.  It saturates at 2^31 - 1.
+ *   d_win_kf   njobs * 2 * WF words: row 2j = local, row 2j + 1 = ref, as bits over the slots
+ *   d_win_mp   njobs * W words: the point set
+ *   d_win_out  d_win_out[4j..] = {n_local, n_ref, n_mp, n_obs}
+ *   A job slot out of range gives {-1, 0, 0, 0}; its rows and lists are left untouched.  m == 0 still runs the hops; the point
+ *   and ref sets are empty.  A job's outputs depend on that job alone, and every call gives the same words in every run.
+ *   Optional lists: d_local_list and d_ref_list (njobs * kf_list_cap ints each, either may be NULL), d_mp_list (njobs *
+ *   mp_list_cap ints or NULL) hold the members in ascending position of d_kf_order / d_mp_order: each a permutation that lists
+ *   the slots / points by ascending mIdKF / mId, the order of the reference's IdLessThan sets and so of mLocalGraphKFs, mRefKFs
+ *   and mLocalGraphMPs.  NULL means index order; entries out of range are skipped.  Truncation shows as a count above the cap;
+ *   entries from min(count, cap) on are left untouched.  The order comes from a prefix sum over the workgroup, without atomics.
+ *
+ * All three calls are asynchronous on the matcher's stream; se2gpu_matcher_sync waits for them.  Integers only: no floating
+ * point, no scratch memory, integer atomics only.  Every index read from an array (a slot, an order entry, a set bit of a
+ * tail word) is checked before it is used.
+ * The argument checks come first and touch neither the handle nor a device; se2gpu_last_error names the argument:
+ * SE2GPU_ERR_INVALID: a NULL handle, d_adj, d_pair_a, d_pair_b, d_slots, d_bits_kf, d_bits_mp, d_job_kf, d_win_kf, d_win_mp or
+ *   d_win_out; nframes < 1, m < 0, npairs < 0, nslots < 0, njobs < 0, search_level < 0, kf_list_cap < 0, mp_list_cap < 0.
+ * SE2GPU_ERR_CAPACITY: nframes > SE2GPU_LOCAL_WINDOW_MAX_FRAMES = 4096 (the rows of a window and its member list are held in
+ *   LDS; it holds for the upkeep calls too, a d_adj the window call cannot read being of no use); (nframes + 2) * W > 2^31 - 1
+ *   as for the covisibility calls (nframes = 4096 admits m up to 33538048); npairs > 2^31 - 256; nslots or njobs > 2^24 - 1 =
+ *   16777215 (a launch's threads stay below 2^32).
+ * npairs == 0, nslots == 0 and njobs == 0 are SE2GPU_OK and launch nothing. */
+#define SE2GPU_LOCAL_WINDOW_MAX_FRAMES 4096
+long long se2gpu_covis_adj_words(int nframes);
+int se2gpu_covis_connect_device(se2gpu_matcher* h, uint64_t* d_adj, int nframes, const int32_t* d_pair_a,
+                                const int32_t* d_pair_b, int npairs, const int32_t* d_pair_out, int flag_mask);
+int se2gpu_covis_disconnect_device(se2gpu_matcher* h, uint64_t* d_adj, int nframes, const int32_t* d_slots, int nslots);
+int se2gpu_local_window_batch_device(se2gpu_matcher* h, const uint64_t* d_bits_kf, const uint64_t* d_bits_mp, int nframes, int m,
+                                     const uint64_t* d_adj, const uint8_t* d_frame_null, const int32_t* d_job_kf, int njobs,
+                                     int search_level, const int32_t* d_kf_order, const int32_t* d_mp_order,
+                                     uint64_t* d_win_kf, uint64_t* d_win_mp, int32_t* d_win_out,
+                                     int32_t* d_local_list, int32_t* d_ref_list, int kf_list_cap,
+                                     int32_t* d_mp_list, int mp_list_cap);
+
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by
  *   LocalMapper::localBA          /root/reference/src/LocalMapper.cpp:232-302

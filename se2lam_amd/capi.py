@@ -155,6 +155,11 @@ SYMBOLS = {
     "se2gpu_covis_build_device": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "se2gpu_covis_pairs_device": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _F, _D, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I]),
     "se2gpu_covis_refset_device": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _I, _I, _I, _D, _VP, _VP]),
+    "se2gpu_covis_adj_words": (C.c_longlong, [_I]),
+    "se2gpu_covis_connect_device": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I]),
+    "se2gpu_covis_disconnect_device": (_I, [_VP, _VP, _I, _VP, _I]),
+    "se2gpu_local_window_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I,
+                                              _VP, _I]),
     # BA
     "se2gpu_ba_create": (_I, [C.POINTER(_VP)]),
     "se2gpu_ba_reserve": (_I, [_I, _I, _I]),

@@ -1,0 +1,110 @@
+"""Python mirror of the local-window calls over the C ABI (harness view; C++ twin: include/se2lam_amd/LocalWindow.h).
+
+Reference: KeyFrame::addCovisibleKF / setNull (src/KeyFrame.cpp:106-114) and Map::updateLocalGraph (src/Map.cpp:285-331).  All
+compute happens in libse2gpu.so (se2gpu_covis_connect_device, se2gpu_covis_disconnect_device,
+se2gpu_local_window_batch_device, HIP) on top of covis.build_device: the adjacency bit matrix stays in device memory next to
+the observation bit matrix.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import capi
+from .capi import ISENT, dev_ptr as _ptr, upload as _up
+from .covis import DeviceCovis, _Pending
+
+WSENT = 0xA5A5A5A5A5A5A5A5   # 64-bit outputs start from this word
+
+
+class DeviceAdjacency:
+    """d_adj of se2gpu_covis_connect_device: nframes rows of WF = ceil(nframes / 64) words, allocated and zeroed here once."""
+
+    def __init__(self, nframes, rows=None):
+        self.nframes, self.WF = int(nframes), (int(nframes) + 63) // 64
+        self.words = int(capi.lib().se2gpu_covis_adj_words(self.nframes))
+        assert self.words == self.nframes * self.WF
+        self.adj = _up(np.zeros(self.words, np.uint64) if rows is None else pack_rows(rows, self.nframes), np.uint64)
+
+    def connect(self, matcher, pair_a, pair_b, pair_out=None, flag_mask=1, sync=True):
+        """addCovisibleKF both ways for host pair lists; pair_out: None (every pair), an (n, 4) host array or the device array
+        se2gpu_covis_pairs_device wrote"""
+        n = len(pair_a)
+        a, b = _up(pair_a, np.int32), _up(pair_b, np.int32)
+        po = pair_out if pair_out is None or isinstance(pair_out, capi.DeviceArray) else _up(pair_out, np.int32)
+        capi.check(capi.lib().se2gpu_covis_connect_device(matcher._h, _ptr(self.adj), self.nframes, _ptr(a), _ptr(b), n, _ptr(po),
+                                                          int(flag_mask)))
+        self._keep = (a, b, po)
+        if sync:
+            matcher.sync()
+        return self
+
+    def disconnect(self, matcher, slots, sync=True):
+        s = _up(slots, np.int32)
+        capi.check(capi.lib().se2gpu_covis_disconnect_device(matcher._h, _ptr(self.adj), self.nframes, _ptr(s), len(slots)))
+        self._keep = (s,)
+        if sync:
+            matcher.sync()
+        return self
+
+    def read(self):
+        """(nframes, WF) uint64"""
+        return self.adj.to_numpy(np.uint64, (self.words,)).reshape(self.nframes, self.WF)
+
+    def read_lists(self):
+        """per slot, the slots of its mCovisibleKFs in ascending order"""
+        return unpack_rows(self.read(), self.nframes)
+
+
+def pack_rows(lists, n):
+    """index lists -> (len(lists), ceil(n / 64)) uint64 bit rows"""
+    WN = (n + 63) // 64
+    rows = np.zeros((len(lists), WN * 64), np.uint8)
+    for r, l in enumerate(lists):
+        rows[r, sorted(l)] = 1
+    return np.packbits(rows, axis=1, bitorder="little").view(np.uint64).reshape(len(lists), WN)
+
+
+def unpack_rows(rows, n):
+    rows = np.ascontiguousarray(rows, np.uint64)
+    if rows.shape[1] == 0:
+        return [[] for _ in range(rows.shape[0])]
+    bits = np.unpackbits(rows.view(np.uint8).reshape(rows.shape[0], -1), axis=1, bitorder="little")
+    assert not bits[:, n:].any()
+    return [[int(x) for x in np.nonzero(b[:n])[0]] for b in bits]
+
+
+def window_device(matcher, cv_kf: DeviceCovis, adj: DeviceAdjacency, job_kf, search_level=3, cv_mp: DeviceCovis = None,
+                  frame_null=None, kf_order=None, mp_order=None, kf_list_cap=None, mp_list_cap=None, sync=True):
+    """se2gpu_local_window_batch_device for a host job list.  cv_mp None: the two sides agree and d_bits_kf is passed twice.
+    kf_list_cap / mp_list_cap None: no lists.  Returns dict(win_kf (n, 2, WF), win_mp (n, W), out (n, 4), local_list / ref_list
+    (n, kf_list_cap) or None, mp_list (n, mp_list_cap) or None); with sync=False an object whose read() gives it after
+    matcher.sync()."""
+    n, nframes, m, W, WF = len(job_kf), cv_kf.nframes, cv_kf.m, cv_kf.W, adj.WF
+    assert adj.nframes == nframes and (cv_mp is None or (cv_mp.nframes, cv_mp.m) == (nframes, m))
+    jobs = _up(job_kf, np.int32)
+    fn = None if frame_null is None else _up(frame_null, np.uint8)
+    ko = None if kf_order is None else _up(kf_order, np.int32)
+    mo = None if mp_order is None else _up(mp_order, np.int32)
+    win_kf = _up(np.full(max(n * 2 * WF, 1), WSENT, np.uint64), np.uint64)
+    win_mp = _up(np.full(max(n * W, 1), WSENT, np.uint64), np.uint64)
+    out = _up(np.full((max(n, 1), 4), ISENT, np.int32), np.int32)
+    nk = 0 if kf_list_cap is None else n * kf_list_cap
+    nm = 0 if mp_list_cap is None else n * mp_list_cap
+    ll = None if kf_list_cap is None else _up(np.full(max(nk, 1), ISENT, np.int32), np.int32)
+    rl = None if kf_list_cap is None else _up(np.full(max(nk, 1), ISENT, np.int32), np.int32)
+    ml = None if mp_list_cap is None else _up(np.full(max(nm, 1), ISENT, np.int32), np.int32)
+    capi.check(capi.lib().se2gpu_local_window_batch_device(
+        matcher._h, _ptr(cv_kf.bits), _ptr((cv_mp or cv_kf).bits), nframes, m, _ptr(adj.adj), _ptr(fn), _ptr(jobs), n,
+        int(search_level), _ptr(ko), _ptr(mo), _ptr(win_kf), _ptr(win_mp), _ptr(out), _ptr(ll), _ptr(rl),
+        0 if kf_list_cap is None else kf_list_cap, _ptr(ml), 0 if mp_list_cap is None else mp_list_cap))
+
+    def read():
+        lst = lambda d, cnt, cap: None if d is None else d.to_numpy(np.int32, (max(cnt, 1),))[:cnt].reshape(n, cap)  # noqa: E731
+        return dict(win_kf=win_kf.to_numpy(np.uint64, (max(n * 2 * WF, 1),))[:n * 2 * WF].reshape(n, 2, WF),
+                    win_mp=win_mp.to_numpy(np.uint64, (max(n * W, 1),))[:n * W].reshape(n, W),
+                    out=out.to_numpy(np.int32, (max(n, 1), 4))[:n],
+                    local_list=lst(ll, nk, kf_list_cap), ref_list=lst(rl, nk, kf_list_cap), mp_list=lst(ml, nm, mp_list_cap))
+    if not sync:
+        return _Pending((jobs, fn, ko, mo, cv_kf, cv_mp, adj), read)
+    matcher.sync()
+    return read()
