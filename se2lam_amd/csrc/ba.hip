@@ -171,9 +171,18 @@ constexpr int kStageEdges = kWaveLds / 12;   // edges whose Dg records (12 doubl
 // words side by side: conflict-free, no barrier - a lane reads back its own words); in registers they cost the kernel a wave of occupancy
 // (186 VGPRs).  Un-fused pass: the pose terms of every edge go to memory (lambda_0); fused pass: a lane's further edges wait in
 // memory (landmarks with more than 8 observations) - the W slot holds the raw block until the second pass.
-template <bool FUSED>
+// DIAG (the opening pass of the un-sharded run, k_open<false>): lambda_0 is all that reads the pose terms there, and it needs
+// the three diagonal entries of Hpp_e only - they go to Hpp_e side by side, 3 per edge, and bp_e stays unwritten.
+template <bool FUSED, bool DIAG = false>
 __device__ __forceinline__ void lin_park(bool first, int e, const double hpl[9], const double hpp[6], const double bpe[3],
                                          double* lds, double* W, double* Hpp_e, double* bp_e) {
+    if constexpr (DIAG) {
+        static_assert(!FUSED, "the fused pass parks whole blocks");
+        Hpp_e[(size_t)e * 3 + 0] = hpp[0];
+        Hpp_e[(size_t)e * 3 + 1] = hpp[3];
+        Hpp_e[(size_t)e * 3 + 2] = hpp[5];
+        return;
+    }
     if (FUSED && first) {
         double* keep = lds + (threadIdx.x >> 6) * kWaveLds + (threadIdx.x & 63);   // word i of the lane: keep[i * 64]
 #pragma unroll
@@ -323,8 +332,18 @@ struct LinArgs {
     const double *poses_b, *lms_b;
     RecSet alt;
 };
-template <bool FUSED>
-__device__ __forceinline__ void d_linearize(const unsigned bx, const LinArgs& a) {
+// OPEN (k_open, the first launch of an un-sharded optimize()): the pass is also the evaluation of the starting state.  lin_edge's
+// r0 is the edge's robust chi^2, bit for bit what d_update computes at x = 0; it is summed as d_update sums it (per lane in edge
+// order, wave_sum, the waves in ascending order), and the workgroup's partial is published to the finisher workgroup
+// (finish_trial; see `publish` below for when).  `lds`: the kernel's stage (the finisher shares it).
+struct LinOpen {
+    double* part;        // 2 doubles per workgroup: {chi^2, 0}
+    unsigned* counter;   // FinArgs::counter
+    double* lds;         // (kBlock / 64) * kWaveLds doubles
+};
+__device__ inline void publish_partial(double* part, unsigned* counter, unsigned bx, double c, double s);
+template <bool FUSED, bool OPEN>
+__device__ __forceinline__ void d_linearize_pass(const unsigned bx, const LinArgs& a, const LinOpen& op) {
     const double *poses = a.poses, *lms = a.lms;
     RecSet rec{a.W, a.Dg, a.Hll, a.bl, a.Ainv, a.zeta};
     double lambda = a.lambda;
@@ -335,7 +354,9 @@ __device__ __forceinline__ void d_linearize(const unsigned bx, const LinArgs& a)
     if (a.ctl) {   // device-side LM: nothing to do after the run has ended, or when the k_update<true> of the slot before has
                    // already written these very records (rec_valid); a retry runs like any other trial (the estimate did not
                    // move, only lambda did)
-        if (a.ctl->done | a.ctl->rec_valid) return;
+        // (OPEN: the finisher moves the controller only after every workgroup has published, so all of them read the same
+        // block here, as in d_update; `done` is the one word that excuses a workgroup from publishing - trial_open tests it too)
+        if (OPEN ? a.ctl->done : (a.ctl->done | a.ctl->rec_valid)) return;
         if (a.ctl->sel) { poses = a.poses_b; lms = a.lms_b; }
         if (a.ctl->rec_sel) rec = a.alt;
         lambda = a.ctl->lambda;
@@ -343,8 +364,15 @@ __device__ __forceinline__ void d_linearize(const unsigned bx, const LinArgs& a)
     const int gid = bx * kBlock + threadIdx.x;
     const int l = gid / kGroup, sub = gid % kGroup;
     double hll[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    __shared__ double keep[(kBlock / 64) * kWaveLds];   // lin_park, lin_landmark
+    double* keep;   // lin_park, lin_landmark
+    if constexpr (OPEN) {
+        keep = op.lds;
+    } else {
+        __shared__ double own[(kBlock / 64) * kWaveLds];
+        keep = own;
+    }
     int beg = 0, end = 0;
+    double chi = 0;
     if (l < a.L) {
         const double lx = lms[3 * l], ly = lms[3 * l + 1], lz = lms[3 * l + 2];
         beg = a.lm_ptr[l];
@@ -354,11 +382,31 @@ __device__ __forceinline__ void d_linearize(const unsigned bx, const LinArgs& a)
             double hpl[9], hpp[6], bpe[3], r0;
             lin_edge(a.cam, poses[3 * kf], poses[3 * kf + 1], poses[3 * kf + 2], lx, ly, lz, a.e_uv[2 * e], a.e_uv[2 * e + 1],
                      a.e_info[3 * e], a.e_info[3 * e + 1], a.e_info[3 * e + 2], !a.fixed[kf], hll, b, hpl, hpp, bpe, r0);
-            lin_park<FUSED>(e == beg + sub, e, hpl, hpp, bpe, keep, rec.W, a.Hpp_e, a.bp_e);
+            if constexpr (OPEN) chi += r0;
+            lin_park<FUSED, OPEN && !FUSED>(e == beg + sub, e, hpl, hpp, bpe, keep, rec.W, a.Hpp_e, a.bp_e);
         }
     }
+    // FUSED (Gauss-Newton): the finisher is a workgroup of this launch and waits for the partial - it goes out before the
+    // landmark stores.  Un-fused (LM): the finisher rides in the next launch (k_lambda0_open) - nothing waits, it goes out last.
+    auto publish = [&]() {
+        __shared__ double sm[kBlock / 64];
+        chi = wave_sum(chi);
+        if ((threadIdx.x & 63) == 0) sm[threadIdx.x / 64] = chi;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double c = 0;
+            for (int i = 0; i < kBlock / 64; ++i) c += sm[i];
+            publish_partial(op.part, op.counter, bx, c, 0.0);
+        }
+    };
+    if constexpr (OPEN && FUSED) publish();
     lin_landmark<FUSED>(l, sub, beg, end, a.L, hll, b, lambda, keep, rec.W, a.Hpp_e, a.bp_e, rec.Hll, rec.bl, rec.Ainv, rec.zeta,
                         rec.Dg);
+    if constexpr (OPEN && !FUSED) publish();
+}
+template <bool FUSED>
+__device__ __forceinline__ void d_linearize(const unsigned bx, const LinArgs& a) {
+    d_linearize_pass<FUSED, false>(bx, a, LinOpen{});
 }
 template <bool FUSED>
 __global__ __launch_bounds__(kBlock) void k_linearize(LinArgs a) {
@@ -379,10 +427,9 @@ struct OdoArgs {
     const BaCtl* ctl;
     const double* poses_b;
 };
-__device__ __forceinline__ void d_odometry(const unsigned bx, const OdoArgs& a) {
+__device__ __forceinline__ void d_odometry_edge(const int k, const OdoArgs& a) {
     const double* poses = a.poses;
     if (a.ctl && a.ctl->sel) poses = a.poses_b;   // (poses = the "a" buffer then: the controller says which holds the estimate)
-    const int k = bx * blockDim.x + threadIdx.x;
     if (k >= a.O) return;
     const int i = a.o_i[k], j = a.o_j[k];
     double e[3], A[9], B[9];
@@ -409,6 +456,9 @@ __device__ __forceinline__ void d_odometry(const unsigned bx, const OdoArgs& a) 
         a.obi[k * 3 + r] = fi ? A[r] * omr[0] + A[3 + r] * omr[1] + A[6 + r] * omr[2] : 0.0;
         a.obj[k * 3 + r] = fj ? B[r] * omr[0] + B[3 + r] * omr[1] + B[6 + r] * omr[2] : 0.0;
     }
+}
+__device__ __forceinline__ void d_odometry(const unsigned bx, const OdoArgs& a) {
+    d_odometry_edge(bx * blockDim.x + threadIdx.x, a);
 }
 __global__ void k_odometry(OdoArgs a) {
     d_odometry(blockIdx.x, a);
@@ -478,20 +528,75 @@ __global__ __launch_bounds__(kBlock) void k_pose_reduce(PoseReduceArgs a) {
 // maximum on the bit pattern (non-negative doubles order like their bits; a maximum is exact whatever the order), and the
 // workgroup that arrives last sets lambda_0 = 1e-5 * max.  One launch and 13 us less in front of the first Schur step.
 constexpr int kL0PerBlock = 8 * kBlock;   // landmarks per workgroup of the landmark part
-__global__ __launch_bounds__(kBlock) void k_lambda0(int P, const int* __restrict__ pose_ptr, const int* __restrict__ pose_edges,
-                                                     const double* __restrict__ Hpp_e, const double* __restrict__ bp_e,
-                                                     const int* __restrict__ podo_ptr, const int* __restrict__ podo_item,
-                                                     const double* __restrict__ Oii, const double* __restrict__ Ojj,
-                                                     const double* __restrict__ obi, const double* __restrict__ obj,
-                                                     double* __restrict__ Hpp, double* __restrict__ bp,
-                                                     const uint8_t* __restrict__ fixed, int L, const double* __restrict__ Hll,
-                                                     unsigned long long* __restrict__ acc, double* __restrict__ out,
-                                                     BaCtl* __restrict__ ctl) {
+
+// The pose part of k_lambda0_open: the largest diagonal entry of pose p's block (lane 0 of the pose's wave), from the three
+// diagonal entries per edge that k_open<false> left (lin_park<false, true>) and the diagonals of the pose's PreEdgeSE2 blocks.
+// One wave per pose, lane l takes the edges l, l + 64, ... and adds them in that order, then wave_sum, then the odometry blocks
+// in list order: the sums of d_pose_reduce_max, bit for bit.  What differs is the schedule: the walk is a chain of dependent
+// index -> entry loads, so a lane fetches the indices of kL0Batch of its edges, then all their entries, then adds.
+constexpr int kL0Batch = 16;   // (1,024 edges per round: one round for the poses of a 200-key-frame window, 400 - 760 edges)
+__device__ __forceinline__ double d_pose_diag_max(const unsigned bx, int P, const int* __restrict__ pose_ptr,
+                                                  const int* __restrict__ pose_edges, const double* __restrict__ D3,
+                                                  const int* __restrict__ podo_ptr, const int* __restrict__ podo_item,
+                                                  const double* __restrict__ Oii, const double* __restrict__ Ojj) {
+    const int p = bx * (kBlock / 64) + threadIdx.x / 64;
+    const int lane = threadIdx.x & 63;
+    if (p >= P) return 0.0;
+    double h[3] = {0, 0, 0};
+    const int t0 = pose_ptr[p], ne = __builtin_amdgcn_readfirstlane(pose_ptr[p + 1] - t0);   // (one pose per wave)
+    for (int base = 0; base < ne; base += kL0Batch * 64) {
+        int ee[kL0Batch];
+        double v[kL0Batch][3];
+#pragma unroll
+        for (int u = 0; u < kL0Batch; ++u) {
+            if (base + u * 64 >= ne) break;   // uniform
+            ee[u] = pose_edges[t0 + min(base + u * 64 + lane, ne - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < kL0Batch; ++u) {
+            if (base + u * 64 >= ne) break;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) v[u][i] = D3[(size_t)ee[u] * 3 + i];
+        }
+#pragma unroll
+        for (int u = 0; u < kL0Batch; ++u) {
+            if (base + u * 64 >= ne) break;
+            if (base + u * 64 + lane < ne) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) h[i] += v[u][i];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) h[i] = wave_sum(h[i]);
+    if (lane != 0) return 0.0;
+    for (int t = podo_ptr[p]; t < podo_ptr[p + 1]; ++t) {
+        const int k = podo_item[t] >> 1, isj = podo_item[t] & 1;
+        const double* M = (isj ? Ojj : Oii) + (size_t)k * 9;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) h[i] += M[4 * i];
+    }
+    return fmax(fabs(h[0]), fmax(fabs(h[1]), fabs(h[2])));
+}
+
+// DIAG: k_lambda0_open, the launch behind k_open<false> (d_pose_diag_max; Hpp and bp are not formed - k_reduce2 builds its
+// own, and nothing else of the un-sharded run reads them: Hpp_e then holds the diagonals, 3 per edge)
+template <bool DIAG>
+__device__ __forceinline__ void d_lambda0(int P, const int* __restrict__ pose_ptr, const int* __restrict__ pose_edges,
+                                          const double* __restrict__ Hpp_e, const double* __restrict__ bp_e,
+                                          const int* __restrict__ podo_ptr, const int* __restrict__ podo_item,
+                                          const double* __restrict__ Oii, const double* __restrict__ Ojj,
+                                          const double* __restrict__ obi, const double* __restrict__ obj,
+                                          double* __restrict__ Hpp, double* __restrict__ bp,
+                                          const uint8_t* __restrict__ fixed, int L, const double* __restrict__ Hll,
+                                          unsigned long long* __restrict__ acc, double* __restrict__ out,
+                                          BaCtl* __restrict__ ctl) {
     __shared__ double sm[kBlock / 64];
     const int nP = (P + kBlock / 64 - 1) / (kBlock / 64), nL = (L + kL0PerBlock - 1) / kL0PerBlock;
     double m = 0.0;
     if ((int)blockIdx.x < nP) {
-        const double dm = d_pose_reduce_max(blockIdx.x, P, pose_ptr, pose_edges, Hpp_e, bp_e, podo_ptr, podo_item, Oii, Ojj, obi, obj, Hpp, bp);
+        const double dm = DIAG ? d_pose_diag_max(blockIdx.x, P, pose_ptr, pose_edges, Hpp_e, podo_ptr, podo_item, Oii, Ojj)
+                               : d_pose_reduce_max(blockIdx.x, P, pose_ptr, pose_edges, Hpp_e, bp_e, podo_ptr, podo_item, Oii, Ojj, obi, obj, Hpp, bp);
         const int p = blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
         if ((threadIdx.x & 63) == 0 && p < P && !fixed[p]) m = dm;
     } else {
@@ -524,6 +629,17 @@ __global__ __launch_bounds__(kBlock) void k_lambda0(int P, const int* __restrict
             ctl->ni = 2;
         }
     }
+}
+__global__ __launch_bounds__(kBlock) void k_lambda0(int P, const int* __restrict__ pose_ptr, const int* __restrict__ pose_edges,
+                                                     const double* __restrict__ Hpp_e, const double* __restrict__ bp_e,
+                                                     const int* __restrict__ podo_ptr, const int* __restrict__ podo_item,
+                                                     const double* __restrict__ Oii, const double* __restrict__ Ojj,
+                                                     const double* __restrict__ obi, const double* __restrict__ obj,
+                                                     double* __restrict__ Hpp, double* __restrict__ bp,
+                                                     const uint8_t* __restrict__ fixed, int L, const double* __restrict__ Hll,
+                                                     unsigned long long* __restrict__ acc, double* __restrict__ out,
+                                                     BaCtl* __restrict__ ctl) {
+    d_lambda0<false>(P, pose_ptr, pose_edges, Hpp_e, bp_e, podo_ptr, podo_item, Oii, Ojj, obi, obj, Hpp, bp, fixed, L, Hll, acc, out, ctl);
 }
 
 // max |diag| over a strided array (computeLambdaInit); single block, deterministic.
@@ -1140,6 +1256,13 @@ __device__ inline d2_t load_agent(const double* p) {
 // express-copy experiment in docs/history/DESIGN_rounds_1-5.md 4.1.1.)
 __device__ inline void store_agent(double* p, d2_t v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+}
+// a workgroup's {chi^2, scale} for the finisher workgroup of its launch (d_linearize<., true>; d_update has the same lines):
+// a write-through store, landed before the counter moves (the finisher may sit behind another L2)
+__device__ inline void publish_partial(double* part, unsigned* counter, unsigned bx, double c, double s) {
+    store_agent(part + 2 * bx, d2_t{c, s});
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #define SE2_WAIT_VM6(a, b, c, d, e, f) \
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : : "memory")
@@ -2058,6 +2181,53 @@ __device__ void finish_trial(const FinArgs& fin, const double* part, double lamb
     block_sum2(chi, scale, fsm);
     if (threadIdx.x == 0) fpost = trial_decide(te, chi, scale, failflag, stopped, /*records=*/true);
     trial_close(te, &fpost);
+}
+
+// k_open: the first launch of an un-sharded SE(2) optimize() behind k_ctl_init - one pass over the edges where there were
+// two (k_update<false> for chi^2 of the starting state, then k_linearize at the same state) and no launch of its own for the
+// PreEdgeSE2 blocks:
+//   workgroups [0, nblk)   d_linearize_pass<FUSED, true>: the linearisation, and the edges' chi^2 as partials for the finisher
+//   workgroup nblk         (<true> only) finish_trial with step == 0: odometry chi^2, lm_begin (a raised stop flag or a run of
+//                          zero iterations ends the run there; the linearisation is then scratch nobody reads)
+//   the ceil(O / 64) last  d_odometry_edge, one wave each: Oii, Ojj, Oij, obi, obj for lambda_0 (LM; they depend on the poses only)
+// <false>: LM, in front of k_lambda0_open, whose last workgroup is the finisher: the decision's tail runs beside the gather of
+// lambda_0 and not behind the edge pass.  <true>: Gauss-Newton (lambda = 0 throughout; k_reduce2 needs no odometry blocks, O = 0).
+struct OpenArgs {
+    LinArgs lin;
+    FinArgs fin;
+    OdoArgs odo;
+    double* part;
+};
+template <bool FUSED>
+__global__ __launch_bounds__(kBlock) void k_open(OpenArgs a) {
+    // the finisher's pose stage; the fused pass parks its blocks there too (lin_park / lin_landmark)
+    __shared__ double lds[FUSED ? (kBlock / 64) * kWaveLds : 3 * 1024];
+    static_assert((kBlock / 64) * kWaveLds >= 3 * 1024, "the finisher's pose stage");
+    const int bx = blockIdx.x, nfin = FUSED ? 1 : 0;
+    if (bx < a.fin.nblk) d_linearize_pass<FUSED, true>(bx, a.lin, LinOpen{a.part, a.fin.counter, lds});
+    else if (FUSED && bx == a.fin.nblk) finish_trial(a.fin, a.part, 0.0, lds);
+    else if (threadIdx.x < 64) d_odometry_edge((bx - a.fin.nblk - nfin) * 64 + (int)threadIdx.x, a.odo);
+}
+
+// k_lambda0_open: the launch behind k_open<false>.  d_lambda0<true>, and one more workgroup, the last, that ends the evaluation
+// of the starting state (finish_trial with step == 0) while the others gather: k_open<false>'s partials are all there (a kernel
+// boundary lies between), and the two write different words of the controller - lm_begin the costs, `stopped` and `done`, the
+// fold lambda and ni - and read none of each other's.
+__global__ __launch_bounds__(kBlock) void k_lambda0_open(int P, const int* __restrict__ pose_ptr, const int* __restrict__ pose_edges,
+                                                          const double* __restrict__ Hpp_e, const int* __restrict__ podo_ptr,
+                                                          const int* __restrict__ podo_item, const double* __restrict__ Oii,
+                                                          const double* __restrict__ Ojj, const uint8_t* __restrict__ fixed, int L,
+                                                          const double* __restrict__ Hll, unsigned long long* __restrict__ acc,
+                                                          double* __restrict__ out, BaCtl* __restrict__ ctl, FinArgs fin,
+                                                          const double* __restrict__ part) {
+    const int nP = (P + kBlock / 64 - 1) / (kBlock / 64), nL = (L + kL0PerBlock - 1) / kL0PerBlock;
+    if ((int)blockIdx.x == nP + nL) {
+        __shared__ double fsp[3 * 1024];
+        finish_trial(fin, part, 0.0, fsp);
+        return;
+    }
+    d_lambda0<true>(P, pose_ptr, pose_edges, Hpp_e, nullptr, podo_ptr, podo_item, Oii, Ojj, nullptr, nullptr, nullptr, nullptr, fixed,
+                    L, Hll, acc, out, ctl);
 }
 
 // k_finalize: single block of 1,024 behind k_update (see FinArgs).  out[0] = chi2_trial, out[1] = scale (local to this rank),
@@ -4562,6 +4732,15 @@ bool ba_env_speculate() {
     static const bool on = env_flag("SE2GPU_BA_SPECULATE", true);
     return on;
 }
+// SE2GPU_BA_OPEN=0: an optimize() opens with the separate launches again (k_update<false>, k_linearize<false>, k_odometry, k_lambda0)
+bool ba_env_open() {
+    static const bool on = env_flag("SE2GPU_BA_OPEN", true);
+    return on;
+}
+// k_open opens the single-window SE(2) run on one GPU (PreEdgeSE2 edges outside the block plan keep k_odometry)
+bool ba_opens_fused(const se2gpu_ba* h) {
+    return ba_env_open() && h->model == 0 && !h->allreduce && !h->comm && h->L > 0 && !h->odo_fallback;
+}
 RecSet rec_own(const se2gpu_ba* h) { return RecSet{h->Hpl.p, h->Dg.p, h->Hll.p, h->bl.p, h->Dinv.p, h->z.p}; }
 // (all null until ba_reserve_twin: BaCtl::rec_sel never leaves 0 on a handle without the twin)
 RecSet rec_twin(const se2gpu_ba* h) {
@@ -4638,6 +4817,15 @@ UpdArgs upd_args(se2gpu_ba* h, const Bufs& B, double lambda, const double* xp, c
                    h->bl.p, B.lb, h->part.p, B.c, B.pb, fin, h->Dinv.p,
                    lin ? SpecArgs{{rec_own(h), rec_twin(h)}, h->Hpp_e.p, h->bp_e.p} : SpecArgs{}};
 }
+
+// k_open: the controller's run (B = bufs(h, true)); lm: the PreEdgeSE2 blocks for k_lambda0 ride along
+OpenArgs open_args(se2gpu_ba* h, const Bufs& B, bool lm, double seq) {
+    OdoArgs odo = odo_args(h, h->poses, true);
+    if (!lm) odo.O = 0;
+    return OpenArgs{lin_args(h, B, 0.0, rec_twin(h)), fin_args(h, B, h->xp.p, trial_end(h, B, 0, 1, 0, seq)), odo, h->part.p};
+}
+// (the finisher workgroup is k_open<true>'s; the LM run's is k_lambda0_open's)
+inline dim3 open_grid(const se2gpu_ba* h, const OpenArgs& a, bool lm) { return dim3(upd_grid(h).x + (lm ? 0 : 1) + (a.odo.O + 63) / 64); }
 
 // SE(2) model (whitened records, k_linearize): h->Hpl holds W_e, h->Dinv the inverse Cholesky factors A_l, h->z the zeta_l;
 // h->Y is not used.  The SE3-expmap model keeps Hpl / Y / Dinv / z as named.
@@ -4908,7 +5096,9 @@ int ba_solve(se2gpu_ba* h, bool ctl = false) {
 
 // lambda_0 = 1e-5 * max |diag H| into the controller block, device to device (no host round trip).  The estimate is in
 // h->poses at this point (first trial of an optimize() call).
-int ba_lambda_init(se2gpu_ba* h) {
+// open: behind k_open<false>, which has computed the PreEdgeSE2 blocks and left the diagonals of Hpp_e and the chi^2 partials of
+// the starting state (k_lambda0_open; open = the end of that evaluation).
+int ba_lambda_init(se2gpu_ba* h, const FinArgs* open = nullptr) {
     hipStream_t st = h->stream;
     if (h->model) {   // diagonal of the pose blocks (observations + prior + odometry), then the common maximum
         SE2_LAUNCH(h->prof, st, "k3_pose_diag", k3_pose_diag, grid1((size_t)h->P * 64, kBlock), dim3(kBlock), 0, h->P,
@@ -4921,11 +5111,16 @@ int ba_lambda_init(se2gpu_ba* h) {
     const bool sharded = h->allreduce && h->world > 1;
     const size_t nd = 3 * (size_t)h->P;
     if (!sharded) {   // the pose blocks and the maximum over their and the landmarks' diagonals in one launch, lambda_0 set by it
-        SE2_CHECK(ba_pose_blocks(h, h->poses, true, /*odometry_only=*/true));
+        if (!open) SE2_CHECK(ba_pose_blocks(h, h->poses, true, /*odometry_only=*/true));
         const int nP = (h->P + kBlock / 64 - 1) / (kBlock / 64), nL = (h->L + kL0PerBlock - 1) / kL0PerBlock;
-        SE2_LAUNCH(h->prof, st, "k_lambda0", k_lambda0, dim3(nP + nL), dim3(kBlock), 0, h->P, h->pose_ptr.p, h->pose_edges.p,
-                   h->Hpp_e.p, h->bp_e.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p, h->Ojj.p, h->obi.p, h->obj.p, h->Hpp.p,
-                   h->bp.p, h->fixed.p, h->L, h->Hll.p, h->l0_acc.p, h->scal.p, h->ctl.p);
+        if (open)
+            SE2_LAUNCH(h->prof, st, "k_lambda0", k_lambda0_open, dim3(nP + nL + 1), dim3(kBlock), 0, h->P, h->pose_ptr.p,
+                       h->pose_edges.p, h->Hpp_e.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p, h->Ojj.p, h->fixed.p, h->L, h->Hll.p,
+                       h->l0_acc.p, h->scal.p, h->ctl.p, *open, (const double*)h->part.p);
+        else
+            SE2_LAUNCH(h->prof, st, "k_lambda0", k_lambda0, dim3(nP + nL), dim3(kBlock), 0, h->P, h->pose_ptr.p, h->pose_edges.p,
+                       h->Hpp_e.p, h->bp_e.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p, h->Ojj.p, h->obi.p, h->obj.p, h->Hpp.p,
+                       h->bp.p, h->fixed.p, h->L, h->Hll.p, h->l0_acc.p, h->scal.p, h->ctl.p);
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
     }
@@ -5008,7 +5203,19 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
     };
-    if (first) {
+    if (first && ba_opens_fused(h)) {
+        // chi^2 of the starting state -> controller, the linearisation at that state and (LM) the PreEdgeSE2 blocks: one launch
+        const OpenArgs oa = open_args(h, B, lm, seq);
+        if (lm) {
+            SE2_LAUNCH(h->prof, st, "k_open", k_open<false>, open_grid(h, oa, true), dim3(kBlock), 0, oa);
+            SE2_CHECK(ba_lambda_init(h, &oa.fin));
+            SE2_CHECK(ba_reduce(h, 0.0, 3, true));
+        } else {
+            SE2_LAUNCH(h->prof, st, "k_open", k_open<true>, open_grid(h, oa, false), dim3(kBlock), 0, oa);
+            SE2_CHECK(ba_reduce(h, 0.0, 0, true));
+        }
+        SE2_HIP(hipGetLastError());
+    } else if (first) {
         SE2_CHECK(evaluate(false, false));                  // chi^2 of the starting state -> controller
         if (lm) {
             SE2_CHECK(ba_linearize(h, -1.0, true));         // lambda_0 needs max diag(H) of this linearisation first
