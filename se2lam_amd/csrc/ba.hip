@@ -2014,7 +2014,7 @@ __device__ inline void end_slot(BaCtl* ctl, volatile double* mail, bool post, in
 }
 
 // ---- The end of a trial, for every pose model and launch shape: finish_trial (the last workgroup of k_update), k_finalize,
-// k3_finalize, k4_finalize and k_lm_decide differ in how they come by (chi^2, scale) and are the same from there on.
+// k6_finalize and k_lm_decide differ in how they come by (chi^2, scale) and are the same from there on.
 //   trial_open    all threads, first: the run is over -> answer a pending notification, leave; else who holds the estimate, lambda
 //   block_sum2    the block's two sums, in thread 0
 //   trial_decide  thread 0: out[0..3], then lm_begin / lm_advance on the controller or, without one, the scalars to the mailbox
@@ -2318,7 +2318,8 @@ __global__ void k_fill_slots(double* __restrict__ dst, const double* __restrict_
 // device-side LM controller): only the per-edge / per-pose arithmetic differs.  Poses are Tcw as 12 doubles (R row-major,
 // t); a pose has D = 6 unknowns (update = (omega, upsilon), estimate <- exp(update) * estimate); reduced-system blocks
 // are 6x6 (36-lane groups, 7 per workgroup); per-edge blocks: Hpl 6x3, Hpp_e sym 6x6 (21), bp_e 6, Y 6x3 and the
-// diagonal record Dg = {sym(Hpp_e - Y Hpl^T) (21), bp_e (6), Hpl z (6)} (33).
+// diagonal record Dg = {sym(Hpp_e - Y Hpl^T) (21), bp_e (6), Hpl z (6)} (33).  Every kernel takes one struct by value
+// (Lin3Args, ...; builders lin3_args, ...) but k3_reduce2; the pose kernels are the k6_* family, shared with the pose graph.
 // [3P g2o 20160424] VertexSE3Expmap, EdgeProjectXYZ2UV, EdgeSE3Expmap, SE3Quat - restated as in oracle/ba3_ref.cpp.
 // =============================================================================================
 constexpr int kGrpPerWG3 = 7;
@@ -2349,34 +2350,58 @@ __device__ inline void schur_edge3(const double* __restrict__ hh, const double d
     }
 }
 
+// The landmark kernels k3_linearize, k3_schur_lm and k3_update (lin3_args).  With `ctl` poses / lms are the "a" buffers, poses_b /
+// lms_b the "b" buffers: the controller says which holds the estimate, and lambda.
+struct Lin3Args {
+    Cam3 cam;
+    int L;
+    const int *lm_ptr, *e_kf;
+    const double *e_uv, *e_info, *poses;
+    const uint8_t* fixed;
+    const double* lms;
+    double *Hpl, *Hpp_e, *bp_e, *Hll, *bl;
+    double lambda;
+    double *Dinv, *z, *Y, *Dg;
+    const BaCtl* ctl;
+    const double *poses_b, *lms_b;
+};
+// the lambda-dependent records of landmark l from its sums (hll, b): Dinv, z and, per edge, schur_edge3
+__device__ __forceinline__ void schur_landmark3(const Lin3Args& a, int l, int sub, const double* hll, const double* b, double lambda) {
+    double d[6];
+    inv_sym3(hll, lambda, d);
+    const double z0 = d[0] * b[0] + d[1] * b[1] + d[2] * b[2];
+    const double z1 = d[1] * b[0] + d[3] * b[1] + d[4] * b[2];
+    const double z2 = d[2] * b[0] + d[4] * b[1] + d[5] * b[2];
+    if (sub == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) a.Dinv[(size_t)l * 6 + i] = d[i];
+        a.z[(size_t)l * 3] = z0; a.z[(size_t)l * 3 + 1] = z1; a.z[(size_t)l * 3 + 2] = z2;
+    }
+    for (int e = a.lm_ptr[l] + sub; e < a.lm_ptr[l + 1]; e += kGroup)
+        schur_edge3(a.Hpl + (size_t)e * 18, d, a.Hpp_e + (size_t)e * 21, a.bp_e + (size_t)e * 6, z0, z1, z2, a.Y + (size_t)e * 18,
+                    a.Dg + (size_t)e * 33);
+}
 template <bool FUSED>
-__global__ __launch_bounds__(kBlock) void k3_linearize(Cam3 cam, int L, const int* __restrict__ lm_ptr,
-                                                        const int* __restrict__ e_kf, const double* __restrict__ e_uv,
-                                                        const double* __restrict__ e_info, const double* __restrict__ poses,
-                                                        const uint8_t* __restrict__ fixed, const double* __restrict__ lms,
-                                                        double* Hpl, double* __restrict__ Hpp_e, double* __restrict__ bp_e,
-                                                        double* __restrict__ Hll, double* __restrict__ bl, double lambda,
-                                                        double* __restrict__ Dinv, double* __restrict__ z,
-                                                        double* __restrict__ Y, double* __restrict__ Dg,
-                                                        const BaCtl* __restrict__ ctl, const double* __restrict__ poses_b,
-                                                        const double* __restrict__ lms_b) {
-    if (ctl) {
-        if (ctl->done | ctl->retry) return;
-        if (ctl->sel) { poses = poses_b; lms = lms_b; }
-        lambda = ctl->lambda;
+__global__ __launch_bounds__(kBlock) void k3_linearize(Lin3Args a) {
+    const double *poses = a.poses, *lms = a.lms;
+    double lambda = a.lambda;
+    if (a.ctl) {
+        if (a.ctl->done | a.ctl->retry) return;
+        if (a.ctl->sel) { poses = a.poses_b; lms = a.lms_b; }
+        lambda = a.ctl->lambda;
     }
     const int gid = blockIdx.x * kBlock + threadIdx.x;
     const int l = gid / kGroup, sub = gid % kGroup;
     double hll[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    if (l < L) {
+    if (l < a.L) {
         const double X0 = lms[3 * (size_t)l], X1 = lms[3 * (size_t)l + 1], X2 = lms[3 * (size_t)l + 2];
-        for (int e = lm_ptr[l] + sub; e < lm_ptr[l + 1]; e += kGroup) {
-            const int kf = e_kf[e];
+        for (int e = a.lm_ptr[l] + sub; e < a.lm_ptr[l + 1]; e += kGroup) {
+            const int kf = a.e_kf[e];
             double e0, e1, Jp[12], Jl[6];
-            proj3<true>(cam, poses + 12 * (size_t)kf, X0, X1, X2, e_uv[2 * (size_t)e], e_uv[2 * (size_t)e + 1], e0, e1, Jp, Jl);
-            const double w = e_info[3 * (size_t)e];   // information = w I
+            proj3<true>(a.cam, poses + 12 * (size_t)kf, X0, X1, X2, a.e_uv[2 * (size_t)e], a.e_uv[2 * (size_t)e + 1], e0, e1, Jp, Jl);
+            const double w = a.e_info[3 * (size_t)e];   // information = w I
             double r0, r1;
-            huber(w * (e0 * e0 + e1 * e1), cam.huber, r0, r1);
+            huber(w * (e0 * e0 + e1 * e1), a.cam.huber, r0, r1);
             const double W = r1 * w, o0 = -W * e0, o1 = -W * e1;
             hll[0] += W * (Jl[0] * Jl[0] + Jl[3] * Jl[3]);
             hll[1] += W * (Jl[0] * Jl[1] + Jl[3] * Jl[4]);
@@ -2386,144 +2411,59 @@ __global__ __launch_bounds__(kBlock) void k3_linearize(Cam3 cam, int L, const in
             hll[5] += W * (Jl[2] * Jl[2] + Jl[5] * Jl[5]);
 #pragma unroll
             for (int r = 0; r < 3; ++r) b[r] += Jl[r] * o0 + Jl[3 + r] * o1;
-            const bool fr = !fixed[kf];
-            double* hpl = Hpl + (size_t)e * 18;
-            double* hpp = Hpp_e + (size_t)e * 21;
+            const bool fr = !a.fixed[kf];
+            double* hpl = a.Hpl + (size_t)e * 18;
+            double* hpp = a.Hpp_e + (size_t)e * 21;
             int k = 0;
+            // (one loop per array: stores that alternate between arrays that may overlap, for all the compiler knows, are not merged)
 #pragma unroll
-            for (int r = 0; r < 6; ++r) {
+            for (int r = 0; r < 6; ++r)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) hpl[3 * r + c] = fr ? W * (Jp[r] * Jl[c] + Jp[6 + r] * Jl[3 + c]) : 0.0;
 #pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
                 for (int c = r; c < 6; ++c, ++k) hpp[k] = fr ? W * (Jp[r] * Jp[c] + Jp[6 + r] * Jp[6 + c]) : 0.0;
-                bp_e[(size_t)e * 6 + r] = fr ? Jp[r] * o0 + Jp[6 + r] * o1 : 0.0;
-            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) a.bp_e[(size_t)e * 6 + r] = fr ? Jp[r] * o0 + Jp[6 + r] * o1 : 0.0;
         }
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) hll[i] = group_sum(hll[i]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) b[i] = group_sum(b[i]);
-    if (l < L && sub == 0) {
+    if (l < a.L && sub == 0) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) Hll[(size_t)l * 6 + i] = hll[i];
+        for (int i = 0; i < 6; ++i) a.Hll[(size_t)l * 6 + i] = hll[i];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) bl[(size_t)l * 3 + i] = b[i];
+        for (int i = 0; i < 3; ++i) a.bl[(size_t)l * 3 + i] = b[i];
     }
-    if (FUSED && l < L) {
-        double d[6];
-        inv_sym3(hll, lambda, d);
-        const double z0 = d[0] * b[0] + d[1] * b[1] + d[2] * b[2];
-        const double z1 = d[1] * b[0] + d[3] * b[1] + d[4] * b[2];
-        const double z2 = d[2] * b[0] + d[4] * b[1] + d[5] * b[2];
-        if (sub == 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) Dinv[(size_t)l * 6 + i] = d[i];
-            z[(size_t)l * 3] = z0; z[(size_t)l * 3 + 1] = z1; z[(size_t)l * 3 + 2] = z2;
-        }
-        for (int e = lm_ptr[l] + sub; e < lm_ptr[l + 1]; e += kGroup)
-            schur_edge3(Hpl + (size_t)e * 18, d, Hpp_e + (size_t)e * 21, bp_e + (size_t)e * 6, z0, z1, z2, Y + (size_t)e * 18,
-                        Dg + (size_t)e * 33);
-    }
+    if (FUSED && l < a.L) schur_landmark3(a, l, sub, hll, b, lambda);
 }
 
-__global__ __launch_bounds__(kBlock) void k3_schur_lm(int L, double lambda, const int* __restrict__ lm_ptr,
-                                                       const double* __restrict__ Hll, const double* __restrict__ bl,
-                                                       const double* __restrict__ Hpl, const double* __restrict__ Hpp_e,
-                                                       const double* __restrict__ bp_e, double* __restrict__ Dinv,
-                                                       double* __restrict__ z, double* __restrict__ Y, double* __restrict__ Dg,
-                                                       const BaCtl* __restrict__ ctl, int force) {
-    if (ctl) {
-        if (ctl->done || !(force | ctl->retry)) return;
-        lambda = ctl->lambda;
+// the fused pass of k3_linearize again, for a new lambda on the same linearisation.  With `ctl`: on a retry, or always with `force`
+__global__ __launch_bounds__(kBlock) void k3_schur_lm(Lin3Args a, int force) {
+    double lambda = a.lambda;
+    if (a.ctl) {
+        if (a.ctl->done || !(force | a.ctl->retry)) return;
+        lambda = a.ctl->lambda;
     }
     const int gid = blockIdx.x * kBlock + threadIdx.x;
     const int l = gid / kGroup, sub = gid % kGroup;
-    if (l >= L) return;
-    double h[6], d[6];
+    if (l >= a.L) return;
+    double h[6], b[3];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) h[i] = Hll[(size_t)l * 6 + i];
-    inv_sym3(h, lambda, d);
-    const double b0 = bl[(size_t)l * 3], b1 = bl[(size_t)l * 3 + 1], b2 = bl[(size_t)l * 3 + 2];
-    const double z0 = d[0] * b0 + d[1] * b1 + d[2] * b2, z1 = d[1] * b0 + d[3] * b1 + d[4] * b2, z2 = d[2] * b0 + d[4] * b1 + d[5] * b2;
-    if (sub == 0) {
+    for (int i = 0; i < 6; ++i) h[i] = a.Hll[(size_t)l * 6 + i];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) Dinv[(size_t)l * 6 + i] = d[i];
-        z[(size_t)l * 3] = z0; z[(size_t)l * 3 + 1] = z1; z[(size_t)l * 3 + 2] = z2;
-    }
-    for (int e = lm_ptr[l] + sub; e < lm_ptr[l + 1]; e += kGroup)
-        schur_edge3(Hpl + (size_t)e * 18, d, Hpp_e + (size_t)e * 21, bp_e + (size_t)e * 6, z0, z1, z2, Y + (size_t)e * 18,
-                    Dg + (size_t)e * 33);
-}
-
-// Per-pose and per-odometry-edge terms that depend on the estimate only (not on lambda): the prior gradient Omega e of
-// EdgeSE3ExpmapPrior (e = log(M T^-1), Jacobian -I: H += Omega, b += Omega e) and the blocks of every EdgeSE3Expmap
-// (e = log(T_j^-1 C T_i), J_i = adj(T_j^-1 C), J_j = -adj(T_i^-1 C^-1)): Oii, Ojj, Oij (6x6), obi, obj (6).
-// One thread per pose, then one thread per odometry edge.
-__global__ __launch_bounds__(64) void k3_terms(int P, int O, const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                         const uint8_t* __restrict__ prior_has, const double* __restrict__ prior_meas,
-                         const double* __restrict__ prior_info, double* __restrict__ pb, const int* __restrict__ o_i,
-                         const int* __restrict__ o_j, const double* __restrict__ o_meas, const double* __restrict__ o_info,
-                         double* __restrict__ Oii, double* __restrict__ Ojj, double* __restrict__ Oij,
-                         double* __restrict__ obi, double* __restrict__ obj, const BaCtl* __restrict__ ctl,
-                         const double* __restrict__ poses_b) {
-    if (ctl) {
-        if (ctl->done | ctl->retry) return;
-        if (ctl->sel) poses = poses_b;
-    }
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < P) {
-        double g[6] = {0, 0, 0, 0, 0, 0};
-        if (prior_has[t] && !fixed[t]) {
-            double e[6];
-            se3_log(se3_mul(se3_load(prior_meas + 12 * (size_t)t), se3_inv(se3_load(poses + 12 * (size_t)t))), e);
-            const double* W = prior_info + 36 * (size_t)t;
-            for (int r = 0; r < 6; ++r)
-                for (int c = 0; c < 6; ++c) g[r] += W[6 * r + c] * e[c];
-        }
-        for (int r = 0; r < 6; ++r) pb[6 * (size_t)t + r] = g[r];
-        return;
-    }
-    const int k = t - P;
-    if (k >= O) return;
-    const int i = o_i[k], j = o_j[k];
-    const Se3 Ti = se3_load(poses + 12 * (size_t)i), Tj = se3_load(poses + 12 * (size_t)j), C = se3_load(o_meas + 12 * (size_t)k);
-    const Se3 TjC = se3_mul(se3_inv(Tj), C);
-    double e[6], Ji[36], Jj[36], We[6];
-    se3_log(se3_mul(TjC, Ti), e);
-    se3_adj(TjC, Ji);
-    se3_adj(se3_mul(se3_inv(Ti), se3_inv(C)), Jj);
-    for (int q = 0; q < 36; ++q) Jj[q] = -Jj[q];
-    const double* W = o_info + 36 * (size_t)k;
-    for (int r = 0; r < 6; ++r) {
-        We[r] = 0;
-        for (int c = 0; c < 6; ++c) We[r] += W[6 * r + c] * e[c];
-    }
-    const bool fi = !fixed[i], fj = !fixed[j];
-    for (int r = 0; r < 6; ++r) {
-        for (int c = 0; c < 6; ++c) {
-            double ii = 0, jj = 0, ij = 0;
-            for (int a = 0; a < 6; ++a) {
-                double wi = 0, wj = 0;
-                for (int q = 0; q < 6; ++q) { wi += W[6 * a + q] * Ji[6 * q + c]; wj += W[6 * a + q] * Jj[6 * q + c]; }
-                ii += Ji[6 * a + r] * wi;
-                jj += Jj[6 * a + r] * wj;
-                ij += Ji[6 * a + r] * wj;
-            }
-            Oii[36 * (size_t)k + 6 * r + c] = fi ? ii : 0.0;
-            Ojj[36 * (size_t)k + 6 * r + c] = fj ? jj : 0.0;
-            Oij[36 * (size_t)k + 6 * r + c] = (fi && fj) ? ij : 0.0;
-        }
-        double bi = 0, bj = 0;
-        for (int q = 0; q < 6; ++q) { bi += Ji[6 * q + r] * We[q]; bj += Jj[6 * q + r] * We[q]; }
-        obi[6 * (size_t)k + r] = fi ? -bi : 0.0;
-        obj[6 * (size_t)k + r] = fj ? -bj : 0.0;
-    }
+    for (int i = 0; i < 3; ++i) b[i] = a.bl[(size_t)l * 3 + i];
+    schur_landmark3(a, l, sub, h, b, lambda);
 }
 
 // The reduced system of the SE3 model in one launch (structure of k_reduce2): off-diagonal 6x6 blocks from the
 // contributor plan (36 lanes per 16-pair chunk, 7 chunks per workgroup), one workgroup per pose for the diagonal
-// block, b_s and b_p (gather of the 33-double records + prior + odometry terms of k3_terms).
+// block, b_s and b_p (gather of the 33-double records + prior + odometry terms of k6_terms).  Both 6-DoF models.
+// (positional, with one launch site, ba_reduce: only as `const T* __restrict__` KERNEL parameters do its uniform loads behind the barrier
+// stay scalar loads; behind a struct, also with a `__restrict__` body underneath, the launch takes 0.9 us longer)
 __global__ __launch_bounds__(kBlock) void k3_reduce2(int P, int ld, int nwg_off, double lambda, const int4* __restrict__ grp,
                                                       const int* __restrict__ blk_a, const int* __restrict__ blk_b,
                                                       const int* __restrict__ pair_i, const int* __restrict__ pair_j,
@@ -2658,19 +2598,24 @@ __global__ __launch_bounds__(kBlock) void k3_reduce2(int P, int ld, int nwg_off,
     }
 }
 
-// diagonal of the un-reduced pose blocks (computeLambdaInit): one wave per pose
-__global__ __launch_bounds__(kBlock) void k3_pose_diag(int P, const int* __restrict__ pose_ptr, const int* __restrict__ pose_edges,
-                                                        const double* __restrict__ Hpp_e, const uint8_t* __restrict__ fixed,
-                                                        const uint8_t* __restrict__ prior_has, const double* __restrict__ prior_info,
-                                                        const int* __restrict__ podo_ptr, const int* __restrict__ podo_item,
-                                                        const double* __restrict__ Oii, const double* __restrict__ Ojj,
-                                                        double* __restrict__ diag) {
+// k3_pose_diag (pose_diag6_args): diagonal of the un-reduced pose blocks (computeLambdaInit), one wave per pose
+struct PoseDiag6Args {
+    int P;
+    const int *pose_ptr, *pose_edges;
+    const double* Hpp_e;
+    const uint8_t *fixed, *prior_has;
+    const double* prior_info;   // the Hessian of the priors (prior_hess)
+    const int *podo_ptr, *podo_item;
+    const double *Oii, *Ojj;
+    double* diag;
+};
+__global__ __launch_bounds__(kBlock) void k3_pose_diag(PoseDiag6Args a) {
     const int p = blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
     const int lane = threadIdx.x & 63;
-    if (p >= P) return;
+    if (p >= a.P) return;
     double d[6] = {0, 0, 0, 0, 0, 0};
-    for (int t = pose_ptr[p] + lane; t < pose_ptr[p + 1]; t += 64) {
-        const double* hp = Hpp_e + (size_t)pose_edges[t] * 21;
+    for (int t = a.pose_ptr[p] + lane; t < a.pose_ptr[p + 1]; t += 64) {
+        const double* hp = a.Hpp_e + (size_t)a.pose_edges[t] * 21;
 #pragma unroll
         for (int r = 0; r < 6; ++r) d[r] += hp[sym6(r, r)];
     }
@@ -2679,65 +2624,43 @@ __global__ __launch_bounds__(kBlock) void k3_pose_diag(int P, const int* __restr
     if (lane == 0) {
         for (int r = 0; r < 6; ++r) {
             double v = d[r];
-            if (!fixed[p]) {
-                if (prior_has[p]) v += prior_info[36 * (size_t)p + 7 * r];
-                for (int t = podo_ptr[p]; t < podo_ptr[p + 1]; ++t)
-                    v += ((podo_item[t] & 1) ? Ojj : Oii)[36 * (size_t)(podo_item[t] >> 1) + 7 * r];
+            if (!a.fixed[p]) {
+                if (a.prior_has[p]) v += a.prior_info[36 * (size_t)p + 7 * r];
+                for (int t = a.podo_ptr[p]; t < a.podo_ptr[p + 1]; ++t)
+                    v += ((a.podo_item[t] & 1) ? a.Ojj : a.Oii)[36 * (size_t)(a.podo_item[t] >> 1) + 7 * r];
             }
-            diag[6 * (size_t)p + r] = v;
+            a.diag[6 * (size_t)p + r] = v;
         }
     }
 }
 
-// trial poses: exp(update) * estimate (VertexSE3Expmap::oplusImpl); estimate copied for fixed poses / without a step
-__global__ void k3_oplus(int P, const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                         const double* __restrict__ xp, double* __restrict__ poses_trial, const BaCtl* __restrict__ ctl) {
-    if (ctl) {
-        if (ctl->done) return;
-        if (ctl->sel) { const double* t = poses; poses = poses_trial; poses_trial = const_cast<double*>(t); }
-    }
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    Se3 T = se3_load(poses + 12 * (size_t)p);
-    if (!fixed[p]) {
-        double u[6];
-        for (int r = 0; r < 6; ++r) u[r] = xp[6 * (size_t)p + r];
-        T = se3_mul(se3_exp(u), T);
-    }
-    se3_store(T, poses_trial + 12 * (size_t)p);
-}
-
-// back-substitution, trial landmarks, robust chi^2 of the landmark's edges at the trial state (poses from k3_oplus)
-__global__ __launch_bounds__(kBlock) void k3_update(Cam3 cam, int L, double lambda, const int* __restrict__ lm_ptr,
-                                                     const int* __restrict__ e_kf, const double* __restrict__ e_uv,
-                                                     const double* __restrict__ e_info, const double* __restrict__ poses_a,
-                                                     const double* __restrict__ poses_b, const double* __restrict__ lms,
-                                                     const double* __restrict__ xp, const double* __restrict__ z,
-                                                     const double* __restrict__ Y, const double* __restrict__ bl,
-                                                     double* __restrict__ lms_trial, double* __restrict__ part,
-                                                     const BaCtl* __restrict__ ctl, int step, double* __restrict__ edge_chi2) {
-    // poses_a / poses_b: "a" / "b" pose buffers.  With a step the TRIAL poses are read (the buffer that does not hold the
-    // estimate), without one the estimate.
-    const double* poses = poses_a;
-    if (ctl) {
-        if (ctl->done && !edge_chi2) return;
-        const bool est_b = ctl->sel != 0;
-        poses = (est_b != (step != 0)) ? poses_b : poses_a;
-        if (est_b) { const double* t = lms; lms = lms_trial; lms_trial = const_cast<double*>(t); }
-        lambda = ctl->lambda;
+// k3_update (lin3_args and what the trial adds): back-substitution, trial landmarks, robust chi^2 of the landmark's edges at the trial
+// state (poses from k6_oplus).  step = 0: evaluate the estimate (xp is not read); edge_chi2 (nullable): chi2() per edge, in landmark order.
+__global__ __launch_bounds__(kBlock) void k3_update(Lin3Args a, const double* __restrict__ xp, double* __restrict__ part, int step,
+                                                     double* __restrict__ edge_chi2) {
+    // With a step the TRIAL poses are read (the buffer that does not hold the estimate), without one the estimate.
+    const double *poses = a.poses, *lms = a.lms;
+    double* lms_trial = const_cast<double*>(a.lms_b);
+    double lambda = a.lambda;
+    if (a.ctl) {
+        if (a.ctl->done && !edge_chi2) return;
+        const bool est_b = a.ctl->sel != 0;
+        if (est_b != (step != 0)) poses = a.poses_b;
+        if (est_b) { lms = a.lms_b; lms_trial = const_cast<double*>(a.lms); }
+        lambda = a.ctl->lambda;
     }
     __shared__ double sm[2][kBlock / 64];
     const int gid = blockIdx.x * kBlock + threadIdx.x;
     const int l = gid / kGroup, sub = gid % kGroup;
     double chi = 0, scale = 0, x[3] = {0, 0, 0};
     int beg = 0, end = 0;
-    if (l < L) {
-        beg = lm_ptr[l];
-        end = lm_ptr[l + 1];
+    if (l < a.L) {
+        beg = a.lm_ptr[l];
+        end = a.lm_ptr[l + 1];
         if (step)
             for (int e = beg + sub; e < end; e += kGroup) {
-                const double* y = Y + (size_t)e * 18;
-                const double* q = xp + 6 * (size_t)e_kf[e];
+                const double* y = a.Y + (size_t)e * 18;
+                const double* q = xp + 6 * (size_t)a.e_kf[e];
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -2746,27 +2669,27 @@ __global__ __launch_bounds__(kBlock) void k3_update(Cam3 cam, int L, double lamb
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) x[c] = group_sum(x[c]);
-    if (l < L) {
+    if (l < a.L) {
         double lw[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            if (step) x[c] += z[(size_t)l * 3 + c];
+            if (step) x[c] += a.z[(size_t)l * 3 + c];
             lw[c] = lms[(size_t)l * 3 + c] + x[c];
         }
         if (sub == 0 && step) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 lms_trial[(size_t)l * 3 + c] = lw[c];
-                scale += x[c] * (lambda * x[c] + bl[(size_t)l * 3 + c]);
+                scale += x[c] * (lambda * x[c] + a.bl[(size_t)l * 3 + c]);
             }
         }
         for (int e = beg + sub; e < end; e += kGroup) {
             double e0, e1, r0, r1;
-            proj3<false>(cam, poses + 12 * (size_t)e_kf[e], lw[0], lw[1], lw[2], e_uv[2 * (size_t)e], e_uv[2 * (size_t)e + 1], e0, e1,
+            proj3<false>(a.cam, poses + 12 * (size_t)a.e_kf[e], lw[0], lw[1], lw[2], a.e_uv[2 * (size_t)e], a.e_uv[2 * (size_t)e + 1], e0, e1,
                          nullptr, nullptr);
-            const double c2 = e_info[3 * (size_t)e] * (e0 * e0 + e1 * e1);
+            const double c2 = a.e_info[3 * (size_t)e] * (e0 * e0 + e1 * e1);
             if (edge_chi2) edge_chi2[e] = c2;
-            huber(c2, cam.huber, r0, r1);
+            huber(c2, a.cam.huber, r0, r1);
             chi += r0;
         }
     }
@@ -2783,69 +2706,16 @@ __global__ __launch_bounds__(kBlock) void k3_update(Cam3 cam, int L, double lamb
     }
 }
 
-// the pose part of computeScale() of the 6-DoF models (SE3-expmap, pose graph): scale += x_p (lambda x_p + b_p) of one free
-// pose, term by term into the caller's running sum
-__device__ inline void scale6(const double* xp, const double* bp, double lambda, size_t p, double& scale) {
-    for (int r = 0; r < 6; ++r) scale += xp[6 * p + r] * (lambda * xp[6 * p + r] + bp[6 * p + r]);
-}
-
-// single block: sums the k3_update partials, adds the prior and odometry chi^2 at the trial poses and the pose part of
-// computeScale(), advances the LM controller (the end of a trial: trial_open ... trial_close)
-__global__ void k3_finalize(int nparts, const double* __restrict__ part, int P, const double* __restrict__ poses_a,
-                            const double* __restrict__ poses_b, const uint8_t* __restrict__ fixed, const double* __restrict__ xp,
-                            const double* __restrict__ bp, const uint8_t* __restrict__ prior_has,
-                            const double* __restrict__ prior_meas, const double* __restrict__ prior_info, int O,
-                            const int* __restrict__ o_i, const int* __restrict__ o_j, const double* __restrict__ o_meas,
-                            const double* __restrict__ o_info, TrialEnd te) {
-    __shared__ double sm[2 * 16];
-    __shared__ int post_s;
-    const TrialState ts = trial_open(te, 0.0);
-    if (!ts.live) return;
-    const double lambda = ts.lambda;
-    const bool step = te.step != 0;
-    const double* poses = (ts.est_b != step) ? poses_b : poses_a;   // k3_oplus has made the trial poses
-    double chi = 0, scale = 0;
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        chi += part[2 * i];
-        scale += part[2 * i + 1];
-    }
-    for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        if (step && !fixed[p]) scale6(xp, bp, lambda, p, scale);
-        if (prior_has[p]) {
-            double e[6];
-            se3_log(se3_mul(se3_load(prior_meas + 12 * (size_t)p), se3_inv(se3_load(poses + 12 * (size_t)p))), e);
-            const double* W = prior_info + 36 * (size_t)p;
-            for (int r = 0; r < 6; ++r) {
-                double v = 0;
-                for (int c = 0; c < 6; ++c) v += W[6 * r + c] * e[c];
-                chi += e[r] * v;
-            }
-        }
-    }
-    for (int k = threadIdx.x; k < O; k += blockDim.x) {
-        const Se3 Ti = se3_load(poses + 12 * (size_t)o_i[k]), Tj = se3_load(poses + 12 * (size_t)o_j[k]);
-        double e[6];
-        se3_log(se3_mul(se3_mul(se3_inv(Tj), se3_load(o_meas + 12 * (size_t)k)), Ti), e);
-        const double* W = o_info + 36 * (size_t)k;
-        for (int r = 0; r < 6; ++r) {
-            double v = 0;
-            for (int c = 0; c < 6; ++c) v += W[6 * r + c] * e[c];
-            chi += e[r] * v;
-        }
-    }
-    block_sum2(chi, scale, sm);
-    if (threadIdx.x == 0) post_s = trial_decide(te, chi, scale, trial_fail(te), trial_stopped(te), /*records=*/false);
-    trial_close(te, &post_s);
-}
-
 // =============================================================================================
 // Pose-graph model: GlobalMapper::GlobalBA (/root/reference/src/GlobalMapper.cpp:328-535) -
 // g2o::VertexSE3 (T_w_c), one EdgeSE3Prior per key frame (addVertexSE3PlaneMotion, src/optimizer.cpp:336-470), EdgeSE3
 // odometry and feature edges; no landmarks, so the "reduced" system is the whole system and the SE3 model's
-// k3_reduce2 / dataflow solve / LM controller run unchanged on the blocks this kernel family produces.
+// k3_reduce2 / dataflow solve / LM controller run unchanged on the blocks k6_terms<PoseGraph> produces.
 // Several edges may join the same two key frames (odometry + feature edge): the edges are grouped into PAIR SLOTS
 // (canonical orientation a < b), one thread sums a slot's edges into H_aa, H_bb, H_ab, b_a, b_b.
 // [3P g2o 20160424 types/slam3d] restated as in oracle/pg_ref.cpp (se3_math.h: to_mqt / from_mqt / mqt_jac_*).
+// k6_terms, k6_oplus and k6_finalize serve both 6-DoF models: one skeleton and one struct each, templated on a pose-model trait (Expmap,
+// PoseGraph) - the retraction, the prior and edge errors, how an error enters chi^2, the blocks of a pose's prior and of a pair of poses.
 // =============================================================================================
 __device__ inline void jtwj6(const double* Ja, const double* W, const double* Jc, double* out, double sgn) {   // out += Ja' W Jc
     for (int r = 0; r < 6; ++r)
@@ -2864,87 +2734,6 @@ __device__ inline void jtwe6(const double* Ja, const double* W, const double* e,
     for (int r = 0; r < 6; ++r) { We[r] = 0; for (int c = 0; c < 6; ++c) We[r] += W[6 * r + c] * e[c]; }
     for (int r = 0; r < 6; ++r) { double v = 0; for (int q = 0; q < 6; ++q) v += Ja[6 * q + r] * We[q]; out[r] -= v; }
 }
-
-__global__ __launch_bounds__(64) void k4_terms(int P, int nslot, const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                         const uint8_t* __restrict__ prior_has, const double* __restrict__ prior_meas,
-                         const double* __restrict__ prior_info, double* __restrict__ ph, double* __restrict__ pb,
-                         const int* __restrict__ slot_a, const int* __restrict__ slot_ptr, const int* __restrict__ e_i,
-                         const int* __restrict__ e_j, const double* __restrict__ e_meas, const double* __restrict__ e_info,
-                         double* __restrict__ Oii, double* __restrict__ Ojj, double* __restrict__ Oij,
-                         double* __restrict__ obi, double* __restrict__ obj, const BaCtl* __restrict__ ctl,
-                         const double* __restrict__ poses_b) {
-    if (ctl) {
-        if (ctl->done | ctl->retry) return;
-        if (ctl->sel) poses = poses_b;
-    }
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < P) {
-        double H[36], g[6];
-        for (int i = 0; i < 36; ++i) H[i] = 0;
-        for (int i = 0; i < 6; ++i) g[i] = 0;
-        if (prior_has[t] && !fixed[t]) {
-            const Se3 E = iso_mul(se3_inv(se3_load(prior_meas + 12 * (size_t)t)), se3_load(poses + 12 * (size_t)t));
-            double e[6], J[36];
-            to_mqt(E, e);
-            mqt_jac_right(E, J);
-            jtwj6(J, prior_info + 36 * (size_t)t, J, H, 1.0);
-            jtwe6(J, prior_info + 36 * (size_t)t, e, g);
-        }
-        for (int i = 0; i < 36; ++i) ph[36 * (size_t)t + i] = H[i];
-        for (int i = 0; i < 6; ++i) pb[6 * (size_t)t + i] = g[i];
-        return;
-    }
-    const int sl = t - P;
-    if (sl >= nslot) return;
-    const int a = slot_a[sl];
-    double Haa[36], Hbb[36], Hab[36], ba[6], bb[6];
-    for (int i = 0; i < 36; ++i) Haa[i] = Hbb[i] = Hab[i] = 0;
-    for (int i = 0; i < 6; ++i) ba[i] = bb[i] = 0;
-    for (int k = slot_ptr[sl]; k < slot_ptr[sl + 1]; ++k) {
-        const int i = e_i[k], j = e_j[k];
-        const Se3 A = se3_inv(se3_load(e_meas + 12 * (size_t)k));
-        const Se3 B = iso_mul(se3_inv(se3_load(poses + 12 * (size_t)i)), se3_load(poses + 12 * (size_t)j));
-        const Se3 E = iso_mul(A, B);
-        double e[6], Ji[36], Jj[36];
-        to_mqt(E, e);
-        mqt_jac_left_inv(A, B, Ji);
-        mqt_jac_right(E, Jj);
-        const double* W = e_info + 36 * (size_t)k;
-        const bool fi = !fixed[i], fj = !fixed[j];
-        // vertex 0 (i) is the slot's `a` or its `b`
-        double* Hi = i == a ? Haa : Hbb;
-        double* Hj = i == a ? Hbb : Haa;
-        double* bi = i == a ? ba : bb;
-        double* bj = i == a ? bb : ba;
-        if (fi) { jtwj6(Ji, W, Ji, Hi, 1.0); jtwe6(Ji, W, e, bi); }
-        if (fj) { jtwj6(Jj, W, Jj, Hj, 1.0); jtwe6(Jj, W, e, bj); }
-        if (fi && fj) {
-            if (i == a) jtwj6(Ji, W, Jj, Hab, 1.0);   // H_ab = J_a' W J_b
-            else jtwj6(Jj, W, Ji, Hab, 1.0);
-        }
-    }
-    for (int q = 0; q < 36; ++q) { Oii[36 * (size_t)sl + q] = Haa[q]; Ojj[36 * (size_t)sl + q] = Hbb[q]; Oij[36 * (size_t)sl + q] = Hab[q]; }
-    for (int q = 0; q < 6; ++q) { obi[6 * (size_t)sl + q] = ba[q]; obj[6 * (size_t)sl + q] = bb[q]; }
-}
-
-// trial poses: estimate * fromVectorMQT(update) (VertexSE3::oplusImpl)
-__global__ void k4_oplus(int P, const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
-                         const double* __restrict__ xp, double* __restrict__ poses_trial, const BaCtl* __restrict__ ctl) {
-    if (ctl) {
-        if (ctl->done) return;
-        if (ctl->sel) { const double* t = poses; poses = poses_trial; poses_trial = const_cast<double*>(t); }
-    }
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    Se3 T = se3_load(poses + 12 * (size_t)p);
-    if (!fixed[p]) {
-        double u[6];
-        for (int r = 0; r < 6; ++r) u[r] = xp[6 * (size_t)p + r];
-        T = iso_mul(T, from_mqt(u));
-    }
-    se3_store(T, poses_trial + 12 * (size_t)p);
-}
-
 __device__ inline double quad6(const double* W, const double* e) {
     double s = 0;
     for (int r = 0; r < 6; ++r) {
@@ -2954,43 +2743,259 @@ __device__ inline double quad6(const double* W, const double* e) {
     }
     return s;
 }
+// the pose part of computeScale(): scale += x_p (lambda x_p + b_p) of one free pose, term by term into the caller's running sum
+__device__ inline void scale6(const double* xp, const double* bp, double lambda, size_t p, double& scale) {
+    for (int r = 0; r < 6; ++r) scale += xp[6 * p + r] * (lambda * xp[6 * p + r] + bp[6 * p + r]);
+}
 
-// chi^2 of the priors and of every EdgeSE3 at the trial poses (the estimate without a step), pose part of computeScale(),
-// LM decision.  edge_chi2 (nullable): chi2() per edge, in slot order; without a controller that is all the kernel gives.
-__global__ void k4_finalize(int P, int nedge, const double* __restrict__ poses_a, const double* __restrict__ poses_b,
-                            const uint8_t* __restrict__ fixed, const double* __restrict__ xp, const double* __restrict__ bp,
-                            const uint8_t* __restrict__ prior_has, const double* __restrict__ prior_meas,
-                            const double* __restrict__ prior_info, const int* __restrict__ e_i, const int* __restrict__ e_j,
-                            const double* __restrict__ e_meas, const double* __restrict__ e_info, TrialEnd te,
-                            double* __restrict__ edge_chi2) {
-    __shared__ double sm[2 * 16];
-    __shared__ int post_s;
-    const TrialState ts = trial_open(te, 0.0);
-    if (!ts.live) return;
-    const double lambda = ts.lambda;
-    const bool step = te.step != 0;
-    const double* poses = (ts.est_b != step) ? poses_b : poses_a;   // k4_oplus has made the trial poses
-    double chi = 0, scale = 0;
-    for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        if (step && !fixed[p]) scale6(xp, bp, lambda, p, scale);
-        if (prior_has[p]) {
-            double e[6];
-            to_mqt(iso_mul(se3_inv(se3_load(prior_meas + 12 * (size_t)p)), se3_load(poses + 12 * (size_t)p)), e);
-            chi += quad6(prior_info + 36 * (size_t)p, e);
+// the binary pose-pose edges a model's kernels walk (edges6): EdgeSE3Expmap / EdgeSE3 in slot order
+struct Edges6 {
+    int n;
+    const int *i, *j;
+    const double *meas, *info;
+};
+// k6_terms: what depends on the estimate only.  One thread per pose (its prior), then one per pair: an odometry edge (expmap) or
+// a slot of parallel edges (pose graph; slot_a, slot_ptr and ph are that model's alone, and O counts slots there, ed.n edges).
+struct Terms6Args {
+    int P, O;   // O: pairs
+    const double* poses;
+    const uint8_t *fixed, *prior_has;
+    const double *prior_meas, *prior_info;
+    double *ph, *pb;
+    const int *slot_a, *slot_ptr;
+    Edges6 ed;
+    double *Oii, *Ojj, *Oij, *obi, *obj;
+    const BaCtl* ctl;
+    const double* poses_b;
+};
+struct Oplus6Args {   // k6_oplus: the trial poses; the estimate is copied for fixed poses
+    int P;
+    const double* poses;
+    const uint8_t* fixed;
+    const double* xp;
+    double* poses_trial;
+    const BaCtl* ctl;
+};
+// k6_finalize.  part: the k3_update partials (none in a pose graph); edge_chi2 (nullable): chi2() per edge, all a run without controller gives
+struct Fin6Args {
+    int nparts;
+    const double* part;
+    int P;
+    const double *poses_a, *poses_b;
+    const uint8_t* fixed;
+    const double *xp, *bp;
+    const uint8_t* prior_has;
+    const double *prior_meas, *prior_info;
+    Edges6 ed;
+    TrialEnd te;
+    double* edge_chi2;
+};
+
+// SE3-expmap: poses Tcw, estimate <- exp(update) * estimate (VertexSE3Expmap::oplusImpl)
+struct Expmap {
+    static __device__ __forceinline__ Se3 oplus(const Se3& T, const double* u) { return se3_mul(se3_exp(u), T); }
+    // EdgeSE3ExpmapPrior: e = log(M T^-1); EdgeSE3Expmap: e = log(T_j^-1 C T_i)
+    static __device__ __forceinline__ void prior_err(const Se3& M, const Se3& T, double* e) { se3_log(se3_mul(M, se3_inv(T)), e); }
+    static __device__ __forceinline__ void edge_err(const Se3& C, const Se3& Ti, const Se3& Tj, double* e) {
+        se3_log(se3_mul(se3_mul(se3_inv(Tj), C), Ti), e);
+    }
+    // chi += e' W e, row by row into the running sum (no per-edge output: this model's edge_chi2 are the projection edges', k3_update)
+    static __device__ __forceinline__ void add_chi2(const double* W, const double* e, double& chi, double*) {
+        for (int r = 0; r < 6; ++r) {
+            double v = 0;
+            for (int c = 0; c < 6; ++c) v += W[6 * r + c] * e[c];
+            chi += e[r] * v;
         }
     }
-    for (int k = threadIdx.x; k < nedge; k += blockDim.x) {
-        double e[6];
-        to_mqt(iso_mul(se3_inv(se3_load(e_meas + 12 * (size_t)k)),
-                       iso_mul(se3_inv(se3_load(poses + 12 * (size_t)e_i[k])), se3_load(poses + 12 * (size_t)e_j[k]))), e);
-        const double c2 = quad6(e_info + 36 * (size_t)k, e);
-        if (edge_chi2) edge_chi2[k] = c2;
+    // the prior gradient Omega e (Jacobian -I: H += Omega, which k3_reduce2 reads from prior_info itself; b += Omega e)
+    static __device__ __forceinline__ void prior_terms(const Terms6Args& a, const double* poses, int t) {
+        double g[6] = {0, 0, 0, 0, 0, 0};
+        if (a.prior_has[t] && !a.fixed[t]) {
+            double e[6];
+            prior_err(se3_load(a.prior_meas + 12 * (size_t)t), se3_load(poses + 12 * (size_t)t), e);
+            const double* W = a.prior_info + 36 * (size_t)t;
+            for (int r = 0; r < 6; ++r)
+                for (int c = 0; c < 6; ++c) g[r] += W[6 * r + c] * e[c];
+        }
+        for (int r = 0; r < 6; ++r) a.pb[6 * (size_t)t + r] = g[r];
+    }
+    // the blocks of one EdgeSE3Expmap (J_i = adj(T_j^-1 C), J_j = -adj(T_i^-1 C^-1)): Oii, Ojj, Oij (6x6), obi, obj (6).  Not through
+    // jtwj6 / jtwe6: `0 - v` stores +0 where -bi stores -0, and W J_j would be formed twice.
+    static __device__ __forceinline__ void pair_terms(const Terms6Args& a, const double* poses, int k) {
+        const int i = a.ed.i[k], j = a.ed.j[k];
+        const Se3 Ti = se3_load(poses + 12 * (size_t)i), Tj = se3_load(poses + 12 * (size_t)j), C = se3_load(a.ed.meas + 12 * (size_t)k);
+        const Se3 TjC = se3_mul(se3_inv(Tj), C);
+        double e[6], Ji[36], Jj[36], We[6];
+        se3_log(se3_mul(TjC, Ti), e);
+        se3_adj(TjC, Ji);
+        se3_adj(se3_mul(se3_inv(Ti), se3_inv(C)), Jj);
+        for (int q = 0; q < 36; ++q) Jj[q] = -Jj[q];
+        double W[36];   // read before the first store: the compiler cannot tell that Oii .. obj do not overlap it
+        for (int q = 0; q < 36; ++q) W[q] = a.ed.info[36 * (size_t)k + q];
+        for (int r = 0; r < 6; ++r) {
+            We[r] = 0;
+            for (int c = 0; c < 6; ++c) We[r] += W[6 * r + c] * e[c];
+        }
+        const bool fi = !a.fixed[i], fj = !a.fixed[j];
+        for (int r = 0; r < 6; ++r) {
+            for (int c = 0; c < 6; ++c) {
+                double ii = 0, jj = 0, ij = 0;
+                for (int u = 0; u < 6; ++u) {
+                    double wi = 0, wj = 0;
+                    for (int q = 0; q < 6; ++q) { wi += W[6 * u + q] * Ji[6 * q + c]; wj += W[6 * u + q] * Jj[6 * q + c]; }
+                    ii += Ji[6 * u + r] * wi;
+                    jj += Jj[6 * u + r] * wj;
+                    ij += Ji[6 * u + r] * wj;
+                }
+                a.Oii[36 * (size_t)k + 6 * r + c] = fi ? ii : 0.0;
+                a.Ojj[36 * (size_t)k + 6 * r + c] = fj ? jj : 0.0;
+                a.Oij[36 * (size_t)k + 6 * r + c] = (fi && fj) ? ij : 0.0;
+            }
+            double bi = 0, bj = 0;
+            for (int q = 0; q < 6; ++q) { bi += Ji[6 * q + r] * We[q]; bj += Jj[6 * q + r] * We[q]; }
+            a.obi[6 * (size_t)k + r] = fi ? -bi : 0.0;
+            a.obj[6 * (size_t)k + r] = fj ? -bj : 0.0;
+        }
+    }
+};
+
+// Pose graph: poses T_w_c, estimate <- estimate * fromVectorMQT(update) (VertexSE3::oplusImpl)
+struct PoseGraph {
+    static __device__ __forceinline__ Se3 oplus(const Se3& T, const double* u) { return iso_mul(T, from_mqt(u)); }
+    // EdgeSE3Prior: e = toVectorMQT(M^-1 T); EdgeSE3: e = toVectorMQT(C^-1 T_i^-1 T_j)
+    static __device__ __forceinline__ void prior_err(const Se3& M, const Se3& T, double* e) { to_mqt(iso_mul(se3_inv(M), T), e); }
+    static __device__ __forceinline__ void edge_err(const Se3& C, const Se3& Ti, const Se3& Tj, double* e) {
+        to_mqt(iso_mul(se3_inv(C), iso_mul(se3_inv(Ti), Tj)), e);
+    }
+    // chi += e' W e as one term; each (nullable): where chi2() of this edge goes
+    static __device__ __forceinline__ void add_chi2(const double* W, const double* e, double& chi, double* each) {
+        const double c2 = quad6(W, e);
+        if (each) *each = c2;
         chi += c2;
     }
-    if (!te.ctl) return;
+    // the prior's Hessian J' Omega J (ph: what k3_reduce2 and k3_pose_diag read, prior_hess) and gradient
+    static __device__ __forceinline__ void prior_terms(const Terms6Args& a, const double* poses, int t) {
+        double H[36], g[6];
+        for (int i = 0; i < 36; ++i) H[i] = 0;
+        for (int i = 0; i < 6; ++i) g[i] = 0;
+        if (a.prior_has[t] && !a.fixed[t]) {
+            const Se3 E = iso_mul(se3_inv(se3_load(a.prior_meas + 12 * (size_t)t)), se3_load(poses + 12 * (size_t)t));
+            double e[6], J[36];
+            to_mqt(E, e);
+            mqt_jac_right(E, J);
+            jtwj6(J, a.prior_info + 36 * (size_t)t, J, H, 1.0);
+            jtwe6(J, a.prior_info + 36 * (size_t)t, e, g);
+        }
+        for (int i = 0; i < 36; ++i) a.ph[36 * (size_t)t + i] = H[i];
+        for (int i = 0; i < 6; ++i) a.pb[6 * (size_t)t + i] = g[i];
+    }
+    static __device__ __forceinline__ void pair_terms(const Terms6Args& a, const double* poses, int sl) {
+        slot_terms(sl, poses, a.fixed, a.slot_a, a.slot_ptr, a.ed.i, a.ed.j, a.ed.meas, a.ed.info, a.Oii, a.Ojj, a.Oij, a.obi, a.obj);
+    }
+    // the sums over one slot's edges (positional: as parameters the pointers can be `__restrict__`, and the stores are merged again)
+    static __device__ __forceinline__ void slot_terms(int sl, const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
+                                                      const int* __restrict__ slot_a, const int* __restrict__ slot_ptr,
+                                                      const int* __restrict__ e_i, const int* __restrict__ e_j,
+                                                      const double* __restrict__ e_meas, const double* __restrict__ e_info,
+                                                      double* __restrict__ Oii, double* __restrict__ Ojj, double* __restrict__ Oij,
+                                                      double* __restrict__ obi, double* __restrict__ obj) {
+        const int sa = slot_a[sl];
+        double Haa[36], Hbb[36], Hab[36], ba[6], bb[6];
+        for (int i = 0; i < 36; ++i) Haa[i] = Hbb[i] = Hab[i] = 0;
+        for (int i = 0; i < 6; ++i) ba[i] = bb[i] = 0;
+        for (int k = slot_ptr[sl]; k < slot_ptr[sl + 1]; ++k) {
+            const int i = e_i[k], j = e_j[k];
+            const Se3 A = se3_inv(se3_load(e_meas + 12 * (size_t)k));
+            const Se3 B = iso_mul(se3_inv(se3_load(poses + 12 * (size_t)i)), se3_load(poses + 12 * (size_t)j));
+            const Se3 E = iso_mul(A, B);
+            double e[6], Ji[36], Jj[36];
+            to_mqt(E, e);
+            mqt_jac_left_inv(A, B, Ji);
+            mqt_jac_right(E, Jj);
+            const double* W = e_info + 36 * (size_t)k;
+            const bool fi = !fixed[i], fj = !fixed[j];
+            // vertex 0 (i) is the slot's `a` or its `b`
+            double* Hi = i == sa ? Haa : Hbb;
+            double* Hj = i == sa ? Hbb : Haa;
+            double* bi = i == sa ? ba : bb;
+            double* bj = i == sa ? bb : ba;
+            if (fi) { jtwj6(Ji, W, Ji, Hi, 1.0); jtwe6(Ji, W, e, bi); }
+            if (fj) { jtwj6(Jj, W, Jj, Hj, 1.0); jtwe6(Jj, W, e, bj); }
+            if (fi && fj) {
+                if (i == sa) jtwj6(Ji, W, Jj, Hab, 1.0);   // H_ab = J_a' W J_b
+                else jtwj6(Jj, W, Ji, Hab, 1.0);
+            }
+        }
+        for (int q = 0; q < 36; ++q) { Oii[36 * (size_t)sl + q] = Haa[q]; Ojj[36 * (size_t)sl + q] = Hbb[q]; Oij[36 * (size_t)sl + q] = Hab[q]; }
+        for (int q = 0; q < 6; ++q) { obi[6 * (size_t)sl + q] = ba[q]; obj[6 * (size_t)sl + q] = bb[q]; }
+    }
+};
+
+template <class M>
+__global__ __launch_bounds__(64) void k6_terms(Terms6Args a) {
+    const double* poses = a.poses;
+    if (a.ctl) {
+        if (a.ctl->done | a.ctl->retry) return;
+        if (a.ctl->sel) poses = a.poses_b;
+    }
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.P) M::prior_terms(a, poses, t);
+    else if (t - a.P < a.O) M::pair_terms(a, poses, t - a.P);
+}
+
+template <class M>
+__global__ void k6_oplus(Oplus6Args a) {
+    const double* poses = a.poses;
+    double* poses_trial = a.poses_trial;
+    if (a.ctl) {
+        if (a.ctl->done) return;
+        if (a.ctl->sel) { poses = a.poses_trial; poses_trial = const_cast<double*>(a.poses); }
+    }
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.P) return;
+    Se3 T = se3_load(poses + 12 * (size_t)p);
+    if (!a.fixed[p]) {
+        double u[6];
+        for (int r = 0; r < 6; ++r) u[r] = a.xp[6 * (size_t)p + r];
+        T = M::oplus(T, u);
+    }
+    se3_store(T, poses_trial + 12 * (size_t)p);
+}
+
+// single block: sums the k3_update partials, adds the chi^2 of the priors and of every binary edge at the trial poses (the estimate
+// without a step) and the pose part of computeScale(), advances the LM controller (the end of a trial: trial_open ... trial_close)
+template <class M>
+__global__ void k6_finalize(Fin6Args a) {
+    __shared__ double sm[2 * 16];
+    __shared__ int post_s;
+    const TrialState ts = trial_open(a.te, 0.0);
+    if (!ts.live) return;
+    const double lambda = ts.lambda;
+    const bool step = a.te.step != 0;
+    const double* poses = a.poses_a;   // k6_oplus has made the trial poses
+    if (ts.est_b != step) poses = a.poses_b;
+    double chi = 0, scale = 0;
+    for (int i = threadIdx.x; i < a.nparts; i += blockDim.x) {
+        chi += a.part[2 * i];
+        scale += a.part[2 * i + 1];
+    }
+    for (int p = threadIdx.x; p < a.P; p += blockDim.x) {
+        if (step && !a.fixed[p]) scale6(a.xp, a.bp, lambda, p, scale);
+        if (a.prior_has[p]) {
+            double e[6];
+            M::prior_err(se3_load(a.prior_meas + 12 * (size_t)p), se3_load(poses + 12 * (size_t)p), e);
+            M::add_chi2(a.prior_info + 36 * (size_t)p, e, chi, nullptr);
+        }
+    }
+    for (int k = threadIdx.x; k < a.ed.n; k += blockDim.x) {
+        double e[6];
+        M::edge_err(se3_load(a.ed.meas + 12 * (size_t)k), se3_load(poses + 12 * (size_t)a.ed.i[k]), se3_load(poses + 12 * (size_t)a.ed.j[k]), e);
+        M::add_chi2(a.ed.info + 36 * (size_t)k, e, chi, a.edge_chi2 ? a.edge_chi2 + k : nullptr);
+    }
+    if (!a.te.ctl) return;
     block_sum2(chi, scale, sm);
-    if (threadIdx.x == 0) post_s = trial_decide(te, chi, scale, trial_fail(te), trial_stopped(te), /*records=*/false);
-    trial_close(te, &post_s);
+    if (threadIdx.x == 0) post_s = trial_decide(a.te, chi, scale, trial_fail(a.te), trial_stopped(a.te), /*records=*/false);
+    trial_close(a.te, &post_s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4818,6 +4823,31 @@ UpdArgs upd_args(se2gpu_ba* h, const Bufs& B, double lambda, const double* xp, c
                    lin ? SpecArgs{{rec_own(h), rec_twin(h)}, h->Hpp_e.p, h->bp_e.p} : SpecArgs{}};
 }
 
+// The 6-DoF kernels' builders (models 1 and 2).  Beyond a kernel's trait the model decides two things, here: edges6 and prior_hess.
+inline const double* prior_hess(const se2gpu_ba* h) { return h->model == 2 ? h->ph.p : h->prior_info.p; }   // J' Omega J / Omega
+inline Edges6 edges6(const se2gpu_ba* h) {
+    if (h->model == 2) return Edges6{h->pg_edges, h->pe_i.p, h->pe_j.p, h->pe_meas.p, h->pe_info.p};
+    return Edges6{h->O, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p};
+}
+inline dim3 terms6_grid(const se2gpu_ba* h) { return grid1((size_t)h->P + h->O, 64); }   // poses, then pairs: h->O = edges (expmap) / slots (pose graph)
+Lin3Args lin3_args(se2gpu_ba* h, const Bufs& B, double lambda) {
+    return Lin3Args{h->cam3, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p, h->Hpp_e.p,
+                    h->bp_e.p, h->Hll.p, h->bl.p, lambda, h->Dinv.p, h->z.p, h->Y.p, h->Dg.p, B.c, B.pb, B.lb};
+}
+Terms6Args terms6_args(se2gpu_ba* h, const Bufs& B) {
+    return Terms6Args{h->P, h->O, B.pa, h->fixed.p, h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->ph.p, h->pb.p, h->slot_a.p,
+                      h->slot_ptr.p, edges6(h), h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p, B.c, B.pb};
+}
+PoseDiag6Args pose_diag6_args(se2gpu_ba* h) {
+    return PoseDiag6Args{h->P, h->pose_ptr.p, h->pose_edges.p, h->Hpp_e.p, h->fixed.p, h->prior_has.p, prior_hess(h), h->podo_ptr.p,
+                         h->podo_item.p, h->Oii.p, h->Ojj.p, h->diag3.p};
+}
+Oplus6Args oplus6_args(se2gpu_ba* h, const Bufs& B) { return Oplus6Args{h->P, B.pa, h->fixed.p, h->xp.p, B.pb, B.c}; }
+Fin6Args fin6_args(se2gpu_ba* h, const Bufs& B, const TrialEnd& te, double* edge_chi2) {
+    return Fin6Args{h->L ? h->nparts : 0, h->part.p, h->P, B.pa, B.pb, h->fixed.p, h->xp.p, h->bp.p, h->prior_has.p,
+                    h->prior_meas.p, h->prior_info.p, edges6(h), te, edge_chi2};
+}
+
 // k_open: the controller's run (B = bufs(h, true)); lm: the PreEdgeSE2 blocks for k_lambda0 ride along
 OpenArgs open_args(se2gpu_ba* h, const Bufs& B, bool lm, double seq) {
     OdoArgs odo = odo_args(h, h->poses, true);
@@ -4834,33 +4864,22 @@ inline dim3 open_grid(const se2gpu_ba* h, const OpenArgs& a, bool lm) { return d
 int ba_linearize(se2gpu_ba* h, double fuse_lambda, bool ctl = false) {
     hipStream_t st = h->stream;
     const Bufs B = bufs(h, ctl);
-    if (h->model == 2) {   // pose graph: nothing but the prior and edge blocks
-        SE2_LAUNCH(h->prof, st, "k4_terms", k4_terms, grid1((size_t)h->P + h->O, 64), dim3(64), 0, h->P, h->O, B.pa, h->fixed.p,
-                   h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->ph.p, h->pb.p, h->slot_a.p, h->slot_ptr.p, h->pe_i.p,
-                   h->pe_j.p, h->pe_meas.p, h->pe_info.p, h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p, B.c, B.pb);
-        SE2_HIP(hipGetLastError());
-        return SE2GPU_OK;
+    const bool fuse = fuse_lambda >= 0.0;
+    switch (h->model) {
+    case 2:   // pose graph: nothing but the prior and slot blocks
+        SE2_LAUNCH(h->prof, st, "k6_terms", k6_terms<PoseGraph>, terms6_grid(h), dim3(64), 0, terms6_args(h, B));
+        break;
+    case 1:   // SE3-expmap: the landmark pass, then the prior gradients and the odometry blocks of this linearisation
+        if (fuse) SE2_LAUNCH(h->prof, st, "k3_linearize", k3_linearize<true>, upd_grid(h), dim3(kBlock), 0, lin3_args(h, B, fuse_lambda));
+        else SE2_LAUNCH(h->prof, st, "k3_linearize", k3_linearize<false>, upd_grid(h), dim3(kBlock), 0, lin3_args(h, B, 0.0));
+        SE2_LAUNCH(h->prof, st, "k6_terms", k6_terms<Expmap>, terms6_grid(h), dim3(64), 0, terms6_args(h, B));
+        break;
+    default: {
+        const LinArgs la = lin_args(h, B, fuse ? fuse_lambda : 0.0, rec_twin(h));
+        if (fuse) SE2_LAUNCH(h->prof, st, "k_linearize", (k_linearize<true>), upd_grid(h), dim3(kBlock), 0, la);
+        else SE2_LAUNCH(h->prof, st, "k_linearize0", (k_linearize<false>), upd_grid(h), dim3(kBlock), 0, la);
     }
-    if (h->model) {
-        if (fuse_lambda >= 0.0)
-            SE2_LAUNCH(h->prof, st, "k3_linearize", (k3_linearize<true>), grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0,
-                       h->cam3, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p,
-                       h->Hpp_e.p, h->bp_e.p, h->Hll.p, h->bl.p, fuse_lambda, h->Dinv.p, h->z.p, h->Y.p, h->Dg.p, B.c, B.pb, B.lb);
-        else
-            SE2_LAUNCH(h->prof, st, "k3_linearize", (k3_linearize<false>), grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0,
-                       h->cam3, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p,
-                       h->Hpp_e.p, h->bp_e.p, h->Hll.p, h->bl.p, 0.0, h->Dinv.p, h->z.p, h->Y.p, h->Dg.p, B.c, B.pb, B.lb);
-        // the prior gradients and the odometry blocks of this linearisation
-        SE2_LAUNCH(h->prof, st, "k3_terms", k3_terms, grid1((size_t)h->P + h->O, 64), dim3(64), 0, h->P, h->O, B.pa, h->fixed.p,
-                   h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->pb.p, h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p,
-                   h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p, B.c, B.pb);
-        SE2_HIP(hipGetLastError());
-        return SE2GPU_OK;
     }
-    const dim3 lg = upd_grid(h);
-    const LinArgs la = lin_args(h, B, fuse_lambda >= 0.0 ? fuse_lambda : 0.0, rec_twin(h));
-    if (fuse_lambda >= 0.0) SE2_LAUNCH(h->prof, st, "k_linearize", (k_linearize<true>), lg, dim3(kBlock), 0, la);
-    else SE2_LAUNCH(h->prof, st, "k_linearize0", (k_linearize<false>), lg, dim3(kBlock), 0, la);
     SE2_HIP(hipGetLastError());
     return SE2GPU_OK;
 }
@@ -4882,17 +4901,13 @@ int ba_reduce(se2gpu_ba* h, double lambda, int schur, bool ctl = false) {
     hipStream_t st = h->stream;
     double* S = h->red;
     const Bufs B = bufs(h, ctl);
-    if (h->model) {
-        const double* pinfo = h->model == 2 ? h->ph.p : h->prior_info.p;   // Hessian of the prior: J' Omega J (pose graph) / Omega
+    if (h->model) {   // both 6-DoF models; the landmark records are the expmap model's
         if (schur && h->model == 1)
-            SE2_LAUNCH(h->prof, st, "k3_schur_lm", k3_schur_lm, grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0, h->L,
-                       lambda, h->lm_ptr.p, h->Hll.p, h->bl.p, h->Hpl.p, h->Hpp_e.p, h->bp_e.p, h->Dinv.p, h->z.p, h->Y.p,
-                       h->Dg.p, B.c, schur == 2 ? 0 : 1);
-        SE2_LAUNCH(h->prof, st, "k3_reduce2", k3_reduce2, dim3(((h->P + 1 + 7) & ~7) + ((h->nwg_off + 7) & ~7)), dim3(kBlock), 0,
-                   h->P, h->ld, h->nwg_off, lambda, h->grp.p, h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p, h->blk_odo.p,
-                   h->Y.p, h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p, h->pose_edges.p, h->podo_ptr.p, h->podo_item.p,
-                   h->prior_has.p, pinfo, h->pb.p, h->Oii.p, h->Ojj.p, h->Oij.p, h->obi.p, h->obj.p, S, h->bp.p, B.c,
-                   &h->ctl.p->epoch);
+            SE2_LAUNCH(h->prof, st, "k3_schur_lm", k3_schur_lm, upd_grid(h), dim3(kBlock), 0, lin3_args(h, B, lambda), schur == 2 ? 0 : 1);
+        SE2_LAUNCH(h->prof, st, "k3_reduce2", k3_reduce2, reduce2_grid(h), dim3(kBlock), 0, h->P, h->ld, h->nwg_off, lambda, h->grp.p,
+                   h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p, h->blk_odo.p, h->Y.p, h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p,
+                   h->pose_edges.p, h->podo_ptr.p, h->podo_item.p, h->prior_has.p, prior_hess(h), h->pb.p, h->Oii.p, h->Ojj.p, h->Oij.p,
+                   h->obi.p, h->obj.p, S, h->bp.p, B.c, &h->ctl.p->epoch);
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
     }
@@ -5101,9 +5116,7 @@ int ba_solve(se2gpu_ba* h, bool ctl = false) {
 int ba_lambda_init(se2gpu_ba* h, const FinArgs* open = nullptr) {
     hipStream_t st = h->stream;
     if (h->model) {   // diagonal of the pose blocks (observations + prior + odometry), then the common maximum
-        SE2_LAUNCH(h->prof, st, "k3_pose_diag", k3_pose_diag, grid1((size_t)h->P * 64, kBlock), dim3(kBlock), 0, h->P,
-                   h->pose_ptr.p, h->pose_edges.p, h->Hpp_e.p, h->fixed.p, h->prior_has.p,
-                   h->model == 2 ? h->ph.p : h->prior_info.p, h->podo_ptr.p, h->podo_item.p, h->Oii.p, h->Ojj.p, h->diag3.p);
+        SE2_LAUNCH(h->prof, st, "k3_pose_diag", k3_pose_diag, grid1((size_t)h->P * 64, kBlock), dim3(kBlock), 0, pose_diag6_args(h));
         SE2_LAUNCH(h->prof, st, "k_maxdiag", k_maxdiag, dim3(1), dim3(1024), 0, maxdiag_args(h, 6, 0, h->ctl.p));
         SE2_HIP(hipGetLastError());
         return SE2GPU_OK;
@@ -5160,24 +5173,17 @@ int ba_enqueue_trial(se2gpu_ba* h, bool first, int know_retry, bool notify, doub
     const Bufs B = bufs(h, true);
     auto evaluate = [&](bool step, bool note) -> int {
         auto te = [&](int decide, bool lin = false) { return trial_end(h, B, step ? 1 : 0, decide, note ? 1 : 0, seq, lin); };
-        if (h->model == 2) {
-            if (step)
-                SE2_LAUNCH(h->prof, st, "k4_oplus", k4_oplus, grid1(h->P, 64), dim3(64), 0, h->P, B.pa, h->fixed.p, h->xp.p, B.pb, B.c);
-            SE2_LAUNCH(h->prof, st, "k4_finalize", k4_finalize, dim3(1), dim3(1024), 0, h->P, h->pg_edges, B.pa, B.pb, h->fixed.p,
-                       h->xp.p, h->bp.p, h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->pe_i.p, h->pe_j.p, h->pe_meas.p,
-                       h->pe_info.p, te(1), (double*)nullptr);
-            SE2_HIP(hipGetLastError());
-            return SE2GPU_OK;
-        }
-        if (h->model) {
-            if (step)
-                SE2_LAUNCH(h->prof, st, "k3_oplus", k3_oplus, grid1(h->P, 64), dim3(64), 0, h->P, B.pa, h->fixed.p, h->xp.p, B.pb, B.c);
-            SE2_LAUNCH(h->prof, st, "k3_update", k3_update, grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0, h->cam3, h->L,
-                       0.0, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, B.pb, B.la, h->xp.p, h->z.p, h->Y.p, h->bl.p,
-                       B.lb, h->part.p, B.c, step ? 1 : 0, (double*)nullptr);
-            SE2_LAUNCH(h->prof, st, "k3_finalize", k3_finalize, dim3(1), dim3(1024), 0, h->L ? h->nparts : 0, h->part.p, h->P,
-                       B.pa, B.pb, h->fixed.p, h->xp.p, h->bp.p, h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->O,
-                       h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, te(1));
+        if (h->model) {   // 6-DoF: trial poses, the landmark part (SE3-expmap), then the pose part and the decision
+            const Fin6Args fa = fin6_args(h, B, te(1), nullptr);
+            if (h->model == 2) {
+                if (step) SE2_LAUNCH(h->prof, st, "k6_oplus", k6_oplus<PoseGraph>, grid1(h->P, 64), dim3(64), 0, oplus6_args(h, B));
+                SE2_LAUNCH(h->prof, st, "k6_finalize", k6_finalize<PoseGraph>, dim3(1), dim3(1024), 0, fa);
+            } else {
+                if (step) SE2_LAUNCH(h->prof, st, "k6_oplus", k6_oplus<Expmap>, grid1(h->P, 64), dim3(64), 0, oplus6_args(h, B));
+                SE2_LAUNCH(h->prof, st, "k3_update", k3_update, upd_grid(h), dim3(kBlock), 0, lin3_args(h, B, 0.0), h->xp.p, h->part.p,
+                           step ? 1 : 0, (double*)nullptr);
+                SE2_LAUNCH(h->prof, st, "k6_finalize", k6_finalize<Expmap>, dim3(1), dim3(1024), 0, fa);
+            }
             SE2_HIP(hipGetLastError());
             return SE2GPU_OK;
         }
@@ -5875,9 +5881,9 @@ int se2gpu_ba_edge_chi2(se2gpu_ba* h, double* chi2, int cap) {
         SE2_REQUIRE(cap >= NT, SE2GPU_ERR_CAPACITY, "edge_chi2: %d edges, room for %d", NT, cap);
         for (int k = 0; k < NT; ++k) chi2[k] = 0.0;   // an edge outside the optimised level reports 0
         if (!NE) return SE2GPU_OK;
-        hipLaunchKernelGGL(k4_finalize, dim3(1), dim3(1024), 0, st, h->P, NE, h->poses, h->poses_t, h->fixed.p, h->xp.p, h->bp.p,
-                           h->prior_has.p, h->prior_meas.p, h->prior_info.p, h->pe_i.p, h->pe_j.p, h->pe_meas.p, h->pe_info.p,
-                           trial_end(h, bufs(h, false), 0, 0, 0, 0.0, false, /*post=*/false), h->edge_chi2.p);
+        const Bufs B = bufs(h, false);
+        hipLaunchKernelGGL(k6_finalize<PoseGraph>, dim3(1), dim3(1024), 0, st,
+                           fin6_args(h, B, trial_end(h, B, 0, 0, 0, 0.0, false, /*post=*/false), h->edge_chi2.p));
         SE2_HIP(hipGetLastError());
         std::vector<double> tmp(NE);
         SE2_HIP(hipMemcpyAsync(tmp.data(), h->edge_chi2.p, (size_t)NE * 8, hipMemcpyDeviceToHost, st));
@@ -5887,9 +5893,7 @@ int se2gpu_ba_edge_chi2(se2gpu_ba* h, double* chi2, int cap) {
     }
     SE2_REQUIRE(cap >= h->E, SE2GPU_ERR_CAPACITY, "edge_chi2: %d edges, room for %d", h->E, cap);
     if (!h->E) return SE2GPU_OK;
-    hipLaunchKernelGGL(k3_update, grid1((size_t)h->L * kGroup, kBlock), dim3(kBlock), 0, st, h->cam3, h->L, 0.0, h->lm_ptr.p,
-                       h->e_kf.p, h->e_uv.p, h->e_info.p, h->poses, h->poses_t, h->lms, (const double*)nullptr, h->z.p, h->Y.p,
-                       h->bl.p, h->lms_t, h->part.p, (const BaCtl*)nullptr, 0, h->edge_chi2.p);
+    hipLaunchKernelGGL(k3_update, upd_grid(h), dim3(kBlock), 0, st, lin3_args(h, bufs(h, false), 0.0), h->xp.p, h->part.p, 0, h->edge_chi2.p);
     SE2_HIP(hipGetLastError());
     std::vector<double> tmp(h->E);
     SE2_HIP(hipMemcpyAsync(tmp.data(), h->edge_chi2.p, (size_t)h->E * 8, hipMemcpyDeviceToHost, st));

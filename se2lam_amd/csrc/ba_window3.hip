@@ -13,10 +13,10 @@
 //   BUILD   one lane per observation, 4 / 8 / 16 / 64 lanes per landmark: proj3<true>, Huber on w |e|^2, Hll / bl by DPP sums, the
 //           factor A = G^-1 of Hll + lambda I, W_e = Hpl_e A^T (6 x 3, registers); Hpp_e - W_e W_e^T (21) and b_e - W_e zeta (6) go to
 //           S by LDS atomics, the pair products W_i W_j^T (36 per pair, each pair once) through the per-wave strip; one lane per pose
-//           adds its prior (Omega, Omega e) and one per odometry edge its blocks (Oii, Ojj, Oij, obi, obj as k3_terms computes them)
+//           adds its prior (Omega, Omega e) and one per odometry edge its blocks (Oii, Ojj, Oij, obi, obj as k6_terms<Expmap> computes them)
 //   SOLVE   left-looking LL^T on 6 x 6 blocks in LDS with the right-hand side as an extra block row; x = L^-T y by one wave
 //   UPDATE  the observations stream in again, the Jacobians are recomputed for the back-substitution x_l = A^T A (bl - q) (A from the
-//           build pass through WindowArgsBase::ainv), exp(dx) T for the free poses (k3_oplus), robust chi^2 of the trial state
+//           build pass through WindowArgsBase::ainv), exp(dx) T for the free poses (k6_oplus<Expmap>), robust chi^2 of the trial state
 //           (projection edges, priors, odometry) and the gain denominator; lm_advance decides
 // Sums into S are atomic, hence in no fixed order: results agree with the multi-launch path to rounding, not bit for bit.
 //
@@ -188,7 +188,7 @@ struct Se3Model {
     // the pose terms, one thread each: t < P the prior of pose t (EdgeSE3ExpmapPrior), t >= P odometry edge t - P (EdgeSE3Expmap)
     // ------------------------------------------------------------------------------------------------------------------
 
-    // e = log(M T^-1), Jacobian -I: H += Omega, b += Omega e (k3_terms); chi^2 e^T Omega e for every pose with a prior (k3_finalize)
+    // e = log(M T^-1), Jacobian -I: H += Omega, b += Omega e (k6_terms<Expmap>); chi^2 e^T Omega e for every pose with a prior (k6_finalize<Expmap>)
     template <int MODE>
     __device__ __forceinline__ static void prior_term(const Ctx<Se3Model>& c, int p, double& chi, double& scale) {
         const Window3Args& a = *c.a;
@@ -235,7 +235,7 @@ struct Se3Model {
         }
     }
 
-    // e = log(T_j^-1 C T_i), J_i = adj(T_j^-1 C), J_j = -adj(T_i^-1 C^-1): Oii, Ojj, Oij, obi, obj as k3_terms computes them
+    // e = log(T_j^-1 C T_i), J_i = adj(T_j^-1 C), J_j = -adj(T_i^-1 C^-1): Oii, Ojj, Oij, obi, obj as k6_terms<Expmap> computes them
     template <int MODE>
     __device__ __forceinline__ static void odometry_term(const Ctx<Se3Model>& c, int k, double& chi, double& scale) {
         const Window3Args& a = *c.a;
@@ -243,7 +243,7 @@ struct Se3Model {
         const double* W = a.o_info + 36 * (size_t)k;
         const Se3 C = se3_load(a.o_meas + 12 * (size_t)k);
         double e[6];
-        if (MODE == kEval || MODE == kUpdate) {   // chi^2 at the estimate / at the trial state (k3_finalize)
+        if (MODE == kEval || MODE == kUpdate) {   // chi^2 at the estimate / at the trial state (k6_finalize<Expmap>)
             const double* ps = MODE == kEval ? c.cur : c.trl;
             se3_log(se3_mul(se3_mul(se3_inv(se3_load(ps + 12 * j)), C), se3_load(ps + 12 * i)), e);
 #pragma unroll

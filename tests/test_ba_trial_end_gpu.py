@@ -1,6 +1,6 @@
 """The end of a Levenberg-Marquardt trial on the multi-launch paths of csrc/ba.hip, per pose model and launch shape: the
 force-stop flag, a run of zero iterations and the synchronous controller (a notification per trial) for the SE(2) model (the
-finisher workgroup of k_update), the SE3-expmap model (k3_finalize), the pose graph (k4_finalize) and a sharded SE(2) run
+finisher workgroup of k_update), the SE3-expmap model (k6_finalize<Expmap>), the pose graph (k6_finalize<PoseGraph>) and a sharded SE(2) run
 (k_finalize + k_lm_decide).  One contract - g2o's solve loop - for all of them."""
 import numpy as np
 import pytest
