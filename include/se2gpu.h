@@ -794,6 +794,16 @@ int se2gpu_ba_debug_solve_plan_neager(int P, int D, const uint8_t* pattern, int 
 /* ... and of the plan an initialised handle runs, read back from the device: *nsys = order of the (padded) system,
  * *permuted = 1 when the fill-reducing order was taken, *ntask = tasks; neager (cap >= *ntask ints) may be NULL. */
 int se2gpu_ba_debug_plan_neager(se2gpu_ba* h, int* nsys, int* permuted, int* ntask, int32_t* neager, int cap);
+/* The flat plan records of the SE(2) model's k_reduce2 (one per group slot, 11 x 4 ints: the group descriptor, {column of a,
+ * column of b, blk_odo, both poses free}, {o_i, o_j, 0, 0} of the block's PreEdgeSE2 edge, then lane t's pair indices
+ * {i_t, j_t, i_(8+t), j_(8+t)}, t < 8, clamped to the chunk's last pair).  The first form runs the record builder on host
+ * arrays, without a device; pair_i / pair_j / pose_off / o_i / o_j may be NULL where no descriptor refers to them. */
+int se2gpu_ba_debug_flat_records_host(int nslots, const int32_t* grp4, const int32_t* blk_a, const int32_t* blk_b, const int32_t* blk_odo,
+                                      const int32_t* pair_i, const int32_t* pair_j, const uint8_t* fixed, const int32_t* pose_off,
+                                      const int32_t* o_i, const int32_t* o_j, int32_t* flat);
+/* ... the second reads back what an initialised handle uses, with its group descriptors (cap_slots * 4 and cap_slots * 44
+ * ints; NULL for both returns *nslots alone; *nslots = 0: the handle runs without the records, SE2GPU_BA_REDUCE_FLAT=0). */
+int se2gpu_ba_debug_flat_records(se2gpu_ba* h, int32_t* grp4, int32_t* flat, int cap_slots, int* nslots);
 
 /* Track::doTriangulate (/root/reference/src/Track.cpp:378-419) for every match of a frame pair in one device pass -
  * SURVEY section 8(f).3.  Per feature i of the reference key frame with match_idx[i] >= 0 and no map point yet:

@@ -752,7 +752,68 @@ struct Reduce2Args {
     const int* pose_off;
     int nsys;
     const double *W_alt, *Dg_alt;
+    // the flat plan records (k_plan_flat; nullptr = SE2GPU_BA_REDUCE_FLAT=0, the chain through grp / blk_* / pair_*)
+    const int4* flat;
 };
+// One flat record per group slot, kFlatQ 16-byte words at (wg * 28 + g) * kFlatQ: everything a group of d_reduce2 needs before its
+// first W round, so the group descriptor, the block's descriptor and the pair indices arrive in ONE round trip.
+//   [0]      grp's descriptor, as it is
+//   [1]      {ca, cb, od, free_ab}: the block's system columns (pose_off resolved), blk_odo, neither pose fixed
+//   [2]      {o_i, o_j, 0, 0} of the block's PreEdgeSE2 edge (od >= 0)
+//   [3 + t]  {i_t, j_t, i_(8+t), j_(8+t)}, t < 8: lane t's indices of the first sixteen pairs, clamped to the chunk's last pair
+constexpr int kFlatQ = 11;
+__host__ __device__ inline void flat_record(const int4 d, const int* blk_a, const int* blk_b, const int* blk_odo,
+                                            const int* pair_i, const int* pair_j, const uint8_t* fixed, const int* pose_off,
+                                            const int* o_i, const int* o_j, int4* rec) {
+    rec[0] = d;
+    for (int t = 1; t < kFlatQ; ++t) rec[t] = make_int4(0, 0, 0, 0);
+    rec[1].z = -1;
+    if (d.x < 0) return;
+    const int a = blk_a[d.x], b = blk_b[d.x], od = blk_odo[d.x];
+    rec[1] = make_int4(pose_off ? pose_off[a] : 3 * a, pose_off ? pose_off[b] : 3 * b, od, (!fixed[a] && !fixed[b]) ? 1 : 0);
+    if (od >= 0) rec[2] = make_int4(o_i[od >> 1], o_j[od >> 1], 0, 0);
+    if (d.z > d.y)
+        for (int t = 0; t < 8; ++t) {
+            const int last = d.z - 1, q0 = d.y + t < last ? d.y + t : last, q1 = d.y + 8 + t < last ? d.y + 8 + t : last;
+            rec[3 + t] = make_int4(pair_i[q0], pair_j[q0], pair_i[q1], pair_j[q1]);
+        }
+}
+struct PlanFlatArgs {
+    int ngrp;   // group slots
+    const int4* grp;
+    const int *blk_a, *blk_b, *blk_odo, *pair_i, *pair_j;
+    const uint8_t* fixed;
+    const int *pose_off, *o_i, *o_j;
+    int4* flat;
+};
+// plan post-pass, behind the packing (grp) and the solve plan (pose_off): one thread per group slot
+__global__ __launch_bounds__(256) void k_plan_flat(PlanFlatArgs a) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < a.ngrp)
+        flat_record(a.grp[t], a.blk_a, a.blk_b, a.blk_odo, a.pair_i, a.pair_j, a.fixed, a.pose_off, a.o_i, a.o_j,
+                    a.flat + (size_t)t * kFlatQ);
+}
+// odo_terms on the poses of i and j and the measurement in registers, the information matrix where it lies (`info` = its nine
+// doubles in global memory: all 18 operands in registers at once cost k_reduce2 its fifth wave per SIMD): the same function on
+// the same values, so the same bits.  (flatten: odo_terms must be inlined here, or the operands go through scratch memory)
+__device__ __forceinline__ __attribute__((flatten)) void odo_terms_regs(const double pij[6], const double meas[3], const double* info, double e[3],
+                                               double A[9], double B[9], double WA[9], double WB[9], double omr[3]) {
+    const int zero = 0, one = 1;
+    odo_terms(pij, nullptr, &zero, &one, meas, info, 0, e, A, B, WA, WB, omr);
+}
+// entry (r, c) of an off-diagonal block's PreEdgeSE2 term A^T W B (transposed when the edge runs b -> a: od & 1), as the
+// combine of d_reduce2 forms it
+__device__ __forceinline__ double odo_block_entry(const double pij[6], const double meas[3], const double* info, int od, int r, int c) {
+    double e[3], A[9], B[9], WA[9], WB[9], omr[3];
+    odo_terms_regs(pij, meas, info, e, A, B, WA, WB, omr);
+    // (selects on arrays of this scope, no dynamic index and no pointer to them: either would put them into scratch memory)
+    const int rr = (od & 1) ? c : r, cc = (od & 1) ? r : c;
+    const double a0 = rr == 0 ? A[0] : (rr == 1 ? A[1] : A[2]), a1 = rr == 0 ? A[3] : (rr == 1 ? A[4] : A[5]),
+                 a2 = rr == 0 ? A[6] : (rr == 1 ? A[7] : A[8]);
+    const double b0 = cc == 0 ? WB[0] : (cc == 1 ? WB[1] : WB[2]), b1 = cc == 0 ? WB[3] : (cc == 1 ? WB[4] : WB[5]),
+                 b2 = cc == 0 ? WB[6] : (cc == 1 ? WB[7] : WB[8]);
+    return a0 * b0 + a1 * b1 + a2 * b2;
+}
 __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& ra) {
     const double *W = ra.W, *Dg = ra.Dg, *poses = ra.poses;
     if (ra.ctl && ra.ctl->rec_sel) { W = ra.W_alt; Dg = ra.Dg_alt; }   // the record set of this slot (RecSet)
@@ -761,6 +822,7 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& 
     // identity padding between its partitions: solve_plan_build); nullptr = natural order, 3 p
     const int n = ra.pose_off ? ra.nsys : 3 * ra.P;
     __shared__ double part[kGrpPerWG][9];
+    __shared__ double odo_part[kGrpPerWG][9];   // flat records: a block's PreEdgeSE2 term, finished in front of the W rounds
     __shared__ double dpart[kBlock / 64][12];
     // grid = [P + 1 diagonal workgroups | off-diagonal workgroups, rounded up to a multiple of the 8 XCDs].  The diagonal
     // ones have the longest dependent chain (edge list -> edge rows -> landmark z, then the PreEdgeSE2 terms) and must
@@ -783,8 +845,17 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& 
         // chain, not a bandwidth, is what a window batch pays for (counters, round 4).  So every link is requested as early
         // as its address is known: the group descriptor beside the controller block, the block descriptor and the indices of
         // ALL pairs of the chunk beside each other, the fixed flags and columns beside the edge blocks.
-        int4 d = make_int4(-1, 0, 0, 0);
-        if (g < kGrpPerWG) d = ra.grp[(size_t)wg * kGrpPerWG + g];
+        // With the flat records (ra.flat) the chain is record -> W -> store: the descriptor, the block's columns and flags
+        // and this lane's pair indices are four 16-byte loads at addresses (wg, g) alone gives.
+        int4 d = make_int4(-1, 0, 0, 0), fb = make_int4(0, 0, -1, 0), fo = make_int4(0, 0, 0, 0), fq = make_int4(0, 0, 0, 0);
+        if (g < kGrpPerWG) {
+            if (ra.flat) {
+                const int4* rec = ra.flat + ((size_t)wg * kGrpPerWG + g) * kFlatQ;
+                d = rec[0]; fb = rec[1]; fo = rec[2]; fq = rec[3 + min(en, 7)];
+            } else {
+                d = ra.grp[(size_t)wg * kGrpPerWG + g];
+            }
+        }
         if (ra.ctl) {
             if (ra.ctl->done) return;
             if (ra.ctl->sel) poses = ra.poses_b;
@@ -798,15 +869,34 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& 
             // its block has more than 28 chunks' worth); slots past the chunk are clamped to its last pair and weighted 0 (no
             // branches inside a round)
             const int gb = 9 * gw, t8 = min(en, 7);
-            int q0 = min(d.y + t8, d.z - 1), q1 = min(d.y + 8 + t8, d.z - 1);
-            int my_i0 = 0, my_j0 = 0, my_i1 = 0, my_j1 = 0;
-            if (d.z > d.y) { my_i0 = ra.pair_i[q0]; my_j0 = ra.pair_j[q0]; my_i1 = ra.pair_i[q1]; my_j1 = ra.pair_j[q1]; }
-            a = ra.blk_a[d.x];
-            b = ra.blk_b[d.x];
-            od = ra.blk_odo[d.x];
-            free_ab = !ra.fixed[a] && !ra.fixed[b];      // (a block may have no pairs at all - an odometry edge only)
-            ca = ra.pose_off ? ra.pose_off[a] : 3 * a;
-            cb = ra.pose_off ? ra.pose_off[b] : 3 * b;
+            int q0, q1, my_i0 = 0, my_j0 = 0, my_i1 = 0, my_j1 = 0;
+            if (ra.flat) {
+                my_i0 = fq.x; my_j0 = fq.y; my_i1 = fq.z; my_j1 = fq.w;
+                ca = fb.x; cb = fb.y; od = fb.z;
+                free_ab = fb.w != 0;
+            } else {
+                q0 = min(d.y + t8, d.z - 1); q1 = min(d.y + 8 + t8, d.z - 1);
+                if (d.z > d.y) { my_i0 = ra.pair_i[q0]; my_j0 = ra.pair_j[q0]; my_i1 = ra.pair_i[q1]; my_j1 = ra.pair_j[q1]; }
+                a = ra.blk_a[d.x];
+                b = ra.blk_b[d.x];
+                od = ra.blk_odo[d.x];
+                free_ab = !ra.fixed[a] && !ra.fixed[b];      // (a block may have no pairs at all - an odometry edge only)
+                ca = ra.pose_off ? ra.pose_off[a] : 3 * a;
+                cb = ra.pose_off ? ra.pose_off[b] : 3 * b;
+            }
+            // The block's PreEdgeSE2 term (the group that combines the block adds it): with the flat record the edge's ends are
+            // known here, so the term is finished in front of the W rounds and parked in LDS - nothing of it is live beside a
+            // round's 32 registers of edge blocks - and the combine behind the barrier only adds it
+            if (ra.flat && free_ab && od >= 0 && (d.w & 0xff) == g) {
+                double opij[6], omeas[3];
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    opij[t] = poses[3 * (size_t)fo.x + t];
+                    opij[3 + t] = poses[3 * (size_t)fo.y + t];
+                    omeas[t] = ra.o_meas[3 * (size_t)(od >> 1) + t];
+                }
+                odo_part[g][en] = odo_block_entry(opij, omeas, ra.o_info + 9 * (size_t)(od >> 1), od, r, c);
+            }
             // The group loads every word ONCE (counters: 21 L1 accesses per load instruction with one row per lane): lane t
             // the t-th word of both 72-byte blocks of every pair (16 load instructions per round of 8 pairs instead of 48),
             // and the row of W_i / row of W_j an entry needs comes from the neighbours' registers (ds_bpermute).
@@ -851,15 +941,19 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& 
             if (free_ab) {
                 out = -tot;
                 if (od >= 0) {  // PreEdgeSE2 between a and b: A^T W B (transposed when the edge runs b -> a)
-                    double e[3], A[9], B[9], WA[9], WB[9], omr[3];
-                    odo_terms(poses, ra.fixed, ra.o_i, ra.o_j, ra.o_meas, ra.o_info, od >> 1, e, A, B, WA, WB, omr);
-                    // (no dynamic index into the private arrays: that would put them - and a scratch segment - into memory)
-                    const int rr = (od & 1) ? c : r, cc = (od & 1) ? r : c;
-                    const double a0 = rr == 0 ? A[0] : (rr == 1 ? A[1] : A[2]), a1 = rr == 0 ? A[3] : (rr == 1 ? A[4] : A[5]),
-                                 a2 = rr == 0 ? A[6] : (rr == 1 ? A[7] : A[8]);
-                    const double b0 = cc == 0 ? WB[0] : (cc == 1 ? WB[1] : WB[2]), b1 = cc == 0 ? WB[3] : (cc == 1 ? WB[4] : WB[5]),
-                                 b2 = cc == 0 ? WB[6] : (cc == 1 ? WB[7] : WB[8]);
-                    out += a0 * b0 + a1 * b1 + a2 * b2;
+                    if (ra.flat) {
+                        out += odo_part[g][en];
+                    } else {
+                        double e[3], A[9], B[9], WA[9], WB[9], omr[3];
+                        odo_terms(poses, ra.fixed, ra.o_i, ra.o_j, ra.o_meas, ra.o_info, od >> 1, e, A, B, WA, WB, omr);
+                        // (no dynamic index into the private arrays: that would put them - and a scratch segment - into memory)
+                        const int rr = (od & 1) ? c : r, cc = (od & 1) ? r : c;
+                        const double a0 = rr == 0 ? A[0] : (rr == 1 ? A[1] : A[2]), a1 = rr == 0 ? A[3] : (rr == 1 ? A[4] : A[5]),
+                                     a2 = rr == 0 ? A[6] : (rr == 1 ? A[7] : A[8]);
+                        const double b0 = cc == 0 ? WB[0] : (cc == 1 ? WB[1] : WB[2]), b1 = cc == 0 ? WB[3] : (cc == 1 ? WB[4] : WB[5]),
+                                     b2 = cc == 0 ? WB[6] : (cc == 1 ? WB[7] : WB[8]);
+                        out += a0 * b0 + a1 * b1 + a2 * b2;
+                    }
                 }
             }
             ra.S[(size_t)(ca + r) * ra.ld + cb + c] = out;
@@ -977,7 +1071,7 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& 
         }
     }
 }
-__global__ __launch_bounds__(kBlock) void k_reduce2(Reduce2Args a) {
+__global__ __launch_bounds__(kBlock, 5) void k_reduce2(Reduce2Args a) {
     d_reduce2(blockIdx.x, a);
 }
 
@@ -3200,6 +3294,11 @@ struct se2gpu_ba {
     DevBuf<int> blk_a, blk_b, blk_ptr, pair_i, pair_j, blk_odo;
     DevBuf<int4> grp;
     int nwg_off = 0, grp_cap_wg = 0;
+    // k_reduce2's flat records (k_plan_flat, the last plan launch of every initialize: grp, fixed and pose_off are final by then);
+    // flat_on = this handle's reductions take them (SE(2) model, SE2GPU_BA_REDUCE_FLAT != 0)
+    DevBuf<int4> grp_flat;
+    size_t flat_slots = 0;
+    bool flat_on = false;
     DevBuf<uint8_t> garena;        // every uploaded graph array lives in this one allocation (one H2D copy)
     DevBuf<int> plan_np, plan_base, plan_key0, plan_key1, plan_idx, plan_hist, plan_offs, plan_out, plan_tsum, plan_toff;  // device plan scratch
     DevBuf<int2> plan_st0, plan_st1;
@@ -4104,6 +4203,10 @@ int ba_copy_stream(int device, hipStream_t* out) {
 }
 
 int ba_allreduce(se2gpu_ba* h, double* ptr, size_t count);
+// SE2GPU_BA_REDUCE_FLAT=0: no flat records; the off-diagonal workgroups of k_reduce2 (alone, in the lock-step batches and in
+// sharded runs) walk grp -> blk_* / pair_* -> W and, behind the barrier, o_i / o_j as before.  (The diagonal workgroups are the
+// same in both forms.)  Read per initialize: a handle keeps the form its plan was built with.
+bool ba_env_reduce_flat() { return env_flag("SE2GPU_BA_REDUCE_FLAT", true); }
 
 int ba_upload_graph(se2gpu_ba* h) {
     static const bool trace = env_flag("SE2GPU_BA_INIT_TRACE", false);
@@ -4670,6 +4773,20 @@ int ba_upload_graph(se2gpu_ba* h) {
         h->nwg_off = std::max(nwg, 1);
     }
     lap("synchronise");
+    // ---- k_reduce2's flat records: behind the packing (the device plan's workgroup count is known now), the measurements and
+    // the solver's order (pose_off); every initialize rebuilds them with the plan
+    h->flat_on = h->model == 0 && ba_env_reduce_flat();
+    if (h->flat_on) {
+        const size_t slots = (size_t)h->nwg_off * gpw;
+        SE2_CHECK(h->grp_flat.reserve(slots * kFlatQ));
+        h->flat_slots = slots;
+        const PlanFlatArgs fa{(int)slots, h->grp.p, h->blk_a.p, h->blk_b.p, h->blk_odo.p, h->pair_i.p, h->pair_j.p,
+                              h->fixed.p, h->pose_off.p, h->o_i.p, h->o_j.p, h->grp_flat.p};
+        hipLaunchKernelGGL(k_plan_flat, grid1(slots, 256), dim3(256), 0, st, fa);
+        SE2_HIP(hipGetLastError());
+        SE2_HIP(hipStreamSynchronize(st));   // (batches read the records on other streams: nothing of initialize stays pending)
+        lap("flat records");
+    }
     // the borrow of se2gpu_ba_load ends here: everything has been copied into the pinned arena and uploaded
     h->bulk_E = 0;
     h->bulk_kf = h->bulk_lm = nullptr;
@@ -4791,7 +4908,7 @@ Reduce2Args reduce2_args(se2gpu_ba* h, const Bufs& B, double lambda, const RecSe
     return Reduce2Args{h->P, h->ld, h->nwg_off, lambda, h->root, h->grp.p, h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p,
                        h->blk_odo.p, h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p, h->pose_edges.p, h->podo_ptr.p, h->podo_item.p,
                        h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, B.pa, h->red, h->bp.p, B.c, B.pb, &h->ctl.p->epoch,
-                       h->pose_off.p, h->nsys, alt.W, alt.Dg};
+                       h->pose_off.p, h->nsys, alt.W, alt.Dg, h->flat_on ? h->grp_flat.p : nullptr};
 }
 // the dataflow solve of h->red into h->xp.  skip: SE2GPU_BA_CHOL_FAULT (ba_solve); head: the task counter, or nullptr (the grid fits);
 // verify: the launch is k_chol_tiles<true>'s (SE2GPU_BA_CHOL_VERIFY=1)
@@ -6217,6 +6334,34 @@ int se2gpu_ba_debug_solve_plan_neager(int P, int D, const uint8_t* pattern, int 
     solve_plan_choose(P, D, pattern, allow_nd != 0, sp, false, tile);
     SE2_REQUIRE(cap >= (int)sp.neager.size(), SE2GPU_ERR_CAPACITY, "debug_solve_plan_neager: %zu tasks", sp.neager.size());
     std::memcpy(neager, sp.neager.data(), sp.neager.size() * 4);
+    return SE2GPU_OK;
+}
+
+// k_plan_flat's record builder (flat_record, the function the kernel calls) on host arrays: nslots group descriptors in, nslots
+// records of 11 x 4 ints out.  No device needed.
+int se2gpu_ba_debug_flat_records_host(int nslots, const int32_t* grp4, const int32_t* blk_a, const int32_t* blk_b, const int32_t* blk_odo,
+                                      const int32_t* pair_i, const int32_t* pair_j, const uint8_t* fixed, const int32_t* pose_off,
+                                      const int32_t* o_i, const int32_t* o_j, int32_t* flat) {
+    SE2_REQUIRE(nslots >= 0 && grp4 && blk_a && blk_b && blk_odo && fixed && flat, SE2GPU_ERR_INVALID, "debug_flat_records_host: bad argument");
+    for (int s = 0; s < nslots; ++s) {
+        int4 rec[kFlatQ];
+        flat_record(make_int4(grp4[4 * s], grp4[4 * s + 1], grp4[4 * s + 2], grp4[4 * s + 3]), blk_a, blk_b, blk_odo, pair_i, pair_j,
+                    fixed, pose_off, o_i, o_j, rec);
+        std::memcpy(flat + (size_t)s * 4 * kFlatQ, rec, sizeof(rec));
+    }
+    return SE2GPU_OK;
+}
+// ... and the records an initialised handle's k_reduce2 reads, with the group descriptors they were made from (cap_slots * 44
+// and cap_slots * 4 ints; both may be NULL to ask for *nslots alone, 0 = the handle runs without them)
+int se2gpu_ba_debug_flat_records(se2gpu_ba* h, int32_t* grp4, int32_t* flat, int cap_slots, int* nslots) {
+    SE2_REQUIRE(h && h->initialized && nslots, SE2GPU_ERR_STATE, "debug_flat_records before initialize");
+    *nslots = h->flat_on ? (int)h->flat_slots : 0;
+    if (!grp4 || !flat || !h->flat_on) return SE2GPU_OK;
+    SE2_REQUIRE(cap_slots >= *nslots, SE2GPU_ERR_CAPACITY, "debug_flat_records: %d slots", *nslots);
+    SE2_CHECK(ba_join(h));
+    SE2_HIP(hipStreamSynchronize(h->stream));
+    SE2_HIP(hipMemcpy(grp4, h->grp.p, h->flat_slots * sizeof(int4), hipMemcpyDeviceToHost));
+    SE2_HIP(hipMemcpy(flat, h->grp_flat.p, h->flat_slots * kFlatQ * sizeof(int4), hipMemcpyDeviceToHost));
     return SE2GPU_OK;
 }
 
