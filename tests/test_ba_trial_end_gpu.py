@@ -8,14 +8,15 @@ import pytest
 from test_ba_gpu import LM_REJECT_CASES, _kidnapped, _opt, _sharded_equals_single
 from test_ba_window_se3_gpu import REJECT, _kidnapped3, _opt3, _resident
 from test_pg_gpu import _pg
+import pg_cases
 
 pytestmark = pytest.mark.gpu
 
-# model -> (handle of a graph, the smallest graph the generator makes for it, a start whose trials get rejected or None)
+# model -> (handle of a graph, the smallest graph the generator makes for it, a start whose trials get rejected)
 MODELS = {
     "se2": (_opt, lambda s: s.ba_graph(8, 60), lambda s: _kidnapped(s, *LM_REJECT_CASES[2][0])),
     "se3": (_opt3, lambda s: s.ba3_graph(8, 60, 0), lambda s: _kidnapped3(s, *REJECT)),
-    "pose_graph": (_pg, lambda s: s.pose_graph(12), None),
+    "pose_graph": (_pg, lambda s: s.pose_graph(12), lambda s: pg_cases.rejecting(24, 1, 7)),
 }
 
 
@@ -53,8 +54,8 @@ def test_stop_flag_and_zero_iterations(synth, model):
 @pytest.mark.parametrize("model", list(MODELS))
 def test_synchronous_controller_equals_the_asynchronous_one(synth, model):
     """setVerbose(True) = the synchronous controller: the host reads the controller block after EVERY trial (each slot ends with
-    a notification) and enqueues only what the next trial needs.  On a start that rejects trials (the pose graph: its
-    generator's start) it takes the decisions of the asynchronous run."""
+    a notification) and enqueues only what the next trial needs.  On a start that rejects trials it takes the decisions of the
+    asynchronous run."""
     make, graph, reject = MODELS[model]
     g = (reject or graph)(synth)
     with _resident("0"):
