@@ -804,6 +804,16 @@ int se2gpu_ba_debug_flat_records_host(int nslots, const int32_t* grp4, const int
 /* ... the second reads back what an initialised handle uses, with its group descriptors (cap_slots * 4 and cap_slots * 44
  * ints; NULL for both returns *nslots alone; *nslots = 0: the handle runs without the records, SE2GPU_BA_REDUCE_FLAT=0). */
 int se2gpu_ba_debug_flat_records(se2gpu_ba* h, int32_t* grp4, int32_t* flat, int cap_slots, int* nslots);
+/* The off-diagonal workgroups of the SE(2) model's k_reduce2: out = {workgroups of the plan, those that hold a group of a block
+ * with a contributor pair or a PreEdgeSE2 edge (the plan packs the empty blocks behind all others; equal to the first without
+ * that order: SE2GPU_BA_REDUCE_EMPTY=0, sharded handles, the 6-DoF models), those the next reduction launches}. */
+int se2gpu_ba_debug_reduce_grid(const se2gpu_ba* h, int out[3]);
+/* The host builder's packing of a graph (edges sorted by landmark) into group descriptors, without a device: grp4 (cap_slots * 4
+ * ints, or NULL) and out = {group slots, workgroups, workgroups of the non-empty blocks}.  empty_last: the order above;
+ * odo_ok = 0: the PreEdgeSE2 edges stay out of the block plan (self loops, duplicates) and only mark their blocks non-empty. */
+int se2gpu_ba_debug_plan_host(int P, int L, int E, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* fixed, int O,
+                              const int32_t* o_i, const int32_t* o_j, int odo_ok, int empty_last, int32_t* grp4, int cap_slots,
+                              int out[3]);
 
 /* Track::doTriangulate (/root/reference/src/Track.cpp:378-419) for every match of a frame pair in one device pass -
  * SURVEY section 8(f).3.  Per feature i of the reference key frame with match_idx[i] >= 0 and no map point yet:

@@ -210,6 +210,8 @@ SYMBOLS = {
     "se2gpu_ba_debug_plan_neager": (_I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _VP, _I]),
     "se2gpu_ba_debug_flat_records_host": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "se2gpu_ba_debug_flat_records": (_I, [_VP, _VP, _VP, _I, C.POINTER(C.c_int)]),
+    "se2gpu_ba_debug_reduce_grid": (_I, [_VP, _VP]),
+    "se2gpu_ba_debug_plan_host": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I, _VP]),
     "se2gpu_triangulate": (_I, [_I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _I, _VP, _VP,
                            C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "se2gpu_track_create": (_I, [C.POINTER(_VP)]),

@@ -736,7 +736,9 @@ constexpr int kChunk = 16;      // contributor pairs per group (d_reduce2 keeps 
 // with several chunks are packed into the same workgroup and combined in LDS in chunk order (deterministic).
 // grp = {block index or -1, first pair, last pair, (first group of the block in this WG) | (number of groups << 8)}
 struct Reduce2Args {
-    int P, ld, nwg_off;
+    // nwg_off workgroups in the XCD-contiguous order, then nwg_tail (0 = not launched) that hold nothing but empty blocks
+    // (pack_takes; reduce2_split decides)
+    int P, ld, nwg_off, nwg_tail;
     double lambda;
     int root;
     const int4* grp;
@@ -793,6 +795,22 @@ __global__ __launch_bounds__(256) void k_plan_flat(PlanFlatArgs a) {
         flat_record(a.grp[t], a.blk_a, a.blk_b, a.blk_odo, a.pair_i, a.pair_j, a.fixed, a.pose_off, a.o_i, a.o_j,
                     a.flat + (size_t)t * kFlatQ);
 }
+// What the workgroups behind the non-empty blocks (group slots first .. first + nslots - 1: empty blocks only, one group each)
+// would store on every trial, stored once by `initialize`: out = -tot = -0.0 between two free poses, 0.0 next to a fixed one.  A
+// reduction that leaves those workgroups out (reduce2_split) then finds in S the very bits the full grid writes.
+__global__ __launch_bounds__(256) void k_plan_empty_blocks(int first, int nslots, const int4* __restrict__ grp, const int* __restrict__ blk_a,
+                                                            const int* __restrict__ blk_b, const uint8_t* __restrict__ fixed,
+                                                            const int* __restrict__ pose_off, double* __restrict__ S, int ld) {
+    const int t = blockIdx.x * 256 + threadIdx.x, s = t / 9, en = t - 9 * s;
+    if (s >= nslots) return;
+    const int4 d = grp[first + s];
+    if (d.x < 0) return;
+    const int a = blk_a[d.x], b = blk_b[d.x], r = en / 3, c = en - 3 * r;
+    const int ca = pose_off ? pose_off[a] : 3 * a, cb = pose_off ? pose_off[b] : 3 * b;
+    const double out = (!fixed[a] && !fixed[b]) ? -0.0 : 0.0;
+    S[(size_t)(ca + r) * ld + cb + c] = out;
+    S[(size_t)(cb + c) * ld + ca + r] = out;
+}
 // odo_terms on the poses of i and j and the measurement in registers, the information matrix where it lies (`info` = its nine
 // doubles in global memory: all 18 operands in registers at once cost k_reduce2 its fifth wave per SIMD): the same function on
 // the same values, so the same bits.  (flatten: odo_terms must be inlined here, or the operands go through scratch memory)
@@ -834,8 +852,16 @@ __device__ __forceinline__ void d_reduce2(const unsigned bx, const Reduce2Args& 
         // XCD-aware order: workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  The plan is ordered
         // by pose block row, so XCD x takes the x-th CONTIGUOUS eighth of it: the W rows of its pose range are
         // fetched into one L2 instead of all eight (measured: 178 MB of HBM traffic per launch for 51 MB of operands).
-        const int wg = (bid & 7) * (nwg_pad >> 3) + (bid >> 3);
-        if (wg >= ra.nwg_off) return;
+        // The workgroups of the empty blocks alone (the plan packs those behind all others), where they are launched at all, take
+        // the indices behind the padded eighths one to one: dispatched last, and no part of the eighths
+        int wg;
+        if (bid < nwg_pad) {
+            wg = (bid & 7) * (nwg_pad >> 3) + (bid >> 3);
+            if (wg >= ra.nwg_off) return;
+        } else {
+            if (bid - nwg_pad >= ra.nwg_tail) return;
+            wg = ra.nwg_off + (bid - nwg_pad);
+        }
         // 7 groups of 9 lanes per wave (lane 63 idles), 4 waves: the 9 lanes of a group share their loads through
         // ds_bpermute, so a group must not straddle two waves
         const int lane = threadIdx.x & 63, gw = lane / 9, en = lane - 9 * gw;
@@ -3294,6 +3320,10 @@ struct se2gpu_ba {
     DevBuf<int> blk_a, blk_b, blk_ptr, pair_i, pair_j, blk_odo;
     DevBuf<int4> grp;
     int nwg_off = 0, grp_cap_wg = 0;
+    // reduce_empty = the plan packs the blocks whose key frames share no landmark and no edge behind all others (SE(2) model, one
+    // GPU, SE2GPU_BA_REDUCE_EMPTY != 0); nwg_real = the workgroups that hold a group of any other block (= nwg_off without the order)
+    int nwg_real = 0;
+    bool reduce_empty = false;
     // k_reduce2's flat records (k_plan_flat, the last plan launch of every initialize: grp, fixed and pose_off are final by then);
     // flat_on = this handle's reductions take them (SE(2) model, SE2GPU_BA_REDUCE_FLAT != 0)
     DevBuf<int4> grp_flat;
@@ -3319,6 +3349,7 @@ struct se2gpu_ba {
     DevBuf<int> col_src;          // system column -> 3 * pose + component, -1 = padding (nullptr = identity)
     std::vector<int> h_pose_off;  // host copy (debug_reduced_system gathers S back into pose order)
     DevBuf<uint8_t> plan_nz;      // per block of the upper triangle: structurally non-zero (k_plan_odo, k_plan_pairs2)
+    DevBuf<uint8_t> plan_cov;     // ... its key frames share a landmark or an edge: the packing classes (reduce_empty)
     DevBuf<double> plan_nzd;      // the same as doubles: what a sharded run's all-reduce can merge
     PinBuf<uint8_t> h_plan_nz;
     DevBuf<uint8_t> solver_arena; // chol_tasks | chol_deps | chol_neager | pose_off | col_src
@@ -3559,13 +3590,14 @@ __global__ void k_lower_bounds(const int* __restrict__ key, int n, int nq, int* 
 // edges take the k_odometry / k_reduce_odo path instead: then blk_odo is nullptr and stays -1, and only nz is marked - the
 // fallback still adds those blocks to S, and the host plan marks them too
 __global__ void k_plan_odo(int P, int O, const int* __restrict__ o_i, const int* __restrict__ o_j, int* __restrict__ blk_odo,
-                           uint8_t* __restrict__ nz) {
+                           uint8_t* __restrict__ nz, uint8_t* __restrict__ cov) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= O) return;
     const int i = o_i[k], j = o_j[k];
     const int q = blk_index_of(P, min(i, j), max(i, j));
     if (blk_odo) blk_odo[q] = 2 * k + (i > j ? 1 : 0);
     if (nz) nz[q] = 1;
+    if (cov) cov[q] = 1;
 }
 
 // Packing of the off-diagonal blocks' 16-pair chunks ("groups") into workgroups of kGrpPerWG groups, exactly as the
@@ -3574,6 +3606,25 @@ __global__ void k_plan_odo(int P, int O, const int* __restrict__ o_i, const int*
 // function {used -> (used', workgroups closed)}, tabulated by one thread for all 28 start states; one thread composes
 // the 256 tables; every thread then replays its run from its now known start and writes the group descriptors.
 // out_n[0] = number of workgroups.
+// Packing ORDER (nz != nullptr: the SE(2) model's plans, SE2GPU_BA_REDUCE_EMPTY): the blocks whose key frames share a landmark
+// or a PreEdgeSE2 edge (`cov`, as k_plan_pairs2 / k_plan_odo mark it beside the solver's pattern - an edge outside the block
+// plan, odo_fallback, counts, and so does a landmark seen by a fixed key frame: such a block is zero but not structurally
+// empty) come first, the empty ones behind them, block order kept inside either class, ONE stream without a workgroup break
+// between the two.  An empty block's group stores eighteen zeros, the same on every trial: its workgroups need not run on a
+// handle whose S keeps them (reduce2_split).  The 256 runs are then 128 over the blocks of either class, so the state in front of run 128 is the
+// end of the first class: out_n[1] = workgroups that hold a group of a non-empty block (= out_n[0] in block order).
+__device__ __host__ inline bool pack_takes(int a, int b, const uint8_t* nz, int kb, int cls) {
+    return a != b && (!nz || (nz[kb] != 0) == (cls == 0));
+}
+constexpr int kPackRuns = 256;
+// run r of kPackRuns: the blocks [b0, b1) of class cls
+__device__ inline void pack_run(int r, int nblk, bool two, int& cls, int& b0, int& b1) {
+    const int rpc = two ? kPackRuns / 2 : kPackRuns;
+    const int per = (nblk + rpc - 1) / rpc;
+    cls = r / rpc;
+    b0 = min((r - cls * rpc) * per, nblk);
+    b1 = min(b0 + per, nblk);
+}
 __device__ inline void pack_step(int cnt, int gpw, int& used, int& wg, int& first, int& ng, int& chunk) {
     chunk = kChunk;
     ng = max(1, (cnt + chunk - 1) / chunk);
@@ -3584,18 +3635,19 @@ __device__ inline void pack_step(int cnt, int gpw, int& used, int& wg, int& firs
 }
 __global__ __launch_bounds__(256) void k_plan_pack(int nblk, const int* __restrict__ blk_a, const int* __restrict__ blk_b,
                                                     const int* __restrict__ blk_ptr, int4* __restrict__ grp,
-                                                    int grp_cap_wg, int* __restrict__ out_n, int gpw) {
+                                                    int grp_cap_wg, int* __restrict__ out_n, int gpw,
+                                                    const uint8_t* __restrict__ nz) {
     __shared__ int tab_used[256][kGrpPerWG], tab_wg[256][kGrpPerWG];
     __shared__ int start_used[256], start_wg[256];
     const int t = threadIdx.x;
-    const int per = (nblk + 255) / 256;
-    const int b0 = min(t * per, nblk), b1 = min(b0 + per, nblk);
+    int cls, b0, b1;
+    pack_run(t, nblk, nz != nullptr, cls, b0, b1);
     {   // the run's transfer function for all 28 start states in ONE pass over its blocks
         int used[kGrpPerWG], wgs[kGrpPerWG];
 #pragma unroll
         for (int u = 0; u < kGrpPerWG; ++u) { used[u] = u; wgs[u] = 0; }
         for (int kb = b0; kb < b1; ++kb) {
-            if (blk_a[kb] == blk_b[kb]) continue;
+            if (!pack_takes(blk_a[kb], blk_b[kb], nz, kb, cls)) continue;
             const int cnt = blk_ptr[kb + 1] - blk_ptr[kb];
             int ng = max(1, (cnt + kChunk - 1) / kChunk);
             if (ng > gpw) { const int chunk = (cnt + gpw - 1) / gpw; ng = (cnt + chunk - 1) / chunk; }
@@ -3611,19 +3663,21 @@ __global__ __launch_bounds__(256) void k_plan_pack(int nblk, const int* __restri
     }
     __syncthreads();
     if (t == 0) {
-        int used = 0, wg = 0;
+        int used = 0, wg = 0, real = -1;
         for (int r = 0; r < 256; ++r) {
+            if (nz && r == kPackRuns / 2) real = wg + (used ? 1 : 0);   // the end of the non-empty blocks
             start_used[r] = used;
             start_wg[r] = wg;
             wg += tab_wg[r][used];
             used = tab_used[r][used];
         }
         out_n[0] = wg + (used ? 1 : 0);
+        out_n[1] = real >= 0 ? real : out_n[0];
     }
     __syncthreads();
     int used = start_used[t], wg = start_wg[t];
     for (int kb = b0; kb < b1; ++kb) {
-        if (blk_a[kb] == blk_b[kb]) continue;
+        if (!pack_takes(blk_a[kb], blk_b[kb], nz, kb, cls)) continue;
         const int q0 = blk_ptr[kb], q1 = blk_ptr[kb + 1];
         int first, ng, chunk;
         pack_step(q1 - q0, gpw, used, wg, first, ng, chunk);
@@ -3644,21 +3698,22 @@ __global__ __launch_bounds__(256) void k_plan_pack(int nblk, const int* __restri
 //                  -> every run's start state, and the number of workgroups;
 //   k_plan_place   one workgroup per run: one lane walks the run from its start state (workgroup, first group of every
 //                  block, in LDS), then all lanes write the group descriptors.
-constexpr int kPackMaxBlk = 96 * 1024, kPackRuns = 256, kPackPerMax = kPackMaxBlk / kPackRuns;
+constexpr int kPackMaxBlk = 96 * 1024, kPackPerMax = 2 * kPackMaxBlk / kPackRuns;   // (two classes: 128 runs over the blocks of each)
 __device__ inline int pack_groups_of(int cnt, int gpw) {
     int ng = max(1, (cnt + kChunk - 1) / kChunk);
     if (ng > gpw) { const int chunk = (cnt + gpw - 1) / gpw; ng = (cnt + chunk - 1) / chunk; }
     return ng;
 }
 __global__ __launch_bounds__(128) void k_plan_tab(int nblk, const int* __restrict__ blk_a, const int* __restrict__ blk_b,
-                                                   const int* __restrict__ blk_ptr, int* __restrict__ tab, int gpw) {
+                                                   const int* __restrict__ blk_ptr, int* __restrict__ tab, int gpw,
+                                                   const uint8_t* __restrict__ nz) {
     __shared__ unsigned char ng8[kPackPerMax];
     const int r = blockIdx.x, t = threadIdx.x;
-    const int per = (nblk + kPackRuns - 1) / kPackRuns;
-    const int b0 = min(r * per, nblk), b1 = min(b0 + per, nblk);
+    int cls, b0, b1;
+    pack_run(r, nblk, nz != nullptr, cls, b0, b1);
     for (int x = t; x < b1 - b0; x += 128) {
-        const int kb = b0 + x;
-        ng8[x] = (unsigned char)(blk_a[kb] != blk_b[kb] ? pack_groups_of(blk_ptr[kb + 1] - blk_ptr[kb], gpw) : 0);   // 0 = diagonal block, skipped
+        const int kb = b0 + x;   // 0 = skipped: a diagonal block, or a block of the other class
+        ng8[x] = (unsigned char)(pack_takes(blk_a[kb], blk_b[kb], nz, kb, cls) ? pack_groups_of(blk_ptr[kb + 1] - blk_ptr[kb], gpw) : 0);
     }
     __syncthreads();
     if (t >= 32) return;
@@ -3675,7 +3730,8 @@ __global__ __launch_bounds__(128) void k_plan_tab(int nblk, const int* __restric
     }
     if (t < kGrpPerWG) tab[r * kGrpPerWG + t] = used | (wgs << 8);
 }
-__global__ __launch_bounds__(1024) void k_plan_tabscan(const int* __restrict__ tab, int* __restrict__ start, int* __restrict__ out_n) {
+__global__ __launch_bounds__(1024) void k_plan_tabscan(const int* __restrict__ tab, int* __restrict__ start, int* __restrict__ out_n,
+                                                        int two) {
     __shared__ int tab0[kPackRuns * kGrpPerWG], tab1[kPackRuns * kGrpPerWG];
     const int t = threadIdx.x;
     for (int e = t; e < kPackRuns * kGrpPerWG; e += 1024) tab0[e] = tab[e];
@@ -3700,19 +3756,22 @@ __global__ __launch_bounds__(1024) void k_plan_tabscan(const int* __restrict__ t
     if (t == 0) {
         const int v = src[(kPackRuns - 1) * kGrpPerWG];
         out_n[0] = (v >> 8) + ((v & 0xff) ? 1 : 0);
+        const int w = two ? src[(kPackRuns / 2 - 1) * kGrpPerWG] : v;   // behind the runs of the non-empty blocks
+        out_n[1] = (w >> 8) + ((w & 0xff) ? 1 : 0);
     }
 }
 __global__ __launch_bounds__(128) void k_plan_place(int nblk, const int* __restrict__ blk_a, const int* __restrict__ blk_b,
                                                      const int* __restrict__ blk_ptr, const int* __restrict__ start,
-                                                     int4* __restrict__ grp, int grp_cap_wg, int gpw) {
+                                                     int4* __restrict__ grp, int grp_cap_wg, int gpw,
+                                                     const uint8_t* __restrict__ nz) {
     __shared__ unsigned char ng8[kPackPerMax];
     __shared__ int place[kPackPerMax];
     const int r = blockIdx.x, t = threadIdx.x;
-    const int per = (nblk + kPackRuns - 1) / kPackRuns;
-    const int b0 = min(r * per, nblk), b1 = min(b0 + per, nblk);
+    int cls, b0, b1;
+    pack_run(r, nblk, nz != nullptr, cls, b0, b1);
     for (int x = t; x < b1 - b0; x += 128) {
         const int kb = b0 + x;
-        ng8[x] = (unsigned char)(blk_a[kb] != blk_b[kb] ? pack_groups_of(blk_ptr[kb + 1] - blk_ptr[kb], gpw) : 0);
+        ng8[x] = (unsigned char)(pack_takes(blk_a[kb], blk_b[kb], nz, kb, cls) ? pack_groups_of(blk_ptr[kb + 1] - blk_ptr[kb], gpw) : 0);
     }
     __syncthreads();
     if (t == 0) {
@@ -3755,7 +3814,8 @@ __global__ __launch_bounds__(256) void k_plan_init(int L, int E, int P, const in
                                                     const uint8_t* __restrict__ fixed, int* __restrict__ lm_ptr,
                                                     int* __restrict__ npair, int* __restrict__ idx, int* __restrict__ blk_a,
                                                     int* __restrict__ blk_b, int* __restrict__ blk_odo, size_t ngrp,
-                                                    int4* __restrict__ grp, int b1, int b2, int b3, uint8_t* __restrict__ nz) {
+                                                    int4* __restrict__ grp, int b1, int b2, int b3, uint8_t* __restrict__ nz,
+                                                    uint8_t* __restrict__ cov) {
     const int bx = blockIdx.x;
     if (bx < b1) {   // landmark CSR + pairs per landmark
         const int l = bx * 256 + threadIdx.x;
@@ -3791,6 +3851,7 @@ __global__ __launch_bounds__(256) void k_plan_init(int L, int E, int P, const in
         blk_b[q] = b;
         blk_odo[q] = -1;
         if (nz) nz[q] = 0;   // the block pattern for the solver's order: set by k_plan_odo and k_plan_pairs2
+        if (cov) cov[q] = 0;  // ... and the packing classes (pack_takes), set by the same two
     } else {   // empty group descriptors
         const size_t i = (size_t)(bx - b3) * 256 + threadIdx.x;
         if (i < ngrp) grp[i] = make_int4(-1, 0, 0, 0);
@@ -3799,7 +3860,7 @@ __global__ __launch_bounds__(256) void k_plan_init(int L, int E, int P, const in
 __global__ __launch_bounds__(256) void k_plan_pairs2(int L, int P, const int* __restrict__ lm_ptr, const int* __restrict__ e_kf,
                                                       const uint8_t* __restrict__ fixed, const int* __restrict__ pair_base,
                                                       int* __restrict__ key, int2* __restrict__ st, int cap, int big, int b1,
-                                                      uint8_t* __restrict__ nz) {
+                                                      uint8_t* __restrict__ nz, uint8_t* __restrict__ cov) {
     if ((int)blockIdx.x < b1) {
         const int l = blockIdx.x * 256 + threadIdx.x;
         if (l >= L) return;
@@ -3807,11 +3868,13 @@ __global__ __launch_bounds__(256) void k_plan_pairs2(int L, int P, const int* __
         const int beg = lm_ptr[l], end = lm_ptr[l + 1];
         for (int s = beg; s < end; ++s) {
             const int a = e_kf[s];
-            if (fixed[a]) continue;
+            if (fixed[a] && !cov) continue;
             for (int t = s + 1; t < end; ++t) {
                 const int b = e_kf[t];
-                if (fixed[b] || a == b) continue;
+                if (a == b) continue;
                 const int q = a < b ? blk_index_of(P, a, b) : blk_index_of(P, b, a);
+                if (cov) cov[q] = 1;   // the two key frames share a landmark, fixed or not
+                if (fixed[a] || fixed[b]) continue;
                 key[o] = q;
                 st[o] = a < b ? make_int2(s, t) : make_int2(t, s);
                 if (nz) nz[q] = 1;   // (the same byte from many lanes: any of them may win)
@@ -3864,11 +3927,13 @@ __global__ void k_solver_pads(double* __restrict__ S, int ld, int nsys, const in
 struct HostPlan {
     std::vector<int> lm_ptr, pose_ptr, pose_edges, blk_a, blk_b, blk_odo, pair_i, pair_j;
     std::vector<uint8_t> blk_nz;   // per block of the upper triangle: any contributor pair or an odometry edge (solve_plan_choose)
+    std::vector<uint8_t> blk_cov;  // ... its key frames share a landmark (fixed or not) or an odometry edge: the packing classes
     std::vector<int4> grp;
-    int nwg_off = 0;
+    int nwg_off = 0, nwg_real = 0;   // workgroups | those that hold a group of a non-empty block (empty_last; = nwg_off without)
 };
+// empty_last: the packing order of pack_takes - the blocks with blk_cov first, the empty ones behind them
 void ba_plan_host(int P, int L, int E, const int* e_kf, const int* e_lm, const uint8_t* fx, int O, const int* o_i,
-                  const int* o_j, bool odo_ok, HostPlan& pl, int gpw = kGrpPerWG) {
+                  const int* o_j, bool odo_ok, HostPlan& pl, int gpw = kGrpPerWG, bool empty_last = false) {
     pl.lm_ptr.assign(L + 1, 0);
     for (int s = 0; s < E; ++s) pl.lm_ptr[e_lm[s] + 1]++;
     for (int l = 0; l < L; ++l) pl.lm_ptr[l + 1] += pl.lm_ptr[l];
@@ -3898,14 +3963,16 @@ void ba_plan_host(int P, int L, int E, const int* e_kf, const int* e_lm, const u
     std::vector<int2> pst;
     pkey.reserve(4 * (size_t)E);
     pst.reserve(4 * (size_t)E);
+    pl.blk_cov.assign(nblk, 0);
     for (int l = 0; l < L; ++l)
         for (int s = lm_ptr[l]; s < lm_ptr[l + 1]; ++s) {
             const int a = e_kf[s];
-            if (fx[a]) continue;
             for (int t = s + 1; t < lm_ptr[l + 1]; ++t) {
                 const int b = e_kf[t];
-                if (fx[b] || a == b) continue;
+                if (a == b) continue;
                 const int q = a < b ? blk_index_of(P, a, b) : blk_index_of(P, b, a);
+                pl.blk_cov[q] = 1;
+                if (fx[a] || fx[b]) continue;
                 pkey.push_back(q);
                 pst.push_back(a < b ? make_int2(s, t) : make_int2(t, s));
                 blk_ptr[q + 1]++;
@@ -3931,7 +3998,9 @@ void ba_plan_host(int P, int L, int E, const int* e_kf, const int* e_lm, const u
         }
     pl.blk_nz.resize(nblk);
     for (int q = 0; q < nblk; ++q) pl.blk_nz[q] = (blk_ptr[q + 1] > blk_ptr[q] || pl.blk_odo[q] >= 0) ? 1 : 0;
-    for (int k = 0; k < O; ++k) pl.blk_nz[blk_index_of(P, std::min(o_i[k], o_j[k]), std::max(o_i[k], o_j[k]))] = 1;
+    for (int k = 0; k < O; ++k)
+        pl.blk_nz[blk_index_of(P, std::min(o_i[k], o_j[k]), std::max(o_i[k], o_j[k]))] =
+            pl.blk_cov[blk_index_of(P, std::min(o_i[k], o_j[k]), std::max(o_i[k], o_j[k]))] = 1;
     // pack 16-pair chunks of the off-diagonal blocks into workgroups of 28 nine-lane groups
     std::vector<int4>& grp = pl.grp;
     grp.clear();
@@ -3940,24 +4009,29 @@ void ba_plan_host(int P, int L, int E, const int* e_kf, const int* e_lm, const u
         while (used % gpw) { grp.push_back(make_int4(-1, 0, 0, 0)); ++used; }
         used = 0;
     };
-    for (int kb = 0; kb < nblk; ++kb) {
-        if (pl.blk_a[kb] == pl.blk_b[kb]) continue;
-        const int q0 = blk_ptr[kb], q1 = blk_ptr[kb + 1];
-        int chunk = kChunk;
-        int ng = std::max(1, (q1 - q0 + chunk - 1) / chunk);
-        if (ng > gpw) { chunk = (q1 - q0 + gpw - 1) / gpw; ng = (q1 - q0 + chunk - 1) / chunk; }
-        if (used + ng > gpw) flush();
-        const int first = used;
-        for (int t = 0; t < ng; ++t) {
-            const int a0 = q0 + t * chunk, a1 = std::min(q1, a0 + chunk);
-            grp.push_back(make_int4(kb, a0, std::max(a0, a1), first | (ng << 8)));
-            ++used;
+    const uint8_t* nz = empty_last ? pl.blk_cov.data() : nullptr;
+    for (int cls = 0; cls < (empty_last ? 2 : 1); ++cls) {
+        for (int kb = 0; kb < nblk; ++kb) {
+            if (!pack_takes(pl.blk_a[kb], pl.blk_b[kb], nz, kb, cls)) continue;
+            const int q0 = blk_ptr[kb], q1 = blk_ptr[kb + 1];
+            int chunk = kChunk;
+            int ng = std::max(1, (q1 - q0 + chunk - 1) / chunk);
+            if (ng > gpw) { chunk = (q1 - q0 + gpw - 1) / gpw; ng = (q1 - q0 + chunk - 1) / chunk; }
+            if (used + ng > gpw) flush();
+            const int first = used;
+            for (int t = 0; t < ng; ++t) {
+                const int a0 = q0 + t * chunk, a1 = std::min(q1, a0 + chunk);
+                grp.push_back(make_int4(kb, a0, std::max(a0, a1), first | (ng << 8)));
+                ++used;
+            }
+            if (used == gpw) used = 0;
         }
-        if (used == gpw) used = 0;
+        if (cls == 0) pl.nwg_real = (int)((grp.size() + gpw - 1) / gpw);   // (the workgroup at the boundary may be mixed)
     }
     flush();
     if (grp.empty()) grp.assign(gpw, make_int4(-1, 0, 0, 0));
     pl.nwg_off = (int)(grp.size() / gpw);
+    if (!empty_last) pl.nwg_real = pl.nwg_off;
 }
 
 // =============================================================================================
@@ -4207,6 +4281,9 @@ int ba_allreduce(se2gpu_ba* h, double* ptr, size_t count);
 // sharded runs) walk grp -> blk_* / pair_* -> W and, behind the barrier, o_i / o_j as before.  (The diagonal workgroups are the
 // same in both forms.)  Read per initialize: a handle keeps the form its plan was built with.
 bool ba_env_reduce_flat() { return env_flag("SE2GPU_BA_REDUCE_FLAT", true); }
+// SE2GPU_BA_REDUCE_EMPTY=0: the plan packs the off-diagonal blocks in block order and every reduction launches all of their
+// workgroups, as before the empty blocks were packed last (pack_takes, reduce2_split).  Read per initialize, like the switch above.
+bool ba_env_reduce_empty() { return env_flag("SE2GPU_BA_REDUCE_EMPTY", true); }
 
 int ba_upload_graph(se2gpu_ba* h) {
     static const bool trace = env_flag("SE2GPU_BA_INIT_TRACE", false);
@@ -4355,11 +4432,14 @@ int ba_upload_graph(se2gpu_ba* h) {
     const int nblk = P * (P + 1) / 2;
     h->nblk = nblk;
     const bool device_plan = P <= 1024 && !env_is("SE2GPU_BA_PLAN", "host");
+    // (a sharded rank sees its own landmarks' pairs only and the in-place all-reduce fills its empty blocks: it keeps block order)
+    h->reduce_empty = h->model == 0 && !h->allreduce && !h->comm && ba_env_reduce_empty();
     lap("edge check + odometry");
     HostPlan pl;
     if (!device_plan) {
-        ba_plan_host(P, L, E, e_kf, e_lm, h->h_fixed.data(), O, o_i.data(), o_j.data(), !h->odo_fallback, pl, gpw);
+        ba_plan_host(P, L, E, e_kf, e_lm, h->h_fixed.data(), O, o_i.data(), o_j.data(), !h->odo_fallback, pl, gpw, h->reduce_empty);
         h->nwg_off = pl.nwg_off;
+        h->nwg_real = pl.nwg_real;
         lap("host plan");
     }
     hipStream_t st = h->stream;
@@ -4592,6 +4672,11 @@ int ba_upload_graph(se2gpu_ba* h) {
             SE2_CHECK(h->h_plan_nz.reserve((size_t)nblk));
             nzp = h->plan_nz.p;
         }
+        uint8_t* nz_pack = nullptr;   // ... and the packing classes, by the same two kernels
+        if (h->reduce_empty) {
+            SE2_CHECK(h->plan_cov.reserve((size_t)nblk));
+            nz_pack = h->plan_cov.p;
+        }
         // landmark CSR + pairs per landmark | edge indices | block table | empty group descriptors
         {
             const int g1 = (int)grid1((size_t)L + 1, 256).x, g2 = (int)grid1(E, 256).x, g3 = (int)grid1((size_t)P * P, 256).x;
@@ -4599,12 +4684,12 @@ int ba_upload_graph(se2gpu_ba* h) {
             const int g4 = (int)grid1(ngrp, 256).x;
             hipLaunchKernelGGL(k_plan_init, dim3(g1 + g2 + g3 + g4), dim3(256), 0, st, L, E, P, h->e_lm.p, h->e_kf.p, h->fixed.p,
                                h->lm_ptr.p, h->plan_np.p, h->plan_idx.p, h->blk_a.p, h->blk_b.p, h->blk_odo.p, ngrp, h->grp.p,
-                               g1, g1 + g2, g1 + g2 + g3, nzp);
+                               g1, g1 + g2, g1 + g2 + g3, nzp, nz_pack);
         }
         hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, st, h->plan_np.p, h->plan_base.p, L);   // 20 per thread
-        if (O && (!h->odo_fallback || nzp))
+        if (O && (!h->odo_fallback || nzp || nz_pack))
             hipLaunchKernelGGL(k_plan_odo, grid1(O, 64), dim3(64), 0, st, P, O, h->o_i.p, h->o_j.p,
-                               h->odo_fallback ? nullptr : h->blk_odo.p, nzp);
+                               h->odo_fallback ? nullptr : h->blk_odo.p, nzp, nz_pack);
         // pose -> edges CSR: edge indices stably sorted by key frame (one pass)
         if (E) SE2_CHECK(radix(h->e_kf.p, h->plan_key0.p, h->plan_idx.p, h->pose_edges.p, (size_t)E, 0, Pb));
         hipLaunchKernelGGL(k_lower_bounds, grid1((size_t)P + 1, 256), dim3(256), 0, st, h->plan_key0.p, E, P, h->pose_ptr.p);
@@ -4614,7 +4699,7 @@ int ba_upload_graph(se2gpu_ba* h) {
         {
             const int g1 = (int)grid1(L, 256).x, g2 = (int)grid1(NP, 256).x;
             hipLaunchKernelGGL(k_plan_pairs2, dim3(g1 + g2), dim3(256), 0, st, L, P, h->lm_ptr.p, h->e_kf.p, h->fixed.p,
-                               h->plan_base.p, h->plan_key0.p, h->plan_st0.p, (int)NP, nblk, g1, nzp);
+                               h->plan_base.p, h->plan_key0.p, h->plan_st0.p, (int)NP, nblk, g1, nzp, nz_pack);
         }
         if (nd_possible) {   // the pattern goes home now: the host chooses the solver's order while the device sorts the pairs
             if (nd_sharded) {   // the union of the ranks' patterns: widen to doubles, the run's all-reduce, narrow again
@@ -4639,17 +4724,18 @@ int ba_upload_graph(se2gpu_ba* h) {
             SE2_CHECK(h->plan_place.reserve((size_t)kPackRuns * (kGrpPerWG + 1)));   // the runs' tables, then their start states
             int* tab = h->plan_place.p;
             int* start = tab + kPackRuns * kGrpPerWG;
-            hipLaunchKernelGGL(k_plan_tab, dim3(kPackRuns), dim3(128), 0, st, nblk, h->blk_a.p, h->blk_b.p, h->blk_ptr.p, tab, gpw);
-            hipLaunchKernelGGL(k_plan_tabscan, dim3(1), dim3(1024), 0, st, tab, start, h->plan_out.p);
+            hipLaunchKernelGGL(k_plan_tab, dim3(kPackRuns), dim3(128), 0, st, nblk, h->blk_a.p, h->blk_b.p, h->blk_ptr.p, tab, gpw,
+                               nz_pack);
+            hipLaunchKernelGGL(k_plan_tabscan, dim3(1), dim3(1024), 0, st, tab, start, h->plan_out.p, nz_pack ? 1 : 0);
             hipLaunchKernelGGL(k_plan_place, dim3(kPackRuns), dim3(128), 0, st, nblk, h->blk_a.p, h->blk_b.p, h->blk_ptr.p, start,
-                               h->grp.p, cap_wg, gpw);
+                               h->grp.p, cap_wg, gpw, nz_pack);
         } else {
             hipLaunchKernelGGL(k_plan_pack, dim3(1), dim3(256), 0, st, nblk, h->blk_a.p, h->blk_b.p, h->blk_ptr.p, h->grp.p,
-                               cap_wg, h->plan_out.p, gpw);
+                               cap_wg, h->plan_out.p, gpw, nz_pack);
         }
         SE2_HIP(hipGetLastError());
         SE2_CHECK(h->h_scal.reserve(8 + (size_t)h->world));
-        SE2_HIP(hipMemcpyAsync(h->h_scal.p, h->plan_out.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        SE2_HIP(hipMemcpyAsync(h->h_scal.p, h->plan_out.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
         lap("plan kernels enqueued");
     }
     // measurements and information matrices (with a local graph the information is evaluated on the device: big_end stops in
@@ -4744,6 +4830,9 @@ int ba_upload_graph(se2gpu_ba* h) {
             h->h_pose_off.clear();
             h->pose_off.release();
             h->col_src.release();
+            // rows 0 .. n - 1 of S start from zero here too: a reduction that leaves the empty blocks' workgroups out
+            // (reduce2_split) relies on it, also on a handle that was cleared and loaded again with another pattern
+            SE2_HIP(hipMemsetAsync(h->red, 0, (size_t)n * h->ld * sizeof(double), st));
         }
         const int nt2 = h->ld / kNB, nbc2 = (h->nsys + kNB - 1) / kNB;
         SE2_CHECK(h->chol_flags.reserve(2 * kSlabs * (size_t)nt2 * nbc2));
@@ -4767,15 +4856,23 @@ int ba_upload_graph(se2gpu_ba* h) {
     }
     SE2_HIP(hipStreamSynchronize(st));
     if (device_plan) {
-        int nwg = 0;
-        std::memcpy(&nwg, h->h_scal.p, sizeof(int));
-        SE2_REQUIRE(nwg <= h->grp_cap_wg, SE2GPU_ERR_CAPACITY, "device plan: %d workgroups exceed the bound %d", nwg, h->grp_cap_wg);
-        h->nwg_off = std::max(nwg, 1);
+        int nwg[2] = {0, 0};   // all | those of the non-empty blocks
+        std::memcpy(nwg, h->h_scal.p, sizeof(nwg));
+        SE2_REQUIRE(nwg[0] <= h->grp_cap_wg, SE2GPU_ERR_CAPACITY, "device plan: %d workgroups exceed the bound %d", nwg[0], h->grp_cap_wg);
+        h->nwg_off = std::max(nwg[0], 1);
+        h->nwg_real = h->reduce_empty ? nwg[1] : h->nwg_off;
     }
     lap("synchronise");
     // ---- k_reduce2's flat records: behind the packing (the device plan's workgroup count is known now), the measurements and
     // the solver's order (pose_off); every initialize rebuilds them with the plan
     h->flat_on = h->model == 0 && ba_env_reduce_flat();
+    if (h->reduce_empty && h->nwg_real < h->nwg_off) {   // the empty blocks behind the workgroups that are always launched: once
+        const int first = h->nwg_real * gpw, nslots = (h->nwg_off - h->nwg_real) * gpw;
+        hipLaunchKernelGGL(k_plan_empty_blocks, grid1((size_t)nslots * 9, 256), dim3(256), 0, st, first, nslots, h->grp.p, h->blk_a.p,
+                           h->blk_b.p, h->fixed.p, (const int*)h->pose_off.p, h->red, h->ld);
+        SE2_HIP(hipGetLastError());
+        if (!h->flat_on) SE2_HIP(hipStreamSynchronize(st));
+    }
     if (h->flat_on) {
         const size_t slots = (size_t)h->nwg_off * gpw;
         SE2_CHECK(h->grp_flat.reserve(slots * kFlatQ));
@@ -4885,7 +4982,26 @@ int ba_reserve_twin(se2gpu_ba* h) { return h->rec_twin.reserve(21 * (size_t)h->E
 // estimate buffer, lambda and the record set from its block; `alt` = the twin record set (rec_twin) or RecSet{}.
 inline double* ba_scal(se2gpu_ba* h) { return h->red + (size_t)h->ld * h->ld; }   // 4 trailing scalars of the fused buffer
 inline dim3 upd_grid(const se2gpu_ba* h) { return grid1((size_t)h->L * kGroup, kBlock); }   // landmark workgroups of k_linearize / k_update
-inline dim3 reduce2_grid(const se2gpu_ba* h) { return dim3(((h->P + 1 + 7) & ~7) + ((h->nwg_off + 7) & ~7)); }
+// The off-diagonal workgroups of a reduction: {in the XCD-contiguous order, tail}.  Read per launch from the handle's CURRENT state.
+// A plan with the empty blocks packed last (reduce_empty) launches only the nwg_real workgroups in front of them where S keeps
+// the zeros `initialize` left in those blocks from one reduction to the next.  Who writes into S besides k_reduce2 - whose
+// off-diagonal part stores nothing outside its groups' blocks - and k_reduce_odo (blocks with an edge: never empty):
+//   k_chol_step    factorises S in place (SE2GPU_BA_CHOL=steps, more than 64 tile rows, and from a time-out of k_chol_tiles on
+//                  for the rest of the handle's life: chol_steps is set there, the graphs are dropped, and the next reduction -
+//                  the redone trial's - comes through here and rewrites every block before the first k_chol_step reads S)
+//   the all-reduce sums the other ranks' blocks into this rank's empty ones in place (allreduce / comm, a caller's ar_buffer)
+// Those launch the tail every time.  k_chol_tiles and k_chol_apply take S as const, the host solve copies it out, the 6-DoF
+// kernels (k3_reduce2) have plans in block order and launch everything.
+struct Reduce2Split { int nwg_off, nwg_tail; };
+inline Reduce2Split reduce2_split(const se2gpu_ba* h) {
+    if (!h->reduce_empty) return Reduce2Split{h->nwg_off, 0};
+    const bool s_keeps_zeros = !h->chol_steps && !h->allreduce && !h->comm && !h->ar_buffer;
+    return Reduce2Split{h->nwg_real, s_keeps_zeros ? 0 : h->nwg_off - h->nwg_real};
+}
+inline dim3 reduce2_grid(const se2gpu_ba* h) {
+    const Reduce2Split sp = reduce2_split(h);
+    return dim3(((h->P + 1 + 7) & ~7) + ((sp.nwg_off + 7) & ~7) + sp.nwg_tail);
+}
 LinArgs lin_args(se2gpu_ba* h, const Bufs& B, double lambda, const RecSet& alt) {
     return LinArgs{h->cam, h->L, h->lm_ptr.p, h->e_kf.p, h->e_uv.p, h->e_info.p, B.pa, h->fixed.p, B.la, h->Hpl.p, h->Hpp_e.p,
                    h->bp_e.p, h->Hll.p, h->bl.p, lambda, h->Dinv.p, h->z.p, h->Dg.p, B.c, B.pb, B.lb, alt};
@@ -4905,7 +5021,8 @@ MaxdiagArgs maxdiag_args(se2gpu_ba* h, int dpp, int stride9, BaCtl* ctl) {
     return MaxdiagArgs{h->L, h->Hll.p, h->P, stride9 ? h->Hpp.p : h->diag3.p, h->fixed.p, h->scal.p, dpp, stride9, ctl};
 }
 Reduce2Args reduce2_args(se2gpu_ba* h, const Bufs& B, double lambda, const RecSet& alt) {
-    return Reduce2Args{h->P, h->ld, h->nwg_off, lambda, h->root, h->grp.p, h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p,
+    const Reduce2Split sp = reduce2_split(h);
+    return Reduce2Args{h->P, h->ld, sp.nwg_off, sp.nwg_tail, lambda, h->root, h->grp.p, h->blk_a.p, h->blk_b.p, h->pair_i.p, h->pair_j.p,
                        h->blk_odo.p, h->Hpl.p, h->Dg.p, h->fixed.p, h->pose_ptr.p, h->pose_edges.p, h->podo_ptr.p, h->podo_item.p,
                        h->o_i.p, h->o_j.p, h->o_meas.p, h->o_info.p, B.pa, h->red, h->bp.p, B.c, B.pb, &h->ctl.p->epoch,
                        h->pose_off.p, h->nsys, alt.W, alt.Dg, h->flat_on ? h->grp_flat.p : nullptr};
@@ -6362,6 +6479,36 @@ int se2gpu_ba_debug_flat_records(se2gpu_ba* h, int32_t* grp4, int32_t* flat, int
     SE2_HIP(hipStreamSynchronize(h->stream));
     SE2_HIP(hipMemcpy(grp4, h->grp.p, h->flat_slots * sizeof(int4), hipMemcpyDeviceToHost));
     SE2_HIP(hipMemcpy(flat, h->grp_flat.p, h->flat_slots * kFlatQ * sizeof(int4), hipMemcpyDeviceToHost));
+    return SE2GPU_OK;
+}
+
+// {off-diagonal workgroups of the plan, those that hold a group of a non-empty block, those the next reduction launches}
+int se2gpu_ba_debug_reduce_grid(const se2gpu_ba* h, int out[3]) {
+    SE2_REQUIRE(h && h->initialized && out, SE2GPU_ERR_STATE, "debug_reduce_grid before initialize");
+    const Reduce2Split sp = reduce2_split(h);
+    out[0] = h->nwg_off; out[1] = h->nwg_real; out[2] = sp.nwg_off + sp.nwg_tail;
+    return SE2GPU_OK;
+}
+// The host builder's packing (ba_plan_host) of a graph whose edges are sorted by landmark, without a device: the group
+// descriptors (cap_slots * 4 ints, may be NULL) and {group slots, workgroups, workgroups of the non-empty blocks}.
+// empty_last: the order of SE2GPU_BA_REDUCE_EMPTY; odo_ok = 0: the edges stay out of the block plan (odo_fallback)
+int se2gpu_ba_debug_plan_host(int P, int L, int E, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* fixed, int O,
+                              const int32_t* o_i, const int32_t* o_j, int odo_ok, int empty_last, int32_t* grp4, int cap_slots,
+                              int out[3]) {
+    SE2_REQUIRE(P > 0 && L >= 0 && E >= 0 && O >= 0 && fixed && out && (!E || (e_kf && e_lm)) && (!O || (o_i && o_j)),
+                SE2GPU_ERR_INVALID, "debug_plan_host: bad argument");
+    for (int k = 0; k < E; ++k)
+        SE2_REQUIRE((unsigned)e_kf[k] < (unsigned)P && (unsigned)e_lm[k] < (unsigned)L && (!k || e_lm[k] >= e_lm[k - 1]),
+                    SE2GPU_ERR_INVALID, "debug_plan_host: edge %d out of range or out of order", k);
+    for (int k = 0; k < O; ++k)
+        SE2_REQUIRE((unsigned)o_i[k] < (unsigned)P && (unsigned)o_j[k] < (unsigned)P, SE2GPU_ERR_INVALID, "debug_plan_host: edge %d", k);
+    HostPlan pl;
+    ba_plan_host(P, L, E, e_kf, e_lm, fixed, O, o_i, o_j, odo_ok != 0, pl, kGrpPerWG, empty_last != 0);
+    out[0] = (int)pl.grp.size(); out[1] = pl.nwg_off; out[2] = pl.nwg_real;
+    if (grp4) {
+        SE2_REQUIRE(cap_slots >= out[0], SE2GPU_ERR_CAPACITY, "debug_plan_host: %d slots", out[0]);
+        std::memcpy(grp4, pl.grp.data(), pl.grp.size() * sizeof(int4));
+    }
     return SE2GPU_OK;
 }
 
