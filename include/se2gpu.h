@@ -425,7 +425,8 @@ int se2gpu_kf_correspd_batch_device(se2gpu_matcher* h,
  *   d_common[3 (p * list_cap + i)..] = {point, e_a, e_b} for the first list_cap common points in ascending point index - the
  *   spMPs GlobalMapper::CreateFeatEdge turns into vPtrMPs (GlobalMapper.cpp:741-750).  e_a / e_b are the CSR entry indices of
  *   the first valid entry of frames a / b in that point's list (-1 if the CSR no longer holds one): gather mp_xyz, m_z and
- *   m_info for se2gpu_feat_edge_batch from d_obs_view / d_obs_info with them.  Truncation shows as n_same > list_cap; entries
+ *   m_info for se2gpu_feat_edge_batch from d_obs_view / d_obs_info with them, or hand d_pair_out and d_common to
+ *   se2gpu_feat_edge_batch_device, which does that on the device.  Truncation shows as n_same > list_cap; entries
  *   from min(n_same, list_cap) on are left untouched.  The order is fixed by a prefix sum over the wave, without atomics.
  *
  * se2gpu_covis_refset_device: double Map::compareViewMPs(pKFNow, spKFsRef, spMPsRet, k) (:373-400) for njobs jobs, one wave
@@ -659,6 +660,74 @@ int se2gpu_feat_edge_batch(int npairs, int mode, int iters, int min_points,
         int32_t* info4 /* per pair: status, points, outliers, points handed to the sparsifier */,
         se2gpu_ba_stats* stats /* per pair, may be NULL */,
         double* z_out12, double* info_out36);
+
+/* CreateFeatEdge on the tables where they lie in device memory: se2gpu_feat_edge_batch behind a gather kernel, for the pairs of
+ * se2gpu_covis_pairs_device (its d_common) or of se2gpu_track_loop_verify_batch_device (its d_matches_mp).  Every array pointer
+ * is device memory.  Asynchronous on the matcher's stream (five launches, one memset with d_stats): nothing is allocated,
+ * nothing uploaded besides kernel arguments, nothing read back and nothing waited for; se2gpu_matcher_sync waits for it.
+ * mode, iters, min_points, huber_delta, outlier_chi2, xrot_info, yrot_info, z_info as for se2gpu_feat_edge_batch; Tbc12 is a
+ * HOST pointer to 12 doubles, copied into a kernel argument.
+ * Common inputs: d_pair_a / d_pair_b (npairs frame slots: _pKFFrom, _pKFTo); d_frame_Twc (nframes x 12 floats, rows 0-2 of
+ * cvu::inv(Tcw): the table of se2gpu_mappoint_parallax_batch_device; the rows of the 3 x 4 matrix become rotation (9) and
+ * translation (3) of kf12, float -> double exactly, as toIsometry3D does); d_pos (m x 3 floats, MapPoint::getPos(), the array the
+ * parallax call writes); row_cap = the point slots a pair gets in every per-point array: pair p's rows start at p * row_cap.
+ * SE2GPU_FEAT_EDGE_COVIS (GlobalMapper.cpp:741-750, :847-927): d_pair_out (4 ints per pair) and d_common (3 ints per entry,
+ *   list_cap entries per pair) as se2gpu_covis_pairs_device wrote them for the same pair arrays; d_obs_view (nobs x 3 floats),
+ *   d_obs_info (nobs x 9).  Pair p takes the entries i < min(n_same, list_cap, row_cap) in list order (ascending point index,
+ *   the stand-in for the reference's std::set order).  An entry {point, e_a, e_b} is valid when point lies in 0..m-1 and e_a,
+ *   e_b in 0..nobs-1; invalid entries are dropped and the rest compacted in order at the head of the row.  A point's start
+ *   value is d_pos[point], its m_z = d_obs_view[e_a], d_obs_view[e_b], its m_info = d_obs_info[e_a], d_obs_info[e_b].
+ *   raw = n_same.  A pair with n_same < 0 or a slot outside 0..nframes-1 is a pair of no points.
+ *   The match route's arrays are not read and may be NULL.
+ * SE2GPU_FEAT_EDGE_MATCH (:929-1032): d_matches (npairs x cap ints) with d_counts (nframes) and cap in the layout of the verify
+ *   call's d_matches_mp; d_ftr_mp (nframes x cap ints: the map point KeyFrame::getObservation(idx) names, as an index into the
+ *   point table, or -1); d_view_pos (nframes x cap x 3 floats, mViewMPs, the table of se2gpu_kf_correspd_batch_device) and
+ *   d_view_info (nframes x cap x 9, mViewMPsInfo).  Raw matches by the verify call's rule: i < min(counts[a], cap) with a
+ *   value j in 0..min(counts[b], cap)-1, in ascending i (std::map<int,int>); raw = their number (:790 tests it).  A raw match
+ *   becomes a point when d_ftr_mp[a][i] lies in 0..m-1 and d_ftr_mp[b][j] >= 0 (:960-965): start value d_pos[d_ftr_mp[a][i]]
+ *   (:968), m_z / m_info from (a, i) and (b, j) of the two view tables (:971-976).  Points beyond row_cap are cut.  A pair with
+ *   a slot outside 0..nframes-1 has no matches.  The reference indexes vIdMPin1 by the match counter and the points by the
+ *   kept-point counter (:956-962 against :1000), so after a skipped match it rejects the wrong points; THE LIBRARY DOES NOT
+ *   REPRODUCE THAT: the outlier flag of a point is the flag of that point.
+ *   The covisibility route's arrays are not read and may be NULL.
+ * A slot out of range gives the identity as that key frame's pose.
+ * Outputs: d_kf12_out (npairs x 24 doubles), d_z_out12 (npairs x 12), d_info_out36 (npairs x 36) as the host call's; optional
+ * (NULL: not wanted) d_mp_xyz_out (npairs x row_cap x 3 doubles), d_outlier (npairs x row_cap bytes), d_edge_chi2 (npairs x
+ * row_cap x 2), whose rows are left untouched from `points` on, and d_stats (per pair);
+ * d_info8[8p..] = {status, points, outliers, points handed to the sparsifier, raw, dropped, cut, 0}: points = the gathered
+ * count; dropped = invalid entries, or raw matches without both points; cut = 1 when list_cap or row_cap truncated the pair.
+ *   status 1  raw < min_points: nothing is run, kf12_out is the input pose, the constraint is zero (outlier / edge_chi2 of
+ *             the gathered points are 0, mp_xyz_out their start values)
+ *   otherwise the pair is optimised on its gathered points, exactly as se2gpu_feat_edge_batch does with those rows and a
+ *             min_points that lets them through - a pair whose gather came out empty included
+ *   status 2  a non-finite result or constraint: the constraint is zero
+ * A pair's words depend on that pair alone: no atomics, the same in every run and wherever the pair stands in the batch.
+ * d_ws: se2gpu_feat_edge_ws_bytes(npairs, row_cap) bytes supplied by the caller, 8-byte aligned, no initialisation needed (the
+ * call fills every word it reads).  se2gpu_feat_edge_ws_bytes returns -1 on arguments the call would refuse (npairs < 0 or
+ * >= 65536, row_cap < 1, 2 * npairs * row_cap > 2^31 - 1).  se2gpu_feat_edge_ws_layout writes the byte offsets inside d_ws
+ * of the SE2GPU_FEAT_EDGE_WS_ARRAYS gathered arrays (n >= that many; SE2GPU_ERR_INVALID otherwise or on those arguments):
+ * counts (npairs ints, followed by raw, dropped and cut, npairs ints each), kf12 (npairs x 24 doubles), prior measurement
+ * (npairs x 24), prior information (npairs x 72), start xyz (npairs x row_cap x 3 doubles), m_z (x 6), m_info (x 18) - valid
+ * after the call.  Both helpers are host only and touch no device.
+ * The argument checks come first and touch neither the handle nor a device:
+ * SE2GPU_ERR_INVALID: a NULL handle, Tbc12, common array, d_ws, d_info8, d_kf12_out, d_z_out12, d_info_out36 or array of the
+ *   mode's route; a mode other than the two; iters outside 1..64; npairs, m or nobs < 0; nframes, cap, row_cap or list_cap
+ *   < 1 (the scalars of both routes are checked whatever the mode: a caller of one route passes 0 / 1 / 1 for the other's).
+ * SE2GPU_ERR_CAPACITY: npairs >= 65536; 2 * npairs * row_cap > 2^31 - 1; nframes * cap > 2^31 - 1.
+ * npairs == 0 is SE2GPU_OK and launches nothing. */
+#define SE2GPU_FEAT_EDGE_WS_ARRAYS 7
+long long se2gpu_feat_edge_ws_bytes(int npairs, int row_cap);
+int se2gpu_feat_edge_ws_layout(int npairs, int row_cap, long long* offsets, int n);
+int se2gpu_feat_edge_batch_device(se2gpu_matcher* h, int mode, int iters, int min_points, double huber_delta, double outlier_chi2,
+        const double* Tbc12 /* host */, double xrot_info, double yrot_info, double z_info,
+        const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs, int nframes,
+        const float* d_frame_Twc, const float* d_pos, int m, int row_cap,
+        const int32_t* d_pair_out, const int32_t* d_common, int list_cap,           /* covisibility route */
+        const float* d_obs_view, const float* d_obs_info, int nobs,
+        const int32_t* d_matches, const int32_t* d_counts, int cap,                  /* match route */
+        const int32_t* d_ftr_mp, const float* d_view_pos, const float* d_view_info,
+        void* d_ws, int32_t* d_info8, double* d_kf12_out, double* d_z_out12, double* d_info_out36,
+        double* d_mp_xyz_out, uint8_t* d_outlier, double* d_edge_chi2, se2gpu_ba_stats* d_stats);
 
 /* Map::loadLocalGraph(SlamOptimizer&) (/root/reference/src/Map.cpp:891-1022) as ONE call on a POD view of the local
  * window - SURVEY.md section 8f.1.  The caller flattens its pointer graph once per key frame (INTEGRATION.md shows the

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../se2gpu.h"
+#include "Covisibility.h"
 #include "optimizer.h"
 #include "types.h"
 
@@ -113,5 +114,85 @@ inline void CreateFeatEdgeMatchBatch(const FeatEdgeView& v, const FeatEdgeParams
                                      int iters = kFeatEdgeMatchIters, int minPoints = kFeatEdgeMatchMinPoints) {
     CreateFeatEdgeBatch(v, SE2GPU_FEAT_EDGE_MATCH, iters, minPoints, par, out);
 }
+
+// ---- The same two calls on the tables where they lie in device memory (se2gpu_feat_edge_batch_device): the outputs of
+// CovisibilityTable::pairsBatchDevice or LoopVerifier::VerifyBatchDevice go in as they are, nothing passes through the host.
+// Where each field comes from in the reference:
+//   pairA[p], pairB[p]  the frame slots of _pKFFrom / _pKFTo                                                       :737, :781
+//   frameTwc            per slot rows 0-2 of cvu::inv(pKF->getPose()) in float, the table of the parallax call; the gather
+//                       turns a row into toIsometry3D's rotation and translation                                   :860-861, :940-946
+//   pos                 MapPoint::getPos() per point slot (float, as the parallax call writes it)                  :877, :968
+//   covisibility form:  CovisPair / CovisCommon of compareViewMPs(_pKFFrom, _pKFTo, spMPs) - the set becomes vPtrMPs in
+//                       ascending point index                                                                     :741-750
+//                       obsView / obsInfo: pKF->mViewMPs[idx] / mViewMPsInfo[idx] per CSR entry, the arrays the parallax
+//                       call writes                                                                               :898-899
+//   match form:         matchesMP = _mapMatchMP as VerifyBatchDevice leaves it: feature i of key frame a -> feature of b
+//                       or -1, walked in ascending i (std::map<int,int>)                                          :790, :956
+//                       ftrMP[f][idx] = the point slot of pKF->getObservation(idx), -1 without one                :957-965
+//                       viewPos / viewInfo: pKF->mViewMPs[idx] / mViewMPsInfo[idx] per feature                    :971-976
+// The reference indexes vIdMPin1 by the match counter and the points by the kept-point counter (:956-962 against :1000); this
+// library does not reproduce that: a point's outlier flag is that point's.
+// d_info8 per pair: FeatEdgeDeviceInfo.  rowCap = the point slots of a pair in the per-point outputs (mpXyz, outlier,
+// edgeChi2: may be null).  ws: wsBytes() bytes of device memory, no initialisation.  Asynchronous on the matcher's stream.
+struct FeatEdgeDeviceInfo {
+    int32_t status, nPoints, nOutliers, nSparsified;   // as FeatEdgeResult
+    int32_t nRaw;        // spMPs.size() / mapMatch.size(): what minPoints is tested against                        :747, :790
+    int32_t nDropped;    // entries with an index out of range / matches without both map points
+    int32_t cut;         // 1: listCap or rowCap truncated the pair
+    int32_t reserved;
+};
+static_assert(sizeof(FeatEdgeDeviceInfo) == 32, "the 8 ints of the C ABI");
+
+struct FeatEdgeDeviceTable {
+    int nframes = 0, M = 0, rowCap = 0;
+    const float* frameTwc = nullptr;        // nframes x 12
+    const float* pos = nullptr;             // M x 3
+    // covisibility form
+    int nobs = 0;
+    const float* obsView = nullptr;         // nobs x 3
+    const float* obsInfo = nullptr;         // nobs x 9
+    // match form
+    int cap = 1;
+    const int32_t* counts = nullptr;        // nframes
+    const int32_t* ftrMP = nullptr;         // nframes x cap
+    const float* viewPos = nullptr;         // nframes x cap x 3
+    const float* viewInfo = nullptr;        // nframes x cap x 9
+    // work space and outputs (device memory, the caller's)
+    void* ws = nullptr;
+    FeatEdgeDeviceInfo* info = nullptr;     // npairs
+    double* kf12 = nullptr;                 // npairs x 24
+    double* z12 = nullptr;                  // npairs x 12
+    double* info36 = nullptr;               // npairs x 36
+    double* mpXyz = nullptr;                // npairs x rowCap x 3, may be null
+    uint8_t* outlier = nullptr;             // npairs x rowCap, may be null
+    double* edgeChi2 = nullptr;             // npairs x rowCap x 2, may be null
+    se2gpu_ba_stats* stats = nullptr;       // npairs, may be null
+
+    long long wsBytes(int npairs) const { return se2gpu_feat_edge_ws_bytes(npairs, rowCap); }
+
+    // CreateFeatEdge(pKFFrom, pKFTo, SE3CnstrOutput) for the pairs CovisibilityTable::pairsBatchDevice was given
+    void CreateFeatEdgeCovisBatchDevice(ORBmatcher& matcher, const int32_t* pairA, const int32_t* pairB, int npairs,
+                                        const CovisPair* pairOut, const CovisCommon* common, int listCap, const FeatEdgeParams& par,
+                                        int iters = kFeatEdgeCovisIters, int minPoints = kFeatEdgeCovisMinPoints) {
+        check(se2gpu_feat_edge_batch_device(matcher.handle(), SE2GPU_FEAT_EDGE_COVIS, iters, minPoints, par.huberDelta, par.outlierChi2,
+                                            par.Tbc12, par.xrotInfo, par.yrotInfo, par.zInfo, pairA, pairB, npairs, nframes, frameTwc,
+                                            pos, M, rowCap, reinterpret_cast<const int32_t*>(pairOut),
+                                            reinterpret_cast<const int32_t*>(common), listCap, obsView, obsInfo, nobs, nullptr, nullptr,
+                                            cap, nullptr, nullptr, nullptr, ws, reinterpret_cast<int32_t*>(info), kf12, z12, info36,
+                                            mpXyz, outlier, edgeChi2, stats),
+              "FeatEdgeDeviceTable::CreateFeatEdgeCovisBatchDevice");
+    }
+    // CreateFeatEdge(pKFFrom, pKFTo, mapMatch, SE3CnstrOutput) for the pairs LoopVerifier::VerifyBatchDevice was given
+    void CreateFeatEdgeMatchBatchDevice(ORBmatcher& matcher, const int32_t* pairA, const int32_t* pairB, int npairs,
+                                        const int32_t* matchesMP, const FeatEdgeParams& par, int iters = kFeatEdgeMatchIters,
+                                        int minPoints = kFeatEdgeMatchMinPoints) {
+        check(se2gpu_feat_edge_batch_device(matcher.handle(), SE2GPU_FEAT_EDGE_MATCH, iters, minPoints, par.huberDelta, par.outlierChi2,
+                                            par.Tbc12, par.xrotInfo, par.yrotInfo, par.zInfo, pairA, pairB, npairs, nframes, frameTwc,
+                                            pos, M, rowCap, nullptr, nullptr, 1, nullptr, nullptr, nobs, matchesMP, counts, cap, ftrMP,
+                                            viewPos, viewInfo, ws, reinterpret_cast<int32_t*>(info), kf12, z12, info36, mpXyz, outlier,
+                                            edgeChi2, stats),
+              "FeatEdgeDeviceTable::CreateFeatEdgeMatchBatchDevice");
+    }
+};
 
 }  // namespace se2lam_amd

@@ -35,6 +35,7 @@ PER_FILE = {
     "new_kf.hip": ["-ffp-contract=off"],     # view_info.h: float arithmetic in the reference's order, equal to the host mirror's
     "covis.hip": ["-ffp-contract=off"],      # the ratios and threshold tests are single IEEE operations, as in the reference
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
+    "feat_edge_device.hip": ["-ffp-contract=off"],   # the plane-motion prior's information equals the host function's to the bit
 }
 
 

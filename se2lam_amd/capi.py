@@ -187,6 +187,11 @@ SYMBOLS = {
     "se2gpu_sparsify_se3xyz": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "se2gpu_feat_edge_batch": (_I, [_I, _I, _I, _I, _VP, _VP, _D, _D, _D, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP,
                                     _VP, _VP, _VP]),
+    "se2gpu_feat_edge_ws_bytes": (C.c_longlong, [_I, _I]),
+    "se2gpu_feat_edge_ws_layout": (_I, [_I, _I, _VP, _I]),
+    "se2gpu_feat_edge_batch_device": (_I, [_VP, _I, _I, _I, _D, _D, _VP, _D, _D, _D, _VP, _VP, _I, _I, _VP, _VP, _I, _I,
+                                           _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP,
+                                           _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "se2gpu_ba_initialize": (_I, [_VP]),
     "se2gpu_ba_set_edge_level": (_I, [_VP, _I, _I]),
     "se2gpu_ba_reset_estimates": (_I, [_VP]),

@@ -6021,33 +6021,7 @@ int se2gpu_ba_add_vertex_iso3(se2gpu_ba* h, int id, const double pose12[12], int
 int se2gpu_plane_motion_prior_iso3(const double* Twc12, const double* Tbc12, double xrot_info, double yrot_info,
                                    double z_info, double* meas12, double* info36) {
     SE2_REQUIRE(Twc12 && Tbc12 && meas12 && info36, SE2GPU_ERR_INVALID, "plane_motion_prior_iso3: NULL argument");
-    const Se3 Twc = se3_load(Twc12), Tbc = se3_load(Tbc12);
-    Se3 Twb = iso_mul(Twc, se3_inv(Tbc));
-    double q[4];
-    quat_of(Twb.R, q);
-    const double nv = std::sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    double yaw = 0;
-    if (nv > 0) yaw = 2 * std::atan2(nv, q[0]) * q[3] / nv;    // z component of the rotation vector (Eigen::AngleAxisd)
-    const double qz[4] = {std::cos(0.5 * yaw), 0, 0, std::sin(0.5 * yaw)};
-    mat_of_quat(qz, Twb.R);
-    Twb.t[2] = 0;
-    se3_store(iso_mul(Twb, Tbc), meas12);
-    double A[36] = {0}, sk[9], sR[9];
-    skew3(Tbc.t, sk);
-    mat3_mul(sk, Tbc.R, sR);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            A[6 * i + j] = Tbc.R[3 * i + j];
-            A[6 * (i + 3) + (j + 3)] = Tbc.R[3 * i + j];
-            A[6 * i + (j + 3)] = sR[3 * i + j];
-        }
-    const double D[6] = {1e-4, 1e-4, z_info, xrot_info, yrot_info, 1e-4};
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double v = 0;
-            for (int k = 0; k < 6; ++k) v += A[6 * k + i] * D[k] * A[6 * k + j];
-            info36[6 * i + j] = v;
-        }
+    plane_motion_prior_iso3(Twc12, Tbc12, xrot_info, yrot_info, z_info, meas12, info36);   // se3_math.h, shared with the device
     return SE2GPU_OK;
 }
 

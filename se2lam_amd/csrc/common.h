@@ -27,6 +27,33 @@ int comm_world(const se2gpu_comm* c);
 int launch_sparsify(hipStream_t stream, int npairs, const double* d_kf12, const int* d_mp_ptr, const double* d_mp_xyz,
                     const int* d_mm_ptr, const int* d_m_kf, const double* d_m_info, const int* d_ord_ptr, const int* d_ord,
                     double* d_kf_blk, double* d_schur, const int* d_mp_cnt, double* d_z_out, double* d_info_out);
+// k_feat_edge (feat_edge.hip) on device arrays, on `stream`: one wave per pair, what se2gpu_feat_edge_batch launches after
+// its uploads.  Pair p's points are the rows [mp_ptr[p], mp_ptr[p+1]) of every per-point array.
+struct FeatEdgeArgs {
+    int npairs, mode, iters, min_points;
+    const double* kf12;         // npairs x 2 x 12
+    const double* prior_meas;   // npairs x 2 x 12
+    const double* prior_info;   // npairs x 2 x 36
+    const int* mp_ptr;
+    const int* mp_cnt;          // optional: only the first mp_cnt[p] rows of pair p count (rows with slack, feat_edge_device.hip)
+    const int* raw_cnt;         // optional: the count min_points is tested against, instead of the number of points
+    const double* m_z;          // per point 2 x 3
+    const double* m_info;       // per point 2 x 9
+    double huber_delta, outlier_chi2;
+    double* pa;                 // the points: the start values on entry; pa / pb alternate as estimate and trial
+    double* pb;
+    double* kf12_out;
+    double* mp_out;
+    uint8_t* outlier;
+    double* edge_chi2;
+    int32_t* info4;
+    se2gpu_ba_stats* stats;     // optional
+    // what k_sparsify reads: a pair's inliers, compacted in input order at the head of its rows
+    double* sp_xyz;
+    double* sp_info;
+    int* sp_cnt;
+};
+int launch_feat_edge(hipStream_t stream, const FeatEdgeArgs& args);
 
 // The SE2GPU_* environment switches (README) are read through these; an unset variable gives `dflt`.  A flag is on for a
 // value that starts with '1', off for one that starts with '0', `dflt` for anything else; env_is compares the whole value.

@@ -227,41 +227,20 @@ __device__ __forceinline__ bool chol12_solve(double* S, double* x) {
     return ok;
 }
 
-struct FeatArgs {
-    int npairs, mode, iters, min_points;
-    const double* kf12;         // npairs x 2 x 12
-    const double* prior_meas;   // npairs x 2 x 12
-    const double* prior_info;   // npairs x 2 x 36
-    const int* mp_ptr;
-    const double* m_z;          // per point 2 x 3
-    const double* m_info;       // per point 2 x 9
-    double huber_delta, outlier_chi2;
-    double* pa;                 // the points: the start values on entry; pa / pb alternate as estimate and trial
-    double* pb;
-    double* kf12_out;
-    double* mp_out;
-    uint8_t* outlier;
-    double* edge_chi2;
-    int32_t* info4;
-    se2gpu_ba_stats* stats;
-    // what k_sparsify reads: a pair's inliers, compacted in input order at the head of its rows
-    double* sp_xyz;
-    double* sp_info;
-    int* sp_cnt;
-};
+using FeatArgs = FeatEdgeArgs;   // common.h
 
 __global__ __launch_bounds__(64) void k_feat_edge(const FeatArgs A) {
     const int p = blockIdx.x;
     if (p >= A.npairs) return;
     const int lane = threadIdx.x;
     __shared__ double strip[78 * 64];
-    const int j0 = A.mp_ptr[p], N = A.mp_ptr[p + 1] - j0;
+    const int j0 = A.mp_ptr[p], N = A.mp_cnt ? A.mp_cnt[p] : A.mp_ptr[p + 1] - j0;
     const double* z = A.m_z + 6 * (size_t)j0;
     const double* W = A.m_info + 18 * (size_t)j0;
     double* cur = A.pa + 3 * (size_t)j0;
     double* trial = A.pb + 3 * (size_t)j0;
     Se3 X[2] = {se3_load(A.kf12 + 24 * (size_t)p), se3_load(A.kf12 + 24 * (size_t)p + 12)};
-    if (N < A.min_points) {   // nothing is run: poses and points as given, no constraint
+    if ((A.raw_cnt ? A.raw_cnt[p] : N) < A.min_points) {   // nothing is run: poses and points as given, no constraint
         for (int j = lane; j < N; j += 64)
             for (int i = 0; i < 3; ++i) A.mp_out[3 * (size_t)(j0 + j) + i] = cur[3 * j + i];
         if (lane == 0) {
@@ -484,6 +463,16 @@ __global__ __launch_bounds__(64) void k_feat_edge(const FeatArgs A) {
 
 }  // namespace
 
+namespace se2gpu {
+
+int launch_feat_edge(hipStream_t st, const FeatEdgeArgs& args) {
+    hipLaunchKernelGGL(k_feat_edge, dim3(args.npairs), dim3(64), 0, st, args);
+    SE2_HIP(hipGetLastError());
+    return SE2GPU_OK;
+}
+
+}  // namespace se2gpu
+
 extern "C" {
 
 int se2gpu_feat_edge_batch(int npairs, int mode, int iters, int min_points, const double* kf12, const double* Tbc12,
@@ -556,11 +545,11 @@ int se2gpu_feat_edge_batch(int npairs, int mode, int iters, int min_points, cons
     FeatArgs a;
     a.npairs = npairs; a.mode = mode; a.iters = iters; a.min_points = min_points;
     a.kf12 = d_kf.p; a.prior_meas = d_pm.p; a.prior_info = d_pi.p; a.mp_ptr = d_mpp.p; a.m_z = d_z.p; a.m_info = d_w.p;
+    a.mp_cnt = nullptr; a.raw_cnt = nullptr;   // dense rows: every point of [mp_ptr[p], mp_ptr[p+1]) counts
     a.huber_delta = huber_delta; a.outlier_chi2 = outlier_chi2;
     a.pa = d_pa.p; a.pb = d_pb.p; a.kf12_out = d_kfo.p; a.mp_out = d_mpo.p; a.outlier = d_outl.p; a.edge_chi2 = d_chi.p;
     a.info4 = d_info4.p; a.stats = d_stats.p; a.sp_xyz = d_spx.p; a.sp_info = d_spi.p; a.sp_cnt = d_cnt.p;
-    hipLaunchKernelGGL(k_feat_edge, dim3(npairs), dim3(64), 0, st, a);
-    SE2_HIP(hipGetLastError());
+    SE2_CHECK(launch_feat_edge(st, a));
     SE2_CHECK(launch_sparsify(st, npairs, d_kfo.p, d_mpp.p, d_spx.p, d_mmp.p, d_mkf.p, d_spi.p, d_ordp.p, d_ord.p, d_blk.p, d_schur.p,
                               d_cnt.p, d_zo.p, d_io.p));
     SE2_HIP(hipMemcpyAsync(kf12_out, d_kfo.p, 24 * (size_t)npairs * 8, hipMemcpyDeviceToHost, st));

@@ -246,6 +246,46 @@ __host__ __device__ inline Se3 from_mqt(const double v[6]) {
     T.t[0] = v[0]; T.t[1] = v[1]; T.t[2] = v[2];
     return T;
 }
+// addVertexSE3PlaneMotion's prior from T_w_c and T_b_c (pose12 each): the arithmetic of se2gpu_plane_motion_prior_iso3 (ba.hip,
+// where the formulas are cited) and of k_plane_prior_iso3 (feat_edge_device.hip), one text for host and device.  info36 has
+// no library call in it and is the same to the bit on both; meas12 goes through atan2 / cos / sin.
+__host__ __device__ inline void plane_motion_prior_iso3(const double* Twc12, const double* Tbc12, double xrot_info, double yrot_info,
+                                                        double z_info, double* meas12, double* info36) {
+    const Se3 Twc = se3_load(Twc12), Tbc = se3_load(Tbc12);
+    Se3 Twb = iso_mul(Twc, se3_inv(Tbc));
+    double q[4];
+    quat_of(Twb.R, q);
+    const double nv = sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    double yaw = 0;
+    if (nv > 0) yaw = 2 * atan2(nv, q[0]) * q[3] / nv;    // z component of the rotation vector (Eigen::AngleAxisd)
+    const double qz[4] = {cos(0.5 * yaw), 0, 0, sin(0.5 * yaw)};
+    mat_of_quat(qz, Twb.R);
+    Twb.t[2] = 0;
+    se3_store(iso_mul(Twb, Tbc), meas12);
+    double A[36], sk[9], sR[9];
+    #pragma unroll
+    for (int i = 0; i < 36; ++i) A[i] = 0;
+    skew3(Tbc.t, sk);
+    mat3_mul(sk, Tbc.R, sR);
+    #pragma unroll
+    for (int i = 0; i < 3; ++i)
+        #pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            A[6 * i + j] = Tbc.R[3 * i + j];
+            A[6 * (i + 3) + (j + 3)] = Tbc.R[3 * i + j];
+            A[6 * i + (j + 3)] = sR[3 * i + j];
+        }
+    const double D[6] = {1e-4, 1e-4, z_info, xrot_info, yrot_info, 1e-4};
+    #pragma unroll
+    for (int i = 0; i < 6; ++i)
+        #pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double v = 0;
+            #pragma unroll
+            for (int k = 0; k < 6; ++k) v += A[6 * k + i] * D[k] * A[6 * k + j];
+            info36[6 * i + j] = v;
+        }
+}
 // d toVectorMQT(E * fromVectorMQT(d)) / d d at 0: [R_E 0; 0  w_E I + [q_E]x]
 __host__ __device__ inline void mqt_jac_right(const Se3& E, double J[36]) {
     double q[4];
