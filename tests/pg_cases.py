@@ -5,6 +5,7 @@ tests/test_pg_model.py holds the cases to their conditions on the CPU (SPD, cond
 on a decision), so that a failure of tests/test_pg_layouts_gpu.py means the kernels."""
 import dataclasses
 import functools
+import os
 
 import numpy as np
 
@@ -100,6 +101,21 @@ def rejecting(P: int, nbad: int, seed: int) -> "synth.PoseGraph":
         axis /= np.linalg.norm(axis)
         poses[a] = poses[a] @ synth.from_mqt_np(np.concatenate([np.zeros(3), 0.9999 * axis]))
     return dataclasses.replace(base, poses=poses)
+
+
+RECORD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pg_layouts.md")
+
+
+def recorded():
+    """{(kind, P): (bound on |H - H_model| / max |H_model|, bound on |b - b_model| / max |b_model|)} of profiles/pg_layouts.md,
+    which `python tests/test_pg_model.py` writes"""
+    out = {}
+    with open(RECORD) as f:
+        for line in f:
+            c = [x.strip() for x in line.strip().strip("|").split("|")]
+            if len(c) == 8 and c[0] in KINDS:
+                out[(c[0], int(c[1]))] = (float(c[6]), float(c[7]))
+    return out
 
 
 def without_edges(g, drop):

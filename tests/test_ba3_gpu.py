@@ -5,22 +5,15 @@ Tolerance as for the SE(2) model: cost and pose updates within 1e-5 relative (ob
 import numpy as np
 import pytest
 
+from ba_cases import REL, env, odo_graph3, odometry_cases3, opt3
+
 pytestmark = pytest.mark.gpu
-REL = 1e-5
-
-
-def _opt3(g):
-    from se2lam_amd import optimizer as op
-    o = op.SlamOptimizer()
-    op.load_se3_graph(o, g)
-    o.initializeOptimization(0)
-    return o
 
 
 @pytest.mark.parametrize("P,L,n_ref", [(8, 60, 0), (21, 800, 0), (21, 800, 4), (50, 5000, 0)])
 def test_chi2_and_reduced_system_match_oracle(oracle, synth, P, L, n_ref):
     g = synth.ba3_graph(P, L, n_ref)
-    o = _opt3(g)
+    o = opt3(g)
     c_ref, ec_ref = oracle.ba3_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c_ref, rel=1e-11)
     from se2lam_amd import optimizer as op
@@ -37,7 +30,7 @@ def test_lm_10_iterations_and_outlier_rule_match_oracle(oracle, synth, P, L, n_r
     """LocalMapper::removeOutlierChi2: optimize(10), then chi2() of every projection edge against 25."""
     from se2lam_amd import optimizer as op
     g = synth.ba3_graph(P, L, n_ref)
-    o = _opt3(g)
+    o = opt3(g)
     assert o.optimize(10) == 10
     p_ref, l_ref, ec_ref, st = oracle.ba3_optimize(g, 10)
     s = o.stats
@@ -67,7 +60,7 @@ def test_se3_windows_in_a_batch_and_mixed_with_se2(synth):
     g3a, g3b, g2 = synth.ba3_graph(21, 800), synth.ba3_graph(50, 5000, 10), synth.ba_graph(21, 800)
     def fresh():
         o2 = SlamOptimizer(); o2.load(g2); o2.initializeOptimization(0)
-        return [_opt3(g3a), o2, _opt3(g3b)]
+        return [opt3(g3a), o2, opt3(g3b)]
     ref = fresh()
     for o in ref:
         o.optimize(6)
@@ -78,9 +71,9 @@ def test_se3_windows_in_a_batch_and_mixed_with_se2(synth):
         assert np.array_equal(a.estimates()[0], b.estimates()[0]) and np.array_equal(a.estimates()[1], b.estimates()[1])
     del ref, got
     for _ in range(2):
-        o = _opt3(g3a); o.optimize(3); c3 = o.stats["chi2_hist"]; del o
+        o = opt3(g3a); o.optimize(3); c3 = o.stats["chi2_hist"]; del o
         o = SlamOptimizer(); o.load(g2); o.initializeOptimization(0); o.optimize(3); c2 = o.stats["chi2_hist"]; del o
-    o = _opt3(g3a); o.optimize(3)
+    o = opt3(g3a); o.optimize(3)
     assert o.stats["chi2_hist"] == c3
 
 
@@ -118,13 +111,7 @@ PLAN_SIZES3 = ((8, 60, 0), (21, 800, 0), (21, 800, 4), (50, 5000, 10))
 
 def _odometry_cases3(sizes=SIZES3):
     from se2lam_amd import synth
-    from test_ba3_oracle import odometry_cases3
     return odometry_cases3(synth, sizes)
-
-
-def _odo_graph3(synth, P, L, n_ref, kind):
-    from test_ba3_oracle import odo_graph3
-    return odo_graph3(synth, P, L, n_ref, kind)
 
 
 @pytest.mark.parametrize("P,L,n_ref,kind", _odometry_cases3())
@@ -133,8 +120,8 @@ def test_odometry_topologies3_match_the_oracle(oracle, synth, P, L, n_ref, kind)
     transposed Oij, and a block that only an odometry edge fills, show here), then 10 LM iterations and the outlier list with the
     assertions of test_lm_10_iterations_and_outlier_rule_match_oracle"""
     from se2lam_amd import optimizer as op
-    g = _odo_graph3(synth, P, L, n_ref, kind)
-    o = _opt3(g)
+    g = odo_graph3(synth, P, L, n_ref, kind)
+    o = opt3(g)
     c_ref, ec_ref = oracle.ba3_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c_ref, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.E), ec_ref, rtol=1e-10)
@@ -168,7 +155,7 @@ def _run_plan3(g, plan, monkeypatch, iters=6):
         monkeypatch.setenv("SE2GPU_BA_PLAN", plan)
     else:
         monkeypatch.delenv("SE2GPU_BA_PLAN", raising=False)
-    o = _opt3(g)
+    o = opt3(g)
     S, bs = o.reduced_system(2.5)
     o.optimize(iters)
     return S, bs, o.stats, o.estimates()
@@ -179,9 +166,8 @@ def test_device_plan_equals_host_plan_on_odometry_topologies3(synth, monkeypatch
     """test_ba_gpu.py::test_device_plan_equals_host_plan for the SE3 model over the layouts: k_plan_odo against ba_plan_host - the
     orientation bit of every odometry block, the empty group of a block without landmark pairs, the lists of a hub - give the same
     sums in the same order: reduced system, statistics and estimates identical"""
-    from test_ba3_oracle import odometry_cases3
     for _, _, _, kind in odometry_cases3(synth, ((P, L, n_ref),)):
-        g = _odo_graph3(synth, P, L, n_ref, kind)
+        g = odo_graph3(synth, P, L, n_ref, kind)
         Sd, bd, sd, (pd_, ld_) = _run_plan3(g, None, monkeypatch)
         Sh, bh, sh, (ph, lh) = _run_plan3(g, "host", monkeypatch)
         assert np.array_equal(Sd, Sh) and np.array_equal(bd, bh), (P, kind)
@@ -192,27 +178,19 @@ def test_device_plan_equals_host_plan_on_odometry_topologies3(synth, monkeypatch
 def test_odometry_topologies3_through_optimize_batch(synth):
     """every layout at 21 key frames and at (50, 5000, 10) in one se2gpu_ba_optimize_batch with the resident path off: bit-identical to the
     one-by-one runs (which test_odometry_topologies3_match_the_oracle holds to the oracle)"""
-    import os
     from se2lam_amd import capi
     from se2lam_amd.optimizer import optimize_batch
-    graphs = [_odo_graph3(synth, *c) for c in _odometry_cases3(PLAN_SIZES3[1:])]
-    old = os.environ.get("SE2GPU_BA_RESIDENT")
-    os.environ["SE2GPU_BA_RESIDENT"] = "0"
-    try:
+    graphs = [odo_graph3(synth, *c) for c in _odometry_cases3(PLAN_SIZES3[1:])]
+    with env(SE2GPU_BA_RESIDENT="0"):
         ref = []
         for g in graphs:
-            o = _opt3(g)
+            o = opt3(g)
             o.optimize(10)
             ref.append((o.stats, o.estimates()))
             del o
-        opts = [_opt3(g) for g in graphs]
+        opts = [opt3(g) for g in graphs]
         its = optimize_batch(opts, 10)
         assert int(capi.lib().se2gpu_ba_last_batch_path()) != 2
-    finally:
-        if old is None:
-            os.environ.pop("SE2GPU_BA_RESIDENT", None)
-        else:
-            os.environ["SE2GPU_BA_RESIDENT"] = old
     for g, o, (st, (p, l)), n in zip(graphs, opts, ref, its):
         assert n == st["iterations"]
         assert o.stats == st, (g.P, g.O)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from se2lam_amd import synth as _synth            # (the parametrisations below; tests take the `synth` fixture)
+from ba_cases import assert_topology3, odo_graph3, odometry_cases3
 from independent import BA3ProblemNumpy, ba3_full_normal_equations, se3_log_g2o
 
 
@@ -86,87 +87,7 @@ def test_remove_outlier_chi2_rule(oracle, synth):
     assert np.median(ec[~bad]) < 3.0
 
 
-# ---- SE3 windows beyond ba3_graph's chain (synth.odometry_topology3) ---------------------------------------------------------
-def odometry_cases3(synth, sizes, kinds=None):
-    """(P, L, n_ref, kind) of every SE3 odometry topology a window of that size can hold: a hub of N edges needs N + 1 local key
-    frames, to_reference needs reference key frames, dense needs DENSE_TERMS - P distinct pairs"""
-    out = []
-    for P, L, n_ref in sizes:
-        nL = P - n_ref
-        for kind in (synth.ODOMETRY_TOPOLOGIES3 if kinds is None else kinds):
-            if kind.startswith("hub") and int(kind[3:]) + 1 > nL:
-                continue
-            if kind == "to_reference" and n_ref == 0:
-                continue
-            if kind == "dense" and synth.DENSE_TERMS - P - (nL - 1) > nL * (nL - 1) // 2 - (nL - 1) + nL * n_ref:
-                continue
-            out.append((P, L, n_ref, kind))
-    return out
-
-
-def assert_topology3(synth, g, kind, base):
-    """the odometry and the priors of `g` have the shape synth.odometry_topology3(base, kind) claims"""
-    P, nL = g.P, synth.n_local(base)
-    oi, oj = np.asarray(g.o_i, np.int64), np.asarray(g.o_j, np.int64)
-    und = sorted(zip(np.minimum(oi, oj).tolist(), np.maximum(oi, oj).tolist()))
-    chain = [(k, k + 1) for k in range(nL - 1)]
-    assert len(set(und)) == len(und) and not (oi == oj).any()          # the SE3 call surface refuses duplicates and self loops
-    assert g.o_meas.shape == (g.O, 4, 4) and g.o_info.shape == (g.O, 6, 6)
-    if kind != "none":
-        assert set(chain) <= set(und)
-        assert np.linalg.eigvalsh(g.o_info).min() > 0
-    if kind not in ("dense", "to_reference"):
-        assert g.O == 0 or max(oi.max(), oj.max()) < nL                # pairs among the local key frames
-    f = np.asarray(g.fixed, bool)
-    if kind != "fixed_ends":
-        assert np.array_equal(g.fixed, base.fixed)
-    if kind != "sparse_priors":
-        assert np.array_equal(g.has_prior, base.has_prior)
-    cov = synth.covisible(g)
-    if kind == "reversed":
-        assert und == chain and (oi > oj).sum() == (nL - 1) // 2 and (oi < oj).any()
-    elif kind == "shuffled":
-        assert und == chain and list(zip(oi.tolist(), oj.tolist())) != chain
-    elif kind == "long":
-        far = [(i, j) for i, j in zip(oi, oj) if abs(i - j) >= 2]
-        assert 2 <= len(far) <= 4 and not any(cov[i, j] for i, j in far)     # only the odometry edge couples these key frames
-        assert any(i < j for i, j in far) and any(i > j for i, j in far)
-    elif kind.startswith("hub"):
-        deg = np.bincount(np.r_[oi, oj], minlength=P)
-        h = int(deg.argmax())
-        assert h == nL // 2 and deg[h] == int(kind[3:]) and (oi == h).sum() >= 2 and (oj == h).sum() >= 2
-    elif kind == "dense":
-        assert P + g.O == synth.DENSE_TERMS > 256
-        assert (oi > oj).sum() > 20 and (oi < oj).sum() > 20
-        assert (np.maximum(oi, oj) >= nL).any() == (nL < P) and np.minimum(oi, oj).max() < nL     # never reference to reference
-    elif kind == "fixed_ends":
-        kinds = set(zip(f[oi].tolist(), f[oj].tolist()))
-        assert {(True, False), (False, True), (True, True), (False, False)} <= kinds
-        assert f[[0, 1, nL // 2, nL - 1]].all() and f[:nL].sum() == 4 and np.array_equal(f[nL:], np.asarray(base.fixed, bool)[nL:])
-        assert g.has_prior[[1, nL // 2, nL - 1]].all()                 # priors on fixed poses other than pose 0
-    elif kind == "to_reference":
-        ref = [(i, j) for i, j in zip(oi, oj) if max(i, j) >= nL]
-        assert 2 <= len(ref) <= 4 and all(min(i, j) < nL for i, j in ref)
-        assert any(i < j for i, j in ref) and any(i > j for i, j in ref)
-    elif kind == "none":
-        assert g.O == 0
-    elif kind == "sparse_priors":
-        assert und == chain
-        free = ~f
-        lost = free & (np.asarray(g.has_prior) == 0)
-        assert lost.sum() == len(np.nonzero(free)[0][2::3]) > 0 and (free & (np.asarray(g.has_prior) == 1)).any()
-        assert np.array_equal(np.asarray(g.has_prior)[f], np.asarray(base.has_prior)[f])
-
-
-def odo_graph3(synth, P, L, n_ref, kind):
-    base = synth.ba3_graph(P, L, n_ref)
-    if kind == "chain":
-        return base
-    g = synth.odometry_topology3(base, kind)
-    assert_topology3(synth, g, kind, base)
-    return g
-
-
+# ---- SE3 windows beyond ba3_graph's chain (synth.odometry_topology3; the cases and their shape checks: tests/ba_cases.py) ----
 def _refined_solve(A, b):
     """A x = b by LU with three rounds of refinement on an extended-precision residual: what is left between two such solutions is
     the difference of the two systems, not the rounding of either solve"""

@@ -6,32 +6,16 @@ linearisation and to ~1e-9 after 10 LM iterations; the asserted bounds are the 1
 north star or tighter.
 """
 import os
-import threading
 
 import numpy as np
 import pytest
 
+from ba_cases import (LM_REJECT_CASES, REL, _info_inputs, kidnapped, odo_graph, odometry_cases, pose_update_close,
+                      sharded_equals_single)
+from ba_cases import opt as _opt      # (three tests below call their optimizer `opt`, the reference's name for it)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-REL = 1e-5
-
-
-def _opt(g):
-    from se2lam_amd.optimizer import SlamOptimizer
-    o = SlamOptimizer()
-    o.load(g)
-    o.initializeOptimization(0)
-    return o
-
-
-def _pose_update_close(p_gpu, p_ref, p0, rel=REL):
-    """pose UPDATES (estimate - initial) agree within `rel` relative (norm-wise per component)."""
-    d_gpu, d_ref = p_gpu - p0, p_ref - p0
-    for c in range(3):
-        scale = np.abs(d_ref[:, c]).max() + 1e-12
-        assert np.abs(d_gpu[:, c] - d_ref[:, c]).max() <= rel * scale, (c, np.abs(d_gpu[:, c] - d_ref[:, c]).max(), scale)
-
 
 def test_chi2_matches_oracle(oracle, synth):
     for P, L in ((8, 60), (50, 5000)):
@@ -66,7 +50,7 @@ def test_lm_10_iterations_match_oracle(oracle, synth, P, L):
     assert s["chi2_init"] == pytest.approx(st["chi2_init"], rel=1e-12)
     assert s["chi2_final"] == pytest.approx(st["chi2_final"], rel=REL)
     poses, lms = o.estimates()
-    _pose_update_close(poses, p_ref, g.poses)
+    pose_update_close(poses, p_ref, g.poses)
     dl = np.abs((lms - g.lms) - (l_ref - g.lms)).max()
     assert dl <= REL * np.abs(l_ref - g.lms).max()
     # the estimate the library holds reproduces its reported cost
@@ -82,7 +66,7 @@ def test_global_window_200kf_20k_landmarks(oracle, synth):
     assert o.stats["trials_hist"] == st["trials_hist"]
     assert np.allclose(o.stats["chi2_hist"], st["chi2_hist"], rtol=REL, atol=0)
     poses, _ = o.estimates()
-    _pose_update_close(poses, p_ref, g.poses)
+    pose_update_close(poses, p_ref, g.poses)
 
 
 def test_gauss_newton_mode(oracle, synth):
@@ -187,7 +171,7 @@ def test_landmark_sharded_two_ranks_on_one_gpu(oracle, synth):
     """The multi-GPU path with world=2 on ONE device: two handles, each holding a
     landmark shard, run their LM loops in two threads; the all-reduce callback sums the fused buffer
     [S | bs | scalars] over the two handles through host memory.  Result == single-handle run."""
-    _sharded_equals_single(synth.ba_graph(8, 60), 6)
+    sharded_equals_single(synth.ba_graph(8, 60), 6)
 
 
 def test_landmark_sharded_lm_schedule_on_a_start_that_rejects(synth):
@@ -196,99 +180,7 @@ def test_landmark_sharded_lm_schedule_on_a_start_that_rejects(synth):
     (rejected trials, gain ratios anywhere in (0, 1)) pins rho, the lambda history and the trial counts to the
     single-handle run."""
     case, trials = LM_REJECT_CASES[2]
-    _sharded_equals_single(_kidnapped(synth, *case), 10, trials)
-
-
-def _sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None, stop=None):
-    """`world` landmark shards as `world` handles on `world` threads of ONE GPU; the all-reduce callback (no caller-owned
-    buffer, so the library hands it the PACKED exchange: the lower-triangular tiles of [S; b^T], se2gpu_ba_exchange_doubles)
-    sums the ranks' buffers on the host.  Same collective pattern as the RCCL path, which takes this buffer too.
-    `stop`: a force-stop flag every handle polls (a raised one ends the runs before any system is exchanged).  Returns the single
-    handle and the ranks' (stats, estimates)."""
-    from se2lam_amd import capi
-    from se2lam_amd.optimizer import SlamOptimizer
-    single = _opt(g)
-    single.setForceStopFlag(stop)
-    single.optimize(iters)
-    if trials is not None:
-        assert single.stats["trials_hist"] == trials
-    # the packed exchange of the system the solver factorises: the ranks of a sharded run re-order the poses like the
-    # single handle does (nested dissection from the merged block pattern), so its size comes from the handle
-    packed = single.exchange_doubles()
-    assert packed >= int(capi.lib().se2gpu_ba_exchange_doubles(g.P))      # = in the natural order, padded partitions otherwise
-    rows = 3 * g.P + 1
-    rect = rows * (-(-rows // 32) * 32)              # the rows of [S; b^T] the rectangular exchange would ship (ld = 32-padded)
-    if packed == int(capi.lib().se2gpu_ba_exchange_doubles(g.P)):
-        assert packed <= rect and (packed < rect or rows <= 32)   # the packed triangle is smaller from two tile rows on
-    barrier = threading.Barrier(world)
-    stage = [None] * world
-    results = [None] * world
-    dbg = [None] * world
-    counts = [set() for _ in range(world)]
-    errors = []
-
-    def make_cb(rank):
-        def cb(ptr, count, stream):
-            counts[rank].add(int(count))
-            capi.check(capi.lib().se2gpu_device_synchronize())
-            buf = np.empty(count)
-            capi.check(capi.lib().se2gpu_memcpy_d2h(capi.vp(buf), ptr, buf.nbytes))
-            stage[rank] = buf
-            barrier.wait()
-            tot = stage[0].copy()                    # fixed summation order on every rank: bit-identical sums
-            for r in range(1, world):
-                tot += stage[r]
-            barrier.wait()
-            capi.check(capi.lib().se2gpu_memcpy_h2d(ptr, capi.vp(tot), tot.nbytes))
-        return cb
-
-    def run(rank):
-        try:
-            o = SlamOptimizer()
-            o.set_shard(rank, world)
-            o.set_allreduce(make_cb(rank))
-            o.load(g.shard(rank, world))
-            o.initializeOptimization(0)
-            o.setForceStopFlag(stop)
-            assert o.exchange_doubles() == packed     # every rank chose the single handle's order
-            if debug_lam is not None:                 # the debug entry points are collectives too (ADVICE r03)
-                dbg[rank] = (o.reduced_system(debug_lam), o.solve(debug_lam))
-            o.optimize(iters)
-            assert o.solver_path() == 0
-            results[rank] = (o.stats, o.estimates())
-        except Exception as exc:  # pragma: no cover
-            errors.append(exc)
-            barrier.abort()
-
-    ts = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    [t.start() for t in ts]
-    [t.join() for t in ts]
-    assert not errors, errors
-    for r in range(world):
-        st, (poses, _) = results[r]
-        assert st["trials_hist"] == single.stats["trials_hist"]
-        assert np.allclose(st["chi2_hist"], single.stats["chi2_hist"], rtol=1e-9)
-        assert np.allclose(st["lambda_hist"], single.stats["lambda_hist"], rtol=1e-9)
-        assert np.allclose(poses, single.estimates()[0], rtol=1e-8, atol=1e-8)
-        assert np.array_equal(poses, results[0][1][0])  # replicated poses stay bit-identical across the ranks
-        # the system exchange went through the packed triangle (the other exchanges are 4 scalars / world slots / 3P diagonals)
-        assert stop is not None or packed in counts[r] and (packed >= rect or debug_lam is not None or not any(c >= rect for c in counts[r])), sorted(counts[r])
-    if debug_lam is not None:   # se2gpu_ba_debug_reduced_system / _solve on a sharded handle whose poses were re-ordered
-        fresh = _opt(g)
-        S0, b0 = fresh.reduced_system(debug_lam)
-        x0, ok0 = fresh.solve(debug_lam)
-        assert ok0
-        for r in range(world):
-            (S, b), (x, ok) = dbg[r]
-            assert ok and np.abs(S - S0).max() <= 1e-10 * np.abs(S0).max() and np.abs(b - b0).max() <= 1e-10 * np.abs(b0).max()
-            assert np.abs(x - x0).max() <= 1e-8 * np.abs(x0).max()
-    # every landmark lives on exactly one rank: the shards' landmark estimates together are the single run's
-    lms = np.full_like(single.estimates()[1], np.nan)
-    for r in range(world):
-        own = g.shard_landmarks(r, world)
-        lms[own] = results[r][1][1]
-    assert np.allclose(lms, single.estimates()[1], rtol=1e-8, atol=1e-6)
-    return single, results
+    sharded_equals_single(kidnapped(synth, *case), 10, trials)
 
 
 @pytest.mark.gpu
@@ -297,7 +189,7 @@ def test_landmark_sharded_config4_packed_exchange(synth, world):
     """VERDICT r02 missing #2: BASELINE config 4 (200 KF / 20,000 landmarks) landmark-sharded over 2 / 4 / 8 ranks on a
     device, through the PACKED exchange (k_tri_pack -> all-reduce -> unpack): trial counts equal, chi^2 / lambda histories
     within 1e-9 of the single-GPU run, replicated poses bit-identical across ranks (Map.cpp:891-1053)."""
-    _sharded_equals_single(synth.ba_graph(200, 20000), 4, world=world)
+    sharded_equals_single(synth.ba_graph(200, 20000), 4, world=world)
 
 
 @pytest.mark.gpu
@@ -309,7 +201,7 @@ def test_sharded_debug_entry_points_reduce_the_reordered_system(synth):
     g = synth.ba_graph(120, 6000)
     o = _opt(g)
     assert o.exchange_doubles() > int(capi.lib().se2gpu_ba_exchange_doubles(g.P)), "expected a re-ordered (padded) system"
-    _sharded_equals_single(g, 3, world=2, debug_lam=7.0)
+    sharded_equals_single(g, 3, world=2, debug_lam=7.0)
 
 
 @pytest.mark.gpu
@@ -317,7 +209,7 @@ def test_sharded_debug_entry_points_reduce_the_reordered_system(synth):
 def test_landmark_sharded_rejecting_start_many_ranks(synth, world):
     """the 50-KF kidnapped start (rejected trials, gain ratios anywhere in (0, 1)) over 4 and 8 shards"""
     case, trials = LM_REJECT_CASES[2]
-    _sharded_equals_single(_kidnapped(synth, *case), 10, trials, world=world)
+    sharded_equals_single(kidnapped(synth, *case), 10, trials, world=world)
 
 
 def test_reserve_parks_a_warm_handle(oracle, synth):
@@ -338,7 +230,6 @@ def test_reserve_parks_a_warm_handle(oracle, synth):
 def test_edge_information_on_device(oracle, synth):
     """SURVEY §8f.1: Map::loadLocalGraph's per-observation information (Map.cpp:1024-1049) computed on the GPU."""
     from se2lam_amd import optimizer as op
-    from test_ba_oracle import _info_inputs
     for P, L in ((12, 200), (50, 5000)):
         inp, g, _ = _info_inputs(synth, P, L)
         got = op.edge_information(**inp)
@@ -407,41 +298,12 @@ def test_dataflow_solve_with_more_tiles_than_resident_workgroups(synth, monkeypa
         assert np.abs(x - x_ref).max() <= 1e-9 * np.abs(x_ref).max()
 
 
-def _kidnapped(synth, P, L, dxy, dth, nbad, seed):
-    """A few key frames displaced by metres / tens of degrees (landmarks untouched, so no point comes near a camera
-    plane): the Gauss-Newton-like first steps overshoot and Levenberg-Marquardt has to REJECT trials."""
-    import copy
-    g = copy.copy(synth.ba_graph(P, L))   # the generator caches its graphs: never modify the shared instance
-    rng = np.random.default_rng(seed)
-    g.poses = g.poses.copy()
-    idx = rng.choice(np.arange(1, g.P), nbad, replace=False)
-    g.poses[idx, :2] += rng.normal(0, dxy, (nbad, 2))
-    g.poses[idx, 2] += rng.normal(0, dth, nbad)
-    # headings stay in [-pi, pi): the reference's Se2 normalises on construction (src/Config.cpp), and an out-of-range
-    # theta would meet PreEdgeSE2's missing angle wrap (EdgeSE2XYZ.h:80) as a 2 pi cost jump at the first oplus
-    g.poses[:, 2] = (g.poses[:, 2] + np.pi) % (2 * np.pi) - np.pi
-    return g
-
-
-# (P, L, dxy [mm], dtheta [rad], displaced key frames, seed) -> the trials per iteration of g2o's policy on that start.
-# Chosen (tools-free search over seeds) so that EVERY accept / reject decision has a wide margin: |rho| >= 0.4 in all
-# trials, where rho = 0 is the decision boundary - the last bits of the host libm cannot flip one - and no observed
-# point is closer than 0.9 m to its camera plane at the start.
-LM_REJECT_CASES = [
-    ((8, 60, 2000.0, 0.8, 1, 4), [1, 1, 6, 5, 1, 3, 2, 3, 4, 3]),
-    ((8, 60, 3000.0, 0.3, 4, 6), [1, 7, 1, 1, 1, 1, 1, 1, 1, 1]),
-    ((21, 800, 3000.0, 0.3, 4, 13), [1, 1, 1, 1, 1, 8, 1, 1, 4, 1]),
-    ((50, 5000, 3000.0, 0.3, 4, 12), [1, 7, 1, 1, 3, 2, 4, 3, 3, 3]),
-    ((50, 5000, 3000.0, 0.3, 2, 23), [1, 1, 7, 1, 1, 3, 3, 2, 3, 4]),
-]
-
-
 @pytest.mark.parametrize("case,trials", LM_REJECT_CASES)
 def test_lm_rejected_trials_follow_the_oracle(oracle, synth, case, trials):
     """The retry path (new lambda on the same linearisation: k_schur_lm -> k_reduce2 -> solve -> evaluate, lambda *= ni,
     ni *= 2, <= 10 trials) takes the oracle's g2o decisions trial for trial, on fixed starts that
     are known to reject - no search, no skip."""
-    g = _kidnapped(synth, *case)
+    g = kidnapped(synth, *case)
     p_ref, l_ref, st = oracle.ba_optimize(g, 10, 0)
     assert st["trials_hist"] == trials                       # the fixture itself: fails loudly if a host ever disagrees
     assert np.abs(st["rho_log"]).min() > 0.2
@@ -452,7 +314,7 @@ def test_lm_rejected_trials_follow_the_oracle(oracle, synth, case, trials):
     assert np.allclose(o.stats["chi2_hist"], st["chi2_hist"], rtol=REL, atol=0)
     assert np.allclose(o.stats["lambda_hist"], st["lambda_hist"], rtol=REL, atol=0)
     poses, _ = o.estimates()
-    _pose_update_close(poses, p_ref, g.poses, rel=1e-4)
+    pose_update_close(poses, p_ref, g.poses, rel=1e-4)
 
 
 def test_pooled_handles_behave_like_new_ones(synth, monkeypatch):
@@ -509,7 +371,7 @@ def test_optimize_batch_equals_one_by_one(synth):
     """se2gpu_ba_optimize_batch: several independent windows (different sizes, one of them a start that rejects trials)
     driven at once, every controller on the device - bit-identical to optimising them one after the other."""
     from se2lam_amd.optimizer import optimize_batch
-    graphs = [synth.ba_graph(50, 5000), synth.ba_graph(8, 60), _kidnapped(synth, *LM_REJECT_CASES[3][0]),
+    graphs = [synth.ba_graph(50, 5000), synth.ba_graph(8, 60), kidnapped(synth, *LM_REJECT_CASES[3][0]),
               synth.ba_graph(21, 800), synth.ba_graph(50, 5000)]
     ref = []
     for g in graphs:
@@ -538,7 +400,7 @@ def test_lockstep_batch_mixed_rejections_repeats_and_gauss_newton(synth):
     second call re-uses the argument packs on the device) and once in Gauss-Newton mode: every window bit-identical to its
     own one-by-one run."""
     from se2lam_amd.optimizer import optimize_batch
-    graphs = [_kidnapped(synth, *c[0]) for c in LM_REJECT_CASES] + [synth.ba_graph(8, 60), synth.ba_graph(30, 2000), synth.ba_graph(50, 5000)]
+    graphs = [kidnapped(synth, *c[0]) for c in LM_REJECT_CASES] + [synth.ba_graph(8, 60), synth.ba_graph(30, 2000), synth.ba_graph(50, 5000)]
     for mode in (0, 1):
         ref = []
         for g in graphs:
@@ -594,7 +456,7 @@ def test_mixed_window_batch_equals_the_oracle_window_by_window(oracle, synth):
     from se2lam_amd.optimizer import optimize_batch
     gs = synth.mixed_windows(14, p_range=(10, 26), l_range=(200, 1100), kidnapped_every=4, seed=77)
     assert len({(g.P, g.L) for g in gs}) == len(gs)
-    gs = gs[:5] + [_kidnapped(synth, *c[0]) for c in LM_REJECT_CASES[:3]] + gs[5:]   # starts whose rejections have wide margins
+    gs = gs[:5] + [kidnapped(synth, *c[0]) for c in LM_REJECT_CASES[:3]] + gs[5:]   # starts whose rejections have wide margins
     opts = [_opt(g) for g in gs]
     optimize_batch(opts, 8)
     rejecting = 0
@@ -706,7 +568,6 @@ def test_load_local_graph_pod_call(synth, oracle):
     sequence spelled out with the free functions (Map.cpp:891-1053) and the oracle's information matrices - with and
     without reference key frames, with an observation by a key frame outside both lists."""
     from se2lam_amd import optimizer as op
-    from test_ba_oracle import _info_inputs
     inp, g, level = _info_inputs(synth, 12, 200)
     K = np.array([[g.fx, 0, g.cx], [0, g.fx, g.cy], [0, 0, 1]], np.float32)
     info = oracle.ba_edge_information(**inp)
@@ -800,7 +661,7 @@ def test_repeated_optimize_replays_a_graph_with_identical_results(synth):
     rejected trial are enqueued directly, after the graph) and for the SE3 / pose-graph models"""
     from se2lam_amd import optimizer as op
     case, trials = LM_REJECT_CASES[1]
-    for g, loader in ((synth.ba_graph(30, 900), None), (_kidnapped(synth, *case), None),
+    for g, loader in ((synth.ba_graph(30, 900), None), (kidnapped(synth, *case), None),
                       (synth.ba3_graph(12, 300, 2), op.load_se3_graph), (synth.pose_graph(40), op.load_pose_graph)):
         o = op.SlamOptimizer()
         if loader:
@@ -822,22 +683,14 @@ def test_repeated_optimize_replays_a_graph_with_identical_results(synth):
 # (odo_fallback) through k_odometry + k_reduce_odo in synchronous mode.  P = 50 and 200 are solved in a fill-reducing order.
 def _odometry_cases():
     from se2lam_amd import synth
-    from test_ba_oracle import odometry_cases
     return odometry_cases(synth, ((8, 60), (21, 800), (50, 3000))) + [(200, 20000, "duplicate_long")]
-
-
-def _odo_graph(synth, P, L, kind):
-    from test_ba_oracle import assert_topology
-    g = synth.odometry_topology(synth.ba_graph(P, L), kind)
-    assert_topology(synth, g, kind)
-    return g
 
 
 @pytest.mark.parametrize("P,L,kind", _odometry_cases())
 def test_odometry_topologies_match_the_oracle(oracle, synth, P, L, kind):
     """every odometry topology: the reduced system against the oracle, the dense solve against a host Cholesky refined in
     extended precision (a tile the solve's pattern lost shows up here), 10 LM iterations against the oracle's g2o run"""
-    g = _odo_graph(synth, P, L, kind)
+    g = odo_graph(synth, P, L, kind)
     o = _opt(g)
     for lam in (3.0, 40.0):
         S, bs = o.reduced_system(lam)
@@ -861,7 +714,7 @@ def test_odometry_topologies_match_the_oracle(oracle, synth, P, L, kind):
     assert np.allclose(s["lambda_hist"], st["lambda_hist"], rtol=REL, atol=0), kind
     assert s["chi2_init"] == pytest.approx(st["chi2_init"], rel=1e-12)
     poses, _ = o.estimates()
-    _pose_update_close(poses, p_ref, g.poses)
+    pose_update_close(poses, p_ref, g.poses)
     f = np.asarray(g.fixed, bool)
     assert np.array_equal(poses[f], g.poses[f])
 
@@ -871,7 +724,7 @@ def test_device_plan_equals_host_plan_on_odometry_topologies(synth, monkeypatch)
     mark every odometry block in the pattern the solver's order is chosen from (the host plan does): same order, same tiles.
     The fallback's odometry blocks are atomic adds, so those windows are compared to rounding, the others bit for bit."""
     for P, L, kind in [c for c in _odometry_cases() if c[0] >= 21]:
-        g = _odo_graph(synth, P, L, kind)
+        g = odo_graph(synth, P, L, kind)
         fallback = kind in ("duplicate", "duplicate_long", "self_loop")
         Sd, bd, sd, (pd_, ld_) = _run_plan(g, None, monkeypatch)
         Sh, bh, sh, (ph, lh) = _run_plan(g, "host", monkeypatch)
@@ -892,9 +745,9 @@ def test_odometry_topologies_through_optimize_batch(oracle, synth):
     the oracle"""
     from se2lam_amd import capi
     from se2lam_amd.optimizer import optimize_batch
-    plain = [_odo_graph(synth, P, L, k) for P, L, k in _odometry_cases()
+    plain = [odo_graph(synth, P, L, k) for P, L, k in _odometry_cases()
              if P in (21, 50) and k not in ("duplicate", "duplicate_long", "self_loop")]
-    odd = [_odo_graph(synth, P, L, k) for P, L, k in _odometry_cases() if P in (21, 50) and k in ("duplicate", "duplicate_long", "self_loop")]
+    odd = [odo_graph(synth, P, L, k) for P, L, k in _odometry_cases() if P in (21, 50) and k in ("duplicate", "duplicate_long", "self_loop")]
     for graphs, path in ((plain, 1), (plain[:3] + odd, 0)):
         ref = []
         for g in graphs:
@@ -917,4 +770,4 @@ def test_odometry_topologies_through_optimize_batch(oracle, synth):
             p_ref, _, so = oracle.ba_optimize(g, 10, 0)
             assert o.stats["trials_hist"] == so["trials_hist"]
             assert np.allclose(o.stats["chi2_hist"], so["chi2_hist"], rtol=REL, atol=0)
-            _pose_update_close(pp, p_ref, g.poses)
+            pose_update_close(pp, p_ref, g.poses)

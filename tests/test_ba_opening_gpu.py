@@ -7,22 +7,17 @@ compared BIT FOR BIT with the old opening's (SE2GPU_BA_OPEN=0, read once per pro
 module), in the graph-replayed form (this process) and in the synchronous form (SE2GPU_BA_SYNC=1, a second child), and with the
 CPU oracle under the bounds of test_ba_gpu.py.
 """
-import dataclasses
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, ROOT):   # (the file is also the child processes' script: nothing has set the path up there)
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import ba_ab
+from ba_ab import assert_equal_runs, same_bits
+from ba_cases import LM_REJECT_CASES, REL, bare_pose, kidnapped, no_odometry, opt, pose_update_close
 
-from test_ba_gpu import LM_REJECT_CASES, REL, _kidnapped, _opt, _pose_update_close  # noqa: E402
+pytestmark = pytest.mark.gpu
 
 # poses with fewer than 64 edges (a lane of k_lambda0 has zero or one); ~400 edges per pose (one partial batch of eight rounds);
 # ~600 edges per pose (one full batch and a remainder)
@@ -31,44 +26,19 @@ LM, GN = 0, 1
 BARE_POSE = 2   # the key frame of ba_graph(30, 2000) whose observation edges are taken away
 
 
-def _no_odometry(synth):
-    """O = 0.  Without PreEdgeSE2 edges one fixed key frame leaves the scale of the window free, and Gauss-Newton (no damping)
-    then factorises a singular system; a second fixed key frame takes that freedom away, so LM and GN are both well posed."""
-    g = synth.ba_graph(30, 2000)
-    fx = g.fixed.copy()
-    fx[1] = 1
-    return dataclasses.replace(g, fixed=fx, o_i=g.o_i[:0], o_j=g.o_j[:0], o_meas=g.o_meas[:0], o_info=g.o_info[:0])
-
-
-def _pose_without_observations(synth):
-    """key frame BARE_POSE keeps its two PreEdgeSE2 edges and loses every EdgeSE2XYZ (its wave of k_lambda0 gathers nothing).
-    It is the key frame whose edges can go while every landmark keeps two observations: a landmark with one has a singular
-    block, which Gauss-Newton cannot invert."""
-    g = synth.ba_graph(30, 2000)
-    keep = g.e_kf != BARE_POSE
-    assert 0 < keep.sum() < g.E and not g.fixed[BARE_POSE]
-    assert np.bincount(g.e_lm[keep], minlength=g.L).min() >= 2
-    return dataclasses.replace(g, e_kf=g.e_kf[keep], e_lm=g.e_lm[keep], e_uv=g.e_uv[keep], e_info=g.e_info[keep])
-
-
 def _graphs(synth):
     """(name, graph): the three plain windows, the kidnapped starts that reject trials, O = 0, a pose without observations"""
     out = [("plain%d" % i, synth.ba_graph(P, L)) for i, (P, L) in enumerate(PLAIN)]
-    out += [("reject%d" % i, _kidnapped(synth, *c[0])) for i, c in enumerate(LM_REJECT_CASES)]
-    out += [("no_odometry", _no_odometry(synth)), ("bare_pose", _pose_without_observations(synth))]
+    out += [("reject%d" % i, kidnapped(synth, *c[0])) for i, c in enumerate(LM_REJECT_CASES)]
+    out += [("no_odometry", no_odometry(synth)), ("bare_pose", bare_pose(synth, BARE_POSE))]
     return out
 
 
+SWITCHES = ("SE2GPU_BA_OPEN", "SE2GPU_BA_SYNC")
+
+
 def _record(o, out, key):
-    s = o.stats
-    poses, lms = o.estimates()
-    out[key + "/trials"] = np.asarray(s["trials_hist"], np.int64)
-    out[key + "/lambda"] = np.asarray(s["lambda_hist"], np.float64)
-    out[key + "/chi2"] = np.asarray(s["chi2_hist"] + [s["chi2_init"], s["chi2_final"]], np.float64)
-    out[key + "/poses"] = np.array(poses, np.float64)
-    out[key + "/lms"] = np.array(lms, np.float64)
-    # (runs, skips; the third count is the size of the record twin: a handle out of the pool may bring a larger one along)
-    out[key + "/counts"] = np.asarray(o.linearize_counts()[:2], np.int64)
+    ba_ab.record(o, out, key, counts=2)
 
 
 def _scenarios(synth, out):
@@ -77,13 +47,13 @@ def _scenarios(synth, out):
     for name, g in _graphs(synth):
         for mode in (LM, GN):
             for sc, calls in (("a", [10]), ("b", [1]), ("c", [3, 3])):
-                o = _opt(g)
+                o = opt(g)
                 for ci, n in enumerate(calls):
                     o.optimize(n, mode)
                     _record(o, out, "%s/m%d/%s%d" % (name, mode, sc, ci))
     for mode in (LM, GN):
         g = synth.ba_graph(30, 2000)
-        o = _opt(g)
+        o = opt(g)
         flag = np.ones(1, np.uint8)
         o.setForceStopFlag(flag)
         assert o.optimize(10, mode) == 0 and o.stats["stopped"]
@@ -93,45 +63,6 @@ def _scenarios(synth, out):
         _record(o, out, "stop/m%d/after" % mode)
 
 
-def _child_main(argv):
-    """python test_ba_opening_gpu.py OUT.npz"""
-    from se2lam_amd import synth
-    out = {}
-    _scenarios(synth, out)
-    np.savez(argv[0], **out)
-
-
-def _child(tmp, name, **env_set):
-    path = str(tmp / (name + ".npz"))
-    env = dict(os.environ)
-    env.pop("SE2GPU_BA_OPEN", None)
-    env.pop("SE2GPU_BA_SYNC", None)
-    env.update(env_set)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), path], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _assert_equal_runs(new, old):
-    assert sorted(new) == sorted(old)
-    bad = []
-    for k in sorted(new):
-        if not _same_bits(new[k], old[k]):
-            d = float("nan")
-            if new[k].shape == old[k].shape and new[k].dtype == np.float64:
-                with np.errstate(all="ignore"):
-                    d = float(np.nanmax(np.abs(new[k] - old[k]) / np.maximum(np.abs(old[k]), 1e-300)))
-            print("differs:", k, "max relative difference", d)
-            bad.append(k)
-    assert not bad, bad
-
-
 @pytest.fixture(scope="module")
 def runs(synth, tmp_path_factory):
     """the scenarios by the new opening (this process: graph-replayed form), by the old one and by the new one's synchronous form"""
@@ -139,8 +70,8 @@ def runs(synth, tmp_path_factory):
     new = {}
     _scenarios(synth, new)
     tmp = tmp_path_factory.mktemp("opening")
-    old = _child(tmp, "old", SE2GPU_BA_OPEN="0")
-    sync = _child(tmp, "sync", SE2GPU_BA_SYNC="1")
+    old = ba_ab.child(__file__, tmp, "old", unset=SWITCHES, env_set={"SE2GPU_BA_OPEN": "0"})
+    sync = ba_ab.child(__file__, tmp, "sync", unset=SWITCHES, env_set={"SE2GPU_BA_SYNC": "1"})
     return new, old, sync
 
 
@@ -150,7 +81,7 @@ def test_same_results_as_the_old_opening(runs):
     new, old, _ = runs
     n = sum(1 for k in new if k.endswith("/trials") and not k.startswith("stop"))
     assert n == (len(PLAIN) + len(LM_REJECT_CASES) + 2) * 2 * 4
-    _assert_equal_runs(new, old)
+    assert_equal_runs(new, old)
     for gi, (_, trials) in enumerate(LM_REJECT_CASES):     # the fixtures did reject (and so did the new opening)
         assert new["reject%d/m0/a0/trials" % gi].tolist() == trials
 
@@ -158,7 +89,7 @@ def test_same_results_as_the_old_opening(runs):
 def test_synchronous_form_equals_the_old_opening(runs):
     """SE2GPU_BA_SYNC=1 (one slot enqueued at a time, the form the per-kernel pass takes): the same bits again"""
     _, old, sync = runs
-    _assert_equal_runs(sync, old)
+    assert_equal_runs(sync, old)
 
 
 def test_stop_flag_before_the_run(runs, synth):
@@ -172,7 +103,7 @@ def test_stop_flag_before_the_run(runs, synth):
         assert new[k + "before/counts"].tolist() == [0, 0]
         assert new[k + "before/chi2"][-2] == new[k + "after/chi2"][-2] == new["plain1/m%d/a0/chi2" % mode][-2]
         for f in ("trials", "lambda", "chi2", "poses", "lms", "counts"):
-            assert _same_bits(new[k + "after/" + f], old[k + "after/" + f]), (mode, f)
+            assert same_bits(new[k + "after/" + f], old[k + "after/" + f]), (mode, f)
 
 
 # Gauss-Newton on ba_graph(50, 5000) is not among the oracle's cases: the oracle's own fifth undamped step there meets a
@@ -199,10 +130,10 @@ def test_matches_oracle(runs, oracle, synth, which, mode):
     assert np.allclose(new[k + "lambda"][:n], st["lambda_hist"], rtol=REL, atol=0)
     assert chi2[-2] == pytest.approx(st["chi2_init"], rel=1e-12)
     assert chi2[-1] == pytest.approx(st["chi2_final"], rel=REL)
-    _pose_update_close(new[k + "poses"], p_ref, g.poses)
+    pose_update_close(new[k + "poses"], p_ref, g.poses)
     dl = np.abs((new[k + "lms"] - g.lms) - (l_ref - g.lms)).max()
     assert dl <= REL * np.abs(l_ref - g.lms).max()
 
 
 if __name__ == "__main__":
-    _child_main(sys.argv[1:])
+    ba_ab.child_main(_scenarios, sys.argv[1:])

@@ -8,6 +8,8 @@ weights, g2o's LM policy invariants, and algebraic properties of the Schur reduc
 import numpy as np
 import pytest
 
+from ba_cases import LM_REJECT_CASES, _info_inputs, assert_topology, kidnapped, odometry_cases
+
 
 def _num_jac(f, x, h=1e-6):
     x = np.asarray(x, float)
@@ -161,49 +163,6 @@ def _reduced_system_equals_full_model(oracle, g, lam):
     assert np.abs(S[np.ix_(fp, fp)] - Sm).max() <= 1e-9 * np.abs(Sm).max()
 
 
-def odometry_cases(synth, sizes):
-    """(P, L, kind) of every odometry topology that a window of P key frames can hold (a hub of N edges needs N + 1 of them)"""
-    return [(P, L, kind) for P, L in sizes for kind in synth.ODOMETRY_TOPOLOGIES
-            if not (kind.startswith("hub") and int(kind[3:]) + 1 > P)]
-
-
-def assert_topology(synth, g, kind):
-    """the odometry of `g` has the shape synth.odometry_topology(.., kind) claims"""
-    P = g.P
-    oi, oj = np.asarray(g.o_i, np.int64), np.asarray(g.o_j, np.int64)
-    und = sorted(zip(np.minimum(oi, oj).tolist(), np.maximum(oi, oj).tolist()))
-    chain = [(k, k + 1) for k in range(P - 1)]
-    cov = synth.covisible(g)
-    far = [(i, j) for i, j in zip(oi, oj) if abs(i - j) >= 2 and not cov[i, j]]
-    dup = len(set(und)) < len(und)
-    loops = int((oi == oj).sum())
-    if kind == "reversed":
-        assert und == chain and (oi > oj).sum() == (P - 1) // 2 and (oi < oj).any()
-    elif kind == "shuffled":
-        assert und == chain and list(zip(oi.tolist(), oj.tolist())) != chain
-    elif kind in ("long", "duplicate_long"):
-        assert 2 <= len(far) <= 4, far                      # poses that share no landmark: only odometry couples them
-    if kind.startswith("hub"):
-        deg = np.bincount(np.r_[oi, oj], minlength=P)
-        h = int(deg.argmax())
-        nb = set(oj[oi == h].tolist()) | set(oi[oj == h].tolist())
-        assert deg[h] == int(kind[3:]) == len(nb) and h not in nb and (oi == h).any() and (oj == h).any()
-    if kind == "fixed_ends":
-        f = np.asarray(g.fixed, bool)
-        kinds = set(zip(f[oi].tolist(), f[oj].tolist()))
-        assert {(True, False), (False, True), (True, True), (False, False)} <= kinds and f.sum() >= 3
-    if kind in ("duplicate", "duplicate_long"):
-        pairs = list(zip(oi.tolist(), oj.tolist()))
-        assert dup and loops == 0
-        assert any(pairs.count(p) == 2 for p in pairs)                        # one pair twice, same direction
-        assert any(p[0] > p[1] and (p[1], p[0]) in pairs for p in pairs)      # and one as both (a, b) and (b, a)
-    elif kind == "self_loop":
-        k = int(np.nonzero(oi == oj)[0][0])
-        assert loops == 1 and np.abs(g.o_meas[k]).max() > 0
-    else:
-        assert not dup and loops == 0
-
-
 def test_odometry_topologies_reduce_like_the_full_model(oracle, synth):
     """The oracle's odometry terms (ba_ref.cpp: any (i, j), a self loop included) against the independent numpy model of the
     full normal equations, over every odometry topology the GPU tests use, at 8 and 21 key frames"""
@@ -286,27 +245,6 @@ def test_library_shard_partition_matches_generator(synth):
         assert cnt.min() > 0.9 * g.E / world and cnt.max() < 1.1 * g.E / world
 
 
-def _info_inputs(synth, P=12, L=200, seed=0):
-    """Inputs of Map::loadLocalGraph's information computation (Map.cpp:1024-1049) for a synthetic window."""
-    g = synth.ba_graph(P, L)
-    rng = np.random.default_rng(seed)
-    Rcb = g.Rbc.T
-    tcb = -Rcb @ g.tbc
-    _, _, _, lc = synth._project(g.poses, g.lms, g.e_kf, g.e_lm, Rcb, tcb, g.fx, 0.0, 0.0)
-    th = g.poses[:, 2]
-    Rbw = np.zeros((g.P, 3, 3))
-    Rbw[:, 0, 0] = np.cos(th); Rbw[:, 0, 1] = np.sin(th); Rbw[:, 1, 0] = -np.sin(th); Rbw[:, 1, 1] = np.cos(th)
-    Rbw[:, 2, 2] = 1
-    Rcw = (Rcb[None] @ Rbw).astype(np.float32)
-    level = rng.integers(0, 8, g.E)
-    sf = np.ones(8, np.float32)
-    for i in range(1, 8):
-        sf[i] = sf[i - 1] * np.float32(1.2)
-    sig2 = (sf * sf).astype(np.float32)
-    return dict(lc=lc.astype(np.float32), lw=g.lms[g.e_lm].astype(np.float32), e_kf=g.e_kf, sigma2=sig2[level],
-                Rcw=Rcw.reshape(g.P, 9), twb_xy=g.poses[:, :2].astype(np.float32), fx=np.float32(g.fx)), g, level
-
-
 def test_edge_information_oracle_vs_generator(oracle, synth):
     """oracle/ba_ref.cpp::ba_ref_edge_information (C++ restatement of Map.cpp:1024-1049) against the independent
     numpy restatement used by the generator; both must give SPD 2x2 information matrices bounded by 1/sigma2."""
@@ -320,14 +258,11 @@ def test_edge_information_oracle_vs_generator(oracle, synth):
 
 
 def test_lm_reject_fixtures_have_wide_decision_margins(oracle, synth):
-    """The fixed starts of tests/test_ba_gpu.py::LM_REJECT_CASES really reject, with the frozen trial counts, and no
-    accept / reject decision is closer than |rho| = 0.2 to its boundary (CPU half of that test)."""
-    import importlib.util, os
-    spec = importlib.util.spec_from_file_location("_ba_gpu", os.path.join(os.path.dirname(__file__), "test_ba_gpu.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    for case, trials in m.LM_REJECT_CASES:
-        g = m._kidnapped(synth, *case)
+    """The fixed starts of tests/ba_cases.py::LM_REJECT_CASES really reject, with the frozen trial counts, and no
+    accept / reject decision is closer than |rho| = 0.2 to its boundary (CPU half of
+    tests/test_ba_gpu.py::test_lm_rejected_trials_follow_the_oracle)."""
+    for case, trials in LM_REJECT_CASES:
+        g = kidnapped(synth, *case)
         _, _, st = oracle.ba_optimize(g, 10, 0)
         assert st["trials_hist"] == trials, case
         assert np.abs(st["rho_log"]).min() > 0.2, case

@@ -16,50 +16,23 @@ The windows (the smallest that reach a branch):
                landmarks that keep two edges: 172 of the 2,000 would keep one): most blocks empty, whole tail workgroups, three
                block columns in the solve
     thin_long  thin with PreEdgeSE2 edges between key frames that share no landmark: blocks with an edge and no pairs are real
-    dense      test_ba_reduce_flat_gpu's window, all key frames sharing all landmarks: nwg_real == nwg_all
+    dense      ba_cases.dense_window, all key frames sharing all landmarks: nwg_real == nwg_all
     ring50     ba_graph(50, 5000): the permuted plan (pose_off); 727 of 1,225 blocks empty
 """
-import contextlib
 import dataclasses
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, ROOT):   # (the file is also the child processes' script: nothing has set the path up there)
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import ba_ab
+from ba_ab import assert_equal_runs, record, same_bits
+from ba_cases import dense_window, env, opt, thin, thin4
 
 GRP_PER_WG, CHUNK = 28, 16   # csrc/ba.hip: kGrpPerWG, kChunk
 LAMBDA = 3.0e-2
 SWITCHES = ("SE2GPU_BA_REDUCE_EMPTY", "SE2GPU_BA_SYNC", "SE2GPU_BA_CHOL", "SE2GPU_BA_PLAN")
-
-
-def _opt(g):
-    from se2lam_amd.optimizer import SlamOptimizer
-    o = SlamOptimizer()
-    o.load(g)
-    o.initializeOptimization(0)
-    return o
-
-
-@contextlib.contextmanager
-def _env(**kw):
-    """switches the library reads at every initialize (SE2GPU_BA_CHOL, SE2GPU_BA_PLAN), for the handles made inside"""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update(kw)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _grid(o):
@@ -70,61 +43,18 @@ def _grid(o):
     return [int(v) for v in out]
 
 
-def _keep_edges(g, keep):
-    """the graph with the edges `keep` and the landmarks that still have two of them"""
-    n = np.bincount(g.e_lm[keep], minlength=g.L)
-    keep = keep & (n[g.e_lm] >= 2)
-    lm_keep = np.nonzero(n >= 2)[0]
-    remap = -np.ones(g.L, np.int64)
-    remap[lm_keep] = np.arange(lm_keep.size)
-    return dataclasses.replace(g, lms=g.lms[lm_keep].copy(), e_kf=g.e_kf[keep].copy(), e_lm=remap[g.e_lm[keep]].astype(np.int32),
-                               e_uv=g.e_uv[keep].copy(), e_info=g.e_info[keep].copy(), lms_true=g.lms_true[lm_keep].copy(),
-                               e_level=g.e_level[keep].copy())
-
-
-def _thin(synth):
-    g = synth.ba_graph(30, 2000)
-    first = np.full(g.L, g.P, np.int64)
-    np.minimum.at(first, g.e_lm, g.e_kf)
-    return _keep_edges(g, g.e_kf - first[g.e_lm] <= 2)
-
-
-def _thin4(synth):
-    """a thin window with the dense window's four key frames: 0, 1, 12, 13 of `thin` (0 fixed), chained by three PreEdgeSE2
-    edges: blocks (0, 2), (0, 3), (1, 3) are empty, (1, 2) has an edge and no pairs, (2, 3) has pairs"""
-    g = _thin(synth)
-    kfs = np.array([0, 1, 12, 13])
-    remap = -np.ones(g.P, np.int64)
-    remap[kfs] = np.arange(4)
-    w = _keep_edges(g, np.isin(g.e_kf, kfs))
-    w = dataclasses.replace(w, poses=g.poses[kfs].copy(), fixed=g.fixed[kfs].copy(), poses_true=g.poses_true[kfs].copy(),
-                            e_kf=remap[w.e_kf].astype(np.int32))
-    return synth.with_odometry(w, [(0, 1), (1, 2), (2, 3)], seed=3)
-
-
 def _graphs(synth):
-    from test_ba_reduce_flat_gpu import _dense_window
-    thin = _thin(synth)
-    return [("tiny", synth.ba_graph(8, 60)), ("thin", thin), ("thin_long", synth.odometry_topology(thin, "long", seed=1)),
-            ("dense", _dense_window(synth)), ("ring50", synth.ba_graph(50, 5000))]
+    t = thin(synth)
+    return [("tiny", synth.ba_graph(8, 60)), ("thin", t), ("thin_long", synth.odometry_topology(t, "long", seed=1)),
+            ("dense", dense_window(synth)), ("ring50", synth.ba_graph(50, 5000))]
 
 
 BATCH = ("tiny", "thin", "thin_long")
-
-
-def _record(o, out, key):
-    s = o.stats
-    poses, lms = o.estimates()
-    out[key + "/trials"] = np.asarray(s["trials_hist"], np.int64)
-    out[key + "/lambda"] = np.asarray(s["lambda_hist"], np.float64)
-    out[key + "/chi2"] = np.asarray(s["chi2_hist"] + [s["chi2_init"], s["chi2_final"]], np.float64)
-    out[key + "/poses"] = np.array(poses, np.float64)
-    out[key + "/lms"] = np.array(lms, np.float64)
+EXEMPT = ("/grid",)   # what the two sides differ in by design
 
 
 def _system(o, out, key):
-    S, bs = o.reduced_system(LAMBDA)
-    out[key + "/S"], out[key + "/bs"] = np.array(S, np.float64), np.array(bs, np.float64)
+    ba_ab.system(o, out, key, LAMBDA)
 
 
 def _scenarios(synth, out):
@@ -133,49 +63,49 @@ def _scenarios(synth, out):
     graphs = _graphs(synth)
     by_name = dict(graphs)
     for name, g in graphs:
-        o = _opt(g)
+        o = opt(g)
         out[name + "/grid"] = np.asarray(_grid(o), np.int64)
         _system(o, out, name)
         out[name + "/permuted"] = np.asarray([int(o.plan_neager()[1])], np.int64)
         for n in (10, 3):   # (the third run of a shape is the replayed graph)
-            o = _opt(g)
+            o = opt(g)
             for _ in range(3):
                 o.reset_estimates()
                 o.optimize(n)
-            _record(o, out, "%s/n%d" % (name, n))
-    opts = [_opt(by_name[k]) for k in BATCH]
+            record(o, out, "%s/n%d" % (name, n))
+    opts = [opt(by_name[k]) for k in BATCH]
     optimize_batch(opts, 10)
     out["batch/path"] = np.asarray([int(capi.lib().se2gpu_ba_last_batch_path())], np.int64)
     for k, o in zip(BATCH, opts):
-        _record(o, out, "batch/" + k)
+        record(o, out, "batch/" + k)
     # reload: a handle that held a window with more non-zero blocks, optimised, cleared, loaded with a thin window of the same P
-    for key, before, after in (("reload4", by_name["dense"], _thin4(synth)), ("reload30", synth.ba_graph(30, 2000), by_name["thin"])):
+    for key, before, after in (("reload4", by_name["dense"], thin4(synth)), ("reload30", synth.ba_graph(30, 2000), by_name["thin"])):
         assert before.P == after.P
-        o = _opt(before)
+        o = opt(before)
         o.optimize(10)
         o.clear()
         o.load(after)
         o.initializeOptimization(0)
         out[key + "/grid"] = np.asarray(_grid(o), np.int64)
         _system(o, out, key)
-        _system(_opt(after), out, key + "_fresh")
+        _system(opt(after), out, key + "_fresh")
     # the in-place factorisation writes into the empty blocks: optimize(10) twice, then the reduced system
-    with _env(SE2GPU_BA_CHOL="steps"):
-        o = _opt(by_name["thin"])
+    with env(SE2GPU_BA_CHOL="steps"):
+        o = opt(by_name["thin"])
         out["steps/path"] = np.asarray([o.solver_path()], np.int64)
         out["steps/grid"] = np.asarray(_grid(o), np.int64)
         for _ in range(2):
             o.optimize(10)
-        _record(o, out, "steps/n10")
+        record(o, out, "steps/n10")
         _system(o, out, "steps")
     # the host builder of the plan: the device kernels' mirror
-    with _env(SE2GPU_BA_PLAN="host"):
+    with env(SE2GPU_BA_PLAN="host"):
         for name in ("thin", "ring50"):
-            o = _opt(by_name[name])
+            o = opt(by_name[name])
             out["host_%s/grid" % name] = np.asarray(_grid(o), np.int64)
             _system(o, out, "host_" + name)
             o.optimize(10)
-            _record(o, out, "host_%s/n10" % name)
+            record(o, out, "host_%s/n10" % name)
     # a handle with an all-reduce set (world 1: the callback has nothing to add) keeps block order and the full grid
     o = SlamOptimizer()
     o.set_allreduce(lambda ptr, count, stream: None)
@@ -183,46 +113,6 @@ def _scenarios(synth, out):
     o.initializeOptimization(0)
     out["sharded/grid"] = np.asarray(_grid(o), np.int64)
     _system(o, out, "sharded")
-
-
-def _child_main(argv):
-    """python test_ba_reduce_empty_gpu.py OUT.npz"""
-    from se2lam_amd import synth
-    out = {}
-    _scenarios(synth, out)
-    np.savez(argv[0], **out)
-
-
-def _child(tmp, name, **env_set):
-    path = str(tmp / (name + ".npz"))
-    env = dict(os.environ)
-    for k in SWITCHES:
-        env.pop(k, None)
-    env.update(env_set)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), path], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _assert_equal_runs(new, old, skip=()):
-    assert sorted(new) == sorted(old)
-    bad = []
-    for k in sorted(new):
-        if k in skip or k.endswith("/grid") or _same_bits(new[k], old[k]):   # (grid: what the two sides differ in by design)
-            continue
-        d = float("nan")
-        if new[k].shape == old[k].shape and new[k].dtype == np.float64:
-            with np.errstate(all="ignore"):
-                d = float(np.nanmax(np.abs(new[k] - old[k]) / np.maximum(np.abs(old[k]), 1e-300)))
-        print("differs:", k, "max relative difference", d)
-        bad.append(k)
-    assert not bad, bad
 
 
 @pytest.fixture(scope="module")
@@ -233,8 +123,8 @@ def runs(synth, tmp_path_factory):
     new = {}
     _scenarios(synth, new)
     tmp = tmp_path_factory.mktemp("reduce_empty")
-    old = _child(tmp, "old", SE2GPU_BA_REDUCE_EMPTY="0")
-    sync = _child(tmp, "sync", SE2GPU_BA_SYNC="1")
+    old = ba_ab.child(__file__, tmp, "old", unset=SWITCHES, env_set={"SE2GPU_BA_REDUCE_EMPTY": "0"})
+    sync = ba_ab.child(__file__, tmp, "sync", unset=SWITCHES, env_set={"SE2GPU_BA_SYNC": "1"})
     return new, old, sync
 
 
@@ -287,14 +177,14 @@ def test_reduced_system_and_runs_equal_block_order(runs):
     new, old, _ = runs
     assert sum(1 for k in new if k.endswith("/S")) == 5 + 4 + 1 + 2 + 1
     assert sum(1 for k in new if k.endswith("/trials")) == 5 * 2 + len(BATCH) + 1 + 2
-    _assert_equal_runs(new, old)
+    assert_equal_runs(new, old, exempt_suffix=EXEMPT)
 
 
 @pytest.mark.gpu
 def test_synchronous_form_equals_block_order(runs):
     """SE2GPU_BA_SYNC=1 with the empty blocks packed last: the same bits again"""
     _, old, sync = runs
-    _assert_equal_runs(sync, old, skip=("batch/path",))   # (a synchronous process runs the windows of a batch one by one)
+    assert_equal_runs(sync, old, exempt_suffix=EXEMPT, skip=("batch/path",))   # (a synchronous process runs the windows of a batch one by one)
 
 
 @pytest.mark.gpu
@@ -304,10 +194,10 @@ def test_reloaded_handle_equals_a_fresh_one(runs):
     new, _, sync = runs
     for r in (new, sync):
         for key in ("reload4", "reload30"):
-            assert _same_bits(r[key + "/S"], r[key + "_fresh/S"]) and _same_bits(r[key + "/bs"], r[key + "_fresh/bs"]), key
+            assert same_bits(r[key + "/S"], r[key + "_fresh/S"]) and same_bits(r[key + "/bs"], r[key + "_fresh/bs"]), key
         for name in ("thin", "ring50"):
-            assert _same_bits(r["host_%s/S" % name], r[name + "/S"]) and _same_bits(r["host_%s/bs" % name], r[name + "/bs"]), name
-        assert _same_bits(r["sharded/S"], r["thin/S"])
+            assert same_bits(r["host_%s/S" % name], r[name + "/S"]) and same_bits(r["host_%s/bs" % name], r[name + "/bs"]), name
+        assert same_bits(r["sharded/S"], r["thin/S"])
 
 
 def _descriptors(o):
@@ -326,11 +216,11 @@ def test_device_packers_equal_the_host_builder(synth):
     """the group descriptors of the device plan are the host builder's, element for element, in the new order: k_plan_tab /
     k_plan_tabscan / k_plan_place (up to 96 K blocks) and k_plan_pack (450 key frames: 101,475 blocks)"""
     assert os.environ.get("SE2GPU_BA_REDUCE_EMPTY", "1") != "0" and "SE2GPU_BA_PLAN" not in os.environ
-    for g in (_thin(synth), synth.ba_graph(50, 5000), synth.ba_graph(450, 1500)):
+    for g in (thin(synth), synth.ba_graph(50, 5000), synth.ba_graph(450, 1500)):
         assert g.P != 450 or g.P * (g.P + 1) // 2 > 96 * 1024
-        dev = _opt(g)
-        with _env(SE2GPU_BA_PLAN="host"):
-            host = _opt(g)
+        dev = opt(g)
+        with env(SE2GPU_BA_PLAN="host"):
+            host = opt(g)
         assert _grid(dev) == _grid(host) and _grid(dev)[1] < _grid(dev)[0], g.P
         a, b = _descriptors(dev), _descriptors(host)
         assert a.shape == b.shape and np.array_equal(a, b), g.P
@@ -453,14 +343,13 @@ def _check_packing(g, empty_last, odo_ok=1):
 
 def test_host_packing_equals_its_model(synth):
     """ba_plan_host through se2gpu_ba_debug_plan_host against the model above, in both orders"""
-    from test_ba_reduce_flat_gpu import _dense_window
-    thin = _thin(synth)
-    for g in (synth.ba_graph(8, 60), thin, synth.odometry_topology(thin, "long", seed=1), _thin4(synth), _dense_window(synth)):
+    t = thin(synth)
+    for g in (synth.ba_graph(8, 60), t, synth.odometry_topology(t, "long", seed=1), thin4(synth), dense_window(synth)):
         for empty_last in (False, True):
             _check_packing(g, empty_last)
     # PreEdgeSE2 edges outside the block plan (odo_ok = 0) still make their blocks non-empty
-    assert _check_packing(synth.odometry_topology(thin, "long", seed=1), True, odo_ok=0)[:2] == \
-        _check_packing(synth.odometry_topology(thin, "long", seed=1), True)[:2]
+    assert _check_packing(synth.odometry_topology(t, "long", seed=1), True, odo_ok=0)[:2] == \
+        _check_packing(synth.odometry_topology(t, "long", seed=1), True)[:2]
     nwg, real, empty, nblk = _check_packing(synth.ba_graph(50, 5000), True)
     assert (empty, nblk) == (727, 1225) and real < nwg
 
@@ -483,4 +372,4 @@ def test_host_packing_of_the_headline_window(synth):
 
 
 if __name__ == "__main__":
-    _child_main(sys.argv[1:])
+    ba_ab.child_main(_scenarios, sys.argv[1:])

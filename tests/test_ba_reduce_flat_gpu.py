@@ -8,77 +8,19 @@ through the old arrays (SE2GPU_BA_REDUCE_FLAT=0, read at initialize: a child pro
 graph-replayed form (this process) and in the synchronous form (SE2GPU_BA_SYNC=1, a second child).  The bounds against the
 oracle are test_ba_gpu.py's and are not restated here.
 """
-import dataclasses
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, ROOT):   # (the file is also the child processes' script: nothing has set the path up there)
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import ba_ab
+from ba_ab import assert_equal_runs, record
+from ba_cases import bare_pose, dense_window, no_odometry, opt
 
 GRP_PER_WG, CHUNK, FLAT_Q = 28, 16, 11   # csrc/ba.hip: kGrpPerWG, kChunk, kFlatQ
 LAMBDA = 3.0e-2
-DENSE_KFS, DENSE_LMS = (10, 11, 12, 13), 500
-
-
-def _opt(g):
-    from se2lam_amd.optimizer import SlamOptimizer
-    o = SlamOptimizer()
-    o.load(g)
-    o.initializeOptimization(0)
-    return o
-
-
-def _dense_window(synth):
-    """four neighbouring key frames of ba_graph(50, 5000), the first fixed, that ALL observe the same 500 landmarks: each of the
-    three blocks between free key frames has 500 contributor pairs, more than 28 chunks of 16, so its chunks are longer than
-    sixteen pairs (the indices past the record); block (0, 1) has an edge, a fixed end and no pairs"""
-    g = synth.ba_graph(50, 5000)
-    kfs = list(DENSE_KFS)
-    P = len(kfs)
-    Rcb = synth.RBC.T
-    tcb = -Rcb @ synth.TBC
-    kf, lm = np.repeat(np.arange(P), g.L), np.tile(np.arange(g.L), P)
-    u, v, z, _ = synth._project(g.poses_true[kfs], g.lms_true, kf, lm, Rcb, tcb, synth.FX, synth.CX, synth.CY)
-    vis = ((z >= 300.0) & (z <= 12000.0) & (u >= 0) & (u < synth.IMG_W) & (v >= 0) & (v < synth.IMG_H)).reshape(P, -1)
-    pick = np.nonzero(vis.all(axis=0))[0][:DENSE_LMS]
-    assert pick.size == DENSE_LMS > GRP_PER_WG * CHUNK
-    rng = np.random.default_rng(77)
-    e_lm = np.repeat(np.arange(DENSE_LMS), P).astype(np.int32)
-    e_kf = np.tile(np.arange(P), DENSE_LMS).astype(np.int32)
-    lms_t, poses_t = g.lms_true[pick], g.poses_true[kfs]
-    u, v, _, _ = synth._project(poses_t, lms_t, e_kf, e_lm, Rcb, tcb, synth.FX, synth.CX, synth.CY)
-    level = rng.integers(0, 8, e_kf.size)
-    e_uv = np.stack([u, v], axis=1) + rng.normal(0.0, 1.0, (e_kf.size, 2)) * (1.2 ** level)[:, None]
-    poses0, lms0 = g.poses[kfs].copy(), g.lms[pick].copy()
-    fixed = np.array([1, 0, 0, 0], np.uint8)
-    w = synth.BAGraph(poses=poses0, fixed=fixed, lms=lms0, e_kf=e_kf, e_lm=e_lm, e_uv=e_uv,
-                      e_info=synth.edge_information(poses0, lms0, e_kf, e_lm, level, synth.RBC, synth.TBC, synth.FX),
-                      o_i=np.zeros(0, np.int32), o_j=np.zeros(0, np.int32), o_meas=np.zeros((0, 3)), o_info=np.zeros((0, 9)),
-                      poses_true=poses_t, lms_true=lms_t, e_level=level.astype(np.int32))
-    return synth.with_odometry(w, [(0, 1), (2, 1), (2, 3)], seed=5)
-
-
-def _no_odometry(synth):
-    """O = 0 (a second fixed key frame takes the free scale away)"""
-    g = synth.ba_graph(30, 2000)
-    fx = g.fixed.copy()
-    fx[1] = 1
-    return dataclasses.replace(g, fixed=fx, o_i=g.o_i[:0], o_j=g.o_j[:0], o_meas=g.o_meas[:0], o_info=g.o_info[:0])
-
-
-def _bare_pose(synth, pose=2):
-    """a key frame that keeps its two PreEdgeSE2 edges and loses every observation edge"""
-    g = synth.ba_graph(30, 2000)
-    keep = g.e_kf != pose
-    assert 0 < keep.sum() < g.E and not g.fixed[pose] and np.bincount(g.e_lm[keep], minlength=g.L).min() >= 2
-    return dataclasses.replace(g, e_kf=g.e_kf[keep], e_lm=g.e_lm[keep], e_uv=g.e_uv[keep], e_info=g.e_info[keep])
+SWITCHES = ("SE2GPU_BA_REDUCE_FLAT", "SE2GPU_BA_SYNC")
 
 
 def _graphs(synth):
@@ -93,24 +35,15 @@ def _graphs(synth):
         bare_pose    a key frame without observation edges
         ring50       50 key frames: the solver takes its fill-reducing order (pose_off)"""
     g30 = synth.ba_graph(30, 2000)
-    return [("tiny", synth.ba_graph(8, 60)), ("plain", g30), ("dense", _dense_window(synth)),
+    return [("tiny", synth.ba_graph(8, 60)), ("plain", g30), ("dense", dense_window(synth)),
             ("long", synth.odometry_topology(g30, "long", seed=1)),
             ("hub12", synth.odometry_topology(synth.ba_graph(21, 800), "hub12", seed=1)),
             ("fixed_ends", synth.odometry_topology(g30, "fixed_ends", seed=1)),
-            ("no_odometry", _no_odometry(synth)), ("bare_pose", _bare_pose(synth)), ("ring50", synth.ba_graph(50, 5000))]
+            ("no_odometry", no_odometry(synth)), ("bare_pose", bare_pose(synth)), ("ring50", synth.ba_graph(50, 5000))]
 
 
 BATCH = ("tiny", "hub12", "fixed_ends")   # the lock-step batch: three distinct small windows
-
-
-def _record(o, out, key):
-    s = o.stats
-    poses, lms = o.estimates()
-    out[key + "/trials"] = np.asarray(s["trials_hist"], np.int64)
-    out[key + "/lambda"] = np.asarray(s["lambda_hist"], np.float64)
-    out[key + "/chi2"] = np.asarray(s["chi2_hist"] + [s["chi2_init"], s["chi2_final"]], np.float64)
-    out[key + "/poses"] = np.array(poses, np.float64)
-    out[key + "/lms"] = np.array(lms, np.float64)
+EXEMPT = ("/nslots",)                     # what the two sides differ in by design
 
 
 def _nslots(o):
@@ -142,64 +75,23 @@ def _scenarios(synth, out):
     from se2lam_amd.optimizer import optimize_batch
     graphs = _graphs(synth)
     for name, g in graphs:
-        o = _opt(g)
-        S, bs = o.reduced_system(LAMBDA)
-        out[name + "/S"], out[name + "/bs"] = np.array(S, np.float64), np.array(bs, np.float64)
+        o = opt(g)
+        ba_ab.system(o, out, name, LAMBDA)
         nsys, permuted, _ = o.plan_neager()
         out[name + "/permuted"] = np.asarray([int(permuted)], np.int64)
         out[name + "/nslots"] = np.asarray([_nslots(o)], np.int64)
         for n in (10, 3):
-            o = _opt(g)
+            o = opt(g)
             for _ in range(3):
                 o.reset_estimates()
                 o.optimize(n)
-            _record(o, out, "%s/n%d" % (name, n))
+            record(o, out, "%s/n%d" % (name, n))
     by_name = dict(graphs)
-    opts = [_opt(by_name[k]) for k in BATCH]
+    opts = [opt(by_name[k]) for k in BATCH]
     optimize_batch(opts, 10)
     out["batch/path"] = np.asarray([int(capi.lib().se2gpu_ba_last_batch_path())], np.int64)
     for k, o in zip(BATCH, opts):
-        _record(o, out, "batch/" + k)
-
-
-def _child_main(argv):
-    """python test_ba_reduce_flat_gpu.py OUT.npz"""
-    from se2lam_amd import synth
-    out = {}
-    _scenarios(synth, out)
-    np.savez(argv[0], **out)
-
-
-def _child(tmp, name, **env_set):
-    path = str(tmp / (name + ".npz"))
-    env = dict(os.environ)
-    for k in ("SE2GPU_BA_REDUCE_FLAT", "SE2GPU_BA_SYNC"):
-        env.pop(k, None)
-    env.update(env_set)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), path], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _assert_equal_runs(new, old, skip=()):
-    assert sorted(new) == sorted(old)
-    bad = []
-    for k in sorted(new):
-        if k in skip or k.endswith("/nslots") or _same_bits(new[k], old[k]):   # (nslots: what the two sides differ in by design)
-            continue
-        d = float("nan")
-        if new[k].shape == old[k].shape and new[k].dtype == np.float64:
-            with np.errstate(all="ignore"):
-                d = float(np.nanmax(np.abs(new[k] - old[k]) / np.maximum(np.abs(old[k]), 1e-300)))
-        print("differs:", k, "max relative difference", d)
-        bad.append(k)
-    assert not bad, bad
+        record(o, out, "batch/" + k)
 
 
 @pytest.fixture(scope="module")
@@ -209,8 +101,8 @@ def runs(synth, tmp_path_factory):
     new = {}
     _scenarios(synth, new)
     tmp = tmp_path_factory.mktemp("reduce_flat")
-    old = _child(tmp, "old", SE2GPU_BA_REDUCE_FLAT="0")
-    sync = _child(tmp, "sync", SE2GPU_BA_SYNC="1")
+    old = ba_ab.child(__file__, tmp, "old", unset=SWITCHES, env_set={"SE2GPU_BA_REDUCE_FLAT": "0"})
+    sync = ba_ab.child(__file__, tmp, "sync", unset=SWITCHES, env_set={"SE2GPU_BA_SYNC": "1"})
     return new, old, sync
 
 
@@ -239,7 +131,7 @@ def test_the_graphs_reach_the_branches(runs, synth):
     # tiny: ONE workgroup, all 28 slots taken by the 28 blocks of 8 key frames (those of the fixed one: not free, no pairs);
     # plain: several workgroups, in each the used slots first and the padding behind them, and some do end in padding
     for name in ("tiny", "plain"):
-        grp, flat = _readback(_opt(g[name]))
+        grp, flat = _readback(opt(g[name]))
         assert np.array_equal(flat[:, 0], grp)
         used = grp[:, 0] >= 0
         per_wg = used.reshape(-1, GRP_PER_WG)
@@ -252,7 +144,7 @@ def test_the_graphs_reach_the_branches(runs, synth):
         else:
             assert (per_wg.sum(axis=1) < GRP_PER_WG).any() and per_wg[-1].any()
     # dense: whole workgroups of 28 slots
-    grp, flat = _readback(_opt(g["dense"]))
+    grp, flat = _readback(opt(g["dense"]))
     assert np.array_equal(flat[:, 0], grp)
     used = grp[:, 0] >= 0
     # three blocks of 500 pairs in 28 chunks each: 27 of 18 pairs - longer than the sixteen a record holds - and one of 14
@@ -267,14 +159,14 @@ def test_reduced_system_and_runs_equal_the_old_chain(runs):
     new, old, _ = runs
     assert sum(1 for k in new if k.endswith("/S")) == 9
     assert sum(1 for k in new if k.endswith("/trials")) == 9 * 2 + len(BATCH)
-    _assert_equal_runs(new, old)
+    assert_equal_runs(new, old, exempt_suffix=EXEMPT)
 
 
 @pytest.mark.gpu
 def test_synchronous_form_equals_the_old_chain(runs):
     """SE2GPU_BA_SYNC=1 with the records: the same bits again"""
     _, old, sync = runs
-    _assert_equal_runs(sync, old, skip=("batch/path",))   # (a synchronous process runs the windows of a batch one by one)
+    assert_equal_runs(sync, old, exempt_suffix=EXEMPT, skip=("batch/path",))   # (a synchronous process runs the windows of a batch one by one)
 
 
 # ---- the record builder against a model of it: host code, no device
@@ -329,4 +221,4 @@ def test_record_builder_equals_its_model(permuted):
 
 
 if __name__ == "__main__":
-    _child_main(sys.argv[1:])
+    ba_ab.child_main(_scenarios, sys.argv[1:])

@@ -10,17 +10,11 @@ import sys
 import numpy as np
 import pytest
 
+from ba_cases import opt
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAMBDAS = (30.0, 3.0)
-
-
-def _opt(g):
-    from se2lam_amd.optimizer import SlamOptimizer
-    o = SlamOptimizer()
-    o.load(g)
-    o.initializeOptimization(0)
-    return o
 
 
 def _refined(S, bs):
@@ -57,7 +51,7 @@ def _check_solves(o, key):
 
 
 def test_ring_plan_is_permuted_and_has_a_two_way_junction(synth):
-    o = _opt(synth.ba_graph(50, 5000))
+    o = opt(synth.ba_graph(50, 5000))
     nsys, permuted, ne = o.plan_neager()
     assert o.solver_path() == 0
     assert permuted and nsys > 150 and nsys % 32 == 0
@@ -65,7 +59,7 @@ def test_ring_plan_is_permuted_and_has_a_two_way_junction(synth):
 
 
 def test_ring_plan_solve_matches_refined_host_cholesky(synth):
-    o = _opt(synth.ba_graph(50, 5000))
+    o = opt(synth.ba_graph(50, 5000))
     assert o.plan_neager()[1] and o.plan_neager()[2].max() >= 2
     _check_solves(o, "ring 50")
     assert o.solver_path() == 0                         # no time-out, no fallback to the column launches
@@ -73,7 +67,7 @@ def test_ring_plan_solve_matches_refined_host_cholesky(synth):
 
 def test_two_fresh_handles_agree_to_the_bit(synth):
     g = synth.ba_graph(50, 5000)
-    a, b = _opt(g), _opt(g)
+    a, b = opt(g), opt(g)
     for lam in LAMBDAS:
         xa, oka = a.solve(lam)
         xb, okb = b.solve(lam)
@@ -86,7 +80,7 @@ def test_two_fresh_handles_agree_to_the_bit(synth):
 
 
 def test_unpermuted_plan_with_the_rhs_row_inside_the_last_diagonal_tile(synth):
-    o = _opt(synth.ba_graph(21, 600))
+    o = opt(synth.ba_graph(21, 600))
     nsys, permuted, ne = o.plan_neager()
     assert not permuted and nsys == 63 and nsys // 32 == (nsys - 1) // 32       # row 63 = the last row of diagonal tile 1
     assert ne.max() == 1
@@ -102,7 +96,7 @@ sys.path.insert(0, %r)
 from se2lam_amd import synth
 import test_ba_solve_order_gpu as t
 mode = sys.argv[1]
-o = t._opt(synth.ba_graph(50, 5000))
+o = t.opt(synth.ba_graph(50, 5000))
 nsys, permuted, ne = o.plan_neager()
 if mode == "natural":
     assert not permuted and nsys == 150 and ne.max() == 1, (nsys, permuted, ne.max())

@@ -16,32 +16,22 @@ import time
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, ROOT):   # (the file is also the child process's script: nothing has set the path up there)
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+import ba_ab
+from ba_ab import same_bits
+from ba_cases import LM_REJECT_CASES, REL, ROOT, kidnapped, opt, pose_update_close
 
-from test_ba_gpu import LM_REJECT_CASES, REL, _kidnapped, _opt, _pose_update_close  # noqa: E402
+pytestmark = pytest.mark.gpu
 
 PLAIN = [(8, 60), (30, 2000), (50, 5000)]
 LM, GN = 0, 1
 
 
 def _graphs(synth):
-    return [synth.ba_graph(P, L) for P, L in PLAIN] + [_kidnapped(synth, *c[0]) for c in LM_REJECT_CASES]
+    return [synth.ba_graph(P, L) for P, L in PLAIN] + [kidnapped(synth, *c[0]) for c in LM_REJECT_CASES]
 
 
 def _record(o, out, key):
-    s = o.stats
-    poses, lms = o.estimates()
-    out[key + "/trials"] = np.asarray(s["trials_hist"], np.int64)
-    out[key + "/lambda"] = np.asarray(s["lambda_hist"], np.float64)
-    out[key + "/chi2"] = np.asarray(s["chi2_hist"] + [s["chi2_init"], s["chi2_final"]], np.float64)
-    out[key + "/poses"] = np.array(poses, np.float64)
-    out[key + "/lms"] = np.array(lms, np.float64)
-    out[key + "/counts"] = np.asarray(o.linearize_counts(), np.int64)
+    ba_ab.record(o, out, key, counts=3)
 
 
 def _scenarios(synth, out):
@@ -50,21 +40,21 @@ def _scenarios(synth, out):
     for gi, g in enumerate(_graphs(synth)):
         for mode in (LM, GN):
             for name, calls in (("a", [10]), ("b", [1]), ("c", [3, 3])):
-                o = _opt(g)
+                o = opt(g)
                 for ci, n in enumerate(calls):
                     o.optimize(n, mode)
                     _record(o, out, "g%d/m%d/%s%d" % (gi, mode, name, ci))
     for gi, g in enumerate(_graphs(synth)):
-        o = _opt(g)
+        o = opt(g)
         o.optimize(5)
         o.reset_estimates()
         o.optimize(5)
         _record(o, out, "reset/g%d" % gi)
-        f = _opt(g)
+        f = opt(g)
         f.optimize(5)
         _record(f, out, "fresh/g%d" % gi)
     g = synth.ba_graph(30, 2000)
-    o = _opt(g)
+    o = opt(g)
     flag = np.ones(1, np.uint8)
     o.setForceStopFlag(flag)
     assert o.optimize(10) == 0 and o.stats["stopped"]
@@ -74,69 +64,45 @@ def _scenarios(synth, out):
     _record(o, out, "stop/after")
 
 
-def _child_main(argv):
+def _child_scenarios(synth, out, which, *args):
     """python test_ba_speculate_gpu.py OUT.npz all | python test_ba_speculate_gpu.py OUT.npz iters P L K MODE"""
-    from se2lam_amd import synth
-    out = {}
-    if argv[1] == "all":
-        _scenarios(synth, out)
-    else:
-        P, L, k, mode = (int(a) for a in argv[2:6])
-        o = _opt(synth.ba_graph(P, L))
-        o.optimize(k, mode)
-        _record(o, out, "iters")
-    np.savez(argv[0], **out)
+    if which == "all":
+        return _scenarios(synth, out)
+    P, L, k, mode = (int(a) for a in args)
+    o = opt(synth.ba_graph(P, L))
+    o.optimize(k, mode)
+    _record(o, out, "iters")
 
 
 def _old_slot(tmp_path, *args):
-    """the same work by the old slot: a child process with SE2GPU_BA_SPECULATE=0 (under its own time limit)"""
-    path = str(tmp_path / ("old_%s.npz" % "_".join(str(a) for a in args)))
-    env = dict(os.environ)
-    env["SE2GPU_BA_SPECULATE"] = "0"
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), path] + [str(a) for a in args], capture_output=True, text=True,
-                       env=env, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
+    """the same work by the old slot: a child process that inherits this environment with SE2GPU_BA_SPECULATE=0"""
+    return ba_ab.child(__file__, tmp_path, "old_" + "_".join(str(a) for a in args), *args, env_set={"SE2GPU_BA_SPECULATE": "0"})
 
 
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+def _counts(k, new, old):
+    """the counters are the one thing that differs (the old slot never skips)"""
+    assert old[1] == 0 and old[2] == 0, (k, old)      # old slot: no skip, no second record set
+    assert new[0] + new[1] == old[0], (k, new, old)
 
 
-def _assert_equal_runs(new, old, keys=None):
-    """histories identical, cost / poses / landmarks bit for bit; the counters are the one thing that differs (the old slot
-    never skips)"""
-    assert sorted(new) == sorted(old)
-    worst = 0.0
-    for k in sorted(new):
-        if keys is not None and not k.startswith(keys):
-            continue
-        if k.endswith("/counts"):
-            assert old[k][1] == 0 and old[k][2] == 0, (k, old[k])      # old slot: no skip, no second record set
-            assert new[k][0] + new[k][1] == old[k][0], (k, new[k], old[k])
-            continue
-        if not _same_bits(new[k], old[k]) and new[k].shape == old[k].shape and new[k].dtype == np.float64:
-            with np.errstate(all="ignore"):
-                d = np.abs(new[k] - old[k]) / np.maximum(np.abs(old[k]), 1e-300)
-            worst = max(worst, float(np.nanmax(d)))
-            print("differs:", k, "max relative difference", float(np.nanmax(d)))
-        assert _same_bits(new[k], old[k]), (k, "worst relative difference so far", worst)
+def _assert_equal_runs(new, old, only):
+    """histories identical, cost / poses / landmarks bit for bit"""
+    ba_ab.assert_equal_runs(new, old, only=only, special={"/counts": _counts})
 
 
 @pytest.fixture(scope="module")
-def both(synth, tmp_path_factory):
+def runs(synth, tmp_path_factory):
+    """the scenarios by the speculating slot (this process) and by the old one"""
     new = {}
     _scenarios(synth, new)
     old = _old_slot(tmp_path_factory.mktemp("speculate"), "all")
     return new, old
 
 
-def test_same_results_as_the_old_slot(both):
+def test_same_results_as_the_old_slot(runs):
     """3 plain windows + the five starts that reject trials, LM and GN, optimize(10) / optimize(1) / optimize(3) twice: trial and
     lambda histories identical, chi^2, poses and landmarks equal to the bit"""
-    new, old = both
+    new, old = runs
     n = sum(1 for k in new if k.startswith("g") and k.endswith("/trials"))
     assert n == (len(PLAIN) + len(LM_REJECT_CASES)) * 2 * 4
     _assert_equal_runs(new, old, "g")
@@ -144,14 +110,14 @@ def test_same_results_as_the_old_slot(both):
         assert new["g%d/m0/a0/trials" % (len(PLAIN) + gi)].tolist() == trials
 
 
-def test_reset_between_runs_and_stop_flag_before_a_run(both):
+def test_reset_between_runs_and_stop_flag_before_a_run(runs):
     """optimize(5), reset_estimates(), optimize(5) = a fresh handle's optimize(5) (no record of the first run survives); a stop
     flag that is already up leaves the start untouched, and the run after it is the old slot's"""
-    new, old = both
+    new, old = runs
     _assert_equal_runs(new, old, ("reset", "fresh", "stop"))
     for gi in range(len(PLAIN) + len(LM_REJECT_CASES)):
         for f in ("trials", "lambda", "chi2", "poses", "lms"):
-            assert _same_bits(new["reset/g%d/%s" % (gi, f)], new["fresh/g%d/%s" % (gi, f)]), (gi, f)
+            assert same_bits(new["reset/g%d/%s" % (gi, f)], new["fresh/g%d/%s" % (gi, f)]), (gi, f)
         # (the third count is the size of the record twin: a handle out of the pool may bring a larger one along)
         assert new["reset/g%d/counts" % gi][:2].tolist() == new["fresh/g%d/counts" % gi][:2].tolist()
     assert new["stop/before/counts"][:2].tolist() == [0, 0]
@@ -162,7 +128,7 @@ def test_stop_flag_during_a_run(synth, tmp_path):
     with the estimate the old slot has after optimize(k)"""
     P, L = 50, 5000
     g = synth.ba_graph(P, L)
-    o = _opt(g)
+    o = opt(g)
     flag = np.zeros(1, np.uint8)
     o.setForceStopFlag(flag)
 
@@ -182,8 +148,8 @@ def test_stop_flag_during_a_run(synth, tmp_path):
         return
     old = _old_slot(tmp_path, "iters", P, L, k, LM)
     for f in ("trials", "lambda", "poses", "lms"):
-        assert _same_bits(new["iters/" + f], old["iters/" + f]), f
-    assert _same_bits(new["iters/chi2"][:k], old["iters/chi2"][:k])
+        assert same_bits(new["iters/" + f], old["iters/" + f]), f
+    assert same_bits(new["iters/chi2"][:k], old["iters/chi2"][:k])
 
 
 def expected_linearisations(st, mode):
@@ -217,7 +183,7 @@ def test_linearisation_counts_follow_from_the_oracle(oracle, synth):
     for gi, g in enumerate(_graphs(synth)):
         for mode in (LM, GN):
             _, _, st = oracle.ba_optimize(g, 10, mode)
-            o = _opt(g)
+            o = opt(g)
             o.optimize(10, mode)
             runs, skips, twin = o.linearize_counts()
             print("graph", gi, "mode", mode, "trials", st["trials_hist"], "runs", runs, "skips", skips)
@@ -232,7 +198,7 @@ def test_linearisation_counts_follow_from_the_oracle(oracle, synth):
 def test_30kf_2000_landmarks_match_oracle(oracle, synth, mode):
     """the assertions of test_lm_10_iterations_match_oracle on ba_graph(30, 2000), LM and GN"""
     g = synth.ba_graph(30, 2000)
-    o = _opt(g)
+    o = opt(g)
     assert o.optimize(10, mode) == 10
     p_ref, l_ref, st = oracle.ba_optimize(g, 10, mode)
     s = o.stats
@@ -242,7 +208,7 @@ def test_30kf_2000_landmarks_match_oracle(oracle, synth, mode):
     assert s["chi2_init"] == pytest.approx(st["chi2_init"], rel=1e-12)
     assert s["chi2_final"] == pytest.approx(st["chi2_final"], rel=REL)
     poses, lms = o.estimates()
-    _pose_update_close(poses, p_ref, g.poses)
+    pose_update_close(poses, p_ref, g.poses)
     dl = np.abs((lms - g.lms) - (l_ref - g.lms)).max()
     assert dl <= REL * np.abs(l_ref - g.lms).max()
     assert o.activeRobustChi2() == pytest.approx(s["chi2_final"], rel=1e-12)
@@ -278,4 +244,4 @@ def test_no_twin_records_for_a_window_that_only_ran_in_a_resident_batch(tmp_path
 
 
 if __name__ == "__main__":
-    _child_main(sys.argv[1:])
+    ba_ab.child_main(_child_scenarios, sys.argv[1:])

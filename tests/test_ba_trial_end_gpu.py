@@ -5,18 +5,16 @@ finisher workgroup of k_update), the SE3-expmap model (k6_finalize<Expmap>), the
 import numpy as np
 import pytest
 
-from test_ba_gpu import LM_REJECT_CASES, _kidnapped, _opt, _sharded_equals_single
-from test_ba_window_se3_gpu import REJECT, _kidnapped3, _opt3, _resident
-from test_pg_gpu import _pg
 import pg_cases
+from ba_cases import LM_REJECT_CASES, REJECT, env, kidnapped, kidnapped3, opt, opt3, pg, sharded_equals_single
 
 pytestmark = pytest.mark.gpu
 
 # model -> (handle of a graph, the smallest graph the generator makes for it, a start whose trials get rejected)
 MODELS = {
-    "se2": (_opt, lambda s: s.ba_graph(8, 60), lambda s: _kidnapped(s, *LM_REJECT_CASES[2][0])),
-    "se3": (_opt3, lambda s: s.ba3_graph(8, 60, 0), lambda s: _kidnapped3(s, *REJECT)),
-    "pose_graph": (_pg, lambda s: s.pose_graph(12), lambda s: pg_cases.rejecting(24, 1, 7)),
+    "se2": (opt, lambda s: s.ba_graph(8, 60), lambda s: kidnapped(s, *LM_REJECT_CASES[2][0])),
+    "se3": (opt3, lambda s: s.ba3_graph(8, 60, 0), lambda s: kidnapped3(s, *REJECT)),
+    "pose_graph": (pg, lambda s: s.pose_graph(12), lambda s: pg_cases.rejecting(24, 1, 7)),
 }
 
 
@@ -30,7 +28,7 @@ def test_stop_flag_and_zero_iterations(synth, model):
     estimates untouched; lowered again the same handle runs like a fresh one, to the bit.  optimize(0) evaluates the start."""
     make, graph, _ = MODELS[model]
     g = graph(synth)
-    with _resident("0"):   # (the SE3 model: the multi-launch path, as _multi_launch of test_ba_window_se3_gpu takes it)
+    with env(SE2GPU_BA_RESIDENT="0"):   # (the SE3 model: the multi-launch path, as ba_cases.multi_launch takes it)
         o = make(g)
         start = o.estimates()
         flag = np.ones(1, np.uint8)
@@ -58,7 +56,7 @@ def test_synchronous_controller_equals_the_asynchronous_one(synth, model):
     asynchronous run."""
     make, graph, reject = MODELS[model]
     g = (reject or graph)(synth)
-    with _resident("0"):
+    with env(SE2GPU_BA_RESIDENT="0"):
         a = make(g)
         a.optimize(10)
         v = make(g)
@@ -79,7 +77,7 @@ def test_sharded_stop(synth):
     """Two landmark shards on one GPU with the flag raised on both ranks before the run: k_lm_decide's stop branch.  No
     iteration on either rank, `stopped`, the replicated poses untouched."""
     g = synth.ba_graph(8, 60)
-    single, results = _sharded_equals_single(g, 10, stop=np.ones(1, np.uint8))
+    single, results = sharded_equals_single(g, 10, stop=np.ones(1, np.uint8))
     assert single.stats["iterations"] == 0 and single.stats["stopped"]
     for st, (poses, _) in results:
         assert st["iterations"] == 0 and st["stopped"]

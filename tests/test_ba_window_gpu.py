@@ -7,47 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from test_ba_gpu import LM_REJECT_CASES, _kidnapped, _opt
-
-
-def _merged_landmarks(synth, P=40, L=240, groups=12, per_group=3):
-    """landmarks with 17 to 64 observations (the wave-per-landmark class): the generator's landmarks are seen from a dozen
-    neighbouring key frames at most, so `per_group` landmarks whose observers do not overlap are fused into one - its observations
-    then disagree about where it is, which the robust least squares takes like any other outlier-ridden point"""
-    import copy
-    g = copy.copy(synth.ba_graph(P, L))
-    e_kf, e_lm = np.asarray(g.e_kf).copy(), np.asarray(g.e_lm).copy()
-    seen = [set(e_kf[e_lm == l].tolist()) for l in range(g.L)]
-    used, fused = set(), 0
-    for a in range(g.L):
-        if fused == groups:
-            break
-        if a in used:
-            continue
-        members, kfs = [a], set(seen[a])
-        for b in range(a + 1, g.L):
-            if b not in used and not (kfs & seen[b]):
-                members.append(b)
-                kfs |= seen[b]
-                if len(members) == per_group:
-                    break
-        if len(members) == per_group:
-            used.update(members)
-            for b in members[1:]:
-                e_lm[e_lm == b] = a
-            fused += 1
-    assert fused == groups
-    keep = np.unique(e_lm)                       # the fused-away landmarks leave the graph
-    renum = np.full(g.L, -1, np.int64)
-    renum[keep] = np.arange(len(keep))
-    e_lm = renum[e_lm]
-    g.lms = np.asarray(g.lms)[keep].copy()
-    if g.lms_true is not None:
-        g.lms_true = np.asarray(g.lms_true)[keep].copy()
-    order = np.argsort(e_lm, kind="stable")
-    g.e_kf, g.e_lm = e_kf[order].astype(np.int32), e_lm[order].astype(np.int32)
-    g.e_uv, g.e_info = np.asarray(g.e_uv)[order].copy(), np.asarray(g.e_info)[order].copy()
-    return g
+from ba_cases import LM_REJECT_CASES, env, kidnapped, merged_landmarks, multi_launch, odo_graph, opt
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-9      # cost / lambda histories against the multi-launch path and the oracle (observed: 1e-12)
@@ -56,27 +16,12 @@ RTOL = 1e-9      # cost / lambda histories against the multi-launch path and the
 @pytest.fixture
 def resident():
     """every batch through the resident kernel, whatever its size (SE2GPU_BA_RESIDENT is read per call)"""
-    old = os.environ.get("SE2GPU_BA_RESIDENT")
-    os.environ["SE2GPU_BA_RESIDENT"] = "1"
-    yield
-    if old is None:
-        os.environ.pop("SE2GPU_BA_RESIDENT", None)
-    else:
-        os.environ["SE2GPU_BA_RESIDENT"] = old
+    with env(SE2GPU_BA_RESIDENT="1"):
+        yield
 
 
 def _multi_launch(g, iters, mode=0):
-    old = os.environ.get("SE2GPU_BA_RESIDENT")
-    os.environ["SE2GPU_BA_RESIDENT"] = "0"
-    try:
-        o = _opt(g)
-        o.optimize(iters, mode) if mode else o.optimize(iters)
-        return o.stats, o.estimates()
-    finally:
-        if old is None:
-            os.environ.pop("SE2GPU_BA_RESIDENT", None)
-        else:
-            os.environ["SE2GPU_BA_RESIDENT"] = old
+    return multi_launch(g, iters, mode)[:2]
 
 
 def _same(o, st, est, what):
@@ -96,12 +41,12 @@ def test_resident_batch_equals_multi_launch_and_the_oracle(oracle, synth, reside
     trials - in one batch: g2o's decisions trial for trial, costs and poses to 1e-9"""
     from se2lam_amd.optimizer import optimize_batch
     graphs = [synth.ba_graph(8, 60), synth.ba_graph(21, 800), synth.ba_graph(50, 5000), synth.ba_graph(30, 2000),
-              synth.ba_graph(20, 200, obs_per_lm=14.0), synth.ba_graph(40, 150, obs_per_lm=30.0), _merged_landmarks(synth)] + \
-             [_kidnapped(synth, *c[0]) for c in LM_REJECT_CASES]
+              synth.ba_graph(20, 200, obs_per_lm=14.0), synth.ba_graph(40, 150, obs_per_lm=30.0), merged_landmarks(synth)] + \
+             [kidnapped(synth, *c[0]) for c in LM_REJECT_CASES]
     kmax = [int(np.bincount(np.asarray(g.e_lm), minlength=g.L).max()) for g in graphs[:7]]
     assert max(kmax) > 16 and any(8 < k <= 16 for k in kmax), kmax                  # the wide-landmark classes are exercised
     ref = [_multi_launch(g, 10) for g in graphs]
-    opts = [_opt(g) for g in graphs]
+    opts = [opt(g) for g in graphs]
     its = optimize_batch(opts, 10)
     for g, o, (st, est), n in zip(graphs, opts, ref, its):
         assert n == st["iterations"]
@@ -116,8 +61,8 @@ def test_resident_batch_equals_multi_launch_and_the_oracle(oracle, synth, reside
 
 def test_resident_batch_repeats_gauss_newton_short_runs_and_the_stop_flag(synth, resident):
     from se2lam_amd.optimizer import optimize_batch, reset_estimates_batch
-    graphs = [synth.ba_graph(8, 60), synth.ba_graph(30, 2000), _kidnapped(synth, *LM_REJECT_CASES[2][0]), synth.ba_graph(50, 5000)]
-    opts = [_opt(g) for g in graphs]
+    graphs = [synth.ba_graph(8, 60), synth.ba_graph(30, 2000), kidnapped(synth, *LM_REJECT_CASES[2][0]), synth.ba_graph(50, 5000)]
+    opts = [opt(g) for g in graphs]
     for mode, iters in ((0, 10), (1, 10), (0, 4), (0, 0)):
         ref = [_multi_launch(g, iters, mode) for g in graphs]
         for rep in range(2):                       # the second run starts from the reset estimates on the same handles
@@ -154,7 +99,7 @@ def test_windows_too_large_for_the_lds_fall_back(synth, resident):
     from se2lam_amd.optimizer import optimize_batch
     graphs = [synth.ba_graph(8, 60), synth.ba_graph(80, 1500)]
     ref = [_multi_launch(g, 6) for g in graphs]
-    opts = [_opt(g) for g in graphs]
+    opts = [opt(g) for g in graphs]
     optimize_batch(opts, 6)
     for o, (st, est) in zip(opts, ref):
         assert o.stats == st and np.array_equal(o.estimates()[0], est[0])       # (the multi-launch paths are bit-identical)
@@ -167,10 +112,10 @@ def test_default_threshold_keeps_small_batches_on_the_multi_launch_paths(synth):
     os.environ.pop("SE2GPU_BA_RESIDENT", None)
     g = synth.ba_graph(21, 800)
     st, est = _multi_launch(g, 8)
-    small = [_opt(g) for _ in range(3)]
+    small = [opt(g) for _ in range(3)]
     optimize_batch(small, 8)
     assert all(o.stats == st and np.array_equal(o.estimates()[0], est[0]) for o in small)
-    large = [_opt(g) for _ in range(100)]
+    large = [opt(g) for _ in range(100)]
     optimize_batch(large, 8)
     for o in large:
         _same(o, st, est, "100 windows")
@@ -185,7 +130,7 @@ def test_a_window_of_the_128_thread_class_keeps_the_batch_off_the_resident_path_
     small, big = synth.ba_graph(8, 60), synth.ba_graph(62, 400)
     refs = [_multi_launch(small, 5), _multi_launch(big, 5)]
     os.environ.pop("SE2GPU_BA_RESIDENT", None)
-    opts = [_opt(small) for _ in range(99)] + [_opt(big)]
+    opts = [opt(small) for _ in range(99)] + [opt(big)]
     optimize_batch(opts, 5)
     assert capi.lib().se2gpu_ba_last_batch_path() != 2
     for o in opts[:3]:
@@ -193,7 +138,7 @@ def test_a_window_of_the_128_thread_class_keeps_the_batch_off_the_resident_path_
     assert opts[-1].stats == refs[1][0] and np.array_equal(opts[-1].estimates()[0], refs[1][1][0])
     os.environ["SE2GPU_BA_RESIDENT"] = "1"
     try:
-        forced = [_opt(small), _opt(big)]
+        forced = [opt(small), opt(big)]
         optimize_batch(forced, 5)
         assert capi.lib().se2gpu_ba_last_batch_path() == 2
         _same(forced[0], *refs[0], "small window, forced")
@@ -227,7 +172,7 @@ def test_resident_edge_cases(synth, resident):
     single.e_uv, single.e_info = np.asarray(single.e_uv)[keep], np.asarray(single.e_info)[keep]
     graphs = [two, no_odo, one_free, all_fixed, single]
     ref = [_multi_launch(g, 6) for g in graphs]
-    opts = [_opt(g) for g in graphs]
+    opts = [opt(g) for g in graphs]
     optimize_batch(opts, 6)
     from se2lam_amd import capi
     assert int(capi.lib().se2gpu_ba_last_batch_path()) == 2
@@ -243,7 +188,7 @@ def test_a_batch_of_distinct_windows_over_both_workgroup_widths(synth, resident)
     graphs = synth.mixed_windows(24, p_range=(30, 60), l_range=(300, 900), kidnapped_every=5)
     assert min(g.P for g in graphs) < 40 and max(g.P for g in graphs) >= 58          # both widths are in the batch
     ref = [_multi_launch(g, 8) for g in graphs]
-    opts = [_opt(g) for g in graphs]
+    opts = [opt(g) for g in graphs]
     optimize_batch(opts, 8)
     assert int(capi.lib().se2gpu_ba_last_batch_path()) == 2
     for g, o, (st, est) in zip(graphs, opts, ref):
@@ -264,7 +209,7 @@ def test_a_window_without_room_for_the_record_copy_is_left_to_the_other_paths(sy
     g.e_uv, g.e_info = np.asarray(g.e_uv)[keep], np.asarray(g.e_info)[keep]
     assert 16 * g.L + 44 * int(keep.sum()) > 72 * int(keep.sum())
     st, est = _multi_launch(g, 6)
-    o = _opt(g)
+    o = opt(g)
     optimize_batch([o], 6)
     if int(capi.lib().se2gpu_ba_last_batch_path()) == 2:
         _same(o, st, est, "a handle from the pool whose buffer had grown on a larger window before: room after all")
@@ -285,12 +230,11 @@ def test_resident_odometry_topologies(oracle, synth, resident):
     pair in either direction: every window equal to its multi-launch run and to the oracle"""
     from se2lam_amd import capi
     from se2lam_amd.optimizer import optimize_batch
-    from test_ba_gpu import _odo_graph
     cases = [(21, 800, k) for k in ("reversed", "shuffled", "long", "hub9", "hub12", "hub20", "fixed_ends", "duplicate", "duplicate_long")]
     cases += [(50, 3000, k) for k in ("reversed", "long", "hub12", "fixed_ends")]
-    graphs = [_odo_graph(synth, *c) for c in cases]
+    graphs = [odo_graph(synth, *c) for c in cases]
     ref = [_multi_launch(g, 10) for g in graphs]
-    opts = [_opt(g) for g in graphs]
+    opts = [opt(g) for g in graphs]
     its = optimize_batch(opts, 10)
     assert int(capi.lib().se2gpu_ba_last_batch_path()) == 2
     for c, g, o, (st, est), n in zip(cases, graphs, opts, ref, its):
@@ -305,10 +249,9 @@ def test_a_self_loop_keeps_the_batch_off_the_resident_path(oracle, synth, reside
     forced; every window still equals its multi-launch run and the oracle"""
     from se2lam_amd import capi
     from se2lam_amd.optimizer import optimize_batch
-    from test_ba_gpu import _odo_graph
-    graphs = [synth.ba_graph(8, 60), _odo_graph(synth, 21, 800, "self_loop"), _odo_graph(synth, 8, 60, "self_loop")]
+    graphs = [synth.ba_graph(8, 60), odo_graph(synth, 21, 800, "self_loop"), odo_graph(synth, 8, 60, "self_loop")]
     ref = [_multi_launch(g, 10) for g in graphs]
-    opts = [_opt(g) for g in graphs]
+    opts = [opt(g) for g in graphs]
     optimize_batch(opts, 10)
     assert int(capi.lib().se2gpu_ba_last_batch_path()) != 2
     for g, o, (st, est) in zip(graphs, opts, ref):
@@ -359,7 +302,7 @@ def test_a_landmark_of_65_observations_is_refused_and_run_elsewhere(oracle, synt
         wide = _wide_landmark(synth, k)
         graphs = [small, wide]
         ref = [_multi_launch(g, 8) for g in graphs]
-        opts = [_opt(g) for g in graphs]
+        opts = [opt(g) for g in graphs]
         optimize_batch(opts, 8)
         assert int(capi.lib().se2gpu_ba_last_batch_path()) == 2
         _same(opts[0], *ref[0], ("ordinary window next to", k))

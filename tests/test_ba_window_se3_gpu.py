@@ -2,43 +2,17 @@
 Map::loadLocalGraph + LocalMapper::removeOutlierChi2 with EdgeProjectXYZ2UV, EdgeSE3ExpmapPrior and EdgeSE3Expmap).  Sums into the
 reduced system are LDS atomics (no fixed order), so the path is held to the multi-launch k3_* path and to the oracle trial for trial
 and to 1e-9 on costs, poses and landmarks - not bit for bit.  Paths that do not take a batch stay bit-identical to one-by-one runs."""
-import contextlib
 import copy
-import os
+import functools
 
 import numpy as np
 import pytest
 
 from se2lam_amd import synth as _synth            # (for a parametrisation; tests take the `synth` fixture)
-from test_ba_gpu import _opt
+from ba_cases import REJECT, env, kidnapped3, multi_launch, odo_graph3, odometry_cases3, opt, opt3
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-9
-
-
-def _opt3(g):
-    from se2lam_amd import optimizer as op
-    o = op.SlamOptimizer()
-    op.load_se3_graph(o, g)
-    o.initializeOptimization(0)
-    return o
-
-
-@contextlib.contextmanager
-def _resident(value):
-    """SE2GPU_BA_RESIDENT for the body (None: unset); it is read per call"""
-    old = os.environ.get("SE2GPU_BA_RESIDENT")
-    if value is None:
-        os.environ.pop("SE2GPU_BA_RESIDENT", None)
-    else:
-        os.environ["SE2GPU_BA_RESIDENT"] = value
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop("SE2GPU_BA_RESIDENT", None)
-        else:
-            os.environ["SE2GPU_BA_RESIDENT"] = old
 
 
 def _last_path():
@@ -51,12 +25,7 @@ def _edge_chi2(o, g):
     return op.edgeChi2(o, g.E)
 
 
-def _multi_launch(g, iters, mode=0, make=_opt3):
-    """one optimize() on the multi-launch path: stats, estimates and (SE3) the chi2() of every projection edge afterwards"""
-    with _resident("0"):
-        o = make(g)
-        o.optimize(iters, mode)
-        return o.stats, o.estimates(), (_edge_chi2(o, g) if make is _opt3 else None)
+_multi_launch = functools.partial(multi_launch, make=opt3)
 
 
 def _same(o, ref, what, g=None):
@@ -78,20 +47,6 @@ def _same(o, ref, what, g=None):
         assert np.array_equal(got > 25, ec > 25), what                          # removeOutlierChi2's list
 
 
-def _kidnapped3(synth, P, L, n_ref, dxy, dth, nbad, seed):
-    """an SE3 window whose start has a few key frames moved by metres and tens of degrees in the plane: LM rejects trials"""
-    g = copy.copy(synth.ba3_graph(P, L, n_ref))
-    rng = np.random.default_rng(seed)
-    g.poses = g.poses.copy()
-    for a in rng.choice(np.arange(1, g.P - n_ref), nbad, replace=False):
-        th = rng.normal(0, dth)
-        M = np.eye(4)
-        M[:2, :2] = [[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]
-        M[:2, 3] = rng.normal(0, dxy, 2)
-        g.poses[a] = g.poses[a] @ M
-    return g
-
-
 def _renumber(g, e_kf, e_lm):
     keep = np.unique(e_lm)                       # landmarks that lost all their observations leave the graph
     renum = np.full(g.L, -1, np.int64)
@@ -106,7 +61,7 @@ def _renumber(g, e_kf, e_lm):
 
 def _merged3(synth, P=26, L=700, groups=10, per_group=4):
     """landmarks with 9 to 64 observations (the 16-lane and wave-per-landmark classes): up to `per_group` landmarks whose observers
-    do not overlap are fused into one (tests/test_ba_window_gpu.py, _merged_landmarks)"""
+    do not overlap are fused into one (as tests/ba_cases.py, merged_landmarks)"""
     g = copy.copy(synth.ba3_graph(P, L, 0))
     e_kf, e_lm = np.asarray(g.e_kf).copy(), np.asarray(g.e_lm).copy()
     seen = [set(e_kf[e_lm == l].tolist()) for l in range(g.L)]
@@ -151,12 +106,9 @@ def _wide3(synth, k, P=70, L=1500, n_ref=50):
     return g
 
 
-REJECT = (21, 800, 0, 3000.0, 0.8, 2, 3)   # the oracle: trials [1, 1, 6, 3, 1, 3, 2, 3, 1, 2]
-
-
 def _forced_graphs(synth):
     return [synth.ba3_graph(8, 60, 0), synth.ba3_graph(21, 800, 0), synth.ba3_graph(21, 800, 4), synth.ba3_graph(30, 2000, 6),
-            _kidnapped3(synth, *REJECT), _merged3(synth)]
+            kidnapped3(synth, *REJECT), _merged3(synth)]
 
 
 def test_forced_se3_batch_equals_multi_launch_and_the_oracle(oracle, synth):
@@ -168,8 +120,8 @@ def test_forced_se3_batch_equals_multi_launch_and_the_oracle(oracle, synth):
     assert kmax > 16 and ((cnt > 8) & (cnt <= 16)).any(), kmax                                # 16-lane and whole-wave classes
     ref = [_multi_launch(g, 10) for g in graphs]
     assert max(ref[4][0]["trials_hist"]) > 1, ref[4][0]["trials_hist"]                        # the kidnapped start rejects trials
-    opts = [_opt3(g) for g in graphs]
-    with _resident("1"):
+    opts = [opt3(g) for g in graphs]
+    with env(SE2GPU_BA_RESIDENT="1"):
         its = optimize_batch(opts, 10)
     assert _last_path() == 2
     for g, o, r, n in zip(graphs, opts, ref, its):
@@ -183,9 +135,9 @@ def test_forced_se3_batch_equals_multi_launch_and_the_oracle(oracle, synth):
 
 def test_se3_modes_repeats_and_the_stop_flag(synth):
     from se2lam_amd.optimizer import optimize_batch, reset_estimates_batch
-    graphs = [synth.ba3_graph(8, 60, 0), synth.ba3_graph(21, 800, 4), _kidnapped3(synth, *REJECT)]
-    opts = [_opt3(g) for g in graphs]
-    with _resident("1"):
+    graphs = [synth.ba3_graph(8, 60, 0), synth.ba3_graph(21, 800, 4), kidnapped3(synth, *REJECT)]
+    opts = [opt3(g) for g in graphs]
+    with env(SE2GPU_BA_RESIDENT="1"):
         for mode, iters in ((0, 10), (1, 10), (0, 4), (0, 0)):
             ref = [_multi_launch(g, iters, mode) for g in graphs]
             for rep in range(2):                   # the second run starts from the reset estimates on the same handles
@@ -217,19 +169,19 @@ def test_se3_outlier_flow(synth):
     """LocalMapper::removeOutlierChi2: optimize, drop the edges whose chi2() exceeds 25, re-initialise, optimize again - both
     batches resident, equal to the same flow on the multi-launch path"""
     from se2lam_amd.optimizer import optimize_batch
-    graphs = [synth.ba3_graph(21, 800, 4), _kidnapped3(synth, *REJECT), synth.ba3_graph(30, 2000, 6)]
+    graphs = [synth.ba3_graph(21, 800, 4), kidnapped3(synth, *REJECT), synth.ba3_graph(30, 2000, 6)]
     ref1 = [_multi_launch(g, 5) for g in graphs]
     second = [_without(g, r[2] > 25) for g, r in zip(graphs, ref1)]
     assert sum(int((r[2] > 25).sum()) for r in ref1) > 0
     ref2 = [_multi_launch(g, 10) for g in second]
-    with _resident("1"):
-        opts = [_opt3(g) for g in graphs]
+    with env(SE2GPU_BA_RESIDENT="1"):
+        opts = [opt3(g) for g in graphs]
         optimize_batch(opts, 5)
         assert _last_path() == 2
         for g, o, r in zip(graphs, opts, ref1):
             _same(o, r, ("first", g.P), g)
             assert np.array_equal(_edge_chi2(o, g) > 25, r[2] > 25)
-        opts = [_opt3(g) for g in second]
+        opts = [opt3(g) for g in second]
         optimize_batch(opts, 10)
         assert _last_path() == 2
         for g, o, r in zip(second, opts, ref2):
@@ -240,10 +192,10 @@ def test_mixed_se2_and_se3_batch(synth):
     from se2lam_amd.optimizer import optimize_batch
     g2 = [synth.ba_graph(8, 60), synth.ba_graph(21, 800), synth.ba_graph(50, 5000)]
     g3 = [synth.ba3_graph(8, 60, 0), synth.ba3_graph(21, 800, 4), synth.ba3_graph(30, 2000, 6)]
-    ref = [_multi_launch(g, 8, make=_opt) for g in g2] + [_multi_launch(g, 8) for g in g3]
-    opts = [_opt(g) for g in g2] + [_opt3(g) for g in g3]
+    ref = [_multi_launch(g, 8, make=opt) for g in g2] + [_multi_launch(g, 8) for g in g3]
+    opts = [opt(g) for g in g2] + [opt3(g) for g in g3]
     order = [0, 3, 1, 4, 2, 5]                     # interleaved in the call
-    with _resident("1"):
+    with env(SE2GPU_BA_RESIDENT="1"):
         optimize_batch([opts[i] for i in order], 8)
     assert _last_path() == 2
     for i, (o, r) in enumerate(zip(opts, ref)):
@@ -256,8 +208,8 @@ def test_se3_windows_too_large_or_too_wide(oracle, synth):
     from se2lam_amd.optimizer import optimize_batch
     graphs = [synth.ba3_graph(8, 60, 0), synth.ba3_graph(50, 5000, 0)]
     ref = [_multi_launch(g, 6) for g in graphs]
-    opts = [_opt3(g) for g in graphs]
-    with _resident("1"):
+    opts = [opt3(g) for g in graphs]
+    with env(SE2GPU_BA_RESIDENT="1"):
         optimize_batch(opts, 6)
     assert _last_path() != 2
     for o, (st, est, _) in zip(opts, ref):
@@ -266,8 +218,8 @@ def test_se3_windows_too_large_or_too_wide(oracle, synth):
     for k in (65, 64):
         wide = _wide3(synth, k)
         ref = [_multi_launch(g, 8) for g in (small, wide)]
-        opts = [_opt3(small), _opt3(wide)]
-        with _resident("1"):
+        opts = [opt3(small), opt3(wide)]
+        with env(SE2GPU_BA_RESIDENT="1"):
             optimize_batch(opts, 8)
         assert _last_path() == 2
         _same(opts[0], ref[0], ("ordinary window next to", k), small)
@@ -284,14 +236,14 @@ def test_se3_default_threshold(synth):
     from se2lam_amd.optimizer import optimize_batch
     g = synth.ba3_graph(8, 60, 0)
     ref = _multi_launch(g, 6)
-    with _resident(None):
-        small = [_opt3(g) for _ in range(95)]
+    with env(SE2GPU_BA_RESIDENT=None):
+        small = [opt3(g) for _ in range(95)]
         optimize_batch(small, 6)
         assert _last_path() != 2
         for o in small:
             assert o.stats == ref[0] and np.array_equal(o.estimates()[0], ref[1][0]) and np.array_equal(o.estimates()[1], ref[1][1])
         del small
-        large = [_opt3(g) for _ in range(96)]
+        large = [opt3(g) for _ in range(96)]
         optimize_batch(large, 6)
         assert _last_path() == 2
         for o in large[::8]:
@@ -309,7 +261,7 @@ KIDNAP_REVERSED_LONG = (21, 800, 0, 3000.0, 0.8, 2, 8)   # the oracle (picked wi
 def _kidnapped_reversed_long(synth):
     """a kidnapped start under the `reversed` chain plus the `long` kind's extra edges: rejected trials re-evaluate edges stored as
     (i > j) and edges between key frames without a common landmark"""
-    k = _kidnapped3(synth, *KIDNAP_REVERSED_LONG)
+    k = kidnapped3(synth, *KIDNAP_REVERSED_LONG)
     rv, lg = synth.odometry_topology3(k, "reversed"), synth.odometry_topology3(k, "long")
     extra = list(zip(lg.o_i[rv.O:].tolist(), lg.o_j[rv.O:].tolist()))
     cov = synth.covisible(k)
@@ -322,7 +274,6 @@ def _kidnapped_reversed_long(synth):
 def _resident_cases3(synth, kind):
     """the windows of `kind` that fit the resident kernel: RESIDENT_SIZES3, and 20 local + 50 reference key frames for to_reference
     and dense"""
-    from test_ba3_oracle import odo_graph3, odometry_cases3
     cases = odometry_cases3(synth, RESIDENT_SIZES3, (kind,)) + odometry_cases3(synth, ((70, 1500, 50),), (kind,) if kind in ("to_reference", "dense") else ())
     assert cases, kind                                                       # every kind fits somewhere
     return [(c, odo_graph3(synth, *c)) for c in cases]
@@ -343,8 +294,8 @@ def test_forced_se3_odometry_topologies_equal_multi_launch_and_the_oracle(oracle
     ref = [_multi_launch(g, 10) for g in graphs]
     if kind == "kidnapped":
         assert max(ref[0][0]["trials_hist"]) > 1, ref[0][0]["trials_hist"]                    # the kidnapped start rejects trials
-    opts = [_opt3(g) for g in graphs]
-    with _resident("1"):
+    opts = [opt3(g) for g in graphs]
+    with env(SE2GPU_BA_RESIDENT="1"):
         its = optimize_batch(opts, 10)
     assert _last_path() == 2
     for (c, g), o, r, n in zip(cases, opts, ref, its):
@@ -396,29 +347,29 @@ def test_se3_lds_limits(synth):
     from se2lam_amd.optimizer import optimize_batch
     w27, w28, w29, w30 = _limit_windows(synth)
     ref = [_multi_launch(g, 8) for g in (w27, w28, w29, w30)]
-    opts = [_opt3(g) for g in (w27, w28, w29)]
-    with _resident("1"):
+    opts = [opt3(g) for g in (w27, w28, w29)]
+    with env(SE2GPU_BA_RESIDENT="1"):
         optimize_batch(opts, 8)
     assert _last_path() == 2
     for g, o, r in zip((w27, w28, w29), opts, ref):
         _same(o, r, ("free", g.P - 2), g)
-    opts = [_opt3(g) for g in (w27, w30)]
-    with _resident("1"):
+    opts = [opt3(g) for g in (w27, w30)]
+    with env(SE2GPU_BA_RESIDENT="1"):
         optimize_batch(opts, 8)
     assert _last_path() != 2
     for o, (st, est, _) in zip(opts, (ref[0], ref[3])):
         assert o.stats == st and np.array_equal(o.estimates()[0], est[0]) and np.array_equal(o.estimates()[1], est[1])
     small = synth.odometry_topology3(synth.ba3_graph(8, 60, 0), "reversed")
     rs = _multi_launch(small, 8)
-    with _resident(None):
-        opts = [_opt3(small) for _ in range(95)] + [_opt3(w28)]
+    with env(SE2GPU_BA_RESIDENT=None):
+        opts = [opt3(small) for _ in range(95)] + [opt3(w28)]
         optimize_batch(opts, 8)
         assert _last_path() != 2
         for o in opts[:3]:
             assert o.stats == rs[0] and np.array_equal(o.estimates()[0], rs[1][0])
         assert opts[-1].stats == ref[1][0] and np.array_equal(opts[-1].estimates()[0], ref[1][1][0])
         del opts
-        opts = [_opt3(small) for _ in range(95)] + [_opt3(w27)]               # (with a 27-free window instead the batch goes resident)
+        opts = [opt3(small) for _ in range(95)] + [opt3(w27)]               # (with a 27-free window instead the batch goes resident)
         optimize_batch(opts, 8)
         assert _last_path() == 2
         _same(opts[-1], ref[0], "27 free among 96", w27)

@@ -4,23 +4,16 @@ Cost and pose updates within 1e-5 relative (BASELINE north_star's BA tolerance).
 import numpy as np
 import pytest
 
+from ba_cases import REL, pg
+
 pytestmark = pytest.mark.gpu
-REL = 1e-5
-
-
-def _pg(g):
-    from se2lam_amd import optimizer as op
-    o = op.SlamOptimizer()
-    op.load_pose_graph(o, g)
-    o.initializeOptimization(0)
-    return o
 
 
 @pytest.mark.parametrize("P", [12, 60, 200])
 def test_system_and_chi2_match_oracle(oracle, synth, P):
     from se2lam_amd import optimizer as op
     g = synth.pose_graph(P)
-    o = _pg(g)
+    o = pg(g)
     c, ec = oracle.pg_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.O), ec, rtol=1e-9, atol=1e-12)
@@ -36,7 +29,7 @@ def test_global_ba_matches_oracle(oracle, synth, P):
     """optimize(GLOBAL_ITER) on all key frames: LM history, poses, per-edge chi2 (the feature-edge rejection rule)."""
     from se2lam_amd import optimizer as op
     g = synth.pose_graph(P)
-    o = _pg(g)
+    o = pg(g)
     assert o.optimize(10) == 10
     X, ec, st = oracle.pg_optimize(g, 10)
     s = o.stats
@@ -81,7 +74,7 @@ def test_reinitialise_over_the_level_0_edges(oracle, synth):
     for k in bad:
         g.o_meas[k] = g.o_meas[k].copy()
         g.o_meas[k][2, 3] += 800.0
-    o = _pg(g)
+    o = pg(g)
     o.optimize(8)
     ec = op.edgeChi2(o, g.O)
     out = np.nonzero(ec > 30.0)[0]

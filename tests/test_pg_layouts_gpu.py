@@ -17,8 +17,8 @@ import pytest
 
 import pg_cases
 import pg_model
-from test_pg_gpu import REL, _pg
-from test_pg_model import recorded
+from ba_cases import REL, opt, opt3, pg
+from pg_cases import recorded
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +66,7 @@ def _same_run_as_the_oracle(o, g, ref):
 def test_cost_and_system_match_the_oracle_and_the_model(oracle, kind, P):
     from se2lam_amd import optimizer as op
     g = pg_cases.layout(kind, P)
-    o = _pg(g)
+    o = pg(g)
     c, ec = oracle.pg_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.O), ec, rtol=1e-9, atol=1e-12)
@@ -88,7 +88,7 @@ def test_cost_and_system_match_the_oracle_and_the_model(oracle, kind, P):
 @pytest.mark.parametrize("kind,P", CASES)
 def test_optimize_matches_the_oracle_and_the_model(oracle, kind, P):
     g = pg_cases.layout(kind, P)
-    o = _pg(g)
+    o = pg(g)
     assert o.optimize(10) == 10
     got = _same_run_as_the_oracle(o, g, _oracle_run(oracle, (kind, P), g))
     assert o.stats["chi2_init"] == pytest.approx(pg_model.cost(g, g.poses)[0], rel=1e-9)
@@ -99,7 +99,7 @@ def test_optimize_matches_the_oracle_and_the_model(oracle, kind, P):
 @pytest.mark.parametrize("case", REJECTING, ids=_ids)
 def test_rejected_trials_match_the_oracle_and_the_model(oracle, case):
     g = pg_cases.rejecting(*case)
-    o = _pg(g)
+    o = pg(g)
     o.optimize(10)
     assert max(o.stats["trials_hist"]) > 1, o.stats["trials_hist"]
     got = _same_run_as_the_oracle(o, g, _oracle_run(oracle, case, g))
@@ -113,11 +113,11 @@ def test_rejected_trials_synchronous_controller_and_graph_replay(case):
     optimize(10) four times over gives the same record and estimates each time (from the third call of a shape on the captured
     graph is replayed, and the rejected trials are enqueued after it)."""
     g = pg_cases.rejecting(*case)
-    a = _pg(g)
+    a = pg(g)
     a.optimize(10)
     first, est = a.stats, a.estimates()[0].copy()
     assert max(first["trials_hist"]) > 1, first["trials_hist"]
-    v = _pg(g)
+    v = pg(g)
     v.setVerbose(True)
     v.optimize(10)
     assert v.stats["trials_hist"] == first["trials_hist"]
@@ -142,7 +142,7 @@ def test_edge_levels_on_multi_edge_slots(oracle):
     assert g.has_prior[lone] and not g.fixed[lone]
     out = [key.index((1, 2))] + [k for k in range(g.O) if key[k] == (3, 4)] + [k for k in range(g.O) if lone in key[k]]
     out = np.unique(out)
-    o = _pg(g)
+    o = pg(g)
     o.optimize(8)
     first = _poses(o, g)
     for k in out:
@@ -176,9 +176,7 @@ def test_pose_graphs_inside_optimize_batch(synth):
     every handle's record and estimates equal its own optimize() to the bit."""
     from se2lam_amd import capi
     from se2lam_amd.optimizer import optimize_batch
-    from test_ba_gpu import _opt
-    from test_ba_window_se3_gpu import _opt3
-    graphs = [(_pg, pg_cases.layout(k, 6)) for k in pg_cases.KINDS] + [(_pg, pg_cases.rejecting(*c)) for c in REJECTING]
+    graphs = [(pg, pg_cases.layout(k, 6)) for k in pg_cases.KINDS] + [(pg, pg_cases.rejecting(*c)) for c in REJECTING]
     assert len(graphs) == 11
     refs = [_one_by_one(make, g) for make, g in graphs]
     assert max(refs[-1][0]["trials_hist"]) > 1 and max(refs[-2][0]["trials_hist"]) > 1
@@ -188,7 +186,7 @@ def test_pose_graphs_inside_optimize_batch(synth):
     for o, (st, est) in zip(opts, refs):
         assert o.stats == st
         assert all(np.array_equal(x, y) for x, y in zip(o.estimates(), est))
-    mixed = graphs[:5] + [(_opt, synth.ba_graph(8, 60))] + graphs[5:] + [(_opt3, synth.ba3_graph(8, 60, 0))]
+    mixed = graphs[:5] + [(opt, synth.ba_graph(8, 60))] + graphs[5:] + [(opt3, synth.ba3_graph(8, 60, 0))]
     refs = refs[:5] + [_one_by_one(*mixed[5])] + refs[5:] + [_one_by_one(*mixed[-1])]
     opts = [make(g) for make, g in mixed]
     optimize_batch(opts, 10)

@@ -20,24 +20,12 @@ if __name__ == "__main__":
 
 import pg_cases
 import pg_model
+from pg_cases import RECORD, recorded
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RECORD = os.path.join(ROOT, "profiles", "pg_layouts.md")
 SIZES = (6, 17)
 COND_MAX = 1e12
 # (the sizes the GPU tests add - 2, 3 and `complete` at 40 - are held to the same conditions: their rows are read there too)
 LAYOUTS = [(k, P) for P in (2, 3) + SIZES for k in pg_cases.kinds_at(P)] + [("complete", 40)]
-
-
-def recorded():
-    """{(kind, P): (bound on |H - H_model| / max |H_model|, bound on |b - b_model| / max |b_model|)} of profiles/pg_layouts.md"""
-    out = {}
-    with open(RECORD) as f:
-        for line in f:
-            c = [x.strip() for x in line.strip().strip("|").split("|")]
-            if len(c) == 8 and c[0] in pg_cases.KINDS:
-                out[(c[0], int(c[1]))] = (float(c[6]), float(c[7]))
-    return out
 
 
 def _bound(x):

@@ -606,7 +606,7 @@ def _reference_window(synth, n_ref):
     """A 12-key-frame window (tests/test_ba_oracle.py::_info_inputs) as a se2lam::Map: key frames with their key points,
     octaves and camera-frame points, map points, observations both ways, the odometry chain, a star of covisibility around
     key frame 0 that leaves the last n_ref key frames outside - they observe local map points and become reference key frames."""
-    from test_ba_oracle import _info_inputs
+    from ba_cases import _info_inputs
     inp, g, level = _info_inputs(synth, 12, 200)
     K = np.array([[g.fx, 0, g.cx], [0, g.fx, g.cy], [0, 0, 1]], np.float32)
     bTc = np.eye(4); bTc[:3, :3] = g.Rbc; bTc[:3, 3] = g.tbc

@@ -5,12 +5,12 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np
 from se2lam_amd import synth
 from se2lam_amd.optimizer import SlamOptimizer, optimize_batch, reset_estimates_batch
-import test_ba_gpu as T
+import ba_cases as T
 
 def opt(g):
     o = SlamOptimizer(); o.load(g); o.initializeOptimization(0); return o
 
-graphs = [T._kidnapped(synth, *c[0]) for c in T.LM_REJECT_CASES] + [synth.ba_graph(8, 60), synth.ba_graph(30, 2000), synth.ba_graph(50, 5000)]
+graphs = [T.kidnapped(synth, *c[0]) for c in T.LM_REJECT_CASES] + [synth.ba_graph(8, 60), synth.ba_graph(30, 2000), synth.ba_graph(50, 5000)]
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 bad = 0
 for rep in range(reps):

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 
 from se2lam_amd import optimizer as op, synth  # noqa: E402
-import test_ba_gpu as T  # noqa: E402
+import ba_cases as T  # noqa: E402
 
 verify = os.environ.get("SE2GPU_BA_CHOL_VERIFY") == "1"
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
@@ -49,7 +49,7 @@ def opt(g, loader=None):
 
 case, trials = T.LM_REJECT_CASES[seed % len(T.LM_REJECT_CASES)]
 P = 30 + 7 * (seed % 5)
-for name, g, loader in (("se2", synth.ba_graph(P, 30 * P), None), ("se2-reject", T._kidnapped(synth, *case), None),
+for name, g, loader in (("se2", synth.ba_graph(P, 30 * P), None), ("se2-reject", T.kidnapped(synth, *case), None),
                         ("se2-200kf", synth.ba_graph(200, 20000), None) if seed % 4 == 0 else ("se2-50kf", synth.ba_graph(50, 5000), None),
                         ("se3", synth.ba3_graph(12, 300, 2), op.load_se3_graph), ("posegraph", synth.pose_graph(40), op.load_pose_graph)):
     o = opt(g, loader)
@@ -78,7 +78,7 @@ for lockstep in ("1", "0"):
     for round_, iters in enumerate((3, 5, 2, 4, 6)):
         graphs = [synth.ba_graph(9 + round_ + k, 70 + 10 * k, seed=50 + 7 * round_ + k + 13 * seed) for k in range(6)]
         if round_ == 1:
-            graphs += [T._kidnapped(synth, *c[0]) for c in T.LM_REJECT_CASES[:3]]
+            graphs += [T.kidnapped(synth, *c[0]) for c in T.LM_REJECT_CASES[:3]]
         ref = []
         for g in graphs:
             o = opt(g)
