@@ -539,6 +539,99 @@ int se2gpu_local_window_batch_device(se2gpu_matcher* h, const uint64_t* d_bits_k
                                      int32_t* d_local_list, int32_t* d_ref_list, int kf_list_cap,
                                      int32_t* d_mp_list, int mp_list_cap);
 
+/* Local bundle adjustment on the tables where they lie in device memory: Map::loadLocalGraph (src/Map.cpp:891-1053 of the
+ * reference) on the lists se2gpu_local_window_batch_device wrote, chained to the one-workgroup-per-window solver that
+ * se2gpu_ba_optimize_batch uses for resident batches.  Every array pointer is device memory unless marked host.  Asynchronous
+ * on the matcher's stream (three launches: gather, solve, finish): nothing is allocated, nothing uploaded besides kernel
+ * arguments, nothing read back and nothing waited for; se2gpu_matcher_sync waits for it.
+ * The window, as se2gpu_local_window_batch_device wrote it: d_job_kf (njobs slots), d_win_out ({n_local, n_ref, n_mp, n_obs}
+ *   per job), d_local_list / d_ref_list (stride kf_list_cap), d_mp_list (stride mp_list_cap).  All three lists are required.
+ * Frame tables (nframes slots): d_frame_id (KeyFrame::id, which the fixed rule reads - not mIdKF); d_frame_Twb (3 floats: Se2
+ *   Twb); d_frame_Tcw (12 floats: rows 0-2 of Tcw, the table of se2gpu_mappoint_parallax_batch_device; Rcw is its 3 x 3 block);
+ *   d_frame_null (bytes, may be NULL: none is null); preOdomFromSelf as d_odo_to (the slot of .first, or -1), d_odo_meas (3
+ *   doubles) and d_odo_cov (9 doubles, row-major) - all three NULL means no odometry edges.
+ * Feature tables: d_kps_un (nframes x cap key points: x, y and octave are read), d_counts (nframes), cap, d_view_pos (nframes x
+ *   cap x 3 floats, mViewMPs); level_sigma2 is a HOST array of nlevels <= 32 floats (mvLevelSigma2), passed as kernel arguments.
+ * Point tables: d_pos (m x 3 floats) and the observation CSR of the points' own side (MapPoint::mObservations, the side d_bits_mp
+ *   was built from): d_mp_ptr (m + 1), d_obs_frame, d_obs_ftr (nobs), read by the entry and segment rules of obs_table.h.
+ * Configuration (host): fx, cx, cy (Config::Kcam; addCamPara uses fx for both axes); Tbc12 (HOST, 12 doubles: rotation row-major,
+ *   translation); huber_delta (Config::TH_HUBER); xrot_info, z_info (PLANEMOTION_XROT_INFO / _Z_INFO; their reciprocals are
+ *   rounded to float as :1043-1044 do); iters (1..64); mode (SE2GPU_BA_LM / SE2GPU_BA_GN); max_local, max_ref, max_mp, max_obs:
+ *   the sizes the workspace and the launch are cut for.
+ * The gather, one workgroup per job, writes the window's graph into the job's slice of d_ws:
+ *   vertices  local key frame i -> vertex i, reference key frame i -> n_local + i (:925, :966), map point i -> landmark i
+ *   fixed     a reference key frame always (:969); a local one when its id == 1, and with n_ref == 0 the local one(s) with the
+ *             least id (:899-927)
+ *   poses     doubles converted from the float Twb, the heading normalised as g2o::SE2's constructor does (:929)
+ *   odometry  (:935-956) for the local key frames i in order: an edge (i, vertex of d_odo_to[slot]) when that target is a slot
+ *             in range, a LOCAL member and not null; info = cov^-1 by the closed-form cofactor inverse se2gpu_ba_load_local_graph
+ *             uses.  An edge's place comes from a prefix sum over the workgroup.
+ *   landmarks (:980-1051) all n_mp points of d_mp_list in list order, each with its start position d_pos.  A point's edges are
+ *             the entries of its CSR list, in list order, that are valid by the entry rule with d_frame_null (null observers
+ *             are skipped, :995), whose frame is a member of either list (:1021), and that are the first valid entry of that
+ *             frame in the list (getObservations() is a std::set: a frame listed twice counts once, as in
+ *             se2gpu_covis_build_device).  Per edge: e_kf, e_uv = keyPointsUn[ftr].pt, e_info by :1024-1049 with sigma2 =
+ *             level_sigma2[octave]; an octave outside 0..nlevels-1 skips the edge (its frame stays taken) and sets bit 0 of
+ *             the job's flag word.  lm_ptr comes from a prefix sum: the edge order is the same in every run.
+ *             checkAssociationErr (:998) compares the two sides of the pointer graph (the key frame's observation of the point
+ *             against the point's of the key frame); A ONE-SIDED CSR CANNOT EXPRESS IT, and it is not evaluated.
+ *   The information arithmetic is the text k_edge_information runs (csrc/edge_information.h); the two translation units differ in
+ *   their contraction setting, so the values agree with se2gpu_ba_edge_information to rounding, not to the bit.
+ * d_status[j], the first that applies:
+ *   1  the job slot is outside 0..nframes-1, d_win_out[4j] < 0, or a list names a slot / point outside its table: nothing else
+ *      but the job's (zero) counts is written
+ *   2  does not fit: n_local > min(kf_list_cap, max_local), n_ref > min(kf_list_cap, max_ref), n_mp > min(mp_list_cap, max_mp),
+ *      edges > max_obs, more than 64 free key frames (the resident kernel's 192 unknowns), or an odometry self loop
+ *      (d_odo_to[slot] == slot of a local key frame: the resident kernel does not take self loops)
+ *   3  a local key frame of the window is null: not run.  The reference leaves such a key frame without a vertex (:922) and its
+ *      minKFid start (:904) reads a key frame it then skips; the call refuses the window instead of restating that.  A mapper
+ *      disconnects null key frames first (se2gpu_covis_disconnect_device), so that no window holds one.
+ *   4  a landmark with more than 64 edges (the resident kernel's limit); decided by the gather, the solver is not started
+ *   5  nothing to optimise: no free key frame, or no edge at all.  The outputs are the start values.
+ *   0  gathered and run;  6  run, and a pose or landmark came out non-finite
+ *   Statuses 2-4 write the job's counts as far as they were taken (and scratch); 0 and 5 the whole graph.
+ * The solve is one launch of njobs workgroups of the widest of 512 / 256 / 128 threads whose LDS holds a window of max_local +
+ * max_ref key frames, min(max_local, 64) of them free; a workgroup whose status is not 0 returns at once.
+ * Outputs, per job with status 0 (5: the start values): d_kf_out (njobs x (max_local + max_ref) x 3 doubles, local then
+ * reference key frames), d_mp_out (njobs x max_mp x 3 doubles); rows past the job's counts and the rows of other statuses are
+ * left untouched.  d_stats (per job, may be NULL): filled from the controller block for status 0 / 6, zero otherwise.
+ * d_info[8j..] = {n_pose, n_free, n_lm, n_edge, n_odo, entries of the window's points that became no edge, flag bits, 0}.
+ * WRITE-BACK IS THE CALLER'S: the call does not write into d_frame_Twb or d_pos.  Windows of a batch overlap, and the
+ * write-back of Map::optimizeLocalGraph (:754-783) for overlapping windows has no defined order.
+ * A job's words depend on that job alone: no atomic counter, the same in every run and wherever the job stands in the batch.
+ * d_ws: se2gpu_local_ba_ws_bytes(njobs, max_local, max_ref, max_mp, max_obs) bytes supplied by the caller, 16-byte aligned, no
+ * initialisation needed; -1 on arguments the call would refuse.  se2gpu_local_ba_ws_layout writes, for the
+ * SE2GPU_LOCAL_BA_WS_ARRAYS gathered arrays, the byte offset of job 0's slice and the stride from job to job (n >= that many;
+ * SE2GPU_ERR_INVALID otherwise or on those arguments): counts (8 ints, d_info's words), fixed (bytes), poses (x 3 doubles), o_i,
+ * o_j (ints), o_meas (x 3), o_info (x 9), lm_ptr (n_lm + 1 ints), e_kf (ints), e_uv (x 2), e_info (x 3: xx, xy, yy), landmarks
+ * (x 3) - poses and landmarks are the start values, kept apart from the solver's buffers; valid after the call for the jobs of
+ * status 0, 5 and 6.  Both helpers are host only and touch no device.
+ * The argument checks come first and touch neither the handle nor a device; se2gpu_last_error names the argument:
+ * SE2GPU_ERR_INVALID: a NULL handle or required pointer (all but d_frame_null, the three d_odo_* together, d_stats); d_ws not
+ *   16-byte aligned; njobs, m or nobs < 0; nframes, cap, kf_list_cap, mp_list_cap, max_local, max_ref, max_mp or max_obs < 1;
+ *   iters outside 1..64; nlevels outside 1..32; a mode other than the two.
+ * SE2GPU_ERR_CAPACITY: nframes > 4096; njobs > 65535; nframes * cap * 3, m * 3, njobs * kf_list_cap, njobs * mp_list_cap,
+ *   njobs * (max_local + max_ref) * 3, njobs * (max_mp + 1) * 3 or njobs * max_obs * 3 > 2^31 - 1; max_local + max_ref > 4096;
+ *   a window size no launch width holds.
+ * njobs == 0 is SE2GPU_OK and launches nothing. */
+#define SE2GPU_LOCAL_BA_WS_ARRAYS 12
+long long se2gpu_local_ba_ws_bytes(int njobs, int max_local, int max_ref, int max_mp, int max_obs);
+int se2gpu_local_ba_ws_layout(int njobs, int max_local, int max_ref, int max_mp, int max_obs, long long* offsets,
+                              long long* strides, int n);
+struct se2gpu_ba_stats;
+int se2gpu_local_ba_batch_device(se2gpu_matcher* h, const int32_t* d_job_kf, int njobs, const int32_t* d_win_out,
+                                 const int32_t* d_local_list, const int32_t* d_ref_list, int kf_list_cap,
+                                 const int32_t* d_mp_list, int mp_list_cap, int nframes, const int32_t* d_frame_id,
+                                 const float* d_frame_Twb, const float* d_frame_Tcw, const uint8_t* d_frame_null,
+                                 const int32_t* d_odo_to, const double* d_odo_meas, const double* d_odo_cov,
+                                 const se2gpu_keypoint* d_kps_un, const int32_t* d_counts, int cap, const float* d_view_pos,
+                                 const float* level_sigma2 /* host */, int nlevels, const float* d_pos, int m,
+                                 const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr, int nobs,
+                                 float fx, float cx, float cy, const double* Tbc12 /* host */, double huber_delta,
+                                 double xrot_info, double z_info, int iters, int mode, int max_local, int max_ref, int max_mp,
+                                 int max_obs, void* d_ws, int32_t* d_status, double* d_kf_out, double* d_mp_out,
+                                 struct se2gpu_ba_stats* d_stats, int32_t* d_info);
+
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by
  *   LocalMapper::localBA          /root/reference/src/LocalMapper.cpp:232-302

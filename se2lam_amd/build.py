@@ -36,6 +36,7 @@ PER_FILE = {
     "covis.hip": ["-ffp-contract=off"],      # the ratios and threshold tests are single IEEE operations, as in the reference
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
     "feat_edge_device.hip": ["-ffp-contract=off"],   # the plane-motion prior's information equals the host function's to the bit
+    "local_ba_device.hip": ["-ffp-contract=off"],    # the gathered informations are sums and products rounded one by one, as a numpy model's
 }
 
 

@@ -39,6 +39,7 @@
 #include "ba_device.h"
 #include "ba3_device.h"
 #include "ba_window.h"
+#include "edge_information.h"
 
 using namespace se2gpu;
 using namespace se2gpu::badev;
@@ -3199,29 +3200,15 @@ __global__ void k_edge_information(int E, const float* __restrict__ lc_, const f
     double R[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = Rcw_[9 * kf + i];
-    const double zi = 1. / lc2, zi2 = zi * zi;
-    const double j00 = fx * zi, j02 = -fx * lc0 * zi2, j12 = -fx * lc1 * zi2;
-    double A[6];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        A[c] = j00 * R[c] + j02 * R[6 + c];
-        A[3 + c] = j00 * R[3 + c] + j12 * R[6 + c];
-    }
     const double d0 = (double)lw_[3 * k] - (double)twb[2 * kf], d1 = (double)lw_[3 * k + 1] - (double)twb[2 * kf + 1];
     const double d2 = (double)lw_[3 * k + 2];
-    // (A * skew(d))[:, 0] = A[:,1]*d2 - A[:,2]*d1 ; [:, 1] = -A[:,0]*d2 + A[:,2]*d0
-    const double r00 = A[1] * d2 - A[2] * d1, r01 = -A[0] * d2 + A[2] * d0;
-    const double r10 = A[4] * d2 - A[5] * d1, r11 = -A[3] * d2 + A[5] * d0;
-    const double z0 = -A[2], z1 = -A[5];
     const double s2 = sigma2[k];
-    const double S00 = s_rot * (r00 * r00 + r01 * r01) + s_z * z0 * z0 + s2;
-    const double S01 = s_rot * (r00 * r10 + r01 * r11) + s_z * z0 * z1;
-    const double S11 = s_rot * (r10 * r10 + r11 * r11) + s_z * z1 * z1 + s2;
-    const double id = 1.0 / (S00 * S11 - S01 * S01);
+    double xx, xy, yy;
+    edge_information(lc0, lc1, lc2, R, d0, d1, d2, s2, fx, s_rot, s_z, xx, xy, yy);   // csrc/edge_information.h
     if (sym3) {   // (xx, xy, yy): the layout of the graph's e_info
-        out[3 * (size_t)k] = S11 * id; out[3 * (size_t)k + 1] = -S01 * id; out[3 * (size_t)k + 2] = S00 * id;
+        out[3 * (size_t)k] = xx; out[3 * (size_t)k + 1] = xy; out[3 * (size_t)k + 2] = yy;
     } else {
-        out[4 * k] = S11 * id; out[4 * k + 1] = -S01 * id; out[4 * k + 2] = -S01 * id; out[4 * k + 3] = S00 * id;
+        out[4 * k] = xx; out[4 * k + 1] = xy; out[4 * k + 2] = xy; out[4 * k + 3] = yy;
     }
 }
 

@@ -53,6 +53,9 @@ constexpr int kWindowMaxDegree = 64;     // observations of one landmark the ker
 size_t ba_window_lds_bytes(int P, int nfree, int threads);
 // count workgroups of `threads` (128, 256 or 512) threads, one per pack; asynchronous on st
 int ba_window_launch(const WindowArgs* d_args, int count, int threads, size_t lds_bytes, hipStream_t st);
+// the same behind a device-side gather (csrc/local_ba_device.hip): workgroup k returns before it reads its pack when d_status[k] != 0.
+// Serialises its own raise of the dynamic-LDS limit.
+int ba_window_launch_status(const WindowArgs* d_args, const int* d_status, int count, int threads, size_t lds_bytes, hipStream_t st);
 // the same for SE3-expmap windows (csrc/ba_window3.hip)
 size_t ba_window3_lds_bytes(int P, int nfree, int threads);
 int ba_window3_launch(const Window3Args* d_args, int count, int threads, size_t lds_bytes, hipStream_t st);

@@ -24,6 +24,8 @@
 // rounding (1e-12 relative on the cost), not bit for bit - the parity bar of this path is north_star's 1e-5.
 //
 // A landmark with more than 64 observations is refused (BaCtl::error = 2: the caller runs the window on the multi-launch path).
+#include <mutex>
+
 #include "ba_window_skeleton.h"
 
 namespace {
@@ -459,9 +461,45 @@ __global__ __launch_bounds__(NT) void k_window_lm(const WindowArgs* __restrict__
     window_lm<Se2Model, NT>(all[blockIdx.x], sh);
 }
 
+// The same kernel behind a gather that decides on the device which windows run (csrc/local_ba_device.hip): a window whose status is
+// not 0 returns before it reads anything else - its pack may name arrays the gather never filled.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_window_lm_status(const WindowArgs* __restrict__ all, const int* __restrict__ status) {
+    __shared__ WindowShared<3> sh;
+    if (status[blockIdx.x] != 0) return;   // uniform
+    window_lm<Se2Model, NT>(all[blockIdx.x], sh);
+}
+
+// (window_launch's counterpart for the two-argument kernel; the raise of the limit is serialised here, not by the caller)
+template <int NT>
+int window_launch_status(const WindowArgs* d_args, const int* d_status, int count, size_t lds_bytes, hipStream_t st) {
+    static std::mutex mu;
+    static size_t allowed = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (lds_bytes > allowed) {
+            SE2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_lm_status<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds_bytes));
+            allowed = lds_bytes;
+        }
+    }
+    hipLaunchKernelGGL(k_window_lm_status<NT>, dim3(count), dim3(NT), lds_bytes, st, d_args, d_status);
+    SE2_HIP(hipGetLastError());
+    return SE2GPU_OK;
+}
+
 }  // namespace
 
 namespace se2gpu {
+
+int ba_window_launch_status(const WindowArgs* d_args, const int* d_status, int count, int threads, size_t lds_bytes, hipStream_t st) {
+    if (count <= 0) return SE2GPU_OK;
+    if (threads == 512) return window_launch_status<512>(d_args, d_status, count, lds_bytes, st);
+    if (threads == 256) return window_launch_status<256>(d_args, d_status, count, lds_bytes, st);
+    if (threads == 128) return window_launch_status<128>(d_args, d_status, count, lds_bytes, st);
+    set_error("window kernel: 128, 256 or 512 threads");
+    return SE2GPU_ERR_INVALID;
+}
 
 size_t ba_window_lds_bytes(int P, int nfree, int threads) { return window_lds_bytes<Se2Model>(P, nfree, threads); }
 

@@ -105,6 +105,8 @@ def window_device(matcher, cv_kf: DeviceCovis, adj: DeviceAdjacency, job_kf, sea
                     out=out.to_numpy(np.int32, (max(n, 1), 4))[:n],
                     local_list=lst(ll, nk, kf_list_cap), ref_list=lst(rl, nk, kf_list_cap), mp_list=lst(ml, nm, mp_list_cap))
     if not sync:
-        return _Pending((jobs, fn, ko, mo, cv_kf, cv_mp, adj), read)
+        p = _Pending((jobs, fn, ko, mo, cv_kf, cv_mp, adj), read)
+        p.arrays = dict(job_kf=jobs, out=out, local_list=ll, ref_list=rl, mp_list=ml)   # where they lie: the next call on the stream reads them
+        return p
     matcher.sync()
     return read()
