@@ -632,6 +632,80 @@ int se2gpu_local_ba_batch_device(se2gpu_matcher* h, const int32_t* d_job_kf, int
                                  int max_obs, void* d_ws, int32_t* d_status, double* d_kf_out, double* d_mp_out,
                                  struct se2gpu_ba_stats* d_stats, int32_t* d_info);
 
+/* Localisation on the tables where they lie in device memory: the second link of Localizer::run's per-frame chain MatchLocalMap ->
+ * DoLocalBA -> UpdateCovisKFCurr -> UpdateLocalMap (src/Localizer.cpp:32-176 of the reference) for a batch of frames - the
+ * observation renewal of MatchLocalMap (:220-227), the numMPCurr > 30 gate (:95-98), DoLocalBA (:233-302) with
+ * addPlaneMotionSE3Expmap (src/optimizer.cpp:236-314) on the device, and KeyFrame::setPose (:298-299).  Every array pointer is
+ * device memory unless marked host.  Asynchronous on the matcher's stream, ONE launch of one workgroup of 256 threads per job:
+ * nothing is allocated, nothing uploaded besides kernel arguments, nothing read back, nothing waited for and no memset is issued;
+ * se2gpu_matcher_sync waits for it.
+ * Jobs: d_job_frame (njobs ints), the frame slot of mpKFCurr.  THE njobs SLOTS OF A BATCH MUST BE PAIRWISE DISTINCT: a job reads
+ *   and writes the rows of its frame, and two jobs that share a frame would do so in no defined order.  The call cannot see the
+ *   slots (they are device memory) and does not check this.
+ * Frame tables (nframes slots): d_frame_Tcw (12 floats a slot: rows 0-2 of Tcw, the table of
+ *   se2gpu_mappoint_parallax_batch_device), IN / OUT; d_frame_Twb (3 floats a slot: Se2 Twb), out, may be NULL.
+ * Feature tables: d_kps_un (nframes x cap key points: x, y and octave are read), d_counts (nframes), cap; d_ftr_mp (nframes x cap
+ *   ints, IN / OUT): KeyFrame::mDualObservations as a table, feature -> index into the point table, -1 = none; d_kf_observed
+ *   (nframes x cap bytes, in / out, may be NULL): the table of se2gpu_kf_correspd_batch_device / se2gpu_match_projection_device;
+ *   d_match_idx_mp (njobs x cap ints or NULL): row b is the row se2gpu_match_projection_device wrote for job b's frame.
+ * Point table (m points): d_pos (m x 3 floats); d_mp_null, d_good_prl (m bytes each, may be NULL: none is null, all are good),
+ *   with the meaning they have in se2gpu_covis_build_device.
+ * Configuration (host): inv_level_sigma2 is a HOST array of nlevels <= 32 floats (mvInvLevelSigma2), passed as kernel arguments;
+ *   fx, cx, cy (Config::Kcam; addCamPara uses fx for both axes); Tbc12 (HOST, 12 doubles: rotation row-major, translation);
+ *   huber_delta (Config::TH_HUBER); xrot_info, yrot_info, z_info (PLANEMOTION_*_INFO); iters (0..64); min_obs: a job runs with more
+ *   than min_obs observations - 30 for the tracked branch (:95), -1 = run always, the relocalisation branch (:133, :139).
+ * Per job b with frame = d_job_frame[b], d_status[b] is the first that applies:
+ *   1  the frame slot is outside 0..nframes-1.  Only d_status, the (zero) d_info words and counts, and zero d_stats are written.
+ *   Renewal (:220-227), only with d_match_idx_mp: for every feature j < min(d_counts[frame], cap) with q = d_match_idx_mp[b cap + j]
+ *      in 0..m-1 and point q not null (KeyFrame::addObservation returns on a null point, KeyFrame.cpp:197): d_ftr_mp[frame][j] = q
+ *      and d_kf_observed[frame][j] = 1.  Any other q leaves the feature as it was.
+ *   Observations = the features j < min(d_counts[frame], cap) whose d_ftr_mp lies in 0..m-1.  A value outside -1..m-1 is skipped
+ *      and sets bit 0 of the job's flag word.  A point named by several features counts once and keeps the GREATEST feature index
+ *      (mObservations[pMP] = idx overwrites, and both passes of the reference add in ascending feature order).  n_obs = the
+ *      number of distinct points = getSizeObsMP(): null and bad-parallax points count.
+ *   5  n_obs <= min_obs: not run.  d_pose_out[12 b..] is the start pose, the rows of d_frame_Tcw / d_frame_Twb are left alone,
+ *      d_stats is zero.
+ *   Edges (:261-288) = the observations whose point is neither null nor without good parallax, IN ASCENDING FEATURE INDEX (the
+ *      reference walks a std::set of pointers; the order here is the same in every run).  Per edge xyz = the float position
+ *      converted to double, uv = keyPointsUn[j].pt converted to double, w = (double)inv_level_sigma2[octave of feature j]; an
+ *      octave outside 0..nlevels-1 drops the edge and sets bit 1 of the flag word.  Places come from ballots and a prefix sum.
+ *   Start pose = toSE3Quat(getPose()): the 12 floats converted to double, the rotation passed through a unit quaternion as
+ *      SE3Quat(R, t) does.  Prior = se2gpu_plane_motion_prior's arithmetic on that pose, on the device.
+ *   0  run: optimize(iters) by the arithmetic of se2gpu_track_pose_ba.  This translation unit is compiled without floating-point
+ *      contraction and that one with it: the two agree to rounding, not to the bit.
+ *   6  run, and the pose came out non-finite: d_pose_out is written, the tables are not.
+ *   Write-back with status 0: d_frame_Tcw[frame] = the 12 doubles of d_pose_out rounded to float (toCvMat, converter.cpp:92-107);
+ *      d_frame_Twb[frame], if given, = {x, y, theta} of Tcw^-1 * Tbc^-1, computed in FP64 from d_pose_out and Tbc12, theta =
+ *      atan2(R10, R00), each rounded to float once.  THE REFERENCE FORMS THIS PRODUCT WITH OpenCV's float Mat ARITHMETIC [3P]: the
+ *      table value may differ from its by float rounding.  The d_frame_Twc / d_frame_P tables of the neighbouring calls stay the
+ *      caller's, as they are there.
+ * Outputs: d_status (njobs); d_pose_out (njobs x 12 doubles: R row-major, then t; untouched with status 1); d_stats (njobs, may be
+ *   NULL: zero unless the job ran); d_info[8 b..] = {n_features, n_obs, n_edges, renewed, duplicates dropped, flag bits, 0, 0}.
+ * A job's words depend on that job alone: no atomic counter, the same in every run and wherever the job stands in the batch.
+ * d_ws: se2gpu_localizer_ba_ws_bytes(njobs, cap) bytes supplied by the caller, 16-byte aligned, no initialisation needed; -1 on
+ *   arguments the call would refuse.  se2gpu_localizer_ba_ws_layout writes, for the SE2GPU_LOCALIZER_BA_WS_ARRAYS gathered arrays,
+ *   the byte offset of job 0's slice and the stride from job to job (n >= that many; SE2GPU_ERR_INVALID otherwise or on those
+ *   arguments): counts (8 ints, d_info's words), start pose (12 doubles), prior measurement (12), prior information (36, row-major,
+ *   vector order (rotation, translation)), e_ftr (n_edges ints: the feature of edge i), xyz (x 3 doubles), uv (x 2), w - valid after
+ *   the call for the jobs of status 0, 5 and 6.  Both helpers are host only and touch no device.
+ * The argument checks come first and touch neither the handle nor a device; se2gpu_last_error names the argument:
+ * SE2GPU_ERR_INVALID: a NULL handle or required pointer (all but d_frame_Twb, d_kf_observed, d_match_idx_mp, d_mp_null, d_good_prl,
+ *   d_stats); d_ws not 16-byte aligned; njobs or m < 0; nframes or cap < 1; iters outside 0..64; nlevels outside 1..32;
+ *   min_obs < -1.
+ * SE2GPU_ERR_CAPACITY: njobs > 65535; nframes * cap, njobs * cap * 3 or m * 3 > 2^31 - 1.
+ * njobs == 0 is SE2GPU_OK and launches nothing. */
+#define SE2GPU_LOCALIZER_BA_WS_ARRAYS 8
+long long se2gpu_localizer_ba_ws_bytes(int njobs, int cap);
+int se2gpu_localizer_ba_ws_layout(int njobs, int cap, long long* offsets, long long* strides, int n);
+int se2gpu_localizer_ba_batch_device(se2gpu_matcher* h, const int32_t* d_job_frame, int njobs, int nframes, float* d_frame_Tcw,
+                                     float* d_frame_Twb, const se2gpu_keypoint* d_kps_un, const int32_t* d_counts, int cap,
+                                     int32_t* d_ftr_mp, uint8_t* d_kf_observed, const int32_t* d_match_idx_mp, const float* d_pos,
+                                     int m, const uint8_t* d_mp_null, const uint8_t* d_good_prl,
+                                     const float* inv_level_sigma2 /* host */, int nlevels, float fx, float cx, float cy,
+                                     const double* Tbc12 /* host */, double huber_delta, double xrot_info, double yrot_info,
+                                     double z_info, int iters, int min_obs, void* d_ws, int32_t* d_status, double* d_pose_out,
+                                     struct se2gpu_ba_stats* d_stats, int32_t* d_info);
+
 /* ------------------------------------------------------------------------------------------
  * SE(2)-XYZ bundle adjustment  -  replaces the g2o::SparseOptimizer built by
  *   LocalMapper::localBA          /root/reference/src/LocalMapper.cpp:232-302

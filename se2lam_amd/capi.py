@@ -165,6 +165,10 @@ SYMBOLS = {
     "se2gpu_local_ba_batch_device": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                           _VP, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _F, _F, _F, _VP, _D, _D, _D,
                                           _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "se2gpu_localizer_ba_ws_bytes": (C.c_longlong, [_I, _I]),
+    "se2gpu_localizer_ba_ws_layout": (_I, [_I, _I, _VP, _VP, _I]),
+    "se2gpu_localizer_ba_batch_device": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I,
+                                              _F, _F, _F, _VP, _D, _D, _D, _D, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     # BA
     "se2gpu_ba_create": (_I, [C.POINTER(_VP)]),
     "se2gpu_ba_reserve": (_I, [_I, _I, _I]),

@@ -286,6 +286,44 @@ __host__ __device__ inline void plane_motion_prior_iso3(const double* Twc12, con
             info36[6 * i + j] = v;
         }
 }
+// addPlaneMotionSE3Expmap (optimizer.cpp:236-314, the branch that is compiled) from Tcw and Tbc (pose12 each): one text for the
+// host export se2gpu_plane_motion_prior (pose_ba.hip) and for k_localizer_ba (localizer_ba_device.hip).
+__host__ __device__ inline void plane_motion_prior_se3(const double* Tcw12, const double* Tbc12, double xrot_info, double yrot_info,
+                                                       double z_info, double* meas12, double* info36) {
+    const Se3 Tcw = se3_load(Tcw12), Tbc = se3_load(Tbc12);
+    Se3 Tbw = se3_mul(Tbc, Tcw);
+    // Log_Rbw = angle * axis of Rbw as Eigen::AngleAxisd takes it from the QUATERNION (angle = 2 atan2(|q_xyz|, w)); only its
+    // z component survives (:271-274), and the height is dropped (:276-278).  (Until round 4 this went through the logarithm
+    // of the rotation matrix, which loses ten digits near a yaw of pi: 6e-7 mm in the measurement against the compiled
+    // reference, found by tools/fuzz_ref_backend.py.)
+    double q[4];
+    quat_of(Tbw.R, q);
+    const double nv = sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double yaw = nv > 0 ? 2 * atan2(nv, q[0]) * q[3] / nv : 0.0;
+    const double c = cos(yaw), sn = sin(yaw);
+    Tbw.R[0] = c; Tbw.R[1] = -sn; Tbw.R[2] = 0;
+    Tbw.R[3] = sn; Tbw.R[4] = c; Tbw.R[5] = 0;
+    Tbw.R[6] = 0; Tbw.R[7] = 0; Tbw.R[8] = 1;
+    Tbw.t[2] = 0;
+    se3_store(se3_mul(se3_inv(Tbc), Tbw), meas12);
+    // Info_cw = adj(Tbc)^T diag(xrot, yrot, 1e-4, 1e-4, 1e-4, z) adj(Tbc);  SE3Quat::adj = [R 0; skew(t) R, R]
+    double A[36];
+    se3_adj(Tbc, A);
+    const double D[6] = {xrot_info, yrot_info, 1e-4, 1e-4, 1e-4, z_info};
+    #pragma unroll
+    for (int i = 0; i < 6; ++i)
+        #pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double s = 0;
+            #pragma unroll
+            for (int k = 0; k < 6; ++k) s += A[6 * k + i] * D[k] * A[6 * k + j];
+            info36[6 * i + j] = s;
+        }
+    #pragma unroll
+    for (int i = 0; i < 6; ++i)   // "make sure the info matrix is symmetric" (:296-298)
+        #pragma unroll
+        for (int j = 0; j < i; ++j) info36[6 * i + j] = info36[6 * j + i];
+}
 // d toVectorMQT(E * fromVectorMQT(d)) / d d at 0: [R_E 0; 0  w_E I + [q_E]x]
 __host__ __device__ inline void mqt_jac_right(const Se3& E, double J[36]) {
     double q[4];
