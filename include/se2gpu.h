@@ -1050,6 +1050,18 @@ int se2gpu_ba_debug_reduce_grid(const se2gpu_ba* h, int out[3]);
 int se2gpu_ba_debug_plan_host(int P, int L, int E, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* fixed, int O,
                               const int32_t* o_i, const int32_t* o_j, int odo_ok, int empty_last, int32_t* grp4, int cap_slots,
                               int out[3]);
+/* Test introspection of the SE(3) arithmetic the 6-DoF kernels share (csrc/se3_math.h): runs function `op` on the device, one
+ * item per thread, in one launch.  Every item has 24 doubles of input and 36 of output, whatever the op (unused ones are read
+ * as given and written as zero); a pose is pose12 = R row-major (9), t (3):
+ *   EXP (omega, upsilon) -> pose          LOG pose -> (omega, upsilon)         MUL pose A, pose B -> se3_mul(A, B)
+ *   NORMALIZE R (9) -> R (9)              QUAT_OF R (9) -> (w, x, y, z)        TO_MQT pose -> 6      FROM_MQT 6 -> pose
+ *   ADJ pose -> 6x6                       JAC_RIGHT pose E -> 6x6              JAC_LEFT_INV pose A, pose B -> 6x6
+ *   LOG_EXP (omega, upsilon) -> se3_log(se3_exp(.)) */
+enum {
+    SE2GPU_SE3_EXP = 0, SE2GPU_SE3_LOG, SE2GPU_SE3_MUL, SE2GPU_SE3_NORMALIZE, SE2GPU_SE3_QUAT_OF, SE2GPU_SE3_TO_MQT,
+    SE2GPU_SE3_FROM_MQT, SE2GPU_SE3_ADJ, SE2GPU_SE3_JAC_RIGHT, SE2GPU_SE3_JAC_LEFT_INV, SE2GPU_SE3_LOG_EXP, SE2GPU_SE3_OPS
+};
+int se2gpu_debug_se3(int op, int n, const double* in /* n x 24 */, double* out /* n x 36 */);
 
 /* Track::doTriangulate (/root/reference/src/Track.cpp:378-419) for every match of a frame pair in one device pass -
  * SURVEY section 8(f).3.  Per feature i of the reference key frame with match_idx[i] >= 0 and no map point yet:

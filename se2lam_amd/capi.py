@@ -226,6 +226,7 @@ SYMBOLS = {
     "se2gpu_ba_debug_flat_records": (_I, [_VP, _VP, _VP, _I, C.POINTER(C.c_int)]),
     "se2gpu_ba_debug_reduce_grid": (_I, [_VP, _VP]),
     "se2gpu_ba_debug_plan_host": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I, _VP]),
+    "se2gpu_debug_se3": (_I, [_I, _I, _VP, _VP]),
     "se2gpu_triangulate": (_I, [_I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _I, _VP, _VP,
                            C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "se2gpu_track_create": (_I, [C.POINTER(_VP)]),
@@ -465,3 +466,22 @@ class Timer:
                 lib().se2gpu_timer_destroy(self.h)
         except Exception:
             pass
+
+
+# ops of se2gpu_debug_se3 (include/se2gpu.h), with the doubles each reads and writes per item
+SE3_OPS = {"exp": (0, 6, 12), "log": (1, 12, 6), "mul": (2, 24, 12), "normalize": (3, 9, 9), "quat_of": (4, 9, 4),
+           "to_mqt": (5, 12, 6), "from_mqt": (6, 6, 12), "adj": (7, 12, 36), "jac_right": (8, 12, 36),
+           "jac_left_inv": (9, 24, 36), "log_exp": (10, 6, 6)}
+
+
+def debug_se3(op: str, x) -> np.ndarray:
+    """se2gpu_debug_se3: function `op` of csrc/se3_math.h on the device for every row of x (n, doubles the op reads) -> (n, doubles
+    it writes), one launch"""
+    code, nin, nout = SE3_OPS[op]
+    x = np.ascontiguousarray(x, np.float64).reshape(-1, nin)
+    n = x.shape[0]
+    buf = np.zeros((n, 24))
+    buf[:, :nin] = x
+    out = np.zeros((n, 36))
+    check(lib().se2gpu_debug_se3(code, n, vp(buf), vp(out)))
+    return out[:, :nout].copy()

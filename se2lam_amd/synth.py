@@ -1030,3 +1030,49 @@ def kf_pair_reorder(pair, order: str, seed: int = 0):
     else:
         raise ValueError(order)
     return kf, mp, m_kf[idx].copy(), m_mp[idx].copy(), m_info[idx].copy()
+
+
+# --------------------------------------------------------------------------
+# A camera off the body's axes and off the image centre.  RBC is a signed permutation and the principal point is the image centre:
+# every term of a projection or of an adjoint that one of RBC's six zero entries multiplies drops out of every number computed
+# from the generators above.  Additions only: no generator above draws differently because of them.
+# --------------------------------------------------------------------------
+def tbc44(Rbc=RBC, tbc=TBC):
+    T = np.eye(4)
+    T[:3, :3] = Rbc
+    T[:3, 3] = tbc
+    return T
+
+
+# the mount above tilted by (0.05, -0.11, 0.025) rad and moved by (3, -7, 11) mm in the camera's own frame: all nine entries of
+# Rcb lie in (0.02, 0.999) in magnitude
+OFF_AXIS_TBC = tbc44() @ se3_exp_np(np.array([0.05, -0.11, 0.025, 3.0, -7.0, 11.0]))
+OFF_CENTRE_CAM = (517.3, 301.7, 255.4)     # f, cx, cy
+
+
+def with_camera(g: "BAGraph", Tbc=OFF_AXIS_TBC, cam=OFF_CENTRE_CAM) -> "BAGraph":
+    """A copy of `g` seen through another camera: extrinsic Tbc (4x4), intrinsics cam = (f, cx, cy).  Truth, start, edges, levels,
+    odometry and the pixel noise of every observation (outliers included: the noise is what g.e_uv has on top of the projection
+    of the truth through g's own camera) are g's; e_uv is the truth through the new camera plus that noise, e_info is
+    edge_information of the start through the new camera.  g and the generators' random streams are not touched."""
+    import copy
+    assert g.poses_true is not None and g.lms_true is not None and g.e_level is not None
+    Rcb0 = np.asarray(g.Rbc).T
+    u0, v0, _, _ = _project(g.poses_true, g.lms_true, g.e_kf, g.e_lm, Rcb0, -Rcb0 @ np.asarray(g.tbc), g.fx, g.cx, g.cy)
+    noise = g.e_uv - np.stack([u0, v0], axis=1)
+    Tbc = np.asarray(Tbc, np.float64)
+    Rbc, tbc = Tbc[:3, :3].copy(), Tbc[:3, 3].copy()
+    f, cx, cy = (float(c) for c in cam)
+    u, v, _, _ = _project(g.poses_true, g.lms_true, g.e_kf, g.e_lm, Rbc.T, -Rbc.T @ tbc, f, cx, cy)
+    h = copy.copy(g)
+    h.Rbc, h.tbc, h.fx, h.cx, h.cy = Rbc, tbc, f, cx, cy
+    h.e_uv = np.stack([u, v], axis=1) + noise
+    h.e_info = edge_information(g.poses, g.lms, g.e_kf, g.e_lm, g.e_level, Rbc, tbc, f)
+    return h
+
+
+def camera_depths(g: "BAGraph", poses=None, lms=None) -> np.ndarray:
+    """camera-frame Z of every edge of g at (poses, lms), default g's start"""
+    Rcb = np.asarray(g.Rbc).T
+    return _project(g.poses if poses is None else poses, g.lms if lms is None else lms, g.e_kf, g.e_lm, Rcb,
+                    -Rcb @ np.asarray(g.tbc), g.fx, g.cx, g.cy)[2]

@@ -309,9 +309,10 @@ def odo_graph(synth, P, L, kind):
     return g
 
 
-def _info_inputs(synth, P=12, L=200, seed=0):
-    """Inputs of Map::loadLocalGraph's information computation (Map.cpp:1024-1049) for a synthetic window."""
-    g = synth.ba_graph(P, L)
+def _info_inputs(synth, P=12, L=200, seed=0, g=None):
+    """Inputs of Map::loadLocalGraph's information computation (Map.cpp:1024-1049) for a synthetic window (g: that window, with
+    its own camera, instead of synth.ba_graph(P, L))."""
+    g = synth.ba_graph(P, L) if g is None else g
     rng = np.random.default_rng(seed)
     Rcb = g.Rbc.T
     tcb = -Rcb @ g.tbc

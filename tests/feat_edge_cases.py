@@ -46,6 +46,17 @@ OUTLIER_CASES = ((40, 0, 5), (65, 1, 9))          # (N, seed, planted): seeds at
 REJECTING = dict(N=12, seed=1, turn_y=2.2, iters=14)
 
 
+def with_camera(c, Tbc):
+    """the pair c as a camera mounted at Tbc (4x4) on the same body sees it: T_w_c' = T_w_c T_c_c' with T_c_c' = Tbc_old^-1 Tbc, the
+    measurements and their informations turned into the new camera frame; points, noise draws and planted outliers stay"""
+    D = np.linalg.inv(synth.tbc44()) @ np.asarray(Tbc, np.float64)
+    R, t = D[:3, :3], D[:3, 3]
+    out = dict(c, kf=c["kf"] @ D, z=(c["z"] - t) @ R, info=np.einsum("ji,nkjl,lm->nkim", R, c["info"], R))
+    if "kf_true" in c:
+        out["kf_true"] = c["kf_true"] @ D
+    return out
+
+
 def as_tuple(c):
     return c["kf"], c["mp"], c["z"], c["info"]
 

@@ -11,11 +11,14 @@ CAP = 136             # features per frame in the match tables
 
 
 class Tables:
-    def __init__(self, shapes, outliers=None, spare_points=3):
-        """shapes: (N, seed) per world; outliers: {world: planted count}"""
+    def __init__(self, shapes, outliers=None, spare_points=3, Tbc=None):
+        """shapes: (N, seed) per world; outliers: {world: planted count}; Tbc (4x4): the worlds as a camera mounted there sees
+        them (feat_edge_cases.with_camera) instead of synth.RBC / TBC"""
         outliers = outliers or {}
         self.cases = [fc.make_pair(N, seed, n_outliers=outliers.get(w, 0)) if N else fc.empty_pair(seed)
                       for w, (N, seed) in enumerate(shapes)]
+        if Tbc is not None:
+            self.cases = [fc.with_camera(c, Tbc) for c in self.cases]
         self.N = np.array([len(c["mp"]) for c in self.cases])
         self.off = np.concatenate([[0], np.cumsum(self.N)]).astype(int)
         W = len(shapes)

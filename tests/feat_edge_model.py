@@ -37,8 +37,41 @@ def oplus_pose(T, d):
     return T @ synth.from_mqt_np(d)       # VertexSE3::oplusImpl (rotation = identity when |q|^2 > 1)
 
 
+def mqt_eigen(T):
+    """g2o::internal::toVectorMQT on a matrix block that need not be a rotation: Eigen::Quaterniond(M) as Eigen's
+    quaternionbase_assign_impl defines it (the trace, or the largest diagonal entry i with j = i + 1, k = j + 1 cyclically), then
+    normalize() and w >= 0.  The key frames of a map are float tables: their rotation blocks are 4e-8 away from orthonormal, and on
+    such a matrix scipy's conversion (synth.mqt_np) answers another question - its quaternion differs from Eigen's by that 4e-8
+    times the rotation's own size, which is 1e-11 of the cost of a ten-point pair under a tilted extrinsic."""
+    m = np.asarray(T, np.float64)[:3, :3]
+    t = m[0, 0] + m[1, 1] + m[2, 2]
+    q = np.zeros(4)                                   # w, x, y, z
+    if t > 0:
+        t = np.sqrt(t + 1.0)
+        q[0] = 0.5 * t
+        t = 0.5 / t
+        q[1:] = [(m[2, 1] - m[1, 2]) * t, (m[0, 2] - m[2, 0]) * t, (m[1, 0] - m[0, 1]) * t]
+    else:
+        i = 0
+        if m[1, 1] > m[0, 0]:
+            i = 1
+        if m[2, 2] > m[i, i]:
+            i = 2
+        j, k = (i + 1) % 3, (i + 2) % 3
+        t = np.sqrt(m[i, i] - m[j, j] - m[k, k] + 1.0)
+        q[1 + i] = 0.5 * t
+        t = 0.5 / t
+        q[0] = (m[k, j] - m[j, k]) * t
+        q[1 + j] = (m[j, i] + m[i, j]) * t
+        q[1 + k] = (m[k, i] + m[i, k]) * t
+    q /= np.linalg.norm(q)
+    if q[0] < 0:
+        q = -q
+    return np.concatenate([np.asarray(T)[:3, 3], q[1:]])
+
+
 def prior_error(Z, T):
-    return synth.mqt_np(np.linalg.inv(Z) @ T)
+    return mqt_eigen(np.linalg.inv(Z) @ T)
 
 
 def prior_jacobian(Z, T):

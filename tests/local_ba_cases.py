@@ -22,26 +22,28 @@ for _i in range(1, NLEVELS):
 LEVEL_SIGMA2 = (_SCALE * _SCALE).astype(np.float32)
 
 
-def tcw12(twb):
+def tcw12(twb, Tbc12=TBC12):
     """rows 0-2 of Tcw = Tcb * Twb^-1 for the Se2 pose twb, as 12 floats"""
     x, y, th = (float(v) for v in twb)
     c, s = np.cos(th), np.sin(th)
     Twb = np.array([[c, -s, 0, x], [s, c, 0, y], [0, 0, 1, 0], [0, 0, 0, 1]])
     Tbc = np.eye(4)
-    Tbc[:3, :3], Tbc[:3, 3] = RBC, TBC
+    Tbc[:3, :3], Tbc[:3, 3] = np.asarray(Tbc12[:9], np.float64).reshape(3, 3), Tbc12[9:]
     return (np.linalg.inv(Tbc) @ np.linalg.inv(Twb))[:3].astype(np.float32).reshape(12)
 
 
-def scene(seed, nframes, m, per_point=(2, 4), spacing=300.0, pose_noise=(5.0, 0.002), point_noise=20.0):
+def scene(seed, nframes, m, per_point=(2, 4), spacing=300.0, pose_noise=(5.0, 0.002), point_noise=20.0, Tbc12=TBC12, K=K):
     """Key frames along a gently curved path (millimetres), points 1.5 - 4 m ahead of the key frame they were born at, each seen
     by 2-4 neighbouring key frames that still have a free feature; the tables hold the true scene plus noise, so there is
-    something to optimise.  Odometry: a chain i -> i + 1 with the true relative motion."""
+    something to optimise.  Odometry: a chain i -> i + 1 with the true relative motion.  Tbc12, K: the camera (the same random
+    draws whatever it is)."""
+    Tbc12, K = np.asarray(Tbc12, np.float64), np.asarray(K, np.float32)
     rng = np.random.default_rng(seed)
     truth = np.c_[spacing * np.arange(nframes) + rng.normal(0, 20, nframes), rng.normal(0, 40, nframes), rng.normal(0, 0.05, nframes)]
     Twb = (truth + np.c_[rng.normal(0, pose_noise[0], (nframes, 2)), rng.normal(0, pose_noise[1], nframes)]).astype(np.float32)
     Twb[0] = truth[0].astype(np.float32)
-    Tcw = np.stack([tcw12(t) for t in Twb])
-    Tcw_true = np.stack([tcw12(t) for t in truth]).astype(np.float64).reshape(nframes, 3, 4)
+    Tcw = np.stack([tcw12(t, Tbc12) for t in Twb])
+    Tcw_true = np.stack([tcw12(t, Tbc12) for t in truth]).astype(np.float64).reshape(nframes, 3, 4)
     kps_xy = np.zeros((nframes, CAP, 2), np.float32)
     kps_octave = np.zeros((nframes, CAP), np.int32)
     view_pos = np.tile(np.array([0, 0, 1000], np.float32), (nframes, CAP, 1))
@@ -84,7 +86,7 @@ def scene(seed, nframes, m, per_point=(2, 4), spacing=300.0, pose_noise=(5.0, 0.
     return dict(frame_id=(10 + np.arange(nframes)).astype(np.int32), Twb=Twb, Tcw=Tcw, frame_null=np.zeros(nframes, np.uint8),
                 odo_to=odo_to, odo_meas=odo_meas, odo_cov=odo_cov, kps_xy=kps_xy, kps_octave=kps_octave, counts=counts, cap=CAP,
                 view_pos=view_pos, level_sigma2=LEVEL_SIGMA2.copy(), pos=pos, mp_ptr=mp_ptr, obs_frame=obs_frame, obs_ftr=obs_ftr,
-                K=K, Tbc12=TBC12, huber=HUBER, xrot_info=XROT_INFO, z_info=Z_INFO)
+                K=K, Tbc12=Tbc12, huber=HUBER, xrot_info=XROT_INFO, z_info=Z_INFO)
 
 
 def copy_map(T):
@@ -127,7 +129,7 @@ def kidnap(T, slots, seed, dxy=2000.0, dth=0.6):
         T["Twb"][f, :2] += rng.normal(0, dxy, 2).astype(np.float32)
         th = float(T["Twb"][f, 2]) + rng.normal(0, dth)
         T["Twb"][f, 2] = np.float32((th + np.pi) % (2 * np.pi) - np.pi)
-        T["Tcw"][f] = tcw12(T["Twb"][f])
+        T["Tcw"][f] = tcw12(T["Twb"][f], T["Tbc12"])
     return T
 
 

@@ -21,12 +21,14 @@ def inv_level_sigma2():
     return (np.float32(1.0) / (sf * sf)).astype(np.float32)
 
 
-def tbc12():
-    return np.concatenate([TBC[:3, :3].reshape(-1), TBC[:3, 3]]).astype(np.float64)
+def tbc12(Tbc=TBC):
+    return np.concatenate([Tbc[:3, :3].reshape(-1), Tbc[:3, 3]]).astype(np.float64)
 
 
-def tables(seed=0, edges=EDGES, shift_uv=None):
-    """shift_uv = (frame, pixels): every key point of that frame moved, so that every edge is a gross outlier and LM rejects trials"""
+def tables(seed=0, edges=EDGES, shift_uv=None, Tbc=TBC, cam=(F, CX, CY)):
+    """shift_uv = (frame, pixels): every key point of that frame moved, so that every edge is a gross outlier and LM rejects trials.
+    Tbc (4x4), cam = (f, cx, cy): the camera; the random draws are the same whatever it is."""
+    TBC, (F, CX, CY) = np.asarray(Tbc, np.float64), cam
     rng = np.random.default_rng(seed)
     pose = np.array([rng.uniform(-2000, 2000), rng.uniform(-2000, 2000), rng.uniform(-3, 3)])
     Twc_ref = _Twb(*pose) @ TBC
@@ -38,7 +40,7 @@ def tables(seed=0, edges=EDGES, shift_uv=None):
     T = dict(Tcw=np.zeros((NFRAMES, 12), np.float32), Twb=np.zeros((NFRAMES, 3), np.float32), kps_xy=np.zeros((NFRAMES, CAP, 2), np.float32),
              kps_octave=np.zeros((NFRAMES, CAP), np.int32), counts=np.zeros(NFRAMES, np.int32), ftr_mp=np.full((NFRAMES, CAP), -1, np.int32),
              kf_observed=np.zeros((NFRAMES, CAP), np.uint8), pos=pos, mp_null=mp_null, good_prl=good_prl, inv_level_sigma2=inv_level_sigma2(),
-             Tbc12=tbc12(), xrot_info=1e6, yrot_info=1e6, z_info=1.0, K=np.array([[F, 0, CX], [0, F, CY], [0, 0, 1]], np.float32),
+             Tbc12=tbc12(TBC), xrot_info=1e6, yrot_info=1e6, z_info=1.0, K=np.array([[F, 0, CX], [0, F, CY], [0, 0, 1]], np.float32),
              huber=DELTA, true_pose=np.zeros((NFRAMES, 3)), plan=[])
     for f in range(NFRAMES):
         true = pose + np.r_[rng.normal(0, 60, 2), rng.normal(0, 0.02)]            # every frame looks at the same part of the map

@@ -442,3 +442,37 @@ def test_without_the_optional_outputs_the_required_ones_are_the_same_words(match
         for k in ("info8", "kf12", "z12", "info"):
             assert np.array_equal(a[k], b[k]), k
         assert b["stats"]["iterations"] == 0 and len(b["mp"]) == 0
+
+
+# ---- a camera off the body's axes ----------------------------------------------------------------------------------------------
+
+def test_off_axis_camera_prior_and_a_pair_against_the_model_and_the_host_route(matcher, oracle):
+    """two worlds of `tab` (10 and 65 points, the same draws) as a camera at synth.OFF_AXIS_TBC sees them, the call given that
+    Tbc12: in k_plane_prior_iso3 the adjoint of Tbc and the products with Tbc^-1 are full matrices.  The prior as
+    test_prior_information_to_the_bit_and_measurement_within_the_bound, the pairs as test_covis_route_against_the_model_and_the_host_route."""
+    from se2lam_amd import capi, feat_edge as fe, synth
+    Tbc = synth.OFF_AXIS_TBC
+    tbc = fe.Tbc12(Tbc[:3, :3], Tbc[:3, 3])
+    assert np.abs(tbc[:9]).min() > 0.02
+    t = dc.Tables(((10, 0), (65, 0)), Tbc=Tbc)
+    worlds = [1, 0]
+    buf, g = _run_covis(matcher, t, worlds, 130, 130, tbc=tbc)
+    got, res = _check_gather(buf, g, "off axis")
+    kf = np.ascontiguousarray(g["kf12"].reshape(-1, 12))
+    meas, info = np.zeros((len(kf), 12)), np.zeros((len(kf), 36))
+    for i in range(len(kf)):
+        capi.check(capi.lib().se2gpu_plane_motion_prior_iso3(kf[i].ctypes.data, tbc.ctypes.data, 1e6, 1e6, 1.0, meas[i].ctypes.data,
+                                                             info[i].ctypes.data))
+    assert np.array_equal(_bits(got["prior_info"].reshape(-1, 36)), _bits(info))
+    diff = np.abs(got["prior_meas"].reshape(-1, 12) - meas).max(axis=1)
+    assert np.all(diff <= 1e-12 * np.maximum(1.0, np.abs(kf[:, 9:]).max(axis=1)))
+    assert np.abs(meas - kf).max() > 1e-3
+    host, (kf_in, mp_in) = _host_route(g, fm.COVIS, tbc=tbc)
+    dev = buf.read()
+    for slot, w in enumerate(worlds):
+        c = t.case(w)
+        m = fm.optimize(fm.Problem(c["kf"], c["mp"], c["z"], c["info"], fm.COVIS, prior_kw=dict(Rbc=Tbc[:3, :3], tbc=Tbc[:3, 3])), 15)
+        label = "off axis covis slot %d (%d points)" % (slot, len(c["mp"]))
+        fm.check_against_model(dev[slot], c, m, fm.COVIS, oracle, label)
+        a, b = int(np.sum(g["count"][:slot])), int(np.sum(g["count"][:slot + 1]))
+        _close_to_host(dev[slot], host[slot], kf_in[slot], mp_in[a:b], label)

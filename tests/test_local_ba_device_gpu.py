@@ -250,3 +250,28 @@ def test_the_existing_batch_paths_are_unchanged_by_a_device_route_call(matcher, 
             assert got["status"].tolist() == [0]
             after = run()
             assert before == after, path
+
+
+# ---- a camera off the body's axes ----------------------------------------------------------------------------------------------
+
+def _off_axis_window():
+    """the map and window of the case ref_present (the same random draws), seen through synth.OFF_AXIS_TBC / OFF_CENTRE_CAM: Rcw
+    in the gathered informations and Rcb in the solver are full matrices, the principal point is off the image centre"""
+    from se2lam_amd import synth
+    f, cx, cy = synth.OFF_CENTRE_CAM
+    T = lc.scene(2, 10, 36, Tbc12=np.r_[synth.OFF_AXIS_TBC[:3, :3].reshape(-1), synth.OFF_AXIS_TBC[:3, 3]],
+                 K=np.array([[f, 0, cx], [0, f, cy], [0, 0, 1]], np.float32))
+    return T, lc.window(T, 3, [2, 3, 4])
+
+
+def test_off_axis_camera_gather_equals_the_model_and_results_equal_the_host_route(matcher):
+    T, job = _off_axis_window()
+    assert np.abs(T["Tbc12"][:9]).min() > 0.02 and np.abs(T["Tcw"][:, [0, 1, 2, 4, 5, 6, 8, 9, 10]]).min() > 0.02
+    used = [(f, k) for p in job["mps"] for f, k in zip(lc.observers(T, p), T["obs_ftr"][T["mp_ptr"][p]:T["mp_ptr"][p + 1]])]
+    assert min(T["view_pos"][f, k, 2] for f, k in used) >= 300.0
+    got, want = _device(matcher, T, [job], lc.CAPS), _model(T, [job], lc.CAPS)
+    assert want[0]["status"] == 0
+    _same_gather(got, 0, want[0], "off axis")
+    for resident in (True, False):
+        st, est = _host_route(T, job, ITERS, resident)
+        _same_as_host(got, 0, st, est, ("off axis", resident))

@@ -358,3 +358,42 @@ def test_the_single_call_is_untouched(matcher, plain):
     Run(matcher, cases.tables(), [3, 4])
     T1, s1 = loc.pose_ba(*args), loc.stats
     assert T0.tobytes() == T1.tobytes() and s0 == s1 and loc.stats_tail_intact
+
+
+# ---- a camera off the body's axes ----------------------------------------------------------------------------------------------
+
+def test_off_axis_camera_gather_prior_solve_and_write_back(matcher, oracle):
+    """the tables of `plain` (the same random draws) seen through synth.OFF_AXIS_TBC / OFF_CENTRE_CAM: adj(Tbc) in the plane-motion
+    prior's information and Tbc in its measurement are full matrices, the principal point is off the image centre.  The checks of
+    test_gathered_arrays_and_renewal_against_the_model, test_solve_against_the_single_call_and_the_oracle and test_write_back."""
+    from se2lam_amd import synth
+    from se2lam_amd.localizer import Localizer
+    f_, cx, cy = synth.OFF_CENTRE_CAM
+    T = cases.tables(Tbc=synth.OFF_AXIS_TBC, cam=synth.OFF_CENTRE_CAM)
+    assert np.abs(T["Tbc12"][:9]).min() > 0.02 and T["K"][0, 0] == np.float32(f_) and T["K"][1, 2] == np.float32(cy)
+    r = Run(matcher, T, range(cases.NFRAMES))
+    assert r.status.tolist() == [0] * 6 and r.info[:, 2].tolist() == list(cases.EDGES)
+    for b, f in enumerate(r.jobs):
+        g = _check_gather(r, b, model.job(T, f, None, -1))
+        # the prior against the definitions (tests/independent.py), at test_track_independent.py's bounds
+        import independent as ind
+        mn, infn = ind.plane_motion_prior_numpy(cases.matrix(g["pose0"]), synth.OFF_AXIS_TBC)
+        assert np.allclose(g["prior_info"].reshape(6, 6), infn, rtol=1e-12, atol=0)
+        assert np.allclose(cases.matrix(g["prior_meas"]), mn, atol=1e-9)
+        loc = Localizer()
+        args = (cases.matrix(g["pose0"]), cases.matrix(g["prior_meas"]), g["prior_info"], g["xyz"], g["uv"], g["w"], float(T["K"][0, 0]),
+                float(T["K"][0, 2]), float(T["K"][1, 2]), DELTA, 30)
+        T1 = loc.pose_ba(*args)
+        To, so = oracle.pose_only_ba(*args)
+        if len(g["e_ftr"]) == 0:
+            assert np.allclose(cases.matrix(r.pose[b]), To, atol=1e-9) and np.allclose(cases.matrix(r.pose[b]), T1, atol=1e-9)
+        else:
+            _same_run(r.stats[b], loc.stats)
+            _same_run(r.stats[b], so)
+            _same_pose(r.pose[b], T1)
+            _same_pose(r.pose[b], To)
+        assert np.array_equal(r.Tcw[f], model.tcw_row_of(r.pose[b]))
+        want = model.twb_of(r.pose[b], T["Tbc12"])
+        assert (np.abs(r.Twb[f].astype(np.float64) - want.astype(np.float64)) <= np.spacing(np.abs(want))).all(), (f, r.Twb[f], want)
+        if len(g["e_ftr"]) >= 257:
+            assert np.abs(r.Twb[f][:2] - T["true_pose"][f][:2]).max() < 8.0
