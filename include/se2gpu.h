@@ -1144,6 +1144,57 @@ int se2gpu_track_triangulate(se2gpu_track* h, int n, const se2gpu_keypoint* kps_
                              const float* P_cur, const float* Ocam, float lower_depth, float upper_depth,
                              int min_degree, float* pos_out, uint8_t* good_parallax, int* n_good, int* n_tracked_old);
 
+/* Track::removeOutliers (Track.cpp:308-344) and then Track::doTriangulate (Track.cpp:378-419) for npairs pairs (reference key
+ * frame, current frame) at once: what Track::mTrack runs behind MatchByWindow on every frame.  Every d_ pointer is device
+ * memory.  The frames are in the layouts of se2gpu_match_window_batch_device (d_kps_un, d_counts, cap, nframes), d_matches12 is
+ * the array that call writes, and d_matched12 / d_local_pos are the arrays se2gpu_kf_correspd_batch_device reads, in its layouts;
+ * d_kf_observed / d_view_pos are that call's tables (mViewMPs).
+ *   d_Trc (npairs x 12)  rows 0-2 of cvu::inv(mFrame.Tcr), as se2gpu_kf_correspd_batch_device takes them; Ocam is column 3
+ *   d_P   (npairs x 12)  Config::Kcam * Tcr.rowRange(0,3), formed by the caller as for se2gpu_track_triangulate
+ *   P_ref (host, 12)     Config::PrjMtrxEye
+ *   d_pair_flags         bit 0 set: the triangulation is skipped (Track.cpp:379-381, mFrame.id - mpKF->id < nMinFrames)
+ * For pair p, a = pair_ref[p], b = pair_cur[p], counts clamped to 0..cap:
+ *   raw matches   entries i < counts[a] of row p with a value in 0..counts[b]-1, in ascending i; every other entry counts as -1
+ *   filter        the mask of cv::findFundamentalMat exactly as se2gpu_track_fundamental_mask computes it for those points (the
+ *                 launches of se2gpu_track_loop_verify_batch_device, with its 64 MiB slices of scratch); with fewer than 10
+ *                 inliers - always so below 10 raw matches - the whole row becomes -1 and the inlier count 0
+ *   triangulation per i with a surviving match m, unless flag bit 0 is set:
+ *                 kf_observed[a][i] set: local_pos = view_pos[a][i], counted as tracked old, good_prl = 0
+ *                 else pos = cvu::triangulate(kps_un[a][i], kps_un[b][m], P_ref, P[p]) as se2gpu_track_triangulate forms it, bit
+ *                 for bit; lower_depth <= pos.z <= upper_depth: local_pos = pos, good_prl = cvu::checkParallax(0, Ocam, pos,
+ *                 min_degree); else the match becomes -1
+ * Outputs, every word of them written for every (p, i < cap): d_matched12, d_local_pos (zero where the final match is -1, and
+ * everywhere in a skipped pair), d_good_prl (0 everywhere in a skipped pair: the reference keeps the previous frame's flags
+ * there, that state is the caller's).
+ *   d_info[p * 8 ..] = {n_raw, n_inliers (nMatched of Track.cpp:134, 0 when dropped), n_tracked_old, n_good_prl (mnGoodPrl),
+ *                 n_old_kp, path, n_depth_rejected, status}
+ *                 n_old_kp: set bytes among the first counts[a] of kf_observed[a] (getSizeObsMP() of needNewKF), 0 without it
+ *                 path: as in the loop verification (0 below 10 raw matches, 1 LMedS, 2 RANSAC)
+ *                 status: 0 run, 1 a frame outside 0..nframes-1 (rows of -1, zeros), 2 fewer than 10 inliers, 3 triangulation
+ *                 skipped by flag; the first that applies
+ * Nothing is indexed outside the arrays, whatever they hold.  The outputs must not overlap the inputs.  A pair's outputs depend
+ * on that pair only; they are the same in every run and wherever the pair stands in the batch (no floating-point or global
+ * atomic).  Asynchronous on the handle's stream: nothing is uploaded besides kernel arguments, nothing is read back, nothing
+ * waits; with se2gpu_track_set_stream(h, se2gpu_matcher_stream(m)) extract -> MatchByWindow -> this call -> findCorrespd follow
+ * each other on one stream.  The first call on a handle allocates the scratch of the loop verification (and blocks as that
+ * call's first does); later calls of the same or a smaller size allocate nothing.
+ * SE2GPU_ERR_INVALID: a NULL handle or required pointer (d_kf_observed, d_view_pos and d_pair_flags may be NULL), d_kf_observed
+ *   without d_view_pos, npairs / cap / nframes < 1, min_degree outside 1..4.
+ * SE2GPU_ERR_CAPACITY: cap > 65536 or npairs > 65535, as se2gpu_track_loop_verify_batch_device.
+ * The argument checks come first and use neither the handle nor a device. */
+int se2gpu_track_frames_batch_device(se2gpu_track* h,
+                                     const se2gpu_keypoint* d_kps_un, const int32_t* d_counts, int cap, int nframes,
+                                     const uint8_t* d_kf_observed /* nframes*cap, may be NULL */,
+                                     const float* d_view_pos /* nframes*cap*3; required with d_kf_observed */,
+                                     const int32_t* d_pair_ref, const int32_t* d_pair_cur, int npairs,
+                                     const float* d_Trc /* npairs*12 */, const float* d_P /* npairs*12 */,
+                                     const uint8_t* d_pair_flags /* npairs, may be NULL */,
+                                     const float* P_ref /* host, 12 */,
+                                     const int32_t* d_matches12 /* npairs*cap, in */,
+                                     float lower_depth, float upper_depth, int min_degree,
+                                     int32_t* d_matched12 /* npairs*cap, out */, float* d_local_pos /* npairs*cap*3, out */,
+                                     uint8_t* d_good_prl /* npairs*cap, out */, int32_t* d_info /* npairs*8, out */);
+
 /* Localizer::DoLocalBA (/root/reference/src/Localizer.cpp:233-302) - SURVEY section 8(f).2: pose-only bundle adjustment of one
  * key frame against the fixed map points it observes, the whole optimize(iters) in one launch.
  *   pose12      = rotation row-major (9) then translation (3) of a rigid transform, x_c = R x_w + t (Tcw)

@@ -29,6 +29,7 @@ PER_FILE = {
     "match.hip": ["-ffp-contract=off"],
     "triangulate.hip": ["-ffp-contract=off"],
     "ransac.hip": ["-ffp-contract=off"],
+    "track_frames.hip": ["-ffp-contract=off"],   # triangulate_dlt and the parallax test round as triangulate.hip's, to the bit
     "bow.hip": ["-ffp-contract=off"],        # BowVector values and scores equal the host vocabulary's to the bit
     "voc_train.hip": ["-ffp-contract=off"],  # cut_d = u * sum is one IEEE multiply on host and device
     "mappoint.hip": ["-ffp-contract=off"],   # mMinDist / mMaxDist are IEEE operations, equal to the host's to the bit

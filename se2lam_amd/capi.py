@@ -238,6 +238,8 @@ SYMBOLS = {
     "se2gpu_track_stream": (_VP, [_VP]),
     "se2gpu_track_sync": (_I, [_VP]),
     "se2gpu_track_loop_verify_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "se2gpu_track_frames_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_float,
+                                              C.c_float, _I, _VP, _VP, _VP, _VP]),
     "se2gpu_plane_motion_prior": (_I, [_VP, _VP, _D, _D, _D, _VP, _VP]),
     "se2gpu_track_pose_ba": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _D, _D, _D, _D, _I, _VP, C.POINTER(BaStats)]),
     "se2gpu_track_triangulate": (_I, [_VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _I, _VP, _VP,

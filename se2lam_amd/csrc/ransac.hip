@@ -570,6 +570,51 @@ struct CvRng {   // cv::RNG (multiply-with-carry), seeded with (uint64)-1 by bot
 };
 
 }  // namespace
+
+// track_ws.h: shared by se2gpu_track_loop_verify_batch_device and se2gpu_track_frames_batch_device (track_frames.hip)
+int lv_filter_batch(se2gpu_track* h, const se2gpu_keypoint* d_kps, const int32_t* d_counts, int cap, int nframes,
+                    const uint8_t* d_has_mp, const int32_t* d_num_mps, const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs,
+                    const int32_t* d_matches12, int32_t* d_matches_good, int32_t* d_matches_mp, int32_t* d_info) {
+    if (!h->lv_raw.p) {   // once per handle, blocking: the table is in place whichever stream the calls run on
+        std::vector<uint32_t> raw(kFmRawTable);
+        h->lv_raw_state = fm_raw_fill(raw.data(), kFmRawTable);
+        SE2_CHECK(h->lv_raw.reserve(kFmRawTable));
+        SE2_HIP(hipMemcpy(h->lv_raw.p, raw.data(), raw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    // as few slices as the ceiling allows, of equal size: every slice pays the latency of the five launches once
+    const int fit = (int)std::min<size_t>((size_t)npairs, std::max<size_t>(1, kLvScratchCeiling / lv_pair_bytes(cap)));
+    const int nslices = (npairs + fit - 1) / fit;
+    const int slice = (npairs + nslices - 1) / nslices;
+    SE2_CHECK(h->lv_pts.reserve((size_t)slice * 2 * cap));
+    SE2_CHECK(h->lv_slot.reserve((size_t)slice * cap));
+    SE2_CHECK(h->lv_mask.reserve((size_t)slice * cap));
+    SE2_CHECK(h->lv_meta.reserve((size_t)slice * kLvMeta));
+    SE2_CHECK(h->lv_sub.reserve((size_t)slice * kMaxIters * 7));
+    SE2_CHECK(h->lv_F.reserve((size_t)slice * kMaxIters * 27));
+    SE2_CHECK(h->lv_nm.reserve((size_t)slice * kMaxIters));
+    SE2_CHECK(h->lv_score.reserve((size_t)slice * kMaxIters * 3));
+    const int lmeds_iters = std::max(fm_update_num_iters(kConfidence, kLmedsOutlierRatio, kModelPoints, kMaxIters), 3);
+    const LvBatch b{d_kps, d_counts, d_has_mp, d_num_mps, d_pair_a, d_pair_b, d_matches12, cap, nframes};
+    hipStream_t st = h->stream;
+    for (int p0 = 0; p0 < npairs; p0 += slice) {   // the slices follow each other on the stream and share the scratch
+        const int np = std::min(slice, npairs - p0);
+        hipLaunchKernelGGL(k_lv_gather, dim3(np), dim3(256), 0, st, b, p0, lmeds_iters, h->lv_pts.p, h->lv_slot.p,
+                           h->lv_meta.p);
+        hipLaunchKernelGGL(k_lv_draw, dim3(np), dim3(64), 0, st, (const int*)h->lv_meta.p, (const uint32_t*)h->lv_raw.p,
+                           h->lv_raw_state, h->lv_sub.p);
+        hipLaunchKernelGGL(k_lv_models, dim3((kMaxIters + 63) / 64, np), dim3(64), 0, st, (const int*)h->lv_meta.p, cap,
+                           (const float2*)h->lv_pts.p, (const int*)h->lv_sub.p, h->lv_F.p, h->lv_nm.p);
+        hipLaunchKernelGGL(k_lv_score, dim3((kMaxIters * 3 + 3) / 4, np), dim3(256), 0, st, (const int*)h->lv_meta.p, cap,
+                           (const float2*)h->lv_pts.p, (const double*)h->lv_F.p, (const int*)h->lv_nm.p,
+                           (float)(kThreshold * kThreshold), h->lv_score.p);
+        hipLaunchKernelGGL(k_lv_select, dim3(np), dim3(256), 0, st, b, p0, (const float2*)h->lv_pts.p,
+                           (const int*)h->lv_slot.p, (const int*)h->lv_meta.p, (const double*)h->lv_F.p,
+                           (const double*)h->lv_score.p, h->lv_mask.p, d_matches_good, d_matches_mp, d_info);
+    }
+    SE2_HIP(hipGetLastError());
+    return SE2GPU_OK;
+}
+
 }  // namespace se2gpu
 
 using namespace se2gpu;
@@ -733,44 +778,8 @@ extern "C" int se2gpu_track_loop_verify_batch_device(se2gpu_track* h, const se2g
                 SE2GPU_ERR_INVALID, "loop_verify_batch: NULL argument");
     SE2_REQUIRE(npairs >= 1 && cap >= 1 && nframes >= 1, SE2GPU_ERR_INVALID, "loop_verify_batch: bad sizes");
     SE2_REQUIRE(!d_matches_mp || d_has_mp, SE2GPU_ERR_INVALID, "loop_verify_batch: d_matches_mp without d_has_mp");
-    SE2_REQUIRE(cap <= 64 * 1024, SE2GPU_ERR_CAPACITY, "loop_verify_batch: cap %d exceeds the limit %d", cap, 64 * 1024);
-    SE2_REQUIRE(npairs <= 65535, SE2GPU_ERR_CAPACITY, "loop_verify_batch: %d pairs exceed the limit 65535", npairs);
-    if (!h->lv_raw.p) {   // once per handle, blocking: the table is in place whichever stream the calls run on
-        std::vector<uint32_t> raw(kFmRawTable);
-        h->lv_raw_state = fm_raw_fill(raw.data(), kFmRawTable);
-        SE2_CHECK(h->lv_raw.reserve(kFmRawTable));
-        SE2_HIP(hipMemcpy(h->lv_raw.p, raw.data(), raw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    // as few slices as the ceiling allows, of equal size: every slice pays the latency of the five launches once
-    const int fit = (int)std::min<size_t>((size_t)npairs, std::max<size_t>(1, kLvScratchCeiling / lv_pair_bytes(cap)));
-    const int nslices = (npairs + fit - 1) / fit;
-    const int slice = (npairs + nslices - 1) / nslices;
-    SE2_CHECK(h->lv_pts.reserve((size_t)slice * 2 * cap));
-    SE2_CHECK(h->lv_slot.reserve((size_t)slice * cap));
-    SE2_CHECK(h->lv_mask.reserve((size_t)slice * cap));
-    SE2_CHECK(h->lv_meta.reserve((size_t)slice * kLvMeta));
-    SE2_CHECK(h->lv_sub.reserve((size_t)slice * kMaxIters * 7));
-    SE2_CHECK(h->lv_F.reserve((size_t)slice * kMaxIters * 27));
-    SE2_CHECK(h->lv_nm.reserve((size_t)slice * kMaxIters));
-    SE2_CHECK(h->lv_score.reserve((size_t)slice * kMaxIters * 3));
-    const int lmeds_iters = std::max(fm_update_num_iters(kConfidence, kLmedsOutlierRatio, kModelPoints, kMaxIters), 3);
-    const LvBatch b{d_kps, d_counts, d_has_mp, d_num_mps, d_pair_a, d_pair_b, d_matches12, cap, nframes};
-    hipStream_t st = h->stream;
-    for (int p0 = 0; p0 < npairs; p0 += slice) {   // the slices follow each other on the stream and share the scratch
-        const int np = std::min(slice, npairs - p0);
-        hipLaunchKernelGGL(k_lv_gather, dim3(np), dim3(256), 0, st, b, p0, lmeds_iters, h->lv_pts.p, h->lv_slot.p,
-                           h->lv_meta.p);
-        hipLaunchKernelGGL(k_lv_draw, dim3(np), dim3(64), 0, st, (const int*)h->lv_meta.p, (const uint32_t*)h->lv_raw.p,
-                           h->lv_raw_state, h->lv_sub.p);
-        hipLaunchKernelGGL(k_lv_models, dim3((kMaxIters + 63) / 64, np), dim3(64), 0, st, (const int*)h->lv_meta.p, cap,
-                           (const float2*)h->lv_pts.p, (const int*)h->lv_sub.p, h->lv_F.p, h->lv_nm.p);
-        hipLaunchKernelGGL(k_lv_score, dim3((kMaxIters * 3 + 3) / 4, np), dim3(256), 0, st, (const int*)h->lv_meta.p, cap,
-                           (const float2*)h->lv_pts.p, (const double*)h->lv_F.p, (const int*)h->lv_nm.p,
-                           (float)(kThreshold * kThreshold), h->lv_score.p);
-        hipLaunchKernelGGL(k_lv_select, dim3(np), dim3(256), 0, st, b, p0, (const float2*)h->lv_pts.p,
-                           (const int*)h->lv_slot.p, (const int*)h->lv_meta.p, (const double*)h->lv_F.p,
-                           (const double*)h->lv_score.p, h->lv_mask.p, d_matches_good, d_matches_mp, d_info);
-    }
-    SE2_HIP(hipGetLastError());
-    return SE2GPU_OK;
+    SE2_REQUIRE(cap <= kLvMaxCap, SE2GPU_ERR_CAPACITY, "loop_verify_batch: cap %d exceeds the limit %d", cap, kLvMaxCap);
+    SE2_REQUIRE(npairs <= kLvMaxPairs, SE2GPU_ERR_CAPACITY, "loop_verify_batch: %d pairs exceed the limit %d", npairs, kLvMaxPairs);
+    return lv_filter_batch(h, d_kps, d_counts, cap, nframes, d_has_mp, d_num_mps, d_pair_a, d_pair_b, npairs, d_matches12,
+                           d_matches_good, d_matches_mp, d_info);
 }

@@ -1,7 +1,19 @@
-// Device workspace of one tracking thread, shared by ransac.hip (removeOutliers, the batched loop verification) and
-// triangulate.hip (doTriangulate).
+// Device workspace of one tracking thread, shared by ransac.hip (removeOutliers, the batched loop verification),
+// triangulate.hip (doTriangulate) and track_frames.hip (both, for batches of frame pairs in HBM).
 #pragma once
 #include "common.h"
+
+struct se2gpu_track;
+
+namespace se2gpu {
+constexpr int kLvMaxCap = 64 * 1024;   // the limits of se2gpu_search_by_bow_batch_device
+constexpr int kLvMaxPairs = 65535;
+// The gather / draw / models / score / select launches of se2gpu_track_loop_verify_batch_device on the handle's stream, in
+// slices of the handle's scratch (ransac.hip); the arguments are that call's, already checked by the caller.
+int lv_filter_batch(se2gpu_track* h, const se2gpu_keypoint* d_kps, const int32_t* d_counts, int cap, int nframes,
+                    const uint8_t* d_has_mp, const int32_t* d_num_mps, const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs,
+                    const int32_t* d_matches12, int32_t* d_matches_good, int32_t* d_matches_mp, int32_t* d_info);
+}  // namespace se2gpu
 
 struct se2gpu_track {
     hipStream_t own_stream = nullptr, stream = nullptr;   // stream: own_stream, or the one se2gpu_track_set_stream lent

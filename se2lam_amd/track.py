@@ -4,8 +4,10 @@
     Track.doTriangulate(...)                  Track.cpp:378-419   see matcher.doTriangulate
     Track.loop_verify_batch_device(...)       GlobalMapper.cpp:1207-1276, Localizer.cpp:571-612   RemoveMatchOutlierRansac and
                                               RemoveKPMatch behind SearchByBoW, for a batch of key-frame pairs in HBM
+    Track.track_frames_batch_device(...)      Track.cpp:308-344 then :378-419   removeOutliers and doTriangulate behind
+                                              MatchByWindow, for a batch of (key frame, frame) pairs in HBM
 
-Everything is computed by libse2gpu (csrc/ransac.hip, csrc/triangulate.hip); there is no CPU fallback.
+Everything is computed by libse2gpu (csrc/ransac.hip, csrc/triangulate.hip, csrc/track_frames.hip); there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -18,6 +20,10 @@ from . import capi
 
 # the 8 ints se2gpu_track_loop_verify_batch_device writes per pair
 LOOP_VERIFY_INFO = ("n_raw", "n_good", "n_good_mp", "n_mps_a", "path", "sample", "model", "iterations")
+
+# the 8 ints se2gpu_track_frames_batch_device writes per pair; status: 0 run, 1 a frame index out of range, 2 fewer than 10
+# inliers, 3 triangulation skipped by the pair's flag
+TRACK_FRAMES_INFO = ("n_raw", "n_inliers", "n_tracked_old", "n_good_prl", "n_old_kp", "path", "n_depth_rejected", "status")
 
 
 class Track:
@@ -69,6 +75,22 @@ class Track:
         capi.check(capi.lib().se2gpu_track_loop_verify_batch_device(self._h, d_kps, d_counts, cap, nframes, d_has_mp, d_num_mps,
                                                                     d_pair_a, d_pair_b, npairs, d_matches12, d_matches_good,
                                                                     d_matches_mp, d_info))
+
+    def track_frames_batch_device(self, d_kps_un, d_counts, cap, nframes, d_kf_observed, d_view_pos, d_pair_ref, d_pair_cur, npairs,
+                                  d_Trc, d_P, d_pair_flags, P_ref, d_matches12, lower_depth, upper_depth, min_degree, d_matched12,
+                                  d_local_pos, d_good_prl, d_info):
+        """se2gpu_track_frames_batch_device: removeOutliers and then doTriangulate on the match rows
+        ORBmatcher.match_window_batch_device wrote, for npairs (reference key frame, current frame) pairs; all device pointers
+        except P_ref (Config::PrjMtrxEye, 12 floats on the host).  d_kf_observed / d_view_pos and d_pair_flags may be None.
+        d_matched12 and d_local_pos are what se2gpu_kf_correspd_batch_device reads; d_info gets 8 ints per pair,
+        TRACK_FRAMES_INFO.  Asynchronous on this handle's stream: sync() before the outputs are read."""
+        P1 = np.ascontiguousarray(P_ref, np.float32).reshape(-1)
+        if P1.size != 12:
+            raise ValueError("P_ref must hold 12 floats")
+        capi.check(capi.lib().se2gpu_track_frames_batch_device(
+            self._h, d_kps_un, d_counts, cap, nframes, d_kf_observed, d_view_pos, d_pair_ref, d_pair_cur, npairs, d_Trc, d_P,
+            d_pair_flags, P1.ctypes.data, d_matches12, float(lower_depth), float(upper_depth), int(min_degree), d_matched12,
+            d_local_pos, d_good_prl, d_info))
 
     def sync(self):
         capi.check(capi.lib().se2gpu_track_sync(self._h))
