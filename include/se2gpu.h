@@ -385,6 +385,98 @@ int se2gpu_kf_correspd_batch_device(se2gpu_matcher* h,
                                     int32_t* d_inv, uint8_t* d_kind, int32_t* d_src, float* d_view, float* d_info,
                                     float* d_new_pos_w, float* d_info_prev, int32_t* d_counts_out);
 
+/* The map's bookkeeping for a batch of B new key frames, and for pruned ones: what LocalMapper::findCorrespd's addObservation /
+ * setViewMP / insertMP calls (src/LocalMapper.cpp:95-168), MapPoint::addObservation's normal vector (src/MapPoint.cpp:104-122) and
+ * the erasures of KeyFrame::setNull / MapPoint::eraseObservation / MapPoint::setNull (src/KeyFrame.cpp:100-113,
+ * src/MapPoint.cpp:54-101) do to the observation table every other call reads.  It writes a NEW table (CSR and entry rows) of
+ * capacities m_cap / nobs_cap from the old one and the rows se2gpu_kf_correspd_batch_device left, and updates the per-point and
+ * per-feature tables in place.  Every pointer is device memory.
+ *   d_counts, cap, nframes, d_frame_null (nframes bytes or NULL)   the frame slots; a set byte = KeyFrame::isNull()
+ *   d_mp_ptr (m_cap + 1), d_obs_frame, d_obs_ftr (nobs_cap), d_obs_view (nobs_cap x 3), d_obs_info (nobs_cap x 9)   the old table;
+ *       the two entry rows and their new counterparts are optional, all four or none
+ *   d_sizes_in   {m_old, nobs_old} in DEVICE memory, clamped to 0..m_cap and 0..nobs_cap: d_sizes_out + 1 of the call before,
+ *       so that calls follow one another without the host knowing the sizes (the two may be the same buffer)
+ *   d_job_prev, d_job_new (B), d_kind, d_src, d_view, d_info, d_new_pos_w, d_info_prev (B * cap rows, by the new key frame's
+ *       feature j), d_local_pos (by the previous key frame's feature)   as se2gpu_kf_correspd_batch_device takes / leaves them
+ *   d_good_prl_row (B * cap bytes)   mvbGoodPrl of se2gpu_track_frames_batch_device, by the previous key frame's feature
+ *   kinds   bit k (1..3) = apply the rows of kind k, so the faithful order (passes = 1, apply, parallax, ..., passes = 6, apply)
+ *       can use one row buffer
+ *   d_parallax_status (m_cap ints or NULL)   d_status of se2gpu_mappoint_parallax_batch_device: 2 counts as a null point here
+ *   in place, per point (m_cap): d_pos (x 3), d_good_prl, d_mp_null (bytes), d_mp_normal (x 3)
+ *   in place, per feature (nframes * cap): d_ftr_mp (mDualObservations: the point's slot or -1), d_kf_observed (bytes),
+ *       d_view_pos (x 3), d_view_info (x 9)
+ *   out: d_mp_ptr_new, d_obs_frame_new, d_obs_ftr_new, d_obs_view_new, d_obs_info_new (not the old arrays); d_new_frame (m_cap):
+ *       the frame slot of the entry this call appended to the point (the last job's if several did), -1 for none - what
+ *       se2gpu_mappoint_parallax_batch_device takes as d_new_frame; d_sizes_out (SE2GPU_MAP_APPLY_NSIZES ints, below);
+ *       d_job_counts (B x 6): {1 if the job was skipped, rows of kind 1, 2, 3 applied, rows skipped, duplicate claims}
+ *   d_ws   se2gpu_map_apply_ws_bytes(B, cap, m_cap, nobs_cap) bytes, 16-byte aligned, no initialisation needed; -1 on sizes
+ *       the call would refuse
+ * The rules, in this order:
+ * 1. Erase first, on the state at entry.  An old entry (f, k) of point p < m_old is dropped when
+ *      - it fails the entry rule of se2lam_amd/obs_table.h (f outside 0..nframes-1 or k outside 0..min(counts[f], cap)-1);
+ *      - its point is null or has parallax status 2 - MapPoint::setNull, MapPoint.cpp:68-78: pKF->eraseObservation(idx) makes
+ *        ftr_mp[f][k] = -1 and kf_observed[f][k] = 0, mbNull = true and mbGoodParallax = false (:69-70);
+ *      - its frame is null - KeyFrame::setNull, KeyFrame.cpp:101-104: pMP->eraseObservation(pThis) for each of its points.  With
+ *        size = the point's entries left after this erase (entries that fail the entry rule never counted), size > 0 updates
+ *        mNormalVector = (mNormalVector * (float)(size + 1) - normPos) * (1.f / (float)size), normPos = viewPos * (1.f /
+ *        cv::norm(viewPos)), viewPos = view_pos[f][k] (MapPoint.cpp:89-90, :98-99), in list order.
+ *    Every null frame's ftr_mp row becomes -1 and its kf_observed row 0 (KeyFrame.cpp:110-111).  A point that was not null and is
+ *    left without entries becomes null with good_prl cleared (MapPoint.cpp:93-94, :56-57).  Kept entries keep their order.
+ * 2. Rows of kind 1 and 2 append one entry (job_new[b], j) to point p = ftr_mp[job_prev[b]][src] as it was at entry (kind 1,
+ *    pPrefKF->getObservation(i), LocalMapper.cpp:97) or p = src (kind 2, :122), after the kept entries; several jobs that add
+ *    to one point append in ascending job index.  The call writes view_pos / view_info of the feature (setViewMP, :103, :138),
+ *    ftr_mp = p and kf_observed = 1 (KeyFrame::addObservation, KeyFrame.cpp:199-200), the entry's rows, and mNormalVector =
+ *    (mNormalVector * (float)oldObsSize + newNorm) * (1.f / (float)(oldObsSize + 1)) with oldObsSize = the list's length before
+ *    the append (MapPoint.cpp:107, :115-117).  A row is skipped, counted, its kf_observed byte cleared and nothing else written
+ *    when it names no point or one outside 0..m_old-1; a point that is null after rule 1 (KeyFrame::addObservation returns,
+ *    KeyFrame.cpp:197); a point that keeps an entry of that frame (std::map::insert keeps the old one, MapPoint.cpp:108).  If
+ *    several features of one job name one point the greatest j wins, whatever becomes of it; the others are skipped and also
+ *    counted as duplicate claims.
+ * 3. Rows of kind 3 create a point (LocalMapper.cpp:145-168).  src must lie in 0..min(counts[prev], cap)-1 (else skipped);
+ *    of several rows with one src the greatest j wins (the others: skipped, duplicate).  Slot = m_old + the winners of earlier
+ *    jobs + the row's rank among its job's winners by ascending src: the loop at :145 runs over the previous key frame's features
+ *    and MapPoint::mId grows in that order.  Entries (prev, src) then (new, j) (:160-161); pos = new_pos_w, good_prl =
+ *    good_prl_row[b][src] (:158), mp_null = 0, the normal from the two appends starting at zero; view_pos[prev][src] =
+ *    local_pos[b][src], view_info[prev][src] = info_prev[b][j] (:156); the new key frame's feature as in rule 2; ftr_mp and
+ *    kf_observed of both features (:162-163).
+ * 4. Padding: mp_ptr_new[p] = nobs_new for p = m_new..m_cap; the point slots from m_new on are null, not good-parallax, with
+ *    new_frame = -1.  The table can therefore be handed to every consumer with m = m_cap and nobs = nobs_cap.
+ * 5. Capacity: m_new > m_cap or nobs_new > nobs_cap gives status 2 in d_sizes_out; the sizes and counts say what was needed,
+ *    nothing in place has been modified and the new table is undefined.
+ * 6. The 2 B frame slots of a batch are pairwise distinct, as for se2gpu_kf_correspd_batch_device.  A job with a slot out of
+ *    range, prev == new or a null frame is skipped (d_job_counts[6b] = 1, its rows are not looked at).  B == 0 is a pure erase
+ *    pass: Map::pruneRedundantKF's KeyFrame::setNull, or the points se2gpu_mappoint_parallax_batch_device abandoned.
+ * Asynchronous on the matcher's stream (memsets and launches; nothing allocated, read back or waited for); every output word
+ * is the same in every run: integer atomicMax picks a claim's winner, integer atomicAdd only sums counters, places come from
+ * prefix sums.  The argument checks come first and touch neither the handle nor a device:
+ * SE2GPU_ERR_INVALID: a NULL handle or required pointer (optional: d_frame_null, the four entry rows together,
+ *   d_parallax_status; with B == 0 the job arrays and d_job_counts; without bit 3 of kinds d_new_pos_w, d_info_prev, d_local_pos,
+ *   d_good_prl_row); B < 0, m_cap < 0, nobs_cap < 0, cap < 1, nframes < 1; kinds with bits outside 1..3; a new array equal to
+ *   its old one; d_ws not 16-byte aligned.
+ * SE2GPU_ERR_CAPACITY: nframes * cap > 2^31 - 1; B > 65535, B * m_cap > 2^31 - 1, m_cap + B * cap or nobs_cap + 2 B cap + 1 not
+ *   below 2^31 - 1; ws_bytes too small.   B == 0 with m_cap == 0 (no job, and no point slot to erase anything from) is
+ *   SE2GPU_OK, launches nothing and writes nothing: d_sizes_out and d_mp_ptr_new are NOT written either, so such a call is
+ *   no link of a chain (a later call must not take its d_sizes_in from it).   SE2GPU_ERR_NO_DEVICE after all of these. */
+enum { SE2GPU_MAP_APPLY_STATUS = 0,   /* 0 done, 2 capacity */
+       SE2GPU_MAP_APPLY_M_NEW, SE2GPU_MAP_APPLY_NOBS_NEW, SE2GPU_MAP_APPLY_ADDED, SE2GPU_MAP_APPLY_ERASED,
+       SE2GPU_MAP_APPLY_CREATED, SE2GPU_MAP_APPLY_NULLED, SE2GPU_MAP_APPLY_SKIPPED, SE2GPU_MAP_APPLY_DUP,
+       SE2GPU_MAP_APPLY_NSIZES };
+long long se2gpu_map_apply_ws_bytes(int B, int cap, int m_cap, int nobs_cap);
+int se2gpu_map_apply_batch_device(se2gpu_matcher* h,
+                                  const int32_t* d_counts, int cap, int nframes, const uint8_t* d_frame_null,
+                                  const int32_t* d_mp_ptr, const int32_t* d_obs_frame, const int32_t* d_obs_ftr,
+                                  const float* d_obs_view, const float* d_obs_info,
+                                  const int32_t* d_sizes_in, int m_cap, int nobs_cap,
+                                  const int32_t* d_job_prev, const int32_t* d_job_new, int B,
+                                  const uint8_t* d_kind, const int32_t* d_src, const float* d_view, const float* d_info,
+                                  const float* d_new_pos_w, const float* d_info_prev, const float* d_local_pos,
+                                  const uint8_t* d_good_prl_row, int kinds, const int32_t* d_parallax_status,
+                                  float* d_pos, uint8_t* d_good_prl, uint8_t* d_mp_null, float* d_mp_normal,
+                                  int32_t* d_ftr_mp, uint8_t* d_kf_observed, float* d_view_pos, float* d_view_info,
+                                  int32_t* d_mp_ptr_new, int32_t* d_obs_frame_new, int32_t* d_obs_ftr_new,
+                                  float* d_obs_view_new, float* d_obs_info_new, int32_t* d_new_frame,
+                                  int32_t* d_sizes_out, int32_t* d_job_counts, void* d_ws, long long ws_bytes);
+
 /* Covisibility: Map::compareViewMPs (src/Map.cpp:354-400 of the reference, both overloads) for batches, on the observation
  * CSR of se2gpu_mappoint_parallax_batch_device.  The observation sets live in a caller-supplied bit matrix d_bits of
  * (nframes + 2) rows of W = ceil(m / 64) 64-bit words, bit p & 63 of word p / 64 = point p:

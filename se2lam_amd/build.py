@@ -34,6 +34,7 @@ PER_FILE = {
     "voc_train.hip": ["-ffp-contract=off"],  # cut_d = u * sum is one IEEE multiply on host and device
     "mappoint.hip": ["-ffp-contract=off"],   # mMinDist / mMaxDist are IEEE operations, equal to the host's to the bit
     "new_kf.hip": ["-ffp-contract=off"],     # view_info.h: float arithmetic in the reference's order, equal to the host mirror's
+    "map_apply.hip": ["-ffp-contract=off"],  # map_normal.h: mNormalVector rounds operation by operation, as the host mirror's
     "covis.hip": ["-ffp-contract=off"],      # the ratios and threshold tests are single IEEE operations, as in the reference
     "sparsify.hip": ["-ffp-contract=off"],   # forward differences with delta 1e-6 decide the result: reproduce them to the bit
     "feat_edge_device.hip": ["-ffp-contract=off"],   # the plane-motion prior's information equals the host function's to the bit
@@ -70,7 +71,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     sub2 = os.path.join(INCLUDE, "se2lam_amd", "VocabularyTrain.h")   # voc_train.hip shares its inline functions with the host mirror
     sub3 = os.path.join(INCLUDE, "se2lam_amd", "view_info.h")         # triangulate.hip / new_kf.hip share it with FindCorrespd.h
     sub4 = os.path.join(INCLUDE, "se2lam_amd", "obs_table.h")         # mappoint.hip / new_kf.hip / covis.hip share it with their mirrors
-    headers += [sub, sub2, sub3, sub4, os.path.abspath(__file__)]
+    sub5 = os.path.join(INCLUDE, "se2lam_amd", "map_normal.h")        # map_apply.hip shares it with MapUpdate.h
+    headers += [sub, sub2, sub3, sub4, sub5, os.path.abspath(__file__)]
     objs = []
     for src in sources():
         obj = os.path.join(OBJDIR, src[:-4] + ".o")

@@ -151,6 +151,9 @@ SYMBOLS = {
     "se2gpu_kf_correspd_batch_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                              _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _F, _F, _F, _I, _VP, _VP, _VP, _VP, _VP,
                                              _VP, _VP, _VP]),
+    "se2gpu_map_apply_ws_bytes": (C.c_longlong, [_I, _I, _I, _I]),
+    "se2gpu_map_apply_batch_device": (_I, [_VP, _VP, _I, _I, _VP] + [_VP] * 5 + [_VP, _I, _I, _VP, _VP, _I] + [_VP] * 8 +
+                                      [_I, _VP] + [_VP] * 16 + [_VP, C.c_longlong]),
     "se2gpu_covis_bits_words": (C.c_longlong, [_I, _I]),
     "se2gpu_covis_build_device": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "se2gpu_covis_pairs_device": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _F, _D, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I]),
