@@ -10,6 +10,8 @@ import threading
 
 import numpy as np
 
+import scaled_parity as sp
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -496,6 +498,8 @@ def sharded_equals_single(g, iters, trials=None, world=2, debug_lam=None, stop=N
             (S, b), (x, ok) = dbg[r]
             assert ok and np.abs(S - S0).max() <= 1e-10 * np.abs(S0).max() and np.abs(b - b0).max() <= 1e-10 * np.abs(b0).max()
             assert np.abs(x - x0).max() <= 1e-8 * np.abs(x0).max()
+            sp.close(S, b, S0, b0, 1e-10, ("shard", r, "against the single handle"))     # the same in the system's own scale
+            assert sp.step_distance(x, x0, 3) <= 1e-8
     # every landmark lives on exactly one rank: the shards' landmark estimates together are the single run's
     lms = np.full_like(single.estimates()[1], np.nan)
     for r in range(world):

@@ -400,9 +400,61 @@ def check_sparsify(pair, z, info, model=None, spectrum=True):
 
 
 def check_sparsify_equals(z, info, z_ref, info_ref):
-    """an implementation's output against the restatement's FOR THE SAME MEASUREMENT ORDER: the suite's tolerances"""
+    """an implementation's output against the restatement's FOR THE SAME MEASUREMENT ORDER: the suite's tolerances.  The bound
+    is 1e-5 of the LARGEST entry - 0.1 absolute wherever a rotation eigenvalue sits at the 1e4 clamp - so the relative
+    information distance is printed beside it (asserted only where the reference is not noise in it: check_sparsify_relative)"""
     assert np.allclose(z, z_ref, atol=1e-12)
+    try:
+        d = info_distance(info, info_ref)
+    except np.linalg.LinAlgError:      # (a reference that is not positive definite to working precision: nothing to print)
+        d = float("nan")
+    print("sparsify: |info - ref| / max %.2e, relative information distance %.2e" % (np.abs(info - info_ref).max() / np.abs(info_ref).max(), d))
     assert np.abs(info - info_ref).max() <= 1e-5 * np.abs(info_ref).max(), np.abs(info - info_ref).max() / np.abs(info_ref).max()
+
+
+def info_distance(info, info_ref):
+    """max |w - 1| over the generalised eigenvalues w of (info, info_ref): the largest relative difference of the information the
+    two matrices hold about any direction - millimetre and radian directions weigh the same, which max |info - ref| / max |ref|
+    does not do (there the translation block may be 100 % off under a rotation block at the 1e4 clamp)"""
+    import scipy.linalg
+    return float(np.abs(scipy.linalg.eigh(np.asarray(info, np.float64), np.asarray(info_ref, np.float64), eigvals_only=True) - 1.0).max())
+
+
+def sparsify_ulp_floor(sparsify, pair, draws=4, seed=0):
+    """The reference's own noise in info_distance: the largest distance of sparsify(pair)'s information to that of `draws` copies
+    of the pair in which every entry of m_info (kept symmetric) and of mp is moved by one ulp, up or down at random."""
+    kf, mp, m_kf, m_mp, m_info = pair
+    info0 = sparsify(*pair)[1]
+    rng = np.random.default_rng(seed)
+    iu = np.triu_indices(3, 1)
+
+    def ulp(a):
+        a = np.asarray(a, np.float64)
+        return np.nextafter(a, np.where(rng.integers(0, 2, a.shape) == 1, np.inf, -np.inf))
+    out = []
+    for _ in range(draws):
+        mi = ulp(m_info)
+        mi[:, iu[1], iu[0]] = mi[:, iu[0], iu[1]]
+        out.append(info_distance(sparsify(kf, ulp(mp), m_kf, m_mp, mi)[1], info0))
+    return max(out)
+
+
+FLOOR_MARGIN = 64      # four draws undersample the floor
+
+
+def check_sparsify_relative(z, info, z_ref, info_ref, floor):
+    """an implementation against the restatement on a pair where the restatement is well determined: the information within
+    FLOOR_MARGIN x the restatement's own one-ulp floor in the relative measure, and a rotation eigenvalue (the three largest)
+    strictly inside the clamp (1e-6, 1e4) - the regime these pairs are there for"""
+    assert np.allclose(z, z_ref, atol=1e-12)
+    assert np.abs(info - info.T).max() == 0
+    d = info_distance(info, info_ref)
+    rot = np.sort(np.linalg.eigvalsh(info_ref))[3:]
+    print("sparsify: relative information distance %.2e, one-ulp floor of the reference %.2e (bound %d x), rotation eigenvalues %s"
+          % (d, floor, FLOOR_MARGIN, ["%.4g" % x for x in rot]))
+    assert ((rot > 1e-6 * (1 + 1e-6)) & (rot < 1e4 * (1 - 1e-6))).any(), rot
+    assert d <= FLOOR_MARGIN * floor, (d, floor)
+    return d
 
 
 # ------------------------------------------------------------------------------------------------------- pose-only BA

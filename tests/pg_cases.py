@@ -118,6 +118,18 @@ def recorded():
     return out
 
 
+def recorded_scaled():
+    """the same for pg_model.scaled_distance: {(kind, P): (bound on the scaled distance of H, of b)}, from the file's second
+    table (six columns, so that the rows of the two tables cannot be taken for each other)"""
+    out = {}
+    with open(RECORD) as f:
+        for line in f:
+            c = [x.strip() for x in line.strip().strip("|").split("|")]
+            if len(c) == 6 and c[0] in KINDS:
+                out[(c[0], int(c[1]))] = (float(c[4]), float(c[5]))
+    return out
+
+
 def without_edges(g, drop):
     keep = np.setdiff1d(np.arange(g.O), np.asarray(drop, np.int64))
     return dataclasses.replace(g, o_i=g.o_i[keep], o_j=g.o_j[keep], o_meas=g.o_meas[keep], o_info=g.o_info[keep]), keep

@@ -105,3 +105,11 @@ def distance(g, H, b, Hm, bm):
     """(max |H - Hm| / max |Hm|, max |b - bm| / max |bm|) over the free key frames"""
     f = free_mask(g)
     return (np.abs(H[f][:, f] - Hm[f][:, f]).max() / np.abs(Hm[f][:, f]).max(), np.abs(b[f] - bm[f]).max() / np.abs(bm[f]).max())
+
+
+def scaled_distance(g, H, b, Hm, bm):
+    """`distance` in the system's own scale (tests/scaled_parity.py): every entry over d_i d_j, d = sqrt(diag(Hm)), so that the
+    translation entries are not measured against the rotation entries' 1e6"""
+    import scaled_parity as sp
+    f = free_mask(g)
+    return sp.scaled_distance(H[f][:, f], Hm[f][:, f]), sp.scaled_rhs_distance(b[f], bm[f], Hm[f][:, f])

@@ -5,6 +5,7 @@ Tolerance as for the SE(2) model: cost and pose updates within 1e-5 relative (ob
 import numpy as np
 import pytest
 
+import scaled_parity as sp
 from ba_cases import REL, env, odo_graph3, odometry_cases3, opt3
 
 pytestmark = pytest.mark.gpu
@@ -18,11 +19,13 @@ def test_chi2_and_reduced_system_match_oracle(oracle, synth, P, L, n_ref):
     assert o.activeRobustChi2() == pytest.approx(c_ref, rel=1e-11)
     from se2lam_amd import optimizer as op
     assert np.allclose(op.edgeChi2(o, g.E), ec_ref, rtol=1e-10)
+    tol = sp.bound(oracle.ba3_reduced_system(g, 0.0)[0])
     for lam in (0.0, 2.5):
         S, bs = o.reduced_system(lam)
         Sr, br = oracle.ba3_reduced_system(g, lam)
         assert np.abs(S - Sr).max() <= 1e-10 * np.abs(Sr).max()
         assert np.abs(bs - br).max() <= 1e-10 * np.abs(br).max()
+        sp.close(S, bs, Sr, br, tol, (P, L, n_ref, lam))      # in the system's own scale (tests/scaled_parity.py)
 
 
 @pytest.mark.parametrize("P,L,n_ref", [(8, 60, 0), (21, 800, 4), (50, 5000, 0), (50, 5000, 10)])
@@ -125,11 +128,13 @@ def test_odometry_topologies3_match_the_oracle(oracle, synth, P, L, n_ref, kind)
     c_ref, ec_ref = oracle.ba3_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c_ref, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.E), ec_ref, rtol=1e-10)
+    tol = sp.bound(oracle.ba3_reduced_system(g, 0.0)[0])
     for lam in (0.0, 2.5):
         S, bs = o.reduced_system(lam)
         Sr, br = oracle.ba3_reduced_system(g, lam)
         assert np.abs(S - Sr).max() <= 1e-10 * np.abs(Sr).max(), (kind, lam, np.abs(S - Sr).max() / np.abs(Sr).max())
         assert np.abs(bs - br).max() <= 1e-10 * np.abs(br).max(), (kind, lam)
+        sp.close(S, bs, Sr, br, tol, (P, L, n_ref, kind, lam))
     assert o.optimize(10) == 10
     p_ref, l_ref, ec_ref, st = oracle.ba3_optimize(g, 10)
     s = o.stats

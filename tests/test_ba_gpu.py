@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import scaled_parity as sp
 from ba_cases import (LM_REJECT_CASES, REL, _info_inputs, kidnapped, odo_graph, odometry_cases, pose_update_close,
                       sharded_equals_single)
 from ba_cases import opt as _opt      # (three tests below call their optimizer `opt`, the reference's name for it)
@@ -34,6 +35,8 @@ def test_reduced_system_matches_oracle(oracle, synth):
         assert np.abs(S - ref["S"]).max() <= 1e-11 * scale
         assert np.abs(bs - ref["bs"]).max() <= 1e-11 * np.abs(ref["bs"]).max()
         assert np.abs(S - S.T).max() <= 1e-12 * scale
+        # in the system's own scale (tests/scaled_parity.py): millimetre entries weigh as much as radian entries
+        sp.close(S, bs, ref["S"], ref["bs"], sp.bound(oracle.ba_reduced_system(g, 0.0)["S"]), (P, L, lam))
 
 
 @pytest.mark.parametrize("P,L", [(8, 60), (50, 5000)])
@@ -264,6 +267,7 @@ def test_device_pose_solve_matches_host_cholesky(synth, monkeypatch, path, P, L)
             x, ok = o.solve(lam)
             assert ok
             assert np.abs(x - x_ref.astype(np.float64)).max() <= 1e-9 * np.abs(x_ref).max()
+            assert sp.step_distance(x, x_ref, 3) <= 1e-9              # x, y and theta each against its own maximum
 
 
 @pytest.mark.parametrize("path", ["tiles", "steps"])
@@ -296,6 +300,7 @@ def test_dataflow_solve_with_more_tiles_than_resident_workgroups(synth, monkeypa
         x, ok = o.solve(20.0)
         assert ok
         assert np.abs(x - x_ref).max() <= 1e-9 * np.abs(x_ref).max()
+        assert sp.step_distance(x, x_ref, 3) <= 1e-9
 
 
 @pytest.mark.parametrize("case,trials", LM_REJECT_CASES)
@@ -692,12 +697,14 @@ def test_odometry_topologies_match_the_oracle(oracle, synth, P, L, kind):
     extended precision (a tile the solve's pattern lost shows up here), 10 LM iterations against the oracle's g2o run"""
     g = odo_graph(synth, P, L, kind)
     o = _opt(g)
+    tol = sp.bound(oracle.ba_reduced_system(g, 0.0)["S"])
     for lam in (3.0, 40.0):
         S, bs = o.reduced_system(lam)
         ref = oracle.ba_reduced_system(g, lam)
         scale = np.abs(ref["S"]).max()
         assert np.abs(S - ref["S"]).max() <= 1e-11 * scale, (kind, lam, np.abs(S - ref["S"]).max() / scale)
         assert np.abs(bs - ref["bs"]).max() <= 1e-11 * np.abs(ref["bs"]).max(), kind
+        sp.close(S, bs, ref["S"], ref["bs"], tol, (P, L, kind, lam))
         c = np.linalg.cholesky(S)
         solve = lambda r: np.linalg.solve(c.T, np.linalg.solve(c, r))
         x_ref = solve(bs).astype(np.longdouble)
@@ -706,6 +713,7 @@ def test_odometry_topologies_match_the_oracle(oracle, synth, P, L, kind):
         x, ok = o.solve(lam)
         assert ok
         assert np.abs(x - x_ref.astype(np.float64)).max() <= 1e-9 * np.abs(x_ref).max(), (kind, lam)
+        assert sp.step_distance(x, x_ref, 3) <= 1e-9, (kind, lam)
     assert o.optimize(10) == 10
     p_ref, l_ref, st = oracle.ba_optimize(g, 10, 0)
     s = o.stats
@@ -734,6 +742,7 @@ def test_device_plan_equals_host_plan_on_odometry_topologies(synth, monkeypatch)
             assert np.array_equal(pd_, ph) and np.array_equal(ld_, lh), (P, kind)
             continue
         assert np.abs(Sd - Sh).max() <= 1e-13 * np.abs(Sh).max() and np.abs(bd - bh).max() <= 1e-13 * np.abs(bh).max(), (P, kind)
+        sp.close(Sd, bd, Sh, bh, 1e-13, (P, kind, "device plan against host plan"))
         assert sd["trials_hist"] == sh["trials_hist"], (P, kind)
         assert np.allclose(sd["chi2_hist"], sh["chi2_hist"], rtol=1e-10, atol=0), (P, kind)
         assert np.allclose(pd_, ph, rtol=1e-9, atol=1e-9), (P, kind)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import off_axis_cases as oa
+import scaled_parity as sp
 from ba_cases import REL, _info_inputs, env, multi_launch, opt, pose_update_close
 from independent import BAProblemNumpy
 
@@ -47,6 +48,7 @@ def test_reduced_system_matches_oracle(oracle, P, L):
         assert np.abs(S - ref["S"]).max() <= 1e-11 * scale
         assert np.abs(bs - ref["bs"]).max() <= 1e-11 * np.abs(ref["bs"]).max()
         assert np.abs(S - S.T).max() <= 1e-12 * scale
+        sp.close(S, bs, ref["S"], ref["bs"], sp.bound(oracle.ba_reduced_system(g, 0.0)["S"]), (P, L, lam))   # tests/scaled_parity.py
 
 
 @pytest.mark.parametrize("P,L", oa.SIZES)

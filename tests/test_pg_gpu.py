@@ -4,6 +4,7 @@ Cost and pose updates within 1e-5 relative (BASELINE north_star's BA tolerance).
 import numpy as np
 import pytest
 
+import scaled_parity as sp
 from ba_cases import REL, pg
 
 pytestmark = pytest.mark.gpu
@@ -17,11 +18,13 @@ def test_system_and_chi2_match_oracle(oracle, synth, P):
     c, ec = oracle.pg_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.O), ec, rtol=1e-9, atol=1e-12)
+    tol = sp.bound(oracle.pg_system(g, 0.0)[0])
     for lam in (0.0, 0.7):
         H, b = o.reduced_system(lam)
         Hr, br = oracle.pg_system(g, lam)
         assert np.abs(H - Hr).max() <= 1e-10 * np.abs(Hr).max()
         assert np.abs(b - br).max() <= 1e-10 * np.abs(br).max()
+        sp.close(H, b, Hr, br, tol, (P, lam))                 # in the system's own scale (tests/scaled_parity.py)
 
 
 @pytest.mark.parametrize("P", [12, 60, 200])

@@ -17,8 +17,9 @@ import pytest
 
 import pg_cases
 import pg_model
+import scaled_parity as sp
 from ba_cases import REL, opt, opt3, pg
-from pg_cases import recorded
+from pg_cases import recorded, recorded_scaled
 
 pytestmark = pytest.mark.gpu
 
@@ -70,11 +71,13 @@ def test_cost_and_system_match_the_oracle_and_the_model(oracle, kind, P):
     c, ec = oracle.pg_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.O), ec, rtol=1e-9, atol=1e-12)
+    tol = sp.bound(oracle.pg_system(g, 0.0)[0])
     for lam in (0.0, 0.7):
         H, b = o.reduced_system(lam)
         Hr, br = oracle.pg_system(g, lam)
         assert np.abs(H - Hr).max() <= 1e-10 * np.abs(Hr).max()
         assert np.abs(b - br).max() <= 1e-10 * np.abs(br).max()
+        sp.close(H, b, Hr, br, tol, (kind, P, lam))           # in the system's own scale (tests/scaled_parity.py)
     # independent of the oracle: the cost, and the normal equations within (model-to-oracle distance on record) + (the oracle
     # tolerance above) of the model's - the triangle inequality, no other number
     assert o.activeRobustChi2() == pytest.approx(pg_model.cost(g, g.poses)[0], rel=1e-9)
@@ -83,6 +86,11 @@ def test_cost_and_system_match_the_oracle_and_the_model(oracle, kind, P):
     bH, bb = recorded()[(kind, P)]
     print(f"{kind} P={P}: |H - H_model| / max {dH:.2e} (bound {bH:.0e} + 1e-10), |b - b_model| / max {db:.2e} ({bb:.0e} + 1e-10)")
     assert dH <= bH + 1e-10 and db <= bb + 1e-10
+    # the same triangle in the system's own scale: (model-to-oracle scaled distance on record) + (the scaled oracle tolerance)
+    sH, sb = pg_model.scaled_distance(g, H, b, *pg_model.system(g, g.poses))
+    cH, cb = recorded_scaled()[(kind, P)]
+    print(f"{kind} P={P}: scaled {sH:.2e} (bound {cH:.0e} + {tol:.1e}), {sb:.2e} ({cb:.0e} + {tol:.1e})")
+    assert sH <= cH + tol and sb <= cb + tol
 
 
 @pytest.mark.parametrize("kind,P", CASES)

@@ -20,7 +20,7 @@ if __name__ == "__main__":
 
 import pg_cases
 import pg_model
-from pg_cases import RECORD, recorded
+from pg_cases import RECORD, recorded, recorded_scaled
 
 SIZES = (6, 17)
 COND_MAX = 1e12
@@ -39,12 +39,12 @@ def _measure(oracle, kind, P):
     Hm, bm = pg_model.system(g, g.poses)
     f = pg_model.free_mask(g)
     ev = np.linalg.eigvalsh(H[f][:, f])
-    return g, ev, pg_model.distance(g, H, b, Hm, bm)
+    return g, ev, pg_model.distance(g, H, b, Hm, bm), pg_model.scaled_distance(g, H, b, Hm, bm)
 
 
 @pytest.mark.parametrize("kind,P", LAYOUTS)
 def test_layout_is_well_posed_and_the_oracle_equals_the_model(oracle, kind, P):
-    g, ev, (dH, db) = _measure(oracle, kind, P)
+    g, ev, (dH, db), (sH, sb) = _measure(oracle, kind, P)
     assert ev.min() > 0                                       # SPD on the free key frames
     assert ev.max() / ev.min() < COND_MAX
     c, ec = oracle.pg_chi2(g)
@@ -53,6 +53,9 @@ def test_layout_is_well_posed_and_the_oracle_equals_the_model(oracle, kind, P):
     bH, bb = recorded()[(kind, P)]
     print(f"{kind} P={P}: cond {ev.max() / ev.min():.2e}, |H-Hm|/max {dH:.2e} (recorded bound {bH:.0e}), |b-bm|/max {db:.2e} ({bb:.0e})")
     assert dH <= bH and db <= bb
+    cH, cb = recorded_scaled()[(kind, P)]
+    print(f"{kind} P={P}: in the system's own scale {sH:.2e} (recorded bound {cH:.0e}), {sb:.2e} ({cb:.0e})")
+    assert sH <= cH and sb <= cb
     X, _, st = oracle.pg_optimize(g, 8)                       # a clean run: eight iterations, none given up
     assert st["iterations"] == 8 and not st["terminated"] and np.isfinite(st["chi2_hist"]).all()
     assert st["chi2_final"] == pytest.approx(pg_model.cost(g, X)[0], rel=1e-9)
@@ -108,18 +111,21 @@ def test_rejecting_starts_reject_and_stay_clear_of_a_decision(oracle, case):
 def write_record():
     from oracle import oracle
     oracle.lib()
-    rows = []
+    rows, scaled = [], []
     for P in (2, 3) + SIZES + (40,):
         for kind in pg_cases.kinds_at(P):
             if P == 40 and kind != "complete":
                 continue
-            g, ev, (dH, db) = _measure(oracle, kind, P)
+            g, ev, (dH, db), (sH, sb) = _measure(oracle, kind, P)
             rows.append(f"| {kind} | {P} | {g.O} | {ev.max() / ev.min():.1e} | {dH:.1e} | {db:.1e} | {_bound(dH):.0e} | {_bound(db):.0e} |")
+            scaled.append(f"| {kind} | {P} | {sH:.1e} | {sb:.1e} | {_bound(sH):.0e} | {_bound(sb):.0e} |")
     text = open(RECORD).read() if os.path.exists(RECORD) else "# Pose-graph layouts\n\n<!-- table -->\n"
     head, _, _ = text.partition("<!-- table -->")
     table = ["<!-- table -->", "| kind | P | edges | cond(H free, lambda 0) | dist H | dist b | bound H | bound b |", "|---|---|---|---|---|---|---|---|"]
+    table2 = ["", "The same distances in the system's own scale (`pg_model.scaled_distance`):", "",
+              "| kind | P | scaled H | scaled b | bound sH | bound sb |", "|---|---|---|---|---|---|"]
     with open(RECORD, "w") as f:
-        f.write(head + "\n".join(table + rows) + "\n")
+        f.write(head + "\n".join(table + rows + table2 + scaled) + "\n")
 
 
 if __name__ == "__main__":

@@ -344,54 +344,16 @@ def test_reduced_system_from_the_references_own_jacobians(oracle, synth):
     """The Schur-reduced pose system of a small window assembled in numpy from the COMPILED REFERENCE'S residuals and
     Jacobians (robust weights and constructQuadraticForm as g2o defines them: H += J' rho' Omega J, b -= J' rho' Omega e) equals
     the restatement's, which the HIP kernels are held to at 1e-11 (tests/test_ba_gpu.py)."""
+    import scaled_parity as sp
     g = synth.ba_graph(8, 60)
     lam = 3.0
-    P, L = g.P, g.L
-    n = 3 * P
-    Hpp = np.zeros((n, n)); bp = np.zeros(n); Hll = np.zeros((L, 3, 3)); bl = np.zeros((L, 3)); Hpl = {}
-    for k in range(g.E):
-        kf, lm = int(g.e_kf[k]), int(g.e_lm[k])
-        e, Jp, Jl = ref.edge_se2xyz(g, g.poses[kf], g.lms[lm], g.e_uv[k])
-        w = g.e_info[k]
-        Om = np.array([[w[0], w[1]], [w[1], w[2]]])
-        e2 = e @ Om @ e
-        r1 = 1.0 if e2 <= g.huber ** 2 else g.huber / np.sqrt(e2)
-        Hll[lm] += Jl.T @ (r1 * Om) @ Jl
-        bl[lm] -= Jl.T @ (r1 * Om) @ e
-        if not g.fixed[kf]:
-            Hpp[3 * kf:3 * kf + 3, 3 * kf:3 * kf + 3] += Jp.T @ (r1 * Om) @ Jp
-            bp[3 * kf:3 * kf + 3] -= Jp.T @ (r1 * Om) @ e
-            Hpl[(kf, lm)] = Jp.T @ (r1 * Om) @ Jl
-    for k in range(g.O):
-        i, j = int(g.o_i[k]), int(g.o_j[k])
-        e, A, B = ref.edge_pre_se2(g.poses[i], g.poses[j], g.o_meas[k])
-        W = g.o_info[k].reshape(3, 3)
-        for (a, Ja) in ((i, A), (j, B)):
-            if g.fixed[a]:
-                continue
-            bp[3 * a:3 * a + 3] -= Ja.T @ W @ e
-            for (b, Jb) in ((i, A), (j, B)):
-                if not g.fixed[b]:
-                    Hpp[3 * a:3 * a + 3, 3 * b:3 * b + 3] += Ja.T @ W @ Jb
-    S = Hpp.copy(); bs = bp.copy()
-    for p in range(P):
-        if g.fixed[p]:
-            S[3 * p:3 * p + 3, 3 * p:3 * p + 3] = np.eye(3)
-        else:
-            S[3 * p:3 * p + 3, 3 * p:3 * p + 3] += lam * np.eye(3)
-    by_lm = {}
-    for (kf, lm), blk in Hpl.items():
-        by_lm.setdefault(lm, []).append((kf, blk))
-    for lm, obs in by_lm.items():
-        Dinv = np.linalg.inv(Hll[lm] + lam * np.eye(3))
-        for (a, Ba) in obs:
-            bs[3 * a:3 * a + 3] -= Ba @ Dinv @ bl[lm]
-            for (b, Bb) in obs:
-                S[3 * a:3 * a + 3, 3 * b:3 * b + 3] -= Ba @ Dinv @ Bb.T
+    S, bs = sp.se2_system_from_reference_edges(g, lam, np.float64)     # (the assembly: tests/scaled_parity.py, in any precision)
     want = oracle.ba_reduced_system(g, lam)
     scale = np.abs(want["S"]).max()
     assert np.abs(S - want["S"]).max() <= 1e-10 * scale
     assert np.abs(bs - want["bs"]).max() <= 1e-10 * np.abs(want["bs"]).max()
+    # and in the system's own scale, where a translation entry weighs as much as a rotation entry
+    sp.close(S, bs, want["S"], want["bs"], sp.bound(oracle.ba_reduced_system(g, 0.0)["S"]), "numpy from the reference's edges")
 
 
 # ---- src/optimizer.cpp and src/converter.cpp, compiled whole: the construction surface (SURVEY 8 row a20) and the plane-motion priors

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import pg_model
+import scaled_parity as sp
 import world_cases as wc
 from ba_cases import REL, env, multi_launch, opt3, pg
 
@@ -55,11 +56,13 @@ def test_moved_pose_graph_cost_and_system_match_the_oracle(oracle, name):
     c, ec = oracle.pg_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.O), ec, rtol=1e-9, atol=1e-12)
+    tol = sp.bound(oracle.pg_system(g, 0.0)[0])
     for lam in (0.0, 0.7):
         H, b = o.reduced_system(lam)
         Hr, br = oracle.pg_system(g, lam)
         assert np.abs(H - Hr).max() <= 1e-10 * np.abs(Hr).max()
         assert np.abs(b - br).max() <= 1e-10 * np.abs(br).max()
+        sp.close(H, b, Hr, br, tol, ("pose graph", g.P, lam))   # in the system's own scale (tests/scaled_parity.py)
     assert o.activeRobustChi2() == pytest.approx(pg_model.cost(g, g.poses)[0], rel=1e-9)
 
 
@@ -101,11 +104,13 @@ def test_seam_ring_matches_the_oracle_and_the_model(oracle):
     assert o.activeRobustChi2() == pytest.approx(c, rel=1e-11)
     assert o.activeRobustChi2() == pytest.approx(pg_model.cost(g, g.poses)[0], rel=1e-9)
     assert np.allclose(op.edgeChi2(o, g.O), ec, rtol=1e-9, atol=1e-12)
+    tol = sp.bound(oracle.pg_system(g, 0.0)[0])
     for lam in (0.0, 0.7):
         H, b = o.reduced_system(lam)
         Hr, br = oracle.pg_system(g, lam)
         assert np.abs(H - Hr).max() <= 1e-10 * np.abs(Hr).max()
         assert np.abs(b - br).max() <= 1e-10 * np.abs(br).max()
+        sp.close(H, b, Hr, br, tol, ("pose graph", g.P, lam))   # in the system's own scale (tests/scaled_parity.py)
     assert o.optimize(10) == 10
     X, ec, st = oracle.pg_optimize(g, 10)
     s, got = o.stats, _pg_poses(o, g)
@@ -125,11 +130,13 @@ def test_moved_se3_window_cost_and_system_match_the_oracle(oracle, name):
     c_ref, ec_ref = oracle.ba3_chi2(g)
     assert o.activeRobustChi2() == pytest.approx(c_ref, rel=1e-11)
     assert np.allclose(op.edgeChi2(o, g.E), ec_ref, rtol=1e-10)
+    tol = sp.bound(oracle.ba3_reduced_system(g, 0.0)[0])
     for lam in (0.0, 2.5):
         S, bs = o.reduced_system(lam)
         Sr, br = oracle.ba3_reduced_system(g, lam)
         assert np.abs(S - Sr).max() <= 1e-10 * np.abs(Sr).max()
         assert np.abs(bs - br).max() <= 1e-10 * np.abs(br).max()
+        sp.close(S, bs, Sr, br, tol, (name, lam))
 
 
 @pytest.mark.parametrize("name", wc.BA3_CASES)
