@@ -1154,6 +1154,20 @@ enum {
     SE2GPU_SE3_FROM_MQT, SE2GPU_SE3_ADJ, SE2GPU_SE3_JAC_RIGHT, SE2GPU_SE3_JAC_LEFT_INV, SE2GPU_SE3_LOG_EXP, SE2GPU_SE3_OPS
 };
 int se2gpu_debug_se3(int op, int n, const double* in /* n x 24 */, double* out /* n x 36 */);
+/* Test introspection of the integer wave and workgroup primitives the batch kernels share (csrc/wave_int.h): one workgroup of
+ * `block` threads (64, 256 or 1024) walks in[0..n) in chunks of `block` and applies `op` to every chunk; lanes past n contribute the
+ * identity (0; INT_MAX for MIN, INT_MIN for MAX).  A wave is 64 consecutive values; the I32 ops take (int)in[i].
+ *   SUM / MIN / MAX        out[i] = the sum / minimum / maximum over i's wave, as int
+ *   SCAN_I32 / SCAN_I64    out[i] = the inclusive prefix sum inside i's wave
+ *   RANK                   out[i] = the number of j < i in i's wave with in[j] != 0
+ *   BLOCK_SCAN_I32 / _I64  out[i] = in[0] + .. + in[i - 1]: the workgroup's exclusive scan of every chunk on top of the total of the
+ *                          chunks before it, all on the same words of LDS; out[n] = the sum of all (out has n + 1 words)
+ *   FRESH_SCAN_I32 / _I64  the same with the barrier in front of the LDS write dropped; one chunk, n <= block */
+enum {
+    SE2GPU_WI_SUM = 0, SE2GPU_WI_MIN, SE2GPU_WI_MAX, SE2GPU_WI_SCAN_I32, SE2GPU_WI_SCAN_I64, SE2GPU_WI_RANK, SE2GPU_WI_BLOCK_SCAN_I32,
+    SE2GPU_WI_BLOCK_SCAN_I64, SE2GPU_WI_FRESH_SCAN_I32, SE2GPU_WI_FRESH_SCAN_I64, SE2GPU_WI_OPS
+};
+int se2gpu_debug_wave_int(int op, int block, int n, const long long* in, long long* out);
 
 /* Track::doTriangulate (/root/reference/src/Track.cpp:378-419) for every match of a frame pair in one device pass -
  * SURVEY section 8(f).3.  Per feature i of the reference key frame with match_idx[i] >= 0 and no map point yet:

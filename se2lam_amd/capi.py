@@ -230,6 +230,7 @@ SYMBOLS = {
     "se2gpu_ba_debug_reduce_grid": (_I, [_VP, _VP]),
     "se2gpu_ba_debug_plan_host": (_I, [_I, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I, _VP]),
     "se2gpu_debug_se3": (_I, [_I, _I, _VP, _VP]),
+    "se2gpu_debug_wave_int": (_I, [_I, _I, _I, _VP, _VP]),
     "se2gpu_triangulate": (_I, [_I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _I, _VP, _VP,
                            C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "se2gpu_track_create": (_I, [C.POINTER(_VP)]),
@@ -490,3 +491,18 @@ def debug_se3(op: str, x) -> np.ndarray:
     out = np.zeros((n, 36))
     check(lib().se2gpu_debug_se3(code, n, vp(buf), vp(out)))
     return out[:, :nout].copy()
+
+
+# ops of se2gpu_debug_wave_int (include/se2gpu.h); the workgroup scans write one more word, the sum of all
+WAVE_INT_OPS = {"sum": 0, "min": 1, "max": 2, "scan_i32": 3, "scan_i64": 4, "rank": 5, "block_scan_i32": 6, "block_scan_i64": 7,
+                "fresh_scan_i32": 8, "fresh_scan_i64": 9}
+
+
+def debug_wave_int(op: str, block: int, x) -> np.ndarray:
+    """se2gpu_debug_wave_int: function `op` of csrc/wave_int.h by one workgroup of `block` threads over the int64 values x -> int64
+    (len(x), or len(x) + 1 for the workgroup scans)"""
+    code = WAVE_INT_OPS[op]
+    x = np.ascontiguousarray(x, np.int64).reshape(-1)
+    out = np.zeros(len(x) + (1 if code >= 6 else 0), np.int64)
+    check(lib().se2gpu_debug_wave_int(code, int(block), len(x), vp(x), vp(out)))
+    return out

@@ -40,6 +40,7 @@
 #include "ba3_device.h"
 #include "ba_window.h"
 #include "edge_information.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 using namespace se2gpu::badev;
@@ -228,8 +229,7 @@ __device__ __forceinline__ void lin_landmark(int l, int sub, int beg, int end, i
     if (!FUSED) return;
     // the wave's edge range (lm_ptr is monotone; lanes beyond the last landmark hold 0, and if lane 0 is one, all are)
     int e1 = l < L ? end : 0;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) e1 = max(e1, __shfl_xor(e1, o));
+    e1 = wave_max(e1);
     const int E0 = __builtin_amdgcn_readfirstlane(l < L ? beg : 0), E1 = __builtin_amdgcn_readfirstlane(e1);
     const int ne = E1 - E0;
     const bool staged = ne > 0 && ne <= kStageEdges;
@@ -3455,12 +3455,7 @@ __global__ __launch_bounds__(1024) void k_scan_i32(const int* __restrict__ in, i
     } else {
         for (int i = b; i < e; ++i) s += in[i];
     }
-    int inc = s;                                  // inclusive scan of the chunk sums inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off);
-        if (lane >= off) inc += o;
-    }
+    const int inc = wave_scan_incl(s);            // inclusive scan of the chunk sums inside the wave
     if (lane == 63) wtot[wave] = inc;
     __syncthreads();
     int base = 0;

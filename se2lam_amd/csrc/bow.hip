@@ -14,6 +14,7 @@
 
 #include "../../include/se2lam_amd/VocabularyTree.h"
 #include "common.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -109,12 +110,8 @@ __device__ int run_starts(const unsigned long long* keys, int n_pad, int* start,
     }
     // block-wide exclusive scan of (heads, valid) packed into one int: both are below 1 << 13
     const int v = (heads << 16) | valid;
+    const int inc = wave_scan_incl(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
     if (lane == 63) wave_sums[w] = inc;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off: the ratios and the threshold tests are single IEEE operations.
 #include "common.h"
 #include "obs_table.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -35,12 +36,6 @@ struct CsrArgs {
     __device__ __forceinline__ FrameSlots slots() const { return FrameSlots{counts, nullptr, cap, nframes}; }
     __device__ __forceinline__ ObsCsr csr() const { return ObsCsr{mp_ptr, obs_frame, obs_ftr, m, nobs}; }
 };
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_covis_scatter(CsrArgs c, const uint8_t* mp_null, const uint8_t* good_prl, u64* bits,
                                                        int W) {
@@ -112,14 +107,9 @@ __global__ __launch_bounds__(64) void k_covis_pairs(PairArgs a) {
         nb += __popcll(B);
         same += pc;
         if (base < a.list_cap) {                                       // uniform
-            int incl = pc;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
+            const int incl = wave_scan_incl(pc);
             int at = base + incl - pc;                                 // exclusive prefix: this lane's first place in the list
-            base += __shfl(incl, 63);
+            base += wave_last(incl);
             while (x && at < a.list_cap) {
                 const int pt = 64 * w + __ffsll((long long)x) - 1;
                 x &= x - 1;

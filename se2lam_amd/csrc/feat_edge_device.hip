@@ -17,6 +17,7 @@
 // Compiled with -ffp-contract=off: the prior's information matrix equals the host function's to the bit.
 #include "common.h"
 #include "se3_math.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(64) void k_feat_gather(const GatherArgs A) {
         }
         const unsigned long long mask = __ballot(valid);
         raw += __popcll(__ballot(israw));
-        const int slot = npts + __popcll(mask & ((1ull << lane) - 1ull));
+        const int slot = npts + lane_rank(mask);
         npts += __popcll(mask);
         if (valid && slot < A.row_cap) {
             const size_t r = row0 + slot;

@@ -20,6 +20,7 @@
 #include "ba_window.h"
 #include "common.h"
 #include "edge_information.h"
+#include "wave_int.h"
 #include "se2lam_amd/obs_table.h"
 
 using namespace se2gpu;
@@ -129,43 +130,6 @@ struct GatherArgs {
     int* status;
 };
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-    return v;
-}
-// inclusive prefix sum over the wave
-__device__ __forceinline__ int wave_scan_i(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-// exclusive prefix sum over the workgroup of one value per thread; *total = the sum.  s_w is WAVES ints; two barriers.
-__device__ __forceinline__ int block_scan_excl(int v, int* s_w, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_scan_i(v, lane);
-    __syncthreads();                     // (s_w may still be read from the round before)
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = s_w[w];
-        if (w < wave) base += c;
-        sum += c;
-    }
-    *total = sum;
-    return base + incl - v;
-}
-
 struct JobArrays {
     int* cnt;
     uint8_t* fixed;
@@ -190,7 +154,6 @@ template <bool EMIT>
 __device__ __forceinline__ void point_pass(const GatherArgs& A, const FrameSlots& fs, const ObsCsr& csr, const int* s_vert, u64* bits,
                                            const int* mp_list, int n_mp, const JobArrays& J, long long& edges, long long& entries, int& maxdeg, int& flags) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;
     for (int l = wave; l < n_mp; l += WAVES) {                    // uniform in the wave
         const int p = mp_list[l];                                  // in 0..m-1: the caller has checked the list
         int s, n;
@@ -230,7 +193,7 @@ __device__ __forceinline__ void point_pass(const GatherArgs& A, const FrameSlots
             const bool edge = first && okoct;
             const u64 mask = __ballot(edge);
             if (EMIT && edge) {
-                const size_t at = (size_t)e0 + deg + __popcll(mask & below);
+                const size_t at = (size_t)e0 + deg + lane_rank(mask);
                 const se2gpu_keypoint kp = A.kps_un[fo];
                 J.e_kf[at] = v;
                 J.e_uv[2 * at] = (double)kp.x; J.e_uv[2 * at + 1] = (double)kp.y;
@@ -314,7 +277,7 @@ __global__ __launch_bounds__(BLOCK) void k_local_ba_gather(const GatherArgs A) {
         minid = min(minid, A.frame_id[slot]);
         self_loop |= A.odo_to && A.odo_to[slot] == slot;
     }
-    minid = wave_min_i(minid);
+    minid = wave_min(minid);
     if (lane == 0) atomicMin(&s_minid, minid);
     has_null = __syncthreads_or(has_null);
     self_loop = __syncthreads_or(self_loop);
@@ -334,7 +297,7 @@ __global__ __launch_bounds__(BLOCK) void k_local_ba_gather(const GatherArgs A) {
     point_pass<false>(A, fs, csr, s_vert, s_bits[wave], mp_list, n_mp, J, edges, entries, maxdeg, flags);
     // the sums over the workgroup (a job of two billion entries saturates nothing: nobs <= 2^31 - 1 and a point's segment lies inside it,
     // but the sum over the points is taken in 64 bits below)
-    n_free = wave_sum_i(n_free);
+    n_free = wave_sum(n_free);
     flags = __ballot(flags != 0) != 0ull ? FLAG_OCTAVE : 0;         // (the one flag there is)
     __shared__ long long s_ent[WAVES], s_edges64[WAVES];
     if (lane == 0) {                                               // (lane 0 holds the wave's edges, entries and largest degree)
@@ -363,7 +326,7 @@ __global__ __launch_bounds__(BLOCK) void k_local_ba_gather(const GatherArgs A) {
     };
     int O = 0;
     for (int i = tid; i < n_local; i += BLOCK) O += odo_target(i) >= 0;
-    O = wave_sum_i(O);
+    O = wave_sum(O);
     __syncthreads();
     if (lane == 0) s_w[wave] = O;
     __syncthreads();
@@ -394,7 +357,7 @@ __global__ __launch_bounds__(BLOCK) void k_local_ba_gather(const GatherArgs A) {
         const int i = i0 + tid;
         const int v = odo_target(i);
         int total;
-        const int at = base + block_scan_excl(v >= 0, s_w, &total);
+        const int at = base + block_scan_excl<WAVES>((int)(v >= 0), s_w, total);
         base += total;
         if (v >= 0) {
             const int slot = local_list[i];
@@ -416,7 +379,7 @@ __global__ __launch_bounds__(BLOCK) void k_local_ba_gather(const GatherArgs A) {
         const int l = l0 + tid;
         const int c = l < n_mp ? J.lm_ptr[l + 1] : 0;
         int total;
-        const int at = base + block_scan_excl(c, s_w, &total);
+        const int at = base + block_scan_excl<WAVES>(c, s_w, total);
         base += total;
         if (l < n_mp) J.lm_ptr[l + 1] = at + c;
     }

@@ -15,6 +15,7 @@
 // round is never expanded in that same round (an in-place sweep in ascending slot order would run down a whole chain in one).
 // Integers only; LDS and global integer atomics (OR / AND, order-free); every slot, order entry and tail bit is checked.
 #include "common.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -29,12 +30,6 @@ constexpr int FRAMES = 8;                                    // candidate frames
 constexpr int EMIT = 4;                                      // order entries a thread takes per barrier of a list
 constexpr int MAX_BLOCKS = (1 << 24) - 1;                    // 256 threads each; a launch's threads stay below 2^32
 constexpr int MAX_PAIRS = INT_MAX - 255;                     // the grid of k_adj_connect is computed in unsigned
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // the bits of word w that name an index below n
 __device__ __forceinline__ u64 tail_mask(int w, int n) {
@@ -95,18 +90,13 @@ struct WindowArgs {
 __device__ __forceinline__ int compact_row(const u64* row, int WF, int* list, int lane) {
     u64 x = lane < WF ? row[lane] : 0ull;
     const int pc = __popcll(x);
-    int incl = pc;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
+    const int incl = wave_scan_incl(pc);
     int at = incl - pc;
     while (x) {
         list[at++] = 64 * lane + __ffsll((long long)x) - 1;
         x &= x - 1;
     }
-    return __shfl(incl, 63);
+    return wave_last(incl);
 }
 
 // The members of a set, given as a bit row over n indices, in ascending position of order[] (NULL: index order) into
@@ -144,7 +134,7 @@ __device__ __forceinline__ void emit_list(const u64* row, int n, const int* orde
                 if (v < wave) at += c;
                 base += c;
             }
-            at += __popcll(bal[k] & ((1ull << lane) - 1ull));
+            at += lane_rank(bal[k]);
             if (in[k] && at < cap) out[at] = s[k];
         }
     }

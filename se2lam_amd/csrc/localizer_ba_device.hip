@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "pose_ba_device.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -87,12 +88,6 @@ struct LocArgs {
     se2gpu_ba_stats* stats;
     int* info;
 };
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 __global__ __launch_bounds__(BLOCK) void k_localizer_ba(const LocArgs A) {
     __shared__ __align__(16) int s_pt[CHUNK];                      // read as int4
@@ -229,7 +224,7 @@ __global__ __launch_bounds__(BLOCK) void k_localizer_ba(const LocArgs A) {
         }
         E += total;
     }
-    n_obs = wave_sum_i(n_obs); renewed = wave_sum_i(renewed); dups = wave_sum_i(dups);
+    n_obs = wave_sum(n_obs); renewed = wave_sum(renewed); dups = wave_sum(dups);
     flags = (__ballot(flags & FLAG_ENTRY) ? FLAG_ENTRY : 0) | (__ballot(flags & FLAG_OCTAVE) ? FLAG_OCTAVE : 0);
     if (lane == 0) { s_red[0][wave] = n_obs; s_red[1][wave] = renewed; s_red[2][wave] = dups; s_red[3][wave] = flags; }
     __syncthreads();

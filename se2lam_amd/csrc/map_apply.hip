@@ -21,6 +21,7 @@
 // with the host mirror include/se2lam_amd/MapUpdate.h.  Compiled with -ffp-contract=off like new_kf.hip.
 #include "common.h"
 #include "obs_table.h"
+#include "wave_int.h"
 #include "../../include/se2lam_amd/map_normal.h"
 
 using namespace se2gpu;
@@ -29,7 +30,7 @@ namespace {
 
 enum { H_M_OLD = 0, H_NOBS_OLD, H_STATUS, H_M_NEW, H_NOBS_NEW, H_ADDED, H_ERASED, H_CREATED, H_NULLED, H_SKIPPED, H_DUP, H_KEPT,
        H_WORDS = 16 };
-constexpr int kBlock = 256;
+constexpr int kBlock = 256, kWaves = kBlock / 64;   // the workgroups that scan; their lds is kWaves ints
 
 struct ApplyArgs {
     const int* counts;
@@ -92,35 +93,13 @@ struct ApplyArgs {
     }
 };
 
-// exclusive scan of v over the 256 threads of a workgroup; total: their sum.  lds: 4 ints.
-__device__ __forceinline__ int block_scan(int v, int& total, int* lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();                       // lds may still be read from the call before
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < kBlock / 64; ++k) {
-        if (k < w) base += lds[k];
-        total += lds[k];
-    }
-    return base + inc - v;
-}
-
 // out[i] = in[0] + .. + in[i - 1] for i < n by one workgroup; returns the sum
 __device__ int scan_array(const int* in, int* out, int n, int* lds) {
     int run = 0;
     for (int at = 0; at < n; at += kBlock) {
         const int i = at + (int)threadIdx.x, v = i < n ? in[i] : 0;
         int total;
-        const int ex = block_scan(v, total, lds);
+        const int ex = block_scan_excl<kWaves>(v, lds, total);
         if (i < n) out[i] = run + ex;
         run += total;
     }
@@ -158,7 +137,7 @@ __global__ __launch_bounds__(128) void k_claim(ApplyArgs a) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_job_rank(ApplyArgs a) {
-    __shared__ int lds[4];
+    __shared__ int lds[kWaves];
     const int b = blockIdx.x;
     const size_t row = (size_t)b * a.cap;
     int run = 0;
@@ -166,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_job_rank(ApplyArgs a) {
         const int i = at + (int)threadIdx.x;
         const int has = i < a.cap && a.born[row + i] >= 0;
         int total;
-        const int ex = block_scan(has, total, lds);
+        const int ex = block_scan_excl<kWaves>(has, lds, total);
         if (i < a.cap) a.rank3[row + i] = run + ex;
         run += total;
     }
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void k_job_rank(ApplyArgs a) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_count(ApplyArgs a) {
-    __shared__ int lds[4];
+    __shared__ int lds[kWaves];
     const int p = blockIdx.x * kBlock + threadIdx.x;
     const int m_old = a.hdr[H_M_OLD];
     int len = 0, erased = 0, nulled = 0, added = 0;
@@ -202,18 +181,18 @@ __global__ __launch_bounds__(kBlock) void k_count(ApplyArgs a) {
     }
     if (p < a.m_cap) a.cnt[p] = len;
     int total, t2;
-    block_scan(len, total, lds);
+    block_scan_excl<kWaves>(len, lds, total);
     if (threadIdx.x == 0) a.bsum[blockIdx.x] = total;
-    block_scan(erased, total, lds);
-    block_scan(added, t2, lds);
+    block_scan_excl<kWaves>(erased, lds, total);
+    block_scan_excl<kWaves>(added, lds, t2);
     if (threadIdx.x == 0 && total) atomicAdd(&a.hdr[H_ERASED], total);
     if (threadIdx.x == 0 && t2) atomicAdd(&a.hdr[H_ADDED], t2);
-    block_scan(nulled, total, lds);
+    block_scan_excl<kWaves>(nulled, lds, total);
     if (threadIdx.x == 0 && total) atomicAdd(&a.hdr[H_NULLED], total);
 }
 
 __global__ __launch_bounds__(kBlock) void k_scan_sums(ApplyArgs a) {
-    __shared__ int lds[4];
+    __shared__ int lds[kWaves];
     const int kept = scan_array(a.bsum, a.boff, a.nblk, lds);
     const int born = a.B > 0 ? scan_array(a.n3, a.job_base, a.B, lds) : 0;
     if (threadIdx.x) return;
@@ -228,12 +207,12 @@ __global__ __launch_bounds__(kBlock) void k_scan_sums(ApplyArgs a) {
 }
 
 __global__ __launch_bounds__(kBlock) void k_points(ApplyArgs a) {
-    __shared__ int lds[4];
+    __shared__ int lds[kWaves];
     if (a.hdr[H_STATUS]) return;
     const int p = blockIdx.x * kBlock + threadIdx.x;
     const int m_old = a.hdr[H_M_OLD], m_new = a.hdr[H_M_NEW], kept_all = a.hdr[H_KEPT];
     int total;
-    const int at0 = a.boff[blockIdx.x] + block_scan(p < a.m_cap ? a.cnt[p] : 0, total, lds);
+    const int at0 = a.boff[blockIdx.x] + block_scan_excl<kWaves>(p < a.m_cap ? a.cnt[p] : 0, lds, total);
     if (p > a.m_cap) return;
     if (p >= m_old) {                                                 // new points (k_features fills them) and the padding
         a.mp_ptr_new[p] = kept_all + 2 * (ot_min(p, m_new) - m_old);

@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -170,7 +171,7 @@ __device__ __forceinline__ int scan_candidates(const Bounds& bd, float x, float 
         }
         const unsigned long long m = __ballot(ok);
         if (ok) {
-            const int slot = count + __popcll(m & ((1ull << lane) - 1ull));
+            const int slot = count + lane_rank(m);
             if (slot < kMaxCand) out[slot] = ((uint32_t)idx << 12) | (uint32_t)hamming256(d1, desc2 + 32 * (size_t)idx);
         }
         count += __popcll(m);
@@ -251,12 +252,7 @@ __device__ __forceinline__ void stage_candidates(const uint32_t* __restrict__ ca
             if (n > kMaxCand) { atomicOr(overflow, 1); n = kMaxCand; }   // (informational: such queries take the spill scan)
             local += n;
         }
-        int incl = local;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
+        const int incl = wave_scan_incl(local);
         int run = incl - local;
         for (int i = lane * per; i < min(nq, (lane + 1) * per); ++i) {
             off[i] = run;

@@ -37,6 +37,7 @@
 #include <utility>
 
 #include "common.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 
@@ -1069,11 +1070,7 @@ __global__ __launch_bounds__(256) void k_cell_collect_w(Geom g, const CellGeoRec
             s_lst[lane] = id;
             c = lst_cnt[(size_t)f * g.lst_base[g.nlevels] + id];
         }
-        int incl = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
+        const int incl = wave_scan_incl(c);
         s_off[lane + 1] = incl;
         if (lane == 0) s_off[0] = 0;
         cnt[lane] = 0;
@@ -1237,11 +1234,7 @@ __device__ void cell_collect_wg(const Geom& g, const int f, const int cell, cons
                     s_lst[k] = id;
                     c = lst_cnt[(size_t)f * g.lst_base[g.nlevels] + id];
                 }
-                int incl = c;
-                for (int d = 1; d < 64; d <<= 1) {
-                    const int v = __shfl_up(incl, d);
-                    if (k >= d) incl += v;
-                }
+                const int incl = wave_scan_incl(c);
                 s_off[k + 1] = incl;
                 if (k == 0) s_off[0] = 0;
             }
@@ -1382,7 +1375,7 @@ __device__ __forceinline__ int level_quota(const int* tot, int nCells, int nfc, 
             else { r[k] = t[k]; dist += nfc - t[k]; ++cnt; }
         }
     }
-    for (int s = 1; s < 64; s <<= 1) { dist += __shfl_xor(dist, s); cnt += __shfl_xor(cnt, s); }
+    dist = wave_sum(dist); cnt = wave_sum(cnt);
     while (dist > 0 && cnt < nCells) {
         const int nNew = nfc + (int)ceilf((float)dist / (float)(nCells - cnt));
         int d2 = 0, c2 = 0;
@@ -1392,7 +1385,7 @@ __device__ __forceinline__ int level_quota(const int* tot, int nCells, int nfc, 
                 if (t[k] > nNew) { r[k] = nNew; }
                 else { r[k] = t[k]; d2 += nNew - t[k]; nm[k] = true; ++c2; }
             }
-        for (int s = 1; s < 64; s <<= 1) { d2 += __shfl_xor(d2, s); c2 += __shfl_xor(c2, s); }
+        d2 = wave_sum(d2); c2 = wave_sum(c2);
         dist = d2;
         cnt += c2;
     }
@@ -1401,13 +1394,9 @@ __device__ __forceinline__ int level_quota(const int* tot, int nCells, int nfc, 
     for (int k = 0; k < kQuotaPerLane; ++k) {
         if (64 * k >= nCells) break;   // (uniform: most levels have fewer than 64 cells)
         const int c = lane + 64 * k;
-        int incl = r[k];
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
+        const int incl = wave_scan_incl(r[k]);
         if (c < nCells) { n_ret[c] = r[k]; c_off[c] = base + incl - r[k]; }
-        base += __shfl(incl, 63);
+        base += wave_last(incl);
     }
     return base;
 }

@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "fm_subsets.h"
+#include "wave_int.h"
 
 namespace se2gpu {
 namespace {
@@ -452,7 +453,7 @@ __global__ __launch_bounds__(256) void k_lv_gather(LvBatch b, int p0, int lmeds_
             if (w < wv) off += s_wave[w];
             total += s_wave[w];
         }
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1));
+        const int pos = off + lane_rank(bal);
         if (i < cap) sl[i] = m >= 0 ? pos : -1;
         if (m >= 0) {
             m1[pos] = make_float2(ka[i].x, ka[i].y);

@@ -19,6 +19,7 @@
 #include "../../include/se2lam_amd/VocabularyTrain.h"
 #include "../../include/se2lam_amd/VocabularyTree.h"
 #include "common.h"
+#include "wave_int.h"
 
 using namespace se2gpu;
 namespace vt = se2lam_amd::voctrain;
@@ -43,24 +44,6 @@ struct VtNode {
 __device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
            __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// inclusive scan over the 256 threads of the workgroup; `total` is the sum of all.  s_w: 4 entries.
-__device__ __forceinline__ long long block_scan(long long v, long long* s_w, long long& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();   // s_w may still be read from the previous call
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    long long before = 0;
-    for (int x = 0; x < w; ++x) before += s_w[x];
-    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return inc + before;
 }
 
 // ---- the features -----------------------------------------------------------------------------------------------------
@@ -114,7 +97,7 @@ __global__ void __launch_bounds__(kTile) k_vt_seed_dist(const VtNode* __restrict
                                                         const int32_t* __restrict__ order, const uint4* __restrict__ feat,
                                                         const uint4* __restrict__ centres, int32_t* __restrict__ md,
                                                         long long* __restrict__ tile_sum) {
-    __shared__ long long s_w[4];
+    __shared__ long long s_w[kTile / 64];
     const int node = tile_node[blockIdx.x];
     const VtNode nd = nodes[node];
     if (!nd.seeding) return;
@@ -134,7 +117,7 @@ __global__ void __launch_bounds__(kTile) k_vt_seed_dist(const VtNode* __restrict
         v = m;
     }
     long long total;
-    (void)block_scan(v, s_w, total);
+    (void)block_scan_excl<kTile / 64>((long long)v, s_w, total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
@@ -142,7 +125,7 @@ __global__ void __launch_bounds__(kTile) k_vt_seed_dist(const VtNode* __restrict
 __global__ void __launch_bounds__(kTile) k_vt_seed_pick(VtNode* __restrict__ nodes, int k, const int32_t* __restrict__ order,
                                                         const uint4* __restrict__ feat, uint4* __restrict__ centres,
                                                         const int32_t* __restrict__ md, const long long* __restrict__ tile_sum) {
-    __shared__ long long s_w[4];
+    __shared__ long long s_w[kTile / 64];
     __shared__ double s_cut;
     __shared__ int s_first;
     __shared__ long long s_base;
@@ -151,7 +134,7 @@ __global__ void __launch_bounds__(kTile) k_vt_seed_pick(VtNode* __restrict__ nod
     if (!nd.seeding) return;
     long long part = 0, sum;
     for (int t = tid; t < nd.ntiles; t += kTile) part += tile_sum[nd.tile0 + t];
-    (void)block_scan(part, s_w, sum);
+    (void)block_scan_excl<kTile / 64>(part, s_w, sum);
     if (sum == 0) {   // every member coincides with a seed: fewer than k clusters
         if (tid == 0) nodes[node].seeding = 0;
         return;
@@ -174,7 +157,7 @@ __global__ void __launch_bounds__(kTile) k_vt_seed_pick(VtNode* __restrict__ nod
         const int t = base + tid;
         const long long v = t < nd.ntiles ? tile_sum[nd.tile0 + t] : 0;
         long long chunk;
-        const long long pre = carry + block_scan(v, s_w, chunk);
+        const long long pre = carry + block_scan_excl<kTile / 64>(v, s_w, chunk) + v;   // inclusive
         if (t < nd.ntiles && (double)pre >= cut) atomicMin(&s_first, t);
         __syncthreads();
         tile = s_first;
@@ -194,7 +177,7 @@ __global__ void __launch_bounds__(kTile) k_vt_seed_pick(VtNode* __restrict__ nod
         const int local = tile * kTile + tid;
         const long long v = local < nd.count ? md[nd.start + local] : 0;
         long long unused;
-        const long long pre = before + block_scan(v, s_w, unused);
+        const long long pre = before + block_scan_excl<kTile / 64>(v, s_w, unused) + v;
         if (local < nd.count && (double)pre >= cut) atomicMin(&s_first, local);
         __syncthreads();
         if (s_first != INT_MAX) pick = s_first;
@@ -335,7 +318,7 @@ __device__ __forceinline__ int wave_rank(bool valid, int c, int ncl, int* s_w) {
         const bool mine = valid && c == cc;
         const unsigned long long mask = __ballot(mine);
         if (lane == 0) s_w[w * kMaxK + cc] = __popcll(mask);
-        if (mine) rank = __popcll(mask & ((1ull << lane) - 1ull));
+        if (mine) rank = lane_rank(mask);
     }
     return rank;
 }
@@ -370,12 +353,7 @@ __global__ void __launch_bounds__(64) k_vt_split_scan(const VtNode* __restrict__
             *p = run;
             run += v;
         }
-    int inc = run;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (c >= d) inc += t;
-    }
+    const int inc = wave_scan_incl(run);
     if (c < k) {
         cl_count[(size_t)node * k + c] = run;
         cl_base[(size_t)node * k + c] = inc - run;
